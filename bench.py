@@ -27,11 +27,23 @@ bands r, r+N, ...; every rank holds the whole world), and each launch ends with 
 its F frames' per-rank G-buffer bands (packed losslessly to 8 B/pixel) to rank 0 (total work fixed
 -> "scaling": "strong"); the gather of one launch overlaps the trace of the next.
 
-Rank 0 prints one JSON line.  `roofline` prices the dominant kernel (k_trace_stack) against the
+Rank 0 prints one JSON line.  A plain run does only what that line's headline figure needs: it generates the world,
+counts each path camera's rays (one untimed frame per camera), runs the path for SETTLE_S seconds so that the device's
+clocks settle, warms up, times the K steps and prints.  Everything else runs only with `--full`: the second (warm) world
+generation, the stack-vs-literal parity of every path camera, the diagnostics, the single-frame latency leg, the
+roofline leg, the CPU baseline and, at N > 1, the trace-only figure and the self-check of the gathered frame.
+
+With `--full`, `roofline` prices the dominant kernel (k_trace_stack) against the
 8 TB/s HBM peak using the ALGORITHMIC bytes of the reference algorithm: per ray
 4*node_words + 2*brick_cells + 32*chunk_descriptors (restart-from-root counts, measured for these
 exact frames by the literal kernel's counters) + 32 B G-buffer record per pixel.  `cpu_baseline`
 is the CPU oracle (oracle/, a port of src/Traverse.cpp) timed on this host on one frame of the path.
+
+`--dump-outputs DIR` writes the G-buffer of the last timed step (the last frame; rank 0's gathered frame at N > 1) as
+DIR/<field>.npy in float32 (t, normal, material, flags) and float64 (chunk, node, cell: ids beyond 2^24); a frame
+larger than the 64 MB budget is sampled at fixed, seeded pixels, whose flat indices go to DIR/pixel.npy.  Every value
+written is finite: the reference's NaN normal (cubeNormal of a zero vector, include/svo.h normal_mode) is written as
+(0, 0, 0).
 """
 from __future__ import annotations
 
@@ -74,6 +86,7 @@ FRAMES_PER_LAUNCH = {1: 8, 2: 16, 4: 16, 8: 16}     # consecutive frames marched
 LAUNCH_SHAPE = {"c3_1080p_depth12_4x1x4_shadow": (2, 16), "c4_2160p_depth12_4x1x4_shadow": (2, 16),
                 "ref_default_1080p_depth8_4x4x4_shadow": (2, 16)}     # (7.9 - 8.4 against 7.1 - 7.3 Grays/s with 4 x 8, gpurun_out/s2_refdefault_shapes.txt)
 PATH_CAMERAS = 32
+SETTLE_S = 0.2                 # seconds of untimed path launches before the warm-up steps (see "settle" in run())
 
 
 def camera_path(svo, workload, gw, gd, iw, ih, count=PATH_CAMERAS):
@@ -103,6 +116,36 @@ def camera_path(svo, workload, gw, gd, iw, ih, count=PATH_CAMERAS):
     return cams
 
 
+# --dump-outputs: G-buffer field -> dtype written.  Every value is exact in it (u16 in float32, u32 ids in float64).
+DUMP_FIELDS = [("t", "float32"), ("normal", "float32"), ("material", "float32"), ("flags", "float32"),
+               ("chunk", "float64"), ("node", "float64"), ("cell", "float64")]
+DUMP_BUDGET = 64_000_000       # bytes, all files together
+# svo_hit.normal is normalize(v) for v in {-1,0,1}^3 (SVO_NORMAL_CUBE) or the face normal: NaN in all three components where
+# v = (0,0,0), never partly NaN, never (0,0,0) on a hit.  The dump writes that NaN as (0, 0, 0) - the hit flag tells it from
+# a miss's zero normal - so the files stay finite and lossless.
+
+
+def dump_outputs(out_dir, recs, fields):
+    """recs: HIT_DTYPE[n] of one frame (row-major pixels).  Every field as out_dir/<field>.npy; over the budget, the same
+    fixed, seeded sample of pixels in every field, ascending, with their flat indices in out_dir/pixel.npy."""
+    import numpy as np
+    n = recs.shape[0]
+    per_pixel = sum(np.dtype(dt).itemsize * int(np.prod(recs.dtype[f].shape, dtype=np.int64)) for f, dt in fields)
+    os.makedirs(out_dir, exist_ok=True)
+    if n * per_pixel > DUMP_BUDGET:
+        k = (DUMP_BUDGET - 4096) // (per_pixel + 8)
+        pix = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        recs = recs[pix]
+        np.save(os.path.join(out_dir, "pixel.npy"), pix.astype(np.float64))
+    for f, dt in fields:
+        a = np.ascontiguousarray(recs[f]).astype(dt)
+        if f == "normal":
+            a[np.isnan(a)] = 0.0
+        if not np.isfinite(a).all():
+            raise SystemExit(f"bench.py --dump-outputs: field {f} holds non-finite values")
+        np.save(os.path.join(out_dir, f + ".npy"), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -126,8 +169,13 @@ def parse_args(argv=None):
                          "by one collective): the persistent waves drain once per launch.  1 = one launch per frame")
     ap.add_argument("--frames-per-gather", type=int, default=0, help="older name of --frames-per-launch at N > 1")
     ap.add_argument("--no-gather", action="store_true", help="diagnostic (N > 1): trace only, skip the per-frame gather")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-diagnostics", action="store_true", help="skip the per-camera spread and the identical-view leg")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: warm world generation, stack-vs-literal parity of the path, diagnostics, "
+                         "single-frame latency, roofline leg, CPU baseline (N > 1: trace-only figure, gathered-frame self-check)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's G-buffer fields to DIR/<field>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-diagnostics", action="store_true", help="--full: skip the per-camera spread, the identical-view leg and the single-frame leg")
     ap.add_argument("--cpu-crop", type=int, default=0, help="time the CPU oracle on a centred NxN crop instead of the full frame")
     ap.add_argument("--spawn-selftest", action="store_true",
                     help="no GPU, no tracing: run the N-rank control flow (self-spawn, rendezvous, ranks_seen, band partition, "
@@ -263,22 +311,24 @@ def run(args):
     kernel = {"auto": svo.KERNEL_AUTO, "literal": svo.KERNEL_LITERAL, "stack": svo.KERNEL_STACK}[args.kernel]
 
     # ---- world: generated by every rank for itself, on its own GPU (noise, mips, grow() and the water fill as kernels,
-    # pools left in HBM: deterministic -> identical on every rank).  Generated twice: the first call of a process also
-    # pays the HIP runtime's first-use costs (code object load, first allocations), the second is the builder alone.
+    # pools left in HBM: deterministic -> identical on every rank).  With --full generated twice: the first call of a process
+    # also pays the HIP runtime's first-use costs (code object load, first allocations), the second is the builder alone.
     local_ranks = int(os.environ.get("LOCAL_WORLD_SIZE", str(world_size)))
     gen_threads = max(1, (os.cpu_count() or 1) // max(1, local_ranks))
     gen_kw = svo.c5_scene()["generate"] if args.workload.startswith("c5_") else {}
     t0 = time.time()
     world = svo.World.generate(gw, gh, gd, 128, depth, threads=gen_threads, build_device=local_rank, **gen_kw)
     t_gen = time.time() - t0
-    # the second generation: the library hands the first world's pools on to it (include/svo.h svo_device_cache_trim: destroy
-    # keeps the large device buffers), so it is the builder alone - until round 4 it also paid hipFree + hipMalloc of 12 GB,
-    # which on this pool stalled for ~4 s about once in ten cycles (scripts/alloc_probe.py) and was papered over by a retry here
-    world.destroy()
-    t0 = time.time()
-    world = svo.World.generate(gw, gh, gd, 128, depth, threads=gen_threads, build_device=local_rank, **gen_kw)
-    t_gen_warm = time.time() - t0
-    gen_stalled = t_gen_warm > max(2.0 * t_gen, 0.5)        # slower than the process's FIRST call: not the builder's doing (reported, not retried)
+    t_gen_warm = gen_stalled = None
+    if args.full:
+        # the second generation: the library hands the first world's pools on to it (include/svo.h svo_device_cache_trim: destroy
+        # keeps the large device buffers), so it is the builder alone - until round 4 it also paid hipFree + hipMalloc of 12 GB,
+        # which on this pool stalled for ~4 s about once in ten cycles (scripts/alloc_probe.py) and was papered over by a retry here
+        world.destroy()
+        t0 = time.time()
+        world = svo.World.generate(gw, gh, gd, 128, depth, threads=gen_threads, build_device=local_rank, **gen_kw)
+        t_gen_warm = time.time() - t0
+        gen_stalled = t_gen_warm > max(2.0 * t_gen, 0.5)    # slower than the process's FIRST call: not the builder's doing (reported, not retried)
     t0 = time.time()
     world.upload(local_rank)                       # already resident where it was built: a no-op
     t_up = time.time() - t0
@@ -410,15 +460,17 @@ def run(args):
             dt = float(et.item())
         return dt
 
-    # ---- untimed preamble.  N = 1: every camera of the path is traced once by the literal kernel (its reference work
-    # counters price the algorithmic bytes; its launch also counts the frame's rays), then the path is traced group by
+    # ---- untimed preamble.  N = 1 with --full: every camera of the path is traced once by the literal kernel (its reference
+    # work counters price the algorithmic bytes; its launch also counts the frame's rays), then the path is traced group by
     # group by the timed kernel - launches of the same shape as the timed ones - and every frame must equal the literal
-    # kernel's G-buffer.  N > 1: this rank's share of every camera is traced once and the ray counts are summed over ranks.
+    # kernel's G-buffer.  Otherwise this rank's share of every camera is traced once by the timed kernel, which counts the
+    # same rays (tests/test_gpu_parity.py: last_ray_count == the oracle's), and the ray counts are summed over ranks.
     rays_local = []
     algo_cam = None
     counters_sum = None
-    exempt_records = 0                          # records outside the stack-vs-literal comparison (SVO_ERR_FLAG in either kernel's output)
-    if not multi and not args.emulate_share:
+    exempt_records = None                       # records outside the stack-vs-literal comparison (SVO_ERR_FLAG in either kernel's output)
+    if args.full and not multi and not args.emulate_share:
+        exempt_records = 0
         algo_cam = []
         counters_sum = dict(node_words=0, brick_cells=0, chunk_descs=0, tree_steps=0)
         cnt = torch.zeros((ih * iw, 4), dtype=torch.int32, device=dev)
@@ -471,6 +523,17 @@ def run(args):
     def rays_of(steps, fixed=False):
         return steps * rays_cam[0] if fixed else sum(rays_cam[i % P] for i in range(steps))
 
+    # ---- settle: the path in launches of the timed shape, back to back for SETTLE_S of wall time, before the W warm-up steps.
+    # Without it a short run is timed on a device still raising its clocks (--steps 20 --warmup 5: 1.7 % more ms per step);
+    # before --full existed, the untimed parity pass ahead of the warm-up (~0.16 s of kernels) did this in passing.
+    t_settle, j = time.perf_counter(), 0
+    while time.perf_counter() - t_settle < SETTLE_S:
+        for first in range(0, P, G):
+            trace_group(j % S, cams_of(first, min(G, P - first)))
+            j += 1
+        for st in streams:
+            st.synchronize()
+
     # ---- warmup
     works = [None] * S
     for i in range(args.warmup):
@@ -485,16 +548,17 @@ def run(args):
     kernel_ms_overlapped = sum(kernel_ms) / len(kernel_ms)      # per launch while S launches share the GPU
     lastf = args.steps - 1
     last_slot, last_sub = (lastf // G) % S, lastf % G
-    last_out = bufs[last_slot][:last_sub + 1].clone()            # the last timed launch's G-buffers (parity sample below)
+    if args.full or args.dump_outputs:
+        last_out = bufs[last_slot][:last_sub + 1].clone()        # the last timed launch's G-buffers (parity sample and dump below)
     if rank == 0 and multi and not args.no_gather:
         last_gathered = [g[last_sub].clone() for g in gathered[last_slot]]
 
     # ---- diagnostics, untimed by the contract
     diag = {}
-    if multi and not args.no_gather:
+    if args.full and multi and not args.no_gather:
         dt = timed_region(args.steps, gather=False)             # the same frames without the exchange step
         diag["trace_only_mrays"] = round(rays_of(args.steps) / dt / 1e6, 3)
-    if not multi and not share and not args.no_diagnostics:
+    if args.full and not multi and not share and not args.no_diagnostics:
         if P > 1:
             dt = timed_region(args.steps, fixed=path[0])        # round-1 figure: every frame in flight is the same view
             diag["identical_view_mrays"] = round(rays_of(args.steps, fixed=True) / dt / 1e6, 3)
@@ -521,7 +585,7 @@ def run(args):
     # by the previous frame's per-tile step maxima (svo_trace_params.tile_cost_dev -> svo_tile_order -> tile_order_dev).
     # The ordered figure includes the sort.  Records must be byte-identical either way.
     single = None
-    if not multi and not share and not args.no_diagnostics and args.kernel != "literal" and world.info.wide_nodes > 0:
+    if args.full and not multi and not share and not args.no_diagnostics and args.kernel != "literal" and world.info.wide_nodes > 0:
         st0 = streams[0]
         ntl = ((iw + 7) // 8) * ((ih + 7) // 8)
         cost = torch.zeros(ntl * 2, dtype=torch.int32, device=dev)
@@ -581,7 +645,7 @@ def run(args):
     # rocprofv3 --kernel-trace of `bench.py --streams 1` must agree.
     kernel_ms_avg = kernel_ms_overlapped
     roof_bytes = None
-    if not multi and not args.emulate_share:
+    if args.full and not multi and not args.emulate_share:
         # the launch sizes of the timed region, in its order and proportion (a run that is no multiple of G ends with a shorter launch, whose
         # drain weighs more: it is timed too, as often as it occurs), repeated until at least five launches are timed
         sizes = [k for _, _, k in ev]
@@ -608,11 +672,13 @@ def run(args):
         kernel_ms_avg = kernel_ms_sum / reps
         roof_sizes = sizes
 
-    if rank == 0 and multi and not args.no_gather:
+    frame_full = None
+    if rank == 0 and multi and not args.no_gather and (args.full or args.dump_outputs):
         # de-interleave once (untimed): frame[(k*N + r)*8 + j] = gathered[r][k][j]
         frame_full = svo.partition.deinterleave(last_gathered, ih, BAND)
         assert frame_full.shape[0] == ih
-        # untimed self-check (mandatory): the gathered, de-interleaved frame equals a single-GPU trace of the whole image
+    if frame_full is not None and args.full:
+        # untimed self-check: the gathered, de-interleaved frame equals a single-GPU trace of the whole image
         whole = torch.empty((ih, iw, rec), dtype=torch.uint8, device=dev)
         whole_packed = torch.empty((ih, iw, prec), dtype=torch.uint8, device=dev)
         world.trace(path[lastf % P], prm, (0, 0, iw, ih), whole.data_ptr(), stream)
@@ -651,15 +717,15 @@ def run(args):
                 "partition": "single" if not multi else f"8-row bands round-robin x{world_size} + RCCL gather of 8-B packed G-buffer records",
                 "ranks_seen": ranks_seen, "devices": devices,
                 "launcher": "self-spawned" if os.environ.get("SVO_BENCH_SPAWNED") else ("external" if "WORLD_SIZE" in os.environ else "single process"),
-                "world_generate_s": round(t_gen, 3), "world_generate_warm_s": round(t_gen_warm, 3), "world_generate_allocator_stall_seen": gen_stalled, "stack_vs_literal_exempt_records": exempt_records,
-                "world_generate": "on the rank's GPU (noise, mips, grow, water fill), pools left in HBM; _s = first call of the process, _warm_s = second", "world_generate_threads": gen_threads, "world_upload_s": round(t_up, 3),
+                "world_generate_s": round(t_gen, 3), "world_generate_warm_s": None if t_gen_warm is None else round(t_gen_warm, 3), "world_generate_allocator_stall_seen": gen_stalled, "stack_vs_literal_exempt_records": exempt_records,
+                "world_generate": "on the rank's GPU (noise, mips, grow, water fill), pools left in HBM; _s = first call of the process, _warm_s = second (--full)", "world_generate_threads": gen_threads, "world_upload_s": round(t_up, 3),
             },
         }
         if single:
             result["single_frame_ms"] = single
         if diag:
             result["diagnostics"] = diag
-        if not multi and not args.emulate_share:
+        if args.full and not multi and not args.emulate_share:
             achieved = roof_bytes / (kernel_ms_sum * 1e-3) / 1e9         # algorithmic bytes of the timed launches / their durations
             algo_total = sum(algo_cam[i % P] for i in range(args.steps))
             prof = {}
@@ -748,6 +814,19 @@ def run(args):
                 dt1 = time.perf_counter() - t0
                 result["cpu_baseline"]["single_thread"] = {"value": round(O.last_rays / dt1 / 1e6, 4), "unit": "Mrays/s", "cores": 1,
                                                            "sample": f"centred {c1}x{c1} crop of the same frame, {O.last_rays} rays, {dt1:.2f} s"}
+        if args.dump_outputs:
+            if multi:
+                if frame_full is None:
+                    raise SystemExit("bench.py: --dump-outputs at N > 1 needs the gather (drop --no-gather)")
+                # the gathered 8-B records, unpacked on the device (t, normal, material and flags round trip bit for bit)
+                packed = frame_full.to(dev).contiguous()
+                unpacked = torch.empty((ih, iw, rec), dtype=torch.uint8, device=dev)
+                svo.gbuffer_unpack(packed.data_ptr(), unpacked.data_ptr(), ih * iw, stream)
+                torch.cuda.synchronize()
+                recs, fields = unpacked.cpu().numpy(), DUMP_FIELDS[:4]
+            else:
+                recs, fields = last_out[last_sub].cpu().numpy(), DUMP_FIELDS
+            dump_outputs(args.dump_outputs, recs.reshape(-1, rec).view(svo.HIT_DTYPE).reshape(-1), fields)
         print(json.dumps(result), flush=True)
 
     world.destroy()

@@ -2,7 +2,7 @@
 # Run bench.py once per variant library on the GPU box (AB_REPS times, variants interleaved: A B A B ...);
 # prints value / ms_per_step per variant and run.
 # usage (on the box): [AB_REPS=2] bash scripts/ab.sh "<bench args>" name1 name2 ...
-args="$1"; shift
+args="$1 --full"; shift
 for rep in $(seq 1 ${AB_REPS:-1}); do
 for name in "$@"; do
   SVO_AMD_LIB=$GRAFT_REPO_ROOT/octree-raymarcher_amd/build/libsvo_$name.so timeout -k 10 300 python bench.py $args --no-cpu-baseline > gpurun_out/ab_$name.json 2> gpurun_out/ab_$name.err || { echo "$name FAILED"; tail -3 gpurun_out/ab_$name.err; continue; }

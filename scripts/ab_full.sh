@@ -1,7 +1,7 @@
 #!/bin/bash
 # Like ab.sh, but prints the single-frame figures of the bench line as well (run without --no-diagnostics for them).
 # usage (on the box): [AB_REPS=2] bash scripts/ab_full.sh "<bench args>" name1 name2 ...
-args="$1"; shift
+args="$1 --full"; shift
 for rep in $(seq 1 ${AB_REPS:-1}); do
 for name in "$@"; do
   SVO_AMD_LIB=$GRAFT_REPO_ROOT/octree-raymarcher_amd/build/libsvo_$name.so timeout -k 10 400 python bench.py $args --no-cpu-baseline > gpurun_out/ab_$name.json 2> gpurun_out/ab_$name.err || { echo "$name FAILED"; tail -3 gpurun_out/ab_$name.err; continue; }

@@ -4,7 +4,7 @@
 set -e
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $R/bench.py --no-cpu-baseline"
+BENCH="python3 $R/bench.py --full --no-cpu-baseline"
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_kt -- $BENCH --steps 48 --warmup 4 > $R/gpurun_out/prof_kt.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_kt_serial -- $BENCH --steps 48 --warmup 4 --streams 1 > $R/gpurun_out/prof_kt_serial.log 2>&1
 P="--steps 4 --warmup 1 --streams 1 --frames-per-launch 1"      # counters per frame: one frame per launch

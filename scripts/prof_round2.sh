@@ -6,7 +6,7 @@ set -e
 R=$GRAFT_REPO_ROOT
 rm -rf $R/gpurun_out/prof_kt $R/gpurun_out/prof_kt_serial $R/gpurun_out/prof_pmc* $R/gpurun_out/prof_calib* $R/gpurun_out/prof_*.log $R/gpurun_out/prof_valu_issue.json
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $R/bench.py --no-cpu-baseline --no-diagnostics"
+BENCH="python3 $R/bench.py --full --no-cpu-baseline --no-diagnostics"
 # the timed command of the round: 32-camera path, 4 frames per launch, 4 launches in flight / serialized
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_kt -- $BENCH --steps 64 --warmup 32 > $R/gpurun_out/prof_kt.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_kt_serial -- $BENCH --steps 64 --warmup 32 --streams 1 > $R/gpurun_out/prof_kt_serial.log 2>&1

@@ -3,5 +3,5 @@
 args="$1"; shift
 for cfg in "$@"; do
   set -- $cfg
-  python bench.py $args --no-diagnostics --no-cpu-baseline --streams $1 --frames-per-launch $2 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('S=$1 F=$2 -> frames per launch', r['frames_per_launch'], 'value', d['value'], 'launch ms', r['kernel_ms_avg'], 'frac', r['frac'])"
+  python bench.py $args --full --no-diagnostics --no-cpu-baseline --streams $1 --frames-per-launch $2 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('S=$1 F=$2 -> frames per launch', r['frames_per_launch'], 'value', d['value'], 'launch ms', r['kernel_ms_avg'], 'frac', r['frac'])"
 done

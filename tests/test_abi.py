@@ -29,14 +29,14 @@ def test_library_exports_every_declared_symbol(svo):
     assert svo.lib.svo_abi_version() == 4
 
 
-def test_struct_layouts_match_the_header(svo):
+def test_struct_layouts_match_the_header(svo, tmp_path):
     assert C.sizeof(svo.ChunkDesc) == 56 and C.sizeof(svo.Camera) == 64 and C.sizeof(svo.TraceParams) == 80
     assert C.sizeof(svo.TerrainParams) == 68 and svo.HIT_DTYPE.itemsize == 32
     # compile a C translation unit against the header and print the same sizes
     src = r'''#include "svo.h"
 #include <stdio.h>
 int main(void){printf("%zu %zu %zu %zu %zu %zu\n",sizeof(svo_chunk_desc),sizeof(svo_camera),sizeof(svo_trace_params),sizeof(svo_terrain_params),sizeof(svo_hit),sizeof(svo_world_info));return 0;}'''
-    exe = "/tmp/svo_abi_sizes"
+    exe = str(tmp_path / "svo_abi_sizes")
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=src, text=True, check=True)
     sizes = [int(x) for x in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
     assert sizes == [C.sizeof(svo.ChunkDesc), C.sizeof(svo.Camera), C.sizeof(svo.TraceParams), C.sizeof(svo.TerrainParams), 32, C.sizeof(svo.WorldInfo)]
@@ -163,20 +163,21 @@ def test_argument_validation_precedes_any_device_work(svo):
     assert P.eps == np.float32(1 / 8192) and P.near_plane == 0.125 and P.far_plane == 8192.0
 
 
-def test_stack_kernel_register_budget():
+def test_stack_kernel_register_budget(tmp_path):
     """The stack kernel is budgeted for six waves per SIMD (+9 %): hipcc must fit every instantiation
     into 80 VGPRs, and the hand-written step (csrc/step_asm.hip.h, one asm statement) must be what it compiles - a change that
     silently drops the kernel to five waves, or the build to the C++ step, fails here, on the CPU (hipcc cross-compiles)."""
     import re
     pkg = os.path.join(ROOT, "octree-raymarcher_amd")
+    audit = str(tmp_path / "svo_device_audit.s")
     r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math",
-                        "-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage", "-S", "--cuda-device-only", "-o", "/tmp/svo_device_audit.s",
+                        "-fno-slp-vectorize", "-Rpass-analysis=kernel-resource-usage", "-S", "--cuda-device-only", "-o", audit,
                         os.path.join(pkg, "csrc", "device.hip")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     blocks = re.findall(r"Function Name: (\S*k_trace_stack\S*).*?VGPRs: (\d+).*?Occupancy \[waves/SIMD\]: (\d+)", r.stderr, re.S)
     assert len(blocks) >= 4, "one instantiation per wide-level count"
     for name, vgprs, occ in blocks:
         assert int(vgprs) <= 80 and int(occ) >= 6, (name, vgprs, occ)
-    asm = open("/tmp/svo_device_audit.s").read()
+    asm = open(audit).read()
     body = asm[asm.index("k_trace_stackILi10E"):]
     assert "v_cmpx_ge_f32" in body and ";;#ASMSTART" in body, "the hand-scheduled step is compiled in"
