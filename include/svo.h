@@ -26,6 +26,9 @@
  *   svo_world_shift      <- World::shift                           src/World.cpp:334-378
  *   svo_world_edit_box   <- Ocroot::build / destroy / replace + World::modify   src/Octree.cpp:203-443, src/World.cpp:268-274
  *                           (the caller's pattern: src/Main.cpp:340-367)
+ *   svo_world_compact    <- Ocroot::defragcopy + World::modify(realloc)   src/Octree.cpp:445-614, src/World.cpp:268-274
+ *   svo_world_coarsen    <- Ocroot::lodmm + World::modify(realloc)        src/Octree.cpp:626-765, src/MisraGries.h
+ *                           (the caller's pattern: key 'g', src/Main.cpp:438-448)
  *   svo_shade(_packed)   <- lighting of fragment main               shaders/World.Fragment.glsl:63-138,180-197
  *
  * Conventions
@@ -41,8 +44,8 @@
  *   - svo_trace* launches of one world may overlap on different streams (frames in flight); each
  *     launch owns a private work-cursor slot from a 64-entry ring, and a launch that comes round
  *     to a slot still in use is ordered on the device behind that earlier launch;
- *   - svo_world_update / svo_world_shift / svo_world_edit_box / svo_world_upload are ordered behind every launch issued
- *     before them on any stream (they drain the device before touching HBM, as World::modify is
+ *   - svo_world_update / svo_world_shift / svo_world_edit_box / svo_world_compact / svo_world_coarsen / svo_world_upload
+ *     are ordered behind every launch issued before them on any stream (they drain the device before touching HBM, as World::modify is
  *     ordered on the GL queue) and have completed when they return: launches issued afterwards see
  *     the new world, launches issued before saw the old one, none sees a mixture.
  *
@@ -64,7 +67,8 @@ extern "C" {
 
 #define SVO_ABI_VERSION 4           /* 2: svo_trace_params.normal_mode, SVO_FACE_NORMAL, error bit in the packed record
                                        3: svo_trace_params.tile_cost_dev / tile_order_dev, svo_tile_order
-                                       4: SVO_OK_LITERAL_ONLY, svo_device_cache_trim, svo_trace_params.semantics */
+                                       4: SVO_OK_LITERAL_ONLY, svo_device_cache_trim, svo_trace_params.semantics;
+                                          4 later gained svo_world_compact and svo_world_coarsen (functions added, nothing changed) */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -301,6 +305,20 @@ int svo_world_shift(svo_world *, const int offset[3]);
  * SVO_ERR_NOT_UPLOADED on a world that is not resident. */
 enum { SVO_EDIT_BUILD = 0, SVO_EDIT_DESTROY = 1, SVO_EDIT_REPLACE = 2 };
 int svo_world_edit_box(svo_world *, int chunk, int op, const float lo[3], const float hi[3], uint16_t material);
+
+/* Ocroot::defragcopy (src/Octree.cpp:445-614) followed by World::modify with realloc (src/World.cpp:268-274) on chunk `chunk`:
+ * the chunk is rebuilt from its root into fresh pools - depth-first, root at 0, blocks at 1 + 8k - so that what no BRANCH reaches
+ * (blocks and bricks that edits left behind) is gone, a brick of one value becomes an EMPTY / LEAF node, a BRANCH of eight equal
+ * EMPTY / LEAF children becomes that node, and a BRANCH over two levels of EMPTY / LEAF nodes becomes one brick.  The pools
+ * equal, index for index, what the reference's recursion leaves; the chunk's storage capacities do not shrink.
+ * On an uploaded world it runs on the device the pools live on (nothing visits the host; a host copy is made again on request,
+ * svo_world_chunk), otherwise on the host pools.  SVO_OK, or SVO_OK_LITERAL_ONLY as for svo_world_edit_box. */
+int svo_world_compact(svo_world *, int chunk);
+/* Ocroot::lodmm (src/Octree.cpp:626-765) followed by World::modify with realloc: chunk `chunk` one level coarser, depth ->
+ * depth - 1 (position and size unchanged).  Every BRANCH at level depth-3 becomes a brick whose cells are the majority
+ * (MisraGriesCounter<8>, src/MisraGries.h) of the 8 cells under each; BRANCHes above it are kept, every other node is compacted as
+ * by svo_world_compact.  SVO_ERR_UNSUPPORTED on a chunk of depth 2 (nothing changes); host / device as svo_world_compact. */
+int svo_world_coarsen(svo_world *, int chunk);
 
 /* ---- the hot path ------------------------------------------------------------------------ */
 

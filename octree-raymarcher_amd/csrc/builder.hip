@@ -740,11 +740,30 @@ struct BuilderContext {
     DeviceFiller filler;
     DevBuf<uint32_t> edit_tree;
     DevBuf<uint16_t> edit_twig;
+    std::vector<DevBuf<uint8_t>> sweep;     // compact.hip's level arrays
 };
 static BuilderContext &builder_context(svo_world &w)
 {
     if (!w.builder_ctx) w.builder_ctx = new BuilderContext();
     return *static_cast<BuilderContext *>(w.builder_ctx);
+}
+int edit_scratch(svo_world &w, uint64_t trees, uint64_t twigs, uint32_t **tree, uint16_t **twig)
+{
+    BuilderContext &ctx = builder_context(w);
+    int rc;
+    if ((rc = ctx.edit_tree.reserve(std::max<uint64_t>(trees, 1), false, nullptr)) != SVO_OK ||
+        (rc = ctx.edit_twig.reserve(std::max<uint64_t>(twigs, 1) * TWIG_WORDS, false, nullptr)) != SVO_OK) return rc;
+    *tree = ctx.edit_tree.p; *twig = ctx.edit_twig.p;
+    return SVO_OK;
+}
+int sweep_scratch(svo_world &w, uint32_t k, size_t bytes, void **out)
+{
+    BuilderContext &ctx = builder_context(w);
+    if (ctx.sweep.size() <= k) ctx.sweep.resize(k + 1);
+    const int rc = ctx.sweep[k].reserve(std::max<size_t>(bytes, 16), false, nullptr);
+    if (rc != SVO_OK) return rc;
+    *out = ctx.sweep[k].p;
+    return SVO_OK;
 }
 void free_builder_context(svo_world &w)
 {

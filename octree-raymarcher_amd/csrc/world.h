@@ -72,4 +72,10 @@ void free_builder_context(svo_world &w);
 int  edit_box_resident(svo_world &w, int chunk, int op, const float lo[3], const float hi[3], uint32_t material);
 // builder.hip: World::shift's entering plane generated on the device the world is uploaded to
 int  shift_world_resident(svo_world &w, int axis, int sign);
+// builder.hip: the working buffers svo_world_edit_box keeps between calls, lent to compact.hip - the edit's output pools (grown to
+// `trees` node words and `twigs` bricks) and numbered sweep arrays (array k grown to `bytes`)
+int  edit_scratch(svo_world &w, uint64_t trees, uint64_t twigs, uint32_t **tree, uint16_t **twig);
+int  sweep_scratch(svo_world &w, uint32_t k, size_t bytes, void **out);
+// compact.hip: Ocroot::defragcopy (lod = false) or Ocroot::lodmm (lod = true) + World::modify on an uploaded world
+int  rebuild_resident(svo_world &w, int chunk, bool lod);
 } // namespace svo
