@@ -19,15 +19,11 @@
         //      returns false, src/Traverse.cpp:97-105): quadratically many steps.  A lane that has just entered a brick
         //      with a creeping history asks whether the whole run of tree steps over this node consists of such misses
         //      (brick_layer_first_touch bounds how far they can go); that run is taken at once, exactly like a run over an EMPTY node.
-        if (__ballot(creepn > 0 || creepn <= -4 * SVO_CREEP_SERIOUS) != 0ull) {      // (what cr and ent below need; most passes: nobody)
+        if (__ballot(creepn > 0 || creepn <= -4 * CREEP_SERIOUS) != 0ull) {      // (what cr and ent below need; most passes: nobody)
             const bool cr = creepn > 0 && (mode == M_TREE || mode == M_TWIG);
-#ifdef SVO_NO_NEST
-            const bool ent = false;
-#else
-            const bool ent = mode == M_TWIG && cnt == A.cap_twig && t == 0.0f && creepn <= -4 * SVO_CREEP_SERIOUS;     // fresh in a brick after a long creep
-#endif
+            const bool ent = mode == M_TWIG && cnt == A.cap_twig && t == 0.0f && creepn <= -4 * CREEP_SERIOUS;     // fresh in a brick after a long creep
             const unsigned long long crm = __ballot(cr);
-            if (eps_pow2 && (__ballot(ent) != 0ull || (crm != 0ull && (__ballot(cr && creepn >= SVO_CREEP_SERIOUS) != 0ull || __popcll(crm) >= SVO_CREEP_LANES)))) {
+            if (eps_pow2 && (__ballot(ent) != 0ull || (crm != 0ull && (__ballot(cr && creepn >= CREEP_SERIOUS) != 0ull || __popcll(crm) >= CREEP_LANES)))) {
                 const bool twig = mode == M_TWIG && !ent;           // closed form inside a brick cell
                 const float Bsize = mode == M_TWIG ? res * 4.0f : csize, inv_res = recip_pow2(res);
                 const float finite_max = __uint_as_float(0x7F7FFFFFu);
@@ -133,16 +129,10 @@
                         bsize = csize;
 #endif
                         mode = M_TREE;
-#ifdef SVO_STACK_TIMING
-                        n_creep_steps += K;
-#endif
                     }
                 } else if (K > 0) {
                     t += (float)K * eps;                            // == K times t + (escape + EPS) with escape == -0
                     cnt -= K; guard += (uint32_t)K; creepn += K;
-#ifdef SVO_STACK_TIMING
-                    n_creep_steps += K;
-#endif
                 }
 #ifdef SVO_STACK_TIMING
                 for (int sh8 = 0; sh8 < 32; sh8 += 8) n_dbg += (unsigned)__popcll(__ballot((n_dbg_e >> sh8) & 1u)) << sh8;

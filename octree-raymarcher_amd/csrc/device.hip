@@ -22,13 +22,6 @@
 #include <string>
 #include <vector>
 
-#ifndef SVO_STACK_REFILL
-#define SVO_STACK_REFILL 8       // retired lanes per wave that trigger a refill (cheap: rays are staged in LDS)
-#endif
-#ifndef SVO_STACK_WAVES
-#define SVO_STACK_WAVES 6        // waves per SIMD the stack kernel is register-budgeted for: 80 VGPRs (the asm step holds 63; spills sit in the rare blocks)
-#endif
-
 #include "kernel_literal.hip.h"
 #include "kernel_stack.hip.h"
 #include "wide_tree.hip.h"
@@ -180,37 +173,6 @@ int release_device(svo_world &w)
     return SVO_OK;
 }
 
-// Persistent grid = the waves the kernel can keep resident (occupancy query), never more than tiles / tiles_per_wave.
-template <int MAXLV, bool BIG, bool GLSL>
-static int launch_stack_as(svo_world *w, const TraceArgs &A, int tiles_per_wave, int in_flight, hipStream_t s)
-{
-    auto kernel = k_trace_stack<MAXLV, SVO_STACK_REFILL, SVO_STACK_WAVES, BIG, GLSL>;
-    if (w->occupancy_blocks <= 0) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, w->device) != hipSuccess) return SVO_ERR_HIP;
-        int per_cu = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, 0) != hipSuccess || per_cu <= 0) per_cu = 16;
-        w->occupancy_blocks = prop.multiProcessorCount * per_cu;
-#ifdef SVO_TEST_HOOKS
-        if (const char *cap = std::getenv("SVO_GRID_WAVES_PER_CU")) { const int c = std::atoi(cap); if (c > 0) w->occupancy_blocks = prop.multiProcessorCount * std::min(c, per_cu); }     // experiments (scripts/sweep_grid.sh)
-#endif
-    }
-    const int64_t per_wave = tiles_per_wave > 1 ? tiles_per_wave : 1;
-    const int64_t tiles = (int64_t)A.ntiles * (A.nframes > 0 ? A.nframes : 1);
-    // launches the caller keeps in flight share the wave slots: 2/n each (include/svo.h, svo_trace_params.launches_in_flight)
-    const int64_t slots = in_flight >= 2 ? std::max<int64_t>(1, (int64_t)w->occupancy_blocks * 2 / in_flight) : w->occupancy_blocks;
-    const int blocks = (int)std::min<int64_t>((tiles + per_wave - 1) / per_wave, slots);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), 0, s, A);
-    return SVO_OK;
-}
-
-template <int MAXLV, bool BIG>
-static int launch_stack(svo_world *w, const TraceArgs &A, int tiles_per_wave, int in_flight, hipStream_t s)
-{
-    return A.glsl ? launch_stack_as<MAXLV, BIG, true>(w, A, tiles_per_wave, in_flight, s) : launch_stack_as<MAXLV, BIG, false>(w, A, tiles_per_wave, in_flight, s);
-}
-
-
 } // namespace svo
 
 extern "C" {
@@ -297,7 +259,7 @@ int alloc_pools(svo_world &w, int device)
         hipMemset(w.d_mask, 0, w.twig_pool_cap * sizeof(uint64_t)) != hipSuccess ||
         hipMemset(w.d_bmat, 0, w.twig_pool_cap * sizeof(uint16_t)) != hipSuccess ||
         hipMemset(w.d_work, 0, WORK_SLOTS * WORK_SLOT_WORDS * sizeof(unsigned long long)) != hipSuccess) { set_error("svo_world_upload: hipMemset failed"); return SVO_ERR_HIP; }
-    w.occupancy_blocks = 0;
+    std::fill(std::begin(w.stack_blocks), std::end(w.stack_blocks), 0);
     w.wide_ok = false;                                                  // until build_wide_all has run
     return SVO_OK;
 }
@@ -800,6 +762,22 @@ int install_resident_chunk(svo_world &w, int chunk, const ChunkPools &meta, cons
     return rc == SVO_OK ? SVO_OK : SVO_OK_LITERAL_ONLY;
 }
 
+// k_trace_stack's instantiations, by depth class, GLSL before CPU semantics: the large-world instantiation (BIG: 64-bit wide-tree and mask
+// addresses, where 32-bit offsets do not reach) in two depth classes - a world that large is built of deep chunks -, the default one in four
+constexpr int STACK_REFILL = 8;         // retired lanes per wave that trigger a refill (cheap: rays are staged in LDS)
+constexpr int STACK_WAVES = 6;          // waves per SIMD the stack kernel is register-budgeted for: 80 VGPRs (the asm step holds 63; spills sit in the rare blocks)
+using StackKernel = void (*)(TraceArgs);
+template <int MAXLV, bool BIG, bool GLSL> constexpr StackKernel stack_kernel = k_trace_stack<MAXLV, STACK_REFILL, STACK_WAVES, BIG, GLSL>;
+static const StackKernel STACK_KERNELS[] = {
+    stack_kernel<10, true, true>, stack_kernel<10, true, false>,
+    stack_kernel<22, true, true>, stack_kernel<22, true, false>,
+    stack_kernel<6, false, true>, stack_kernel<6, false, false>,
+    stack_kernel<10, false, true>, stack_kernel<10, false, false>,
+    stack_kernel<16, false, true>, stack_kernel<16, false, false>,
+    stack_kernel<22, false, true>, stack_kernel<22, false, false>,
+};
+static_assert(sizeof(STACK_KERNELS) / sizeof(StackKernel) == sizeof(svo_world::stack_blocks) / sizeof(int), "one grid size per instantiation");
+
 } // namespace svo
 
 extern "C" {
@@ -879,6 +857,34 @@ static int pick_kernel(const svo_world *w, const svo_trace_params *prm, const Tr
     return (stack_ok && !A.counters) ? SVO_KERNEL_STACK : SVO_KERNEL_LITERAL;
 }
 
+// Persistent grid = the waves the instantiation can keep resident (occupancy query, once per world and instantiation: they differ in
+// LDS), never more than tiles / tiles_per_wave.
+static int launch_stack(svo_world *w, const TraceArgs &A, int tiles_per_wave, int in_flight, hipStream_t s)
+{
+    const int lv = w->max_levels;
+    const int depth = stack_needs_big(w) ? (lv <= 10 ? 0 : 1) : lv <= 6 ? 2 : lv <= 10 ? 3 : lv <= 16 ? 4 : 5;
+    const int which = 2 * depth + (A.glsl ? 0 : 1);
+    const StackKernel kernel = STACK_KERNELS[which];
+    int &resident = w->stack_blocks[which];
+    if (resident <= 0) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, w->device) != hipSuccess) return SVO_ERR_HIP;
+        int per_cu = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, 0) != hipSuccess || per_cu <= 0) per_cu = 16;
+        resident = prop.multiProcessorCount * per_cu;
+#ifdef SVO_TEST_HOOKS
+        if (const char *cap = std::getenv("SVO_GRID_WAVES_PER_CU")) { const int c = std::atoi(cap); if (c > 0) resident = prop.multiProcessorCount * std::min(c, per_cu); }     // experiments (scripts/sweep_grid.sh)
+#endif
+    }
+    const int64_t per_wave = tiles_per_wave > 1 ? tiles_per_wave : 1;
+    const int64_t tiles = (int64_t)A.ntiles * (A.nframes > 0 ? A.nframes : 1);
+    // launches the caller keeps in flight share the wave slots: 2/n each (include/svo.h, svo_trace_params.launches_in_flight)
+    const int64_t slots = in_flight >= 2 ? std::max<int64_t>(1, (int64_t)resident * 2 / in_flight) : resident;
+    const int blocks = (int)std::min<int64_t>((tiles + per_wave - 1) / per_wave, slots);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), 0, s, A);
+    return SVO_OK;
+}
+
 static int launch(svo_world *w, const svo_trace_params *prm, TraceArgs &A, hipStream_t s)
 {
     const int kernel = pick_kernel(w, prm, A);
@@ -902,15 +908,7 @@ static int launch(svo_world *w, const svo_trace_params *prm, TraceArgs &A, hipSt
     } else {
         if (A.ntiles > (1 << 25)) { set_error("svo_trace: more than 2^31 rays in one stack-kernel launch"); return SVO_ERR_UNSUPPORTED; }
         if (A.tile_cost) HIP_TRY(hipMemsetAsync(A.tile_cost, 0, (size_t)A.ntiles * (size_t)(A.from_camera ? A.nframes : 1) * 2 * sizeof(uint32_t), s));
-        int rc;
-        const int tpw = prm ? prm->tiles_per_wave : 0, nfl = prm ? prm->launches_in_flight : 0;
-        // the large-world instantiation (64-bit wide-tree and mask addresses) where 32-bit offsets do not reach: two depth classes
-        // of it are compiled (a world that large is built of deep chunks)
-        if (stack_needs_big(w)) rc = w->max_levels <= 10 ? launch_stack<10, true>(w, A, tpw, nfl, s) : launch_stack<22, true>(w, A, tpw, nfl, s);
-        else if (w->max_levels <= 6) rc = launch_stack<6, false>(w, A, tpw, nfl, s);
-        else if (w->max_levels <= 10) rc = launch_stack<10, false>(w, A, tpw, nfl, s);
-        else if (w->max_levels <= 16) rc = launch_stack<16, false>(w, A, tpw, nfl, s);
-        else rc = launch_stack<22, false>(w, A, tpw, nfl, s);
+        const int rc = launch_stack(w, A, prm ? prm->tiles_per_wave : 0, prm ? prm->launches_in_flight : 0, s);
         if (rc != SVO_OK) { set_error("svo_trace: device query failed"); return rc; }
     }
     HIP_TRY(hipGetLastError());

@@ -52,8 +52,6 @@
 // integer bookkeeping differ.  Divisions by powers of two (chunk edge, node edge) are written as
 // multiplications by the exact reciprocal, which is bit-identical.
 #pragma once
-#include <type_traits>
-
 #include "march.hip.h"
 #include "step_asm.hip.h"
 
@@ -62,49 +60,29 @@ namespace svo {
 constexpr int CW_ESCAPE_PENDING = (int)0x80000000;    // bit of the lane's chunk-step counter: tw still lacks the escape out of the chunk just left
 enum : int { M_DONE = 0, M_WORLD = 1, M_HIT = 2, M_TREE = 3, M_TWIG = 4 };     // (step_asm.hip.h: marching = mode > 2)
 
-#ifndef SVO_VOTE_WORLD
-#define SVO_VOTE_WORLD 8         // lanes waiting for a chunk step that make the wave run it
-#endif
-#ifndef SVO_VOTE_HIT
-#define SVO_VOTE_HIT 16          // primary hits waiting for their G-buffer record
-#endif
-#ifndef SVO_VOTE_BUSY
-#define SVO_VOTE_BUSY 24         // fewer marching lanes than this: serve the waiting ones regardless
-#endif
-// Creeping rays (see the creep block in the kernel): a lane whose last SVO_CREEP_SERIOUS steps all advanced by ~EPS makes
-// the wave run the creep block; SVO_CREEP_LANES creeping lanes do so at once.
-#ifndef SVO_CREEP_SERIOUS
-#define SVO_CREEP_SERIOUS 6
-#endif
-#ifndef SVO_CREEP_LANES
-#define SVO_CREEP_LANES 8
-#endif
-// the step runs up to 1 + SVO_STEP_EXTRA times per pass of the outer loop while at least SVO_STEP_LANES lanes are marching
+// Vote thresholds of the rare blocks (DESIGN.md §6 swept them)
+constexpr int VOTE_WORLD = 8;           // lanes waiting for a chunk step that make the wave run it
+constexpr int VOTE_HIT = 16;            // primary hits waiting for their G-buffer record
+constexpr int VOTE_BUSY = 24;           // fewer marching lanes than this: serve the waiting ones regardless
+// Creeping rays (see the creep block in the kernel): a lane whose last CREEP_SERIOUS steps all advanced by ~EPS makes
+// the wave run the creep block; CREEP_LANES creeping lanes do so at once.
+constexpr int CREEP_SERIOUS = 6;
+constexpr int CREEP_LANES = 8;
 // Block placement: a taken branch costs a shared SIMD about three vector instructions' time, a not-taken one about one
 // (scripts/microbench/valu_issue.hip) - rare blocks go out of line so that the common path falls through.
-#ifdef SVO_NO_EXPECT
-#define SVO_LIKELY(x) (x)
-#define SVO_UNLIKELY(x) (x)
-#else
 #define SVO_LIKELY(x) __builtin_expect(!!(x), 1)
 #define SVO_UNLIKELY(x) __builtin_expect(!!(x), 0)
-#endif
-#ifndef SVO_STEP_EXTRA
-#define SVO_STEP_EXTRA 4
-#endif
+// the step runs up to 1 + STEP_EXTRA times per pass of the outer loop while at least STEP_LANES lanes are marching
+constexpr int STEP_EXTRA = 4;
+constexpr int STEP_LANES = 8;
 // steps per statement while the inner repeat lasts (the drain of a launch: the wave is alone on its SIMD, every instruction of the
 // loop control around the statement costs it ~5 cycles)
-#ifndef SVO_DRAIN_STEPS
-#define SVO_DRAIN_STEPS 8        // (round 4: 8 instead of 4 - one frame 1.62 - 1.63 ms against 1.655 - 1.659, the serialized 16-frame launch 8.79 against 8.91 - 8.99 ms; 16: the same as 8, 2: as 4)
-#endif
+constexpr int DRAIN_STEPS = 8;          // (round 4: 8 instead of 4 - one frame 1.62 - 1.63 ms against 1.655 - 1.659, the serialized 16-frame launch 8.79 against 8.91 - 8.99 ms; 16: the same as 8, 2: as 4)
 // when a wave skips the bricks whose march is bound to miss (step_asm_body.inc, "sure"): the test is ~95 instructions for every wave-step
 // in which some lane enters a brick, so a wave of the bulk would pay more than its lanes win; a draining wave's instructions are its
 // critical path and the test runs while the brick's mask is on its way
 #ifndef SVO_SURE_MISS_WHEN
 #define SVO_SURE_MISS_WHEN __builtin_amdgcn_readfirstlane(more ? 0 : 1)
-#endif
-#ifndef SVO_STEP_LANES
-#define SVO_STEP_LANES 8
 #endif
 
 // 1/x for x an exact power of two (normal range): exponent negation, no division sequence.
@@ -211,10 +189,7 @@ __device__ __forceinline__ FrameCam camera_reloaded(int f)
 // Returns the smallest s at which the ray, widened by r/16 (>> the rounding of p, checked), touches an occupied cell of
 // that layer: +inf if it never does, -1 if a precondition fails.  Marches that stay below that parameter are misses,
 // however they end (leaving the brick, step cap, NaN).  r = voxel edge.
-#ifndef SVO_NEST_INLINE
-#define SVO_NEST_INLINE __noinline__
-#endif
-__device__ SVO_NEST_INLINE float brick_layer_first_touch(int k, V3 a, V3 b, V3 g, V3 bmin, float r, unsigned long long mask)
+__device__ __noinline__ float brick_layer_first_touch(int k, V3 a, V3 b, V3 g, V3 bmin, float r, unsigned long long mask)
 {
     // axis k is the pinned one; u, v = the other two (component selection by k, no indexed arrays)
     const float ak = k == 0 ? a.x : k == 1 ? a.y : a.z, bk = k == 0 ? b.x : k == 1 ? b.y : b.z, mk_ = k == 0 ? bmin.x : k == 1 ? bmin.y : bmin.z;
@@ -263,7 +238,7 @@ __device__ __forceinline__ void note_tile_cost(int outk, uint32_t steps)
 }
 
 // BIG: the large-world instantiation - the chunk's wide tree is a 64-bit address per lane and the brick masks are addressed with
-// 64 bits (step_asm.hip.h: march_steps_asm_big), for wide pools of 4 GiB and more and mask pools of 2^29 bricks and more; the same
+// 64 bits (step_asm.hip.h: march_steps_asm<true, GLSL>), for wide pools of 4 GiB and more and mask pools of 2^29 bricks and more; the same
 // kernel otherwise, the same results.
 // GLSL: the shader twin's march (svo_trace_params.semantics = SVO_SEMANTICS_GLSL; shaders/Chunkmarch.glsl): the guarded escape
 // distance and the LEAF hit at t inside the step (step_asm.hip.h), the entry condition and the missing containment re-check here.
@@ -283,11 +258,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
     const int lane = threadIdx.x;
     const bool want_cost = A.tile_cost != nullptr;      // (one SGPR held; the blocks below must not re-read the kernel arguments for a feature that is off)
     const int n_chunks = A.dimw * A.dimh * A.dimd;
-#ifdef SVO_NO_LDS_CHUNK_TAB      // experiment (scripts/build_variants.sh): what the chunk table costs once it has left LDS (worlds of more than CHUNK_TAB chunks)
-    const bool chunks_in_lds = false;
-#else
     const bool chunks_in_lds = n_chunks <= CHUNK_TAB;
-#endif
     if (chunks_in_lds)
         for (int i = lane; i < n_chunks; i += 64) {
             const DevWide ch = A.wchunks[i];
@@ -301,10 +272,10 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
     unsigned n_world_runs = 0, n_hit_runs = 0, n_refill = 0, n_tilegen = 0, n_fix = 0;
     unsigned n_lane_twig = 0;
     unsigned n_lane_busy = 0;       // per lane: asm steps it entered a statement for as a marching lane; the wave's maximum is its critical path
-    unsigned n_creep_runs = 0, n_creep_steps = 0, n_creep_rounds = 0, n_dbg = 0;   // block runs, lane-steps taken in it (this lane), rounds
-    StepStats step_stats;
+    unsigned n_creep_runs = 0, n_creep_rounds = 0, n_dbg = 0;   // block runs, rounds
     unsigned n_wsteps = 0, n_lsteps = 0, n_hit_wait = 0, n_dead_wait = 0, n_wsteps_b = 0, n_lsteps_b = 0, n_world_wait = 0, n_twig_b = 0;   // step bodies executed, marching lanes summed over them; M_HIT / M_DONE lanes summed over them
 #endif
+    [[maybe_unused]] StepStats step_stats;      // the asm step's own counters (the timing build's; the others leave them untouched)
 
     const V3 wlo = ld3(A.worldmin), whi = ld3(A.worldmax);
     const V3 sdir = ld3(A.sdir);
@@ -347,7 +318,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
     int it_saved = 0;
     // chunk
     V3 clo = mk(0, 0, 0);
-    typename std::conditional<BIG, unsigned long long, uint32_t>::type wide_b = 0;   // the chunk's top wide node: byte offset into the wide pool (BIG: its address)
+    WideRef<BIG> wide_b = 0;        // the chunk's top wide node: byte offset into the wide pool (BIG: its address)
     // entry `e` (64 per wide node, counted from the chunk's top wide node) of the current chunk's wide tree
     auto ld_wide = [&](uint32_t e) -> uint32_t {
         if constexpr (BIG) return *reinterpret_cast<const uint32_t *>((size_t)wide_b + ((size_t)e << 2));
@@ -366,7 +337,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
     int nw_chunk = 1;
     const uint32_t lds_lane = (uint32_t)(size_t)(__attribute__((address_space(3))) uint32_t *)&stk[0][lane];
     StepUniform SU;
-    SU.csize = csize; SU.eps = eps; SU.eps2 = 2.0f * eps; SU.cap_twig = A.cap_twig; SU.wide = A.wide; SU.mask = A.mask; SU.descend_shift = MAXLV <= 10 ? SVO_DESCEND_SHIFT_SHALLOW : SVO_DESCEND_SHIFT_DEEP;
+    SU.csize = csize; SU.eps = eps; SU.eps2 = 2.0f * eps; SU.cap_twig = A.cap_twig; SU.wide = A.wide; SU.mask = A.mask; SU.descend_shift = MAXLV <= 10 ? DESCEND_SHIFT_SHALLOW : DESCEND_SHIFT_DEEP;
 #endif
     // creeping rays: |creepn| = consecutive advances of this ray by less than 2 EPS (kept across level changes: a ray pinned
     // on a chunk face creeps at every level); > 0 only while the cell located last is known to be empty (creep block armed)
@@ -487,9 +458,9 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
         const int n_busy = __popcll(__ballot(mode == M_TREE || mode == M_TWIG));
         const int n_world = __popcll(__ballot(mode == M_WORLD));
         const int n_hit = __popcll(__ballot(mode == M_HIT));
-        const bool run_world = n_world > 0 && (n_world >= SVO_VOTE_WORLD || n_busy < SVO_VOTE_BUSY ||
-                                               __ballot(mode == M_WORLD && creepn <= -SVO_CREEP_SERIOUS) != 0ull);
-        const bool run_hit = n_hit > 0 && (n_hit >= SVO_VOTE_HIT || n_busy < SVO_VOTE_BUSY);
+        const bool run_world = n_world > 0 && (n_world >= VOTE_WORLD || n_busy < VOTE_BUSY ||
+                                               __ballot(mode == M_WORLD && creepn <= -CREEP_SERIOUS) != 0ull);
+        const bool run_hit = n_hit > 0 && (n_hit >= VOTE_HIT || n_busy < VOTE_BUSY);
 
         if (SVO_UNLIKELY(mode != M_DONE && mode != M_HIT && ++guard > STEP_GUARD)) {     // runaway ray: give up, flag it
             if (outk < 0) store_flags(A.out, outk & 0x7FFFFFFF, SVO_HIT_FLAG | SVO_SHADOW_TRACED | SVO_ERR_FLAG | (A.normal_mode == SVO_NORMAL_FACE ? (uint32_t)SVO_FACE_NORMAL : 0u));
@@ -565,36 +536,20 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
         //      wave is marching and nothing else can be due: that is the state of the waves that carry a launch's longest
         //      rays after the tile cursors ran dry, alone on their SIMD and bound by their own instruction stream.
         int pass = 0;
-        // in the bulk: SVO_STEP_EXTRA more steps, decided once per pass of the outer loop (n_busy: before the chunk step)
-        const int fixed_steps = (n_busy >= SVO_STEP_LANES && __ballot(creepn > 0 || creepn <= -4 * SVO_CREEP_SERIOUS) == 0ull) ? SVO_STEP_EXTRA : 0;
+        // in the bulk: STEP_EXTRA more steps, decided once per pass of the outer loop (n_busy: before the chunk step)
+        const int fixed_steps = (n_busy >= STEP_LANES && __ballot(creepn > 0 || creepn <= -4 * CREEP_SERIOUS) == 0ull) ? STEP_EXTRA : 0;
         for (;;) {
 #ifdef SVO_STACK_TIMING
-        n_lane_twig += mode == M_TWIG ? (pass == 0 ? 1u + (unsigned)fixed_steps : (unsigned)SVO_DRAIN_STEPS) : 0u;        // ... of them started inside a brick
-        n_lane_busy += (mode == M_TREE || mode == M_TWIG) ? (pass == 0 ? 1u + (unsigned)fixed_steps : (unsigned)SVO_DRAIN_STEPS) : 0u;     // steps of the coming statement this lane starts as a marching lane (an upper bound on its own steps)
+        n_lane_twig += mode == M_TWIG ? (pass == 0 ? 1u + (unsigned)fixed_steps : (unsigned)DRAIN_STEPS) : 0u;        // ... of them started inside a brick
+        n_lane_busy += (mode == M_TREE || mode == M_TWIG) ? (pass == 0 ? 1u + (unsigned)fixed_steps : (unsigned)DRAIN_STEPS) : 0u;     // steps of the coming statement this lane starts as a marching lane (an upper bound on its own steps)
         { const int nm = __popcll(__ballot(mode == M_TREE || mode == M_TWIG)); n_wsteps += nm > 0; n_lsteps += nm; if (more) { n_wsteps_b += nm > 0; n_lsteps_b += nm; n_hit_wait += __popcll(__ballot(mode == M_HIT)); n_dead_wait += __popcll(__ballot(mode == M_DONE)); n_world_wait += __popcll(__ballot(mode == M_WORLD)); n_twig_b += __popcll(__ballot(mode == M_TWIG)); } }
 #endif
 #ifndef SVO_CXX_STEP
         // (step_asm.hip.h) the steps of this pass in one statement: 1 + fixed_steps at first, single steps while the inner repeat lasts
-        const int nsteps = pass == 0 ? 1 + fixed_steps : SVO_DRAIN_STEPS;
+        const int nsteps = pass == 0 ? 1 + fixed_steps : DRAIN_STEPS;
         const int sure_miss = SVO_SURE_MISS_WHEN;      // (step_asm_body.inc: bricks whose march is bound to miss are not entered)
-#ifdef SVO_STACK_TIMING
-#define SVO_STEP_STATS_ARG , step_stats
-#else
-#define SVO_STEP_STATS_ARG
-#endif
-        if constexpr (BIG && GLSL)
-            march_steps_asm_big_glsl(mode, O, Blo, bsize, res, t, cnt, tt_saved, t_miss, it_saved, tw, cw, pux, puy, puz, valid, plev, bmask, creepn,
-                                     beta, g, clo, alpha, levels, nw_chunk, res_tree, wide_b, twig_off, lds_lane, SU, nsteps | (sure_miss << 16) SVO_STEP_STATS_ARG);
-        else if constexpr (GLSL)
-            march_steps_asm_glsl(mode, O, Blo, bsize, res, t, cnt, tt_saved, t_miss, it_saved, tw, cw, pux, puy, puz, valid, plev, bmask, creepn,
-                                 beta, g, clo, alpha, levels, nw_chunk, res_tree, wide_b, twig_off, lds_lane, SU, nsteps | (sure_miss << 16) SVO_STEP_STATS_ARG);
-        else if constexpr (BIG)
-            march_steps_asm_big(mode, O, Blo, bsize, res, t, cnt, tt_saved, t_miss, it_saved, tw, cw, pux, puy, puz, valid, plev, bmask, creepn,
-                                beta, g, clo, alpha, levels, nw_chunk, res_tree, wide_b, twig_off, lds_lane, SU, nsteps | (sure_miss << 16) SVO_STEP_STATS_ARG);
-        else
-            march_steps_asm(mode, O, Blo, bsize, res, t, cnt, tt_saved, t_miss, it_saved, tw, cw, pux, puy, puz, valid, plev, bmask, creepn,
-                            beta, g, clo, alpha, levels, nw_chunk, res_tree, wide_b, twig_off, lds_lane, SU, nsteps | (sure_miss << 16) SVO_STEP_STATS_ARG);
-#undef SVO_STEP_STATS_ARG
+        march_steps_asm<BIG, GLSL>(mode, O, Blo, bsize, res, t, cnt, tt_saved, t_miss, it_saved, tw, cw, pux, puy, puz, valid, plev, bmask, creepn,
+                                   beta, g, clo, alpha, levels, nw_chunk, res_tree, wide_b, twig_off, lds_lane, SU, nsteps | (sure_miss << 16), step_stats);
         pass += nsteps - 1;
 #else
         if (mode == M_TREE || mode == M_TWIG) {
@@ -720,7 +675,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
         if (pass <= fixed_steps) continue;
         if (more || pass >= 256) break;
         const unsigned long long marching = __ballot(mode == M_TREE || mode == M_TWIG);
-        if (marching == 0ull || marching != __ballot(mode != M_DONE) || __ballot(creepn > 0 || creepn <= -4 * SVO_CREEP_SERIOUS) != 0ull) break;
+        if (marching == 0ull || marching != __ballot(mode != M_DONE) || __ballot(creepn > 0 || creepn <= -4 * CREEP_SERIOUS) != 0ull) break;
         }
         guard += pass - 1;
 
@@ -792,7 +747,6 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
     for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off, 64);
     if (lane == 0 && total) atomicAdd(&A.work[1], (unsigned long long)total);
 #ifdef SVO_STACK_TIMING
-    (void)n_creep_steps;
     unsigned busiest = n_lane_busy;
     for (int off = 32; off > 0; off >>= 1) busiest = max(busiest, (unsigned)__shfl_xor((int)busiest, off, 64));
     unsigned busiest_twig = n_lane_busy == busiest ? n_lane_twig : 0u;          // the busiest lane's share inside bricks
@@ -809,9 +763,6 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
         uint4 h2; h2.x = n_wsteps_b; h2.y = n_lsteps_b; h2.z = n_world_wait; h2.w = n_twig_b;
         reinterpret_cast<uint4 *>(A.counters)[6 * blockIdx.x + 4] = h2;
         uint4 h3; h3.x = step_stats.steps; h3.y = step_stats.lanes; h3.z = step_stats.stalls; h3.w = step_stats.chased;
-#ifdef SVO_SURE_STAT_WORD  // (measurement: the last word counts the brick entries skipped as sure misses instead)
-        h3.w = step_stats.sure;
-#endif
         reinterpret_cast<uint4 *>(A.counters)[6 * blockIdx.x + 5] = h3;
     }
 #endif

@@ -34,82 +34,33 @@
 //
 // Lane modes are numbered so that "marching" is one unsigned compare: DONE 0, WORLD 1, HIT 2, TREE 3, TWIG 4.
 //
-// Two addressing variants of the same statement (step_asm_body.inc is included twice):
-//   march_steps_asm      the chunk's wide tree as a 32-bit byte offset into the wide pool, the brick mask as a 32-bit byte offset
-//                        into the mask pool, both against a scalar base (one VGPR of address each): wide pools below 4 GiB, fewer
-//                        than 2^29 bricks - every world up to a few tens of GB;
-//   march_steps_asm_big  the chunk's wide tree as a 64-bit address per lane, entry and mask addresses formed by one v_mad_u64_u32
-//                        each (32-bit index * size + 64-bit base): any world that fits the device.  One VGPR more of lane state,
-//                        the same instruction count.
+// Two addressing variants of the same statement (each in both semantics: step_asm_body.inc is included four times):
+//   march_steps_asm<false, GLSL>  the chunk's wide tree as a 32-bit byte offset into the wide pool, the brick mask as a 32-bit byte
+//                                 offset into the mask pool, both against a scalar base (one VGPR of address each): wide pools below
+//                                 4 GiB, fewer than 2^29 bricks - every world up to a few tens of GB;
+//   march_steps_asm<true, GLSL>   the chunk's wide tree as a 64-bit address per lane, entry and mask addresses formed by one
+//                                 v_mad_u64_u32 each (32-bit index * size + 64-bit base): any world that fits the device.  One VGPR
+//                                 more of lane state, the same instruction count.
 #pragma once
+#include <type_traits>
+
 #include "march.hip.h"
 
-// A wide level is taken inside the step when more than 1 / 2^shift of the wave's tree lanes stand at a BRANCH entry (StepUniform::descend_shift).
-// Round 4 re-swept it: a HALF (shift 1) instead of a quarter is +1.2 % on C3, +3 % on C2, nothing on C4 - and -2.6 % on C5, whose fresh rays
-// descend seven wide levels from the root: shallow trees (<= 10 branch levels) use 1, deeper ones 2 (shift 3: -3 % on C3; 0 = never: C3 +0.2 %, C5 -7 %).
-#ifndef SVO_DESCEND_SHIFT_SHALLOW
-#define SVO_DESCEND_SHIFT_SHALLOW 1
-#endif
-#ifndef SVO_DESCEND_SHIFT_DEEP
-#define SVO_DESCEND_SHIFT_DEEP 2
-#endif
 #ifdef SVO_STACK_TIMING
 #define SVO_STAT(text) text
 #else
 #define SVO_STAT(text) ""
 #endif
-// (-DSVO_STACK_TIMING -DSVO_SURE_STAT=k: StepStats::sure counts the lanes that reach stage k of the sure-miss test - 1 entering a brick while
-// the wave drains, 2 p(t_miss) provably outside, 3 guard passed, 4 skipped; of a draining wave: 5 lanes that leave a brick whose march missed, 6 lanes that hit a cell; default 4)
-#ifndef SVO_SURE_STAT
-#define SVO_SURE_STAT 4
-#endif
-#define SVO_SURE_COUNT(k) SVO_SURE_PICK(k, SVO_SURE_STAT)
-#define SVO_SURE_PICK(k, want) SVO_SURE_PICK_(k, want)
-#define SVO_SURE_PICK_(k, want) SVO_SURE_IS_##k##_##want
-#define SVO_SURE_TEXT SVO_STAT("s_bcnt1_i32_b64 %[na], exec\n\t" "s_add_u32 %[st_sure], %[st_sure], %[na]\n\t")
-#define SVO_SURE_DRAIN_TEXT SVO_STAT("s_bitcmp1_b32 %[nst], 16\n\t" "s_cbranch_scc0 69f\n\t" "s_bcnt1_i32_b64 %[na], exec\n\t" "s_add_u32 %[st_sure], %[st_sure], %[na]\n\t" "69:\n\t")
-#define SVO_SURE_IS_5_5 SVO_SURE_DRAIN_TEXT
-#define SVO_SURE_IS_6_6 SVO_SURE_DRAIN_TEXT
-#define SVO_SURE_IS_1_1 SVO_SURE_TEXT
-#define SVO_SURE_IS_2_2 SVO_SURE_TEXT
-#define SVO_SURE_IS_3_3 SVO_SURE_TEXT
-#define SVO_SURE_IS_4_4 SVO_SURE_TEXT
-#define SVO_SURE_IS_1_2 ""
-#define SVO_SURE_IS_1_3 ""
-#define SVO_SURE_IS_1_4 ""
-#define SVO_SURE_IS_2_1 ""
-#define SVO_SURE_IS_2_3 ""
-#define SVO_SURE_IS_2_4 ""
-#define SVO_SURE_IS_3_1 ""
-#define SVO_SURE_IS_3_2 ""
-#define SVO_SURE_IS_3_4 ""
-#define SVO_SURE_IS_4_1 ""
-#define SVO_SURE_IS_4_2 ""
-#define SVO_SURE_IS_4_3 ""
-#define SVO_SURE_IS_1_5 ""
-#define SVO_SURE_IS_1_6 ""
-#define SVO_SURE_IS_2_5 ""
-#define SVO_SURE_IS_2_6 ""
-#define SVO_SURE_IS_3_5 ""
-#define SVO_SURE_IS_3_6 ""
-#define SVO_SURE_IS_4_5 ""
-#define SVO_SURE_IS_4_6 ""
-#define SVO_SURE_IS_5_1 ""
-#define SVO_SURE_IS_5_2 ""
-#define SVO_SURE_IS_5_3 ""
-#define SVO_SURE_IS_5_4 ""
-#define SVO_SURE_IS_5_6 ""
-#define SVO_SURE_IS_6_1 ""
-#define SVO_SURE_IS_6_2 ""
-#define SVO_SURE_IS_6_3 ""
-#define SVO_SURE_IS_6_4 ""
-#define SVO_SURE_IS_6_5 ""
-#define SVO_STR_(x) #x
-#define SVO_STR(x) SVO_STR_(x)
 
 namespace svo {
 
-struct StepStats { unsigned steps = 0, lanes = 0, stalls = 0, chased = 0, sure = 0; };    // (-DSVO_STACK_TIMING) wave-steps, marching lanes summed over them, lanes that sat a BRANCH out, lanes that took a level inside the step
+// A wide level is taken inside the step when more than 1 / 2^shift of the wave's tree lanes stand at a BRANCH entry (StepUniform::descend_shift).
+// Round 4 re-swept it: a HALF (shift 1) instead of a quarter is +1.2 % on C3, +3 % on C2, nothing on C4 - and -2.6 % on C5, whose fresh rays
+// descend seven wide levels from the root: shallow trees (<= 10 branch levels) use 1, deeper ones 2 (shift 3: -3 % on C3; 0 = never: C3 +0.2 %, C5 -7 %).
+constexpr int DESCEND_SHIFT_SHALLOW = 1;
+constexpr int DESCEND_SHIFT_DEEP = 2;
+
+struct StepStats { unsigned steps = 0, lanes = 0, stalls = 0, chased = 0; };    // (-DSVO_STACK_TIMING) wave-steps, marching lanes summed over them, lanes that sat a BRANCH out, lanes that took a level inside the step
 
 struct StepUniform {            // wave-uniform inputs (SGPRs)
     float csize, eps, eps2;
@@ -118,6 +69,19 @@ struct StepUniform {            // wave-uniform inputs (SGPRs)
     const uint64_t *mask;
     int descend_shift;
 };
+
+// the chunk's wide tree as the step sees it: a byte offset into the wide pool, or (BIG) its address
+template <bool BIG> using WideRef = typename std::conditional<BIG, unsigned long long, uint32_t>::type;
+
+// `nsteps` (>= 1, wave-uniform; bit 16: the wave is draining) steps of every marching lane.  All lanes of the wave must call this
+// together (EXEC is saved and restored inside).  BIG: 64-bit addressing; GLSL: the shader twin's semantics.  One explicit
+// specialization per variant, each defined by step_asm_body.inc below.
+template <bool BIG, bool GLSL>
+__device__ void march_steps_asm(
+    int &mode, V3 &O, V3 &Blo, float &bsize, float &res, float &t, int &cnt, float &tt_saved, float &t_miss, int &it_saved,
+    float &tw, int &cw, int &pux, int &puy, int &puz, int &valid, int &plev, unsigned long long &bmask, int &creepn,
+    const V3 beta, const V3 g, const V3 clo, const V3 alpha, const int levels, const int nw, const float res_tree,
+    const WideRef<BIG> wide_b, const uint32_t twig_off, const uint32_t lds_lane, const StepUniform U, const int nsteps_sure, StepStats &stats);
 
 // The statement's variants (step_asm_body.inc is included once per variant):
 //   addressing   32-bit offsets against scalar bases / 64-bit addresses (entry: index * 4 + the lane's wide-tree address; mask:
@@ -139,8 +103,8 @@ struct StepUniform {            // wave-uniform inputs (SGPRs)
 #define SVO_STEP_GLSL_LEAF "v_mov_b32 %[q1], %[t]\n\t"
 #define SVO_STEP_GLSL_GUARD "v_cmp_gt_f32 vcc, %[eps], %[r1]\n\t" "v_mov_b32 %[q7], 0x3d800000\n\t" "s_nop 0\n\t" "v_cndmask_b32 %[r1], %[r1], %[q7], vcc\n\t"
 
-#define SVO_STEP_FN march_steps_asm
-#define SVO_STEP_WIDE_T uint32_t
+#define SVO_STEP_BIG false
+#define SVO_STEP_GLSL false
 #define SVO_STEP_LOAD_ENTRY SVO_STEP_ADDR32_ENTRY
 #define SVO_STEP_MASK_OFFSET SVO_STEP_ADDR32_MASKOFF
 #define SVO_STEP_LOAD_MASK SVO_STEP_ADDR32_MASK
@@ -148,35 +112,33 @@ struct StepUniform {            // wave-uniform inputs (SGPRs)
 #define SVO_STEP_LEAF_DISTANCE SVO_STEP_CPU_LEAF
 #define SVO_STEP_ESCAPE_GUARD SVO_STEP_CPU_GUARD
 #include "step_asm_body.inc"
-#undef SVO_STEP_FN
+#undef SVO_STEP_GLSL
 #undef SVO_STEP_LEAF_DISTANCE
 #undef SVO_STEP_ESCAPE_GUARD
-#define SVO_STEP_FN march_steps_asm_glsl
+#define SVO_STEP_GLSL true
 #define SVO_STEP_LEAF_DISTANCE SVO_STEP_GLSL_LEAF
 #define SVO_STEP_ESCAPE_GUARD SVO_STEP_GLSL_GUARD
 #include "step_asm_body.inc"
-#undef SVO_STEP_FN
-#undef SVO_STEP_WIDE_T
+#undef SVO_STEP_BIG
 #undef SVO_STEP_LOAD_ENTRY
 #undef SVO_STEP_MASK_OFFSET
 #undef SVO_STEP_LOAD_MASK
 #undef SVO_STEP_LOAD_MASK_HALVES
-#define SVO_STEP_FN march_steps_asm_big_glsl
-#define SVO_STEP_WIDE_T unsigned long long
+#define SVO_STEP_BIG true
 #define SVO_STEP_LOAD_ENTRY SVO_STEP_ADDR64_ENTRY
 #define SVO_STEP_MASK_OFFSET SVO_STEP_ADDR64_MASKOFF
 #define SVO_STEP_LOAD_MASK SVO_STEP_ADDR64_MASK
 #define SVO_STEP_LOAD_MASK_HALVES SVO_STEP_ADDR64_MASK_HALVES
 #include "step_asm_body.inc"
-#undef SVO_STEP_FN
+#undef SVO_STEP_GLSL
 #undef SVO_STEP_LEAF_DISTANCE
 #undef SVO_STEP_ESCAPE_GUARD
-#define SVO_STEP_FN march_steps_asm_big
+#define SVO_STEP_GLSL false
 #define SVO_STEP_LEAF_DISTANCE SVO_STEP_CPU_LEAF
 #define SVO_STEP_ESCAPE_GUARD SVO_STEP_CPU_GUARD
 #include "step_asm_body.inc"
-#undef SVO_STEP_FN
-#undef SVO_STEP_WIDE_T
+#undef SVO_STEP_BIG
+#undef SVO_STEP_GLSL
 #undef SVO_STEP_LOAD_ENTRY
 #undef SVO_STEP_MASK_OFFSET
 #undef SVO_STEP_LOAD_MASK

@@ -1,17 +1,13 @@
-// step_asm_body.inc — the body of the hand-scheduled march step; included by step_asm.hip.h once per addressing variant
-// (SVO_STEP_FN: the function's name; SVO_STEP_WIDE_T: the type of the chunk's wide-tree reference; SVO_STEP_LOAD_ENTRY /
-// SVO_STEP_MASK_OFFSET / SVO_STEP_LOAD_MASK: the three places where an address is formed).  See step_asm.hip.h for the commentary.
-// `nsteps` (>= 1, wave-uniform) steps of every marching lane.  All lanes of the wave must call this together (EXEC is
-// saved and restored here).
-__device__ __forceinline__ void SVO_STEP_FN(
+// step_asm_body.inc — the body of the hand-scheduled march step; included by step_asm.hip.h once per variant, each time the
+// specialization march_steps_asm<SVO_STEP_BIG, SVO_STEP_GLSL> (SVO_STEP_LOAD_ENTRY / SVO_STEP_MASK_OFFSET / SVO_STEP_LOAD_MASK /
+// SVO_STEP_LOAD_MASK_HALVES: the places where an address is formed; SVO_STEP_LEAF_DISTANCE / SVO_STEP_ESCAPE_GUARD: the semantics).
+// See step_asm.hip.h for the commentary.
+template <>
+__device__ __forceinline__ void march_steps_asm<SVO_STEP_BIG, SVO_STEP_GLSL>(
     int &mode, V3 &O, V3 &Blo, float &bsize, float &res, float &t, int &cnt, float &tt_saved, float &t_miss, int &it_saved,
     float &tw, int &cw, int &pux, int &puy, int &puz, int &valid, int &plev, unsigned long long &bmask, int &creepn,
     const V3 beta, const V3 g, const V3 clo, const V3 alpha, const int levels, const int nw, const float res_tree,
-    const SVO_STEP_WIDE_T wide_b, const uint32_t twig_off, const uint32_t lds_lane, const StepUniform U, const int nsteps_sure
-#ifdef SVO_STACK_TIMING
-    , StepStats &stats
-#endif
-    )
+    const WideRef<SVO_STEP_BIG> wide_b, const uint32_t twig_off, const uint32_t lds_lane, const StepUniform U, const int nsteps_sure, StepStats &stats)
 {
     float px, py, pz, q1, q2, q3, q4, q5, q6, q7, r1, r2, r3;     // (r1..r3 double as the lattice quotients, low as 1/res, q7 as the brick cell index)
     int ux, uy, uz, low;
@@ -21,7 +17,6 @@ __device__ __forceinline__ void SVO_STEP_FN(
 #ifdef SVO_STACK_TIMING
     unsigned st_steps = (unsigned)__builtin_amdgcn_readfirstlane((int)stats.steps), st_lanes = (unsigned)__builtin_amdgcn_readfirstlane((int)stats.lanes);
     unsigned st_stalls = (unsigned)__builtin_amdgcn_readfirstlane((int)stats.stalls), st_chased = (unsigned)__builtin_amdgcn_readfirstlane((int)stats.chased);
-    unsigned st_sure = (unsigned)__builtin_amdgcn_readfirstlane((int)stats.sure);
 #endif
     asm volatile(
         "s_mov_b64 %[sall], exec\n\t"
@@ -111,7 +106,6 @@ __device__ __forceinline__ void SVO_STEP_FN(
         "s_andn2_b64 exec, %[smar], %[sstay]\n\t"
         "s_and_b64 exec, exec, %[stw]\n\t"                     // out of a brick (:104-105): resume the tree level at t_miss
         "s_cbranch_execz 8f\n\t"
-        SVO_SURE_COUNT(5)
         "v_mul_f32 %[q1], %[bx], %[tw]\n\t"
         "v_mul_f32 %[q2], %[by], %[tw]\n\t"
         "v_mul_f32 %[q3], %[bz], %[tw]\n\t"
@@ -143,7 +137,6 @@ __device__ __forceinline__ void SVO_STEP_FN(
         "v_cmp_gt_i64 vcc, 0, %[q64]\n\t"                       // occupied
         "s_andn2_b64 %[sadv], exec, vcc\n\t"
         "s_and_b64 exec, exec, vcc\n\t"                         // occupied: hit, :63,101,160
-        SVO_SURE_COUNT(6)
         "v_add_f32 %[q1], %[t], %[tts]\n\t"
         "v_mov_b32 %[cnt], %[q7]\n\t"
         "v_mov_b32 %[md], 2\n\t"
@@ -275,7 +268,6 @@ __device__ __forceinline__ void SVO_STEP_FN(
         //      leave step; lanes of a full wave would pay for them in every step, a draining wave has nothing else to issue.
         "s_bitcmp1_b32 %[nst], 16\n\t"
         "s_cbranch_scc0 60f\n\t"
-        SVO_SURE_COUNT(1)
         SVO_STEP_LOAD_MASK_HALVES                              // the same mask as two words (r3: z = 0, 1; w: z = 2, 3)
         "v_mul_f32 %[ux], %[bx], %[r1]\n\t"                    // p(t_miss) = p + beta * e
         "v_mul_f32 %[uy], %[by], %[r1]\n\t"
@@ -295,7 +287,6 @@ __device__ __forceinline__ void SVO_STEP_FN(
         "s_andn2_b64 exec, %[sent], exec\n\t"
         "v_cmpx_le_f32 vcc, %[eps2], %[r1]\n\t"                // ... and not creeping (e >= 2 EPS): a ray pinned on a face of the node goes through the
         "s_cbranch_execz 61f\n\t"                              // brick as before, where creepn counts its steps and the creep block takes them in closed form
-        SVO_SURE_COUNT(2)
         // no backward step: p lies in its located cell up to the rounding of p - bmin (<= 2^-24 of the box edge), an escape distance
         // is >= -(that) * |1 / beta|, and t_k does not decrease while that stays below EPS: |beta_k| * EPS * 2^22 >= edge on every axis -
         // or beta_k = 0 (every shadow ray of the default light has one): 1 / beta_k is infinite, that axis' distance is +-inf or NaN,
@@ -313,7 +304,6 @@ __device__ __forceinline__ void SVO_STEP_FN(
         "v_sub_u32 %[low], 0x7f000000, %[q4]\n\t"              // 1 / edge (a power of two)
         "v_cmpx_ge_u32 vcc, %[q5], %[r2]\n\t"
         "s_cbranch_execz 61f\n\t"
-        SVO_SURE_COUNT(3)
         "v_mul_f32 %[low], 4.0, %[low]\n\t"                    // 1 / leafsize
         "v_sub_f32 %[ux], %[ux], %[q1]\n\t"
         "v_sub_f32 %[uy], %[uy], %[q2]\n\t"
@@ -377,7 +367,6 @@ __device__ __forceinline__ void SVO_STEP_FN(
         "v_add_f32 %[t], %[t], %[r1]\n\t"                      // the tree level goes on at t_miss
         "v_mov_b32 %[crp], 0\n\t"                              // (what an advance by e >= 2 EPS leaves in creepn)
         "s_andn2_b64 %[sent], %[sent], exec\n\t"
-        SVO_SURE_COUNT(4)
         "61:\n\t"
         "s_waitcnt vmcnt(0)\n\t"                              // (r3 and w are the next step's to overwrite)
         "s_mov_b64 exec, %[sent]\n\t"
@@ -448,7 +437,7 @@ __device__ __forceinline__ void SVO_STEP_FN(
           [r1] "=&v"(r1), [r2] "=&v"(r2), [r3] "=&v"(r3), [low] "=&v"(low), [w] "=&v"(w), [q64] "=&v"(q64),
           [sall] "=&s"(sall), [smar] "=&s"(smar), [stw] "=&s"(stw), [sstay] "=&s"(sstay), [sadv] "=&s"(sadv), [sent] "=&s"(sent), [sctr] "=&s"(sctr), [na] "=&s"(na), [nb] "=&s"(nb)
 #ifdef SVO_STACK_TIMING
-          , [st_steps] "+s"(st_steps), [st_lanes] "+s"(st_lanes), [st_stalls] "+s"(st_stalls), [st_chased] "+s"(st_chased), [st_sure] "+s"(st_sure)
+          , [st_steps] "+s"(st_steps), [st_lanes] "+s"(st_lanes), [st_stalls] "+s"(st_stalls), [st_chased] "+s"(st_chased)
 #endif
         : [bx] "v"(beta.x), [by] "v"(beta.y), [bz] "v"(beta.z), [gx] "v"(g.x), [gy] "v"(g.y), [gz] "v"(g.z),
           [clx] "v"(clo.x), [cly] "v"(clo.y), [clz] "v"(clo.z), [ax] "v"(alpha.x), [ay] "v"(alpha.y), [az] "v"(alpha.z),
@@ -456,7 +445,7 @@ __device__ __forceinline__ void SVO_STEP_FN(
           [csz] "s"(U.csize), [eps] "s"(U.eps), [eps2] "s"(U.eps2), [captw] "s"(U.cap_twig), [wide] "s"(U.wide), [maskp] "s"(U.mask), [nst] "s"(nsteps_sure), [dsh] "s"(U.descend_shift)
         : "vcc", "scc", "memory");
 #ifdef SVO_STACK_TIMING
-    stats.steps = st_steps; stats.lanes = st_lanes; stats.stalls = st_stalls; stats.chased = st_chased; stats.sure = st_sure;
+    stats.steps = st_steps; stats.lanes = st_lanes; stats.stalls = st_stalls; stats.chased = st_chased;
 #endif
 }
 

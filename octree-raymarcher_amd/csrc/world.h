@@ -45,7 +45,7 @@ struct svo_world {
     std::vector<uint64_t> tree_slot, twig_slot;   // capacity of each chunk's slot (nodes / bricks)
     uint64_t tree_pool_len = 0, twig_pool_len = 0;    // elements in use (incl. alignment padding)
     uint64_t tree_pool_cap = 0, twig_pool_cap = 0;    // elements allocated
-    int occupancy_blocks = 0;                     // cached persistent-grid size
+    int stack_blocks[12] = {};                    // persistent-grid size per k_trace_stack instantiation (device.hip: STACK_KERNELS); 0 = not queried yet
 };
 
 namespace svo {

@@ -1,12 +1,14 @@
 #!/bin/bash
-# Build A/B variants of libsvo_amd.so into octree-raymarcher_amd/build/ (experiments only).
+# Build A/B variants of libsvo_amd.so into octree-raymarcher_amd/build/ (experiments only), through the Makefile's own
+# build/libsvo_%.so rule: the same flags and sources as the shipped library, plus the variant's -D switches.
 # usage: scripts/build_variants.sh name1:"-DFOO=1 -DBAR=2" name2:"..."
 set -e
-cd "$(dirname "$0")/../octree-raymarcher_amd"
-mkdir -p build
+cd "$(dirname "$0")/.."
+pids=()
 for spec in "$@"; do
   name="${spec%%:*}"; defs="${spec#*:}"
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-slp-vectorize $defs -shared -o build/libsvo_$name.so csrc/world.cpp csrc/terrain.cpp csrc/device.hip csrc/builder.hip csrc/shade.hip -lpthread &
+  make -B -C octree-raymarcher_amd "build/libsvo_$name.so" "DEFS_$name=$defs" &
+  pids+=($!)
 done
-wait
-ls -la build/*.so
+for p in "${pids[@]}"; do wait "$p"; done
+ls -la octree-raymarcher_amd/build/*.so
