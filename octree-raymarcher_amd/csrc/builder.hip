@@ -706,18 +706,12 @@ static int generate_world_resident_impl(svo_world &w, int device)
         lapt("noise + mips + grow + fill");
     }
     // pack: the layout of svo_world_upload
-    int rc = plan_pools(w);
+    plan_pools(w);
+    int rc = alloc_pools(w, device);
     if (rc != SVO_OK) return rc;
-    if ((rc = alloc_pools(w, device)) != SVO_OK) return rc;
     lapt("alloc pools");
-    for (size_t i = 0; i < chunks.size(); ++i) {
-        const ChunkPools &c = chunks[i];
-        const DevChunk &e = w.table[i];
-        BUILD_TRY(hipMemcpyAsync(w.d_tree + e.tree_off, trees[i], c.trees_on_device * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-        if (c.twigs_on_device)
-            BUILD_TRY(hipMemcpyAsync(w.d_twig + e.twig_off * TWIG_WORDS, bricks[i], c.twigs_on_device * TWIG_WORDS * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
-        if ((rc = launch_brick_masks(w, e.twig_off, c.twigs_on_device, s)) != SVO_OK) return rc;
-    }
+    for (size_t i = 0; i < chunks.size(); ++i)
+        if ((rc = copy_chunk(w, (int)i, trees[i], bricks[i], hipMemcpyDeviceToDevice, 0, chunks[i].trees_on_device, 0, chunks[i].twigs_on_device, s)) != SVO_OK) return rc;
     BUILD_TRY(hipMemcpyAsync(w.d_chunks, w.table.data(), chunks.size() * sizeof(DevChunk), hipMemcpyHostToDevice, s));
     BUILD_TRY(hipStreamSynchronize(s));
     for (size_t i = 0; i < chunks.size(); ++i) {

@@ -145,8 +145,7 @@ int rebuild_host(svo_world &w, int chunk, bool lod, const char *who)
     r.tree.resize(r.trees); r.twig.resize(r.twigs * TWIG_WORDS);
     next.tree.swap(r.tree); next.twig.swap(r.twig);
     next.tree_capacity = cur.tree_capacity; next.twig_capacity = cur.twig_capacity;     // (svo_world_update's floor)
-    while (next.tree_capacity <= next.tree.size() + 8) next.tree_capacity *= 2;
-    while (next.twig_capacity < next.twig_count()) next.twig_capacity *= 2;
+    next.fit_capacity(next.tree.size(), next.twig_count());
     std::string why;
     const int rc = validate_chunk(next, why);
     if (rc != SVO_OK) { set_error(std::string(who) + ": " + why); return rc; }

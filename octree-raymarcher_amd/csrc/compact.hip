@@ -321,8 +321,7 @@ int rebuild_resident_impl(svo_world &w, int chunk, bool lod)
     ChunkPools meta;
     std::memcpy(meta.position, c.position, sizeof meta.position);
     meta.size = c.size; meta.depth = lod ? c.depth - 1 : c.depth;
-    while (meta.tree_capacity <= trees + 8) meta.tree_capacity *= 2;     // (install_resident_chunk keeps the slot's capacity as the floor)
-    while (meta.twig_capacity < twigs) meta.twig_capacity *= 2;
+    meta.fit_capacity(trees, twigs);                                    // (install_resident_chunk keeps the slot's capacity as the floor)
     meta.trees_on_device = trees; meta.twigs_on_device = twigs;
     return install_resident_chunk(w, chunk, meta, tree, twig);
 }

@@ -82,9 +82,8 @@ __global__ __launch_bounds__(256) void k_tile_keys(const uint32_t *cost, uint32_
     idx[i] = (uint32_t)i;
 }
 
-static int launch_masks(svo_world &w, uint64_t first, uint64_t count, hipStream_t s)
+static int launch_brick_masks(svo_world &w, uint64_t first, uint64_t count, hipStream_t s)
 {
-    if (!count) return SVO_OK;
     const uint64_t blocks = (count * 8 + 255) / 256;
     if (blocks > 0x7FFFFFFFull) { set_error("brick pool too large for one mask launch"); return SVO_ERR_UNSUPPORTED; }
     hipLaunchKernelGGL(k_brick_masks, dim3((unsigned)blocks), dim3(256), 0, s, w.d_twig, w.d_mask, w.d_bmat, first, count);
@@ -149,11 +148,11 @@ static void pool_free(void *p)
     if (evict) (void)hipFree(evict);
 }
 
-int release_device(svo_world &w)
+int release_device(svo_world &w, bool keep_builder)
 {
     if (w.device >= 0) {
         (void)hipSetDevice(w.device);
-        free_builder_context(w);
+        if (!keep_builder) free_builder_context(w);
         (void)hipDeviceSynchronize();                       // the large buffers may be handed to another world at once: nothing may still use them
         (void)hipFree(w.d_chunks); pool_free(w.d_tree); pool_free(w.d_twig);
         pool_free(w.d_mask); pool_free(w.d_bmat); (void)hipFree(w.d_work);
@@ -208,14 +207,13 @@ int svo_stream_synchronize(void *stream) { HIP_TRY(hipStreamSynchronize((hipStre
 
 namespace svo {
 
-int launch_brick_masks(svo_world &w, uint64_t first, uint64_t count, void *stream) { return launch_masks(w, first, count, (hipStream_t)stream); }
+// the base of a tree slot at or behind `len` node words: base % 8 == 7, so that the 8-blocks behind a chunk's root are 8-aligned
+static uint64_t tail_slot(uint64_t len) { return ((len + 8) & ~(uint64_t)7) - 1; }
 
 // slots: capacity-sized like the reference (src/Allocator.cpp:30-33), 8-node / 1-brick granular, plus tail slack so that a
 // chunk that outgrows its slot can be re-packed without a full re-upload
-int plan_pools(svo_world &w)
+void plan_pools(svo_world &w)
 {
-    for (const ChunkPools &c : w.chunks)
-        if (c.size != (float)w.chunksize) { set_error("svo_world_upload: every chunk's size must equal chunksize"); return SVO_ERR_UNSUPPORTED; }
     const size_t n = w.chunks.size();
     w.table.assign(n, DevChunk());
     w.wtable.assign(n, DevWide());
@@ -225,7 +223,7 @@ int plan_pools(svo_world &w)
         const ChunkPools &c = w.chunks[i];
         const uint64_t tcap = std::max<uint64_t>(c.tree_capacity, c.tree_count());
         const uint64_t bcap = std::max<uint64_t>(c.twig_capacity, c.twig_count());
-        const uint64_t base = ((tcur + 8) & ~(uint64_t)7) - 1;          // base % 8 == 7, base >= tcur
+        const uint64_t base = tail_slot(tcur);
         DevChunk &e = w.table[i];
         e.bmin[0] = c.position[0]; e.bmin[1] = c.position[1]; e.bmin[2] = c.position[2];
         e.levels = c.depth - TWIG_LEVELS;
@@ -238,7 +236,6 @@ int plan_pools(svo_world &w)
     w.tree_pool_len = tcur; w.twig_pool_len = bcur;
     w.tree_pool_cap = tcur + tcur / 4 + 64;
     w.twig_pool_cap = bcur + bcur / 4 + 16;
-    return SVO_OK;
 }
 
 int alloc_pools(svo_world &w, int device)
@@ -262,6 +259,21 @@ int alloc_pools(svo_world &w, int device)
     std::fill(std::begin(w.stack_blocks), std::end(w.stack_blocks), 0);
     w.wide_ok = false;                                                  // until build_wide_all has run
     return SVO_OK;
+}
+
+// (world.h) host vectors are copied synchronously out of pageable memory, device buffers in order on `stream`
+int copy_chunk(svo_world &w, int i, const uint32_t *tree, const uint16_t *twig, hipMemcpyKind kind,
+               uint64_t tl, uint64_t tr, uint64_t bl, uint64_t br, void *stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    const DevChunk &e = w.table[(size_t)i];
+    auto copy = [&](void *dst, const void *src, size_t bytes) {
+        return kind == hipMemcpyDeviceToDevice ? hipMemcpyAsync(dst, src, bytes, kind, s) : hipMemcpy(dst, src, bytes, kind);
+    };
+    if (tl < tr) HIP_TRY(copy(w.d_tree + e.tree_off + tl, tree + tl, (tr - tl) * sizeof(uint32_t)));
+    if (bl >= br) return SVO_OK;
+    HIP_TRY(copy(w.d_twig + (e.twig_off + bl) * TWIG_WORDS, twig + bl * TWIG_WORDS, (br - bl) * TWIG_WORDS * sizeof(uint16_t)));
+    return launch_brick_masks(w, e.twig_off + bl, br - bl, s);
 }
 
 // A chunk built on the device keeps its node words and bricks there until somebody asks for the host copy.
@@ -289,7 +301,9 @@ int fetch_pools(svo_world &w, int chunk)
 // The wide tree of chunk `chunk` (wide_tree.hip.h) from its node words in the tree pool, level by level, into
 // wide_dst / wbase_dst (room for slot_cap wide nodes); *count = wide nodes written.  The per-entry reference indices that link
 // one level to the next live in the builder's scratch.
-constexpr int WIDE_SLOT_FULL = 100;     // expand_wide_chunk: the chunk's wide tree does not fit slot_cap (not an svo_status: never leaves this file)
+// (results of this file's wide-tree helpers that are not svo_status values: they never leave this file)
+constexpr int WIDE_SLOT_FULL = 100;     // expand_wide_chunk: the chunk's wide tree does not fit slot_cap
+constexpr int WIDE_POOL_LIMIT = 101;    // build_wide_all's grow_pool: the pool would need 2^32 wide nodes or more (the literal kernel marches)
 static int expand_wide_chunk(svo_world &w, int chunk, hipStream_t s, uint32_t *wide_dst, uint32_t *wbase_dst, uint64_t slot_cap, uint64_t *count_out)
 {
     const ChunkPools &c = w.chunks[(size_t)chunk];
@@ -361,8 +375,6 @@ static bool wide_fits(const svo_world &w, int chunk)
     return c.depth - TWIG_LEVELS <= WIDE_MAX_LEVELS && c.twig_count() <= (uint64_t)WIDE_PAYLOAD_MASK && (c.tree_count() / 8 + 1) * 64 < (1ull << 31);
 }
 
-// Wide trees of every chunk: a count pass into scratch sizes the pool (each chunk's slot = its wide nodes + 25 % + 16),
-// the build pass writes them in place.  The node words must already be in the tree pool.
 static void drop_wide(svo_world &w)
 {
     if (w.d_wide || w.d_wbase) (void)hipDeviceSynchronize();
@@ -378,18 +390,33 @@ static void drop_wide_scratch(svo_world &w, bool failed = true)
     if (w.d_wscratch) { (void)hipDeviceSynchronize(); pool_free(w.d_wscratch); w.d_wscratch = nullptr; }
     w.wscratch_words = 0; w.wscan_words = 0;
 }
-// test hook (the `hooks` variant of the Makefile only; the shipped library reads no such variable): SVO_TEST_FAIL_WIDE=1 makes
-// the next wide-tree build fail as an allocation failure would
-static bool wide_fault_injected()
+// the failure exit of a wide-tree build: no wide pool (the literal kernel marches the world) and no scratch
+static int wide_failed(svo_world &w, int rc, const char *why = nullptr)
 {
-#ifdef SVO_TEST_HOOKS
-    const char *e = std::getenv("SVO_TEST_FAIL_WIDE");
-    return e && e[0] == '1';
-#else
-    return false;
-#endif
+    drop_wide(w); drop_wide_scratch(w);
+    if (why) set_error(why);
+    return rc;
 }
 
+// Chunk `chunk`'s wide tree into the throw-away tree at the end of the builder's scratch, reserved for this chunk first (room for all
+// its BRANCH nodes: *wide / *wbase, *count wide nodes)
+static int expand_into_scratch(svo_world &w, int chunk, hipStream_t s, uint32_t **wide, uint32_t **wbase, uint64_t *count)
+{
+    const uint64_t trees = w.chunks[(size_t)chunk].tree_count(), B = trees / 8 + 1;
+    int rc = reserve_wide_scratch(w, trees);
+#ifdef SVO_TEST_HOOKS
+    // (the `hooks` variant only) SVO_TEST_FAIL_WIDE=1 makes the wide-tree build fail as an allocation failure would
+    const char *fail = std::getenv("SVO_TEST_FAIL_WIDE");
+    if (rc == SVO_OK && fail && fail[0] == '1') { set_error("wide tree: injected allocation failure"); rc = SVO_ERR_OUT_OF_MEMORY; }
+#endif
+    if (rc != SVO_OK) return rc;
+    *wide = w.d_wscratch + 2 * B + 3 * 64 * B; *wbase = *wide + 64 * B;
+    rc = expand_wide_chunk(w, chunk, s, *wide, *wbase, B, count);
+    if (rc == WIDE_SLOT_FULL) { set_error("wide tree: more wide nodes than BRANCH nodes"); rc = SVO_ERR_MALFORMED_TREE; }
+    return rc;
+}
+
+// Wide trees of every chunk from the node words, which must already be in the tree pool.
 int build_wide_all(svo_world &w, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
@@ -399,26 +426,21 @@ int build_wide_all(svo_world &w, void *stream)
     // stack kernel reading a null or half-written pool
     drop_wide(w);
     bool fits = true;
-    uint64_t largest = 0;
-    for (size_t i = 0; i < n; ++i) { largest = std::max<uint64_t>(largest, w.chunks[i].tree_count()); if (!wide_fits(w, (int)i)) fits = false; }
+    size_t sample = 0;                                                  // the chunk with the most nodes stands for all of them
+    for (size_t i = 0; i < n; ++i) {
+        if (w.chunks[i].tree_count() > w.chunks[sample].tree_count()) sample = i;
+        if (!wide_fits(w, (int)i)) fits = false;
+    }
     w.wtable.assign(n, DevWide()); w.wide_slot.assign(n, 0);
     if (!fits) return SVO_OK;                                           // the literal kernel marches such a world
-    int rc = reserve_wide_scratch(w, largest);
-    if (rc == SVO_OK && wide_fault_injected()) { set_error("wide tree: injected allocation failure"); rc = SVO_ERR_OUT_OF_MEMORY; }
-    if (rc != SVO_OK) { drop_wide_scratch(w); return rc; }
-    const uint64_t Bmax = largest / 8 + 1;
-    uint32_t *tmp_wide = w.d_wscratch + 2 * Bmax + 3 * 64 * Bmax, *tmp_wbase = tmp_wide + 64 * Bmax;
     // One pass (until round 4 every chunk was expanded twice: a count pass into scratch sized the pool, a build pass filled it): the
     // largest chunk is counted, the pool is sized from its wide nodes per BRANCH node (+ 35 %) for all chunks, and every chunk is built in
     // place behind the previous one's slot (= its wide nodes + 1/8 + 16); a pool that turns out too small is grown (x 1.5, copied):
     // entries hold wide-node indices relative to their chunk's top node, so a built chunk can move.
     uint64_t count0 = 0;
-    size_t sample = 0;                                                          // the chunk with the most nodes stands for all of them
-    for (size_t i = 0; i < n; ++i) if (w.chunks[i].tree_count() > w.chunks[sample].tree_count()) sample = i;
-    if ((rc = expand_wide_chunk(w, (int)sample, s, tmp_wide, tmp_wbase, Bmax, &count0)) != SVO_OK) {
-        if (rc == WIDE_SLOT_FULL) { set_error("wide tree: more wide nodes than BRANCH nodes"); rc = SVO_ERR_MALFORMED_TREE; }
-        drop_wide_scratch(w); return rc;
-    }
+    uint32_t *tmp_wide, *tmp_wbase;
+    int rc = expand_into_scratch(w, (int)sample, s, &tmp_wide, &tmp_wbase, &count0);
+    if (rc != SVO_OK) return wide_failed(w, rc);
     uint64_t branches = 0;
     for (size_t i = 0; i < n; ++i) branches += w.chunks[i].tree_count() / 8 + 1;
     const double per_branch = (double)count0 / (double)(w.chunks[sample].tree_count() / 8 + 1);
@@ -435,15 +457,12 @@ int build_wide_all(svo_world &w, void *stream)
         if (pool_malloc((void **)wbase, nodes * WIDE_BASE_WORDS * sizeof(uint32_t), w.device) != hipSuccess) { pool_free(*wide); *wide = nullptr; return false; }
         return true;
     };
-    if (cap >= (1ull << 32)) { drop_wide_scratch(w); return SVO_OK; }         // wide node indices are 32-bit (1 TiB of wide nodes): literal kernel
-    if (!alloc_pool(cap, &w.d_wide, &w.d_wbase)) {
-        drop_wide(w); drop_wide_scratch(w);
-        set_error("wide tree: hipMalloc of the pool failed"); return SVO_ERR_OUT_OF_MEMORY;
-    }
+    if (cap >= (1ull << 32)) return wide_failed(w, SVO_OK);                   // wide node indices are 32-bit (1 TiB of wide nodes): literal kernel
+    if (!alloc_pool(cap, &w.d_wide, &w.d_wbase)) return wide_failed(w, SVO_ERR_OUT_OF_MEMORY, "wide tree: hipMalloc of the pool failed");
     uint64_t cur = 0, used = 0;
     auto grow_pool = [&](uint64_t at_least) -> int {
         uint64_t bigger = std::max<uint64_t>(cap + cap / 2, at_least + at_least / 16 + 64);
-        if (bigger >= (1ull << 32)) return 1;                                   // literal kernel
+        if (bigger >= (1ull << 32)) return WIDE_POOL_LIMIT;
         uint32_t *nw = nullptr, *nb = nullptr;
         if (!alloc_pool(bigger, &nw, &nb)) return SVO_ERR_OUT_OF_MEMORY;
         if (hipMemcpyAsync(nw, w.d_wide, cur * 64 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess ||
@@ -460,11 +479,11 @@ int build_wide_all(svo_world &w, void *stream)
         if (rc == WIDE_SLOT_FULL || (rc == SVO_OK && cur + slot > cap)) {        // (grow, then this chunk again)
             const uint64_t bound = w.chunks[i].tree_count() / 8 + 1;
             const int g = grow_pool(cur + (rc == SVO_OK ? slot : std::min<uint64_t>(bound, 2 * (cap - cur) + 1024)));
-            if (g == 1) { drop_wide(w); drop_wide_scratch(w); return SVO_OK; }
-            if (g != SVO_OK) { drop_wide(w); drop_wide_scratch(w); set_error("wide tree: growing the pool failed"); return g; }
+            if (g == WIDE_POOL_LIMIT) return wide_failed(w, SVO_OK);
+            if (g != SVO_OK) return wide_failed(w, g, "wide tree: growing the pool failed");
             continue;
         }
-        if (rc != SVO_OK) { drop_wide(w); drop_wide_scratch(w); return rc; }
+        if (rc != SVO_OK) return wide_failed(w, rc);
         const DevChunk &e = w.table[i];
         DevWide &v = w.wtable[i];
         v.bmin[0] = e.bmin[0]; v.bmin[1] = e.bmin[1]; v.bmin[2] = e.bmin[2];
@@ -474,9 +493,8 @@ int build_wide_all(svo_world &w, void *stream)
         used += count;
         ++i;
     }
-    if (hipMemcpy(w.d_wchunks, w.wtable.data(), n * sizeof(DevWide), hipMemcpyHostToDevice) != hipSuccess) {
-        drop_wide(w); drop_wide_scratch(w); set_error("wide tree: chunk table copy failed"); return SVO_ERR_HIP;
-    }
+    if (hipMemcpy(w.d_wchunks, w.wtable.data(), n * sizeof(DevWide), hipMemcpyHostToDevice) != hipSuccess)
+        return wide_failed(w, SVO_ERR_HIP, "wide tree: chunk table copy failed");
     w.wide_pool_len = cur; w.wide_pool_cap = cap; w.wide_nodes_used = used;
     w.wide_ok = true;
     // the builder's scratch (fronts, flags, ranks and a throw-away tree of the largest chunk: ~1 GB at C3) is only needed
@@ -492,19 +510,12 @@ int rebuild_wide_chunk(svo_world &w, int chunk, void *stream)
 {
     hipStream_t s = (hipStream_t)stream;
     if (!w.wide_ok || !wide_fits(w, chunk)) return build_wide_all(w, stream);
-    const ChunkPools &c = w.chunks[(size_t)chunk];
     // any failure below leaves the chunk's old wide tree in the pool while tree[] has changed: the pool is dropped
     // (wide_ok = false) and the literal kernel takes over until a full rebuild succeeds
-    int rc = reserve_wide_scratch(w, c.tree_count());
-    if (rc == SVO_OK && wide_fault_injected()) { set_error("wide tree: injected allocation failure"); rc = SVO_ERR_OUT_OF_MEMORY; }
-    if (rc != SVO_OK) { drop_wide(w); drop_wide_scratch(w); return rc; }
-    const uint64_t Bmax = c.tree_count() / 8 + 1;
-    uint32_t *tmp_wide = w.d_wscratch + 2 * Bmax + 3 * 64 * Bmax, *tmp_wbase = tmp_wide + 64 * Bmax;
     uint64_t count = 0;
-    if ((rc = expand_wide_chunk(w, chunk, s, tmp_wide, tmp_wbase, Bmax, &count)) != SVO_OK) {
-        if (rc == WIDE_SLOT_FULL) { set_error("wide tree: more wide nodes than BRANCH nodes"); rc = SVO_ERR_MALFORMED_TREE; }
-        drop_wide(w); drop_wide_scratch(w); return rc;
-    }
+    uint32_t *tmp_wide, *tmp_wbase;
+    const int rc = expand_into_scratch(w, chunk, s, &tmp_wide, &tmp_wbase, &count);
+    if (rc != SVO_OK) return wide_failed(w, rc);
     DevWide &v = w.wtable[(size_t)chunk];
     const DevChunk &e = w.table[(size_t)chunk];
     if (count > w.wide_slot[(size_t)chunk]) {
@@ -519,16 +530,10 @@ int rebuild_wide_chunk(svo_world &w, int chunk, void *stream)
     if (hipMemcpyAsync(w.d_wide + (uint64_t)v.wide_off * 64, tmp_wide, count * 64 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess ||
         hipMemcpyAsync(w.d_wbase + (uint64_t)v.wide_off * WIDE_BASE_WORDS, tmp_wbase, count * WIDE_BASE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess ||
         hipMemcpyAsync(w.d_wchunks + chunk, &v, sizeof(DevWide), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-        drop_wide(w); drop_wide_scratch(w); set_error("wide tree: copy of the rebuilt chunk failed"); return SVO_ERR_HIP;
-    }
+        hipStreamSynchronize(s) != hipSuccess) return wide_failed(w, SVO_ERR_HIP, "wide tree: copy of the rebuilt chunk failed");
     drop_wide_scratch(w, false);
     return SVO_OK;
 }
-
-} // namespace svo
-
-extern "C" {
 
 static int world_upload_impl(svo_world *w, int device, bool force = false)
 {
@@ -540,43 +545,96 @@ static int world_upload_impl(svo_world *w, int device, bool force = false)
     bool resident_only = false;
     for (const ChunkPools &c : w->chunks) resident_only |= c.twigs_on_device != 0 || c.trees_on_device != 0;
     if (resident_only && w->device == device && !force) return SVO_OK;
+    // the one layout the pools cannot take, refused while a resident world is still intact
+    for (const ChunkPools &c : w->chunks)
+        if (c.size != (float)w->chunksize) { set_error("svo_world_upload: every chunk's size must equal chunksize"); return SVO_ERR_UNSUPPORTED; }
     for (size_t i = 0; i < w->chunks.size(); ++i) {                     // moving elsewhere: the host copy must be complete first
         const int rc = fetch_pools(*w, (int)i);
         if (rc != SVO_OK) return rc;
     }
-    int rc = plan_pools(*w);
-    if (rc != SVO_OK) return rc;
-    const std::vector<DevChunk> table = w->table;
-    const std::vector<uint64_t> tslot = w->tree_slot, bslot = w->twig_slot;
-    const uint64_t tl = w->tree_pool_len, bl = w->twig_pool_len, tc = w->tree_pool_cap, bc = w->twig_pool_cap;
-    void *ctx = w->device == device ? w->builder_ctx : nullptr;          // a re-pack on the same device keeps the builders' buffers: the caller may be one of them
-    if (ctx) w->builder_ctx = nullptr;
-    release_device(*w);                                                 // (clears the plan too)
-    w->builder_ctx = ctx;
-    w->table = table; w->tree_slot = tslot; w->twig_slot = bslot;
-    w->tree_pool_len = tl; w->twig_pool_len = bl; w->tree_pool_cap = tc; w->twig_pool_cap = bc;
-
+    release_device(*w, w->device == device);                            // a re-pack on the same device keeps the builders' buffers: the caller may be one of them
+    plan_pools(*w);
     const size_t n = w->chunks.size();
-    bool literal_only = false;
-    do {
-        if ((rc = alloc_pools(*w, device)) != SVO_OK) break;
-        for (size_t i = 0; i < n && rc == SVO_OK; ++i) {
-            const ChunkPools &c = w->chunks[i];
-            const DevChunk &e = w->table[i];
-            if (hipMemcpy(w->d_tree + e.tree_off, c.tree.data(), c.tree.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess) rc = SVO_ERR_HIP;
-            if (rc == SVO_OK && !c.twig.empty() &&
-                hipMemcpy(w->d_twig + e.twig_off * TWIG_WORDS, c.twig.data(), c.twig.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess) rc = SVO_ERR_HIP;
-            if (rc == SVO_OK) rc = launch_masks(*w, e.twig_off, c.twig_count(), nullptr);
-        }
-        if (rc != SVO_OK) { if (rc == SVO_ERR_HIP) set_error("svo_world_upload: copy failed"); break; }
-        // the stack kernel's wide trees: a failure here (device memory, mostly) leaves a complete world for the literal kernel
-        // (build_wide_all has dropped whatever it had begun), and the caller is told so
-        literal_only = build_wide_all(*w, nullptr) != SVO_OK;
-        if (hipMemcpy(w->d_chunks, w->table.data(), n * sizeof(DevChunk), hipMemcpyHostToDevice) != hipSuccess ||
-            hipDeviceSynchronize() != hipSuccess) { set_error("svo_world_upload: chunk table copy failed"); rc = SVO_ERR_HIP; break; }
-    } while (0);
+    int rc = alloc_pools(*w, device);
+    for (size_t i = 0; i < n && rc == SVO_OK; ++i) {
+        const ChunkPools &c = w->chunks[i];
+        rc = copy_chunk(*w, (int)i, c.tree.data(), c.twig.data(), hipMemcpyHostToDevice, 0, c.tree.size(), 0, c.twig_count(), nullptr);
+    }
     if (rc != SVO_OK) { release_device(*w); return rc; }
+    // the stack kernel's wide trees: a failure here (device memory, mostly) leaves a complete world for the literal kernel
+    // (build_wide_all has dropped whatever it had begun), and the caller is told so
+    const bool literal_only = build_wide_all(*w, nullptr) != SVO_OK;
+    if (hipMemcpy(w->d_chunks, w->table.data(), n * sizeof(DevChunk), hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+        set_error("svo_world_upload: chunk table copy failed"); release_device(*w); return SVO_ERR_HIP;
+    }
     return literal_only ? SVO_OK_LITERAL_ONLY : SVO_OK;
+}
+
+// Chunk `chunk` of an uploaded world, its host metadata (frame, depth, capacities, counts) already current, into its slots from host
+// vectors (node words [tl, tr) and bricks [bl, br) changed) or device buffers (the whole chunk): in place if it fits, an outgrown pool
+// at the pools' tail if that has room, otherwise the world is packed again.  Launches of this world may still be in flight on the
+// caller's streams, which are not ordered against the copies (a march that reads a half-rewritten tree could follow a stale BRANCH
+// chain): like World::modify on the GL queue (src/World.cpp:268-274), the device is drained first.
+static int install_chunk(svo_world &w, int chunk, const uint32_t *tree, const uint16_t *twig, hipMemcpyKind kind,
+                         uint64_t tl, uint64_t tr, uint64_t bl, uint64_t br)
+{
+    HIP_TRY(hipSetDevice(w.device));
+    HIP_TRY(hipDeviceSynchronize());
+    ChunkPools &c = w.chunks[(size_t)chunk];
+    DevChunk &e = w.table[(size_t)chunk];
+    const uint64_t trees = c.tree_count(), twigs = c.twig_count();
+    const bool tree_fits = trees <= w.tree_slot[(size_t)chunk], twig_fits = twigs <= w.twig_slot[(size_t)chunk];
+    const bool trace = std::getenv("SVO_BUILD_TIMING") != nullptr;
+    if (trace) std::fprintf(stderr, "[svo install] chunk %d: %s\n", chunk, tree_fits && twig_fits ? "in place" : "outgrew its slot");
+    bool table_dirty = e.levels != c.depth - TWIG_LEVELS || e.bmin[0] != c.position[0] || e.bmin[1] != c.position[1] || e.bmin[2] != c.position[2];
+    if (!tree_fits || !twig_fits) {
+        const uint64_t tbase = tail_slot(w.tree_pool_len);
+        const uint64_t need_t = tree_fits ? 0 : c.tree_capacity, need_b = twig_fits ? 0 : c.twig_capacity;
+        if ((!tree_fits && tbase + need_t > w.tree_pool_cap) || (!twig_fits && w.twig_pool_len + need_b > w.twig_pool_cap)) {
+            // no room: a chunk that lives on the device comes to the host, then everything is fetched and packed afresh
+            if (trace) std::fprintf(stderr, "[svo install] chunk %d: no room at the tails, packing the world again\n", chunk);
+            if (kind == hipMemcpyDeviceToDevice) {
+                c.tree.resize(trees); c.twig.resize(twigs * TWIG_WORDS);
+                c.trees_on_device = c.twigs_on_device = 0;
+                HIP_TRY(hipMemcpy(c.tree.data(), tree, trees * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                if (twigs) HIP_TRY(hipMemcpy(c.twig.data(), twig, twigs * TWIG_WORDS * sizeof(uint16_t), hipMemcpyDeviceToHost));
+            }
+            return world_upload_impl(&w, w.device, true);
+        }
+        if (!tree_fits) { e.tree_off = tbase; w.tree_slot[(size_t)chunk] = need_t; w.tree_pool_len = tbase + need_t; }
+        if (!twig_fits) { e.twig_off = w.twig_pool_len; w.twig_slot[(size_t)chunk] = need_b; w.twig_pool_len += need_b; }
+        table_dirty = true;
+        tl = 0; tr = trees; bl = 0; br = twigs;                         // a chunk that moved is copied whole, both pools
+    }
+    e.levels = c.depth - TWIG_LEVELS;
+    e.bmin[0] = c.position[0]; e.bmin[1] = c.position[1]; e.bmin[2] = c.position[2];
+    int rc = copy_chunk(w, chunk, tree, twig, kind, tl, std::min(tr, trees), bl, std::min(br, twigs), nullptr);
+    if (rc != SVO_OK) return rc;
+    if (table_dirty) HIP_TRY(hipMemcpy(w.d_chunks + chunk, &e, sizeof(DevChunk), hipMemcpyHostToDevice));
+    // the stack kernel's view of the chunk: rebuilt from the node words now in the pool
+    // (the pools and the chunk table already hold the new chunk: a wide tree that cannot be rebuilt - rebuild_wide_chunk has dropped
+    // the wide pool then - leaves a world the literal kernel marches, and the caller is told so instead of being told "error"
+    // about a change that took effect)
+    rc = rebuild_wide_chunk(w, chunk, nullptr);
+    HIP_TRY(hipDeviceSynchronize());
+    return rc == SVO_OK ? SVO_OK : SVO_OK_LITERAL_ONLY;
+}
+
+// A chunk built on the device (World::shift on an uploaded world, the box edit, compact / coarsen: builder.hip, compact.hip) takes
+// slot `chunk`: its host copy is dropped (svo_world_chunk fetches the pools on request) and the pools are installed device-to-device.
+int install_resident_chunk(svo_world &w, int chunk, const ChunkPools &meta, const uint32_t *tree_dev, const uint16_t *twig_dev)
+{
+    if (w.device < 0 || chunk < 0 || chunk >= (int)w.chunks.size()) return SVO_ERR_INVALID_ARG;
+    ChunkPools &c = w.chunks[(size_t)chunk];
+    std::memcpy(c.position, meta.position, sizeof c.position);
+    c.size = meta.size; c.depth = meta.depth;
+    c.tree_capacity = std::max(c.tree_capacity, meta.tree_capacity);    // (svo_world_update keeps the slot's capacity as the floor too)
+    c.twig_capacity = std::max(c.twig_capacity, meta.twig_capacity);
+    std::vector<uint32_t>().swap(c.tree);
+    std::vector<uint16_t>().swap(c.twig);
+    c.trees_on_device = meta.trees_on_device; c.twigs_on_device = meta.twigs_on_device;
+    classify_world(w);
+    return install_chunk(w, chunk, tree_dev, twig_dev, hipMemcpyDeviceToDevice, 0, c.trees_on_device, 0, c.twigs_on_device);
 }
 
 static int world_update_impl(svo_world *w, int chunk, const svo_chunk_desc *desc,
@@ -610,8 +668,7 @@ static int world_update_impl(svo_world *w, int chunk, const svo_chunk_desc *desc
         if (tl < tr) std::memcpy(cur.tree.data() + tl, desc->tree + tl, (tr - tl) * sizeof(uint32_t));
         if (bl < br) std::memcpy(cur.twig.data() + bl * TWIG_WORDS, desc->twig + bl * TWIG_WORDS, (br - bl) * TWIG_WORDS * sizeof(uint16_t));
         const uint64_t cap_t0 = cur.tree_capacity, cap_b0 = cur.twig_capacity;
-        while (cur.tree_capacity <= cur.tree.size() + 8) cur.tree_capacity *= 2;
-        while (cur.twig_capacity < cur.twig_count()) cur.twig_capacity *= 2;
+        cur.fit_capacity(cur.tree.size(), cur.twig_count());
         rc = validate_chunk(cur, why);
         if (rc != SVO_OK) {
             cur.tree.resize(old_trees); cur.twig.resize(old_twigs * TWIG_WORDS);
@@ -629,8 +686,7 @@ static int world_update_impl(svo_world *w, int chunk, const svo_chunk_desc *desc
         if (desc->twigs) next.twig.assign(desc->twig, desc->twig + desc->twigs * TWIG_WORDS);
         next.tree_capacity = cur.tree_capacity;
         next.twig_capacity = cur.twig_capacity;
-        while (next.tree_capacity <= next.tree.size() + 8) next.tree_capacity *= 2;
-        while (next.twig_capacity < next.twig_count()) next.twig_capacity *= 2;
+        next.fit_capacity(next.tree.size(), next.twig_count());
         rc = validate_chunk(next, why);
         if (rc != SVO_OK) { set_error("svo_world_update: " + why); return rc; }
         if (next.size != (float)w->chunksize) { set_error("svo_world_update: chunk size must equal chunksize"); return SVO_ERR_UNSUPPORTED; }
@@ -641,57 +697,19 @@ static int world_update_impl(svo_world *w, int chunk, const svo_chunk_desc *desc
         std::memcpy(cur.position, next.position, sizeof cur.position);
         cur.size = next.size; cur.depth = next.depth;
         cur.tree_capacity = next.tree_capacity; cur.twig_capacity = next.twig_capacity;
-        if (!realloc_ && (desc->trees != old_trees || desc->twigs != old_twigs)) { tree_left = 0; tree_right = desc->trees; twig_left = 0; twig_right = desc->twigs; }
+        if (realloc_ || desc->trees != old_trees || desc->twigs != old_twigs) { tree_left = 0; tree_right = desc->trees; twig_left = 0; twig_right = desc->twigs; }
     }
-    ChunkPools &c = cur;
     classify_world(*w);
     if (w->device < 0) return SVO_OK;
-
-    // 2. refresh HBM.  Launches of this world may still be in flight on the caller's streams (non-blocking streams are
-    //    not ordered against the copies below, and a march that reads a half-rewritten tree could follow a stale BRANCH
-    //    chain): like World::modify on the GL queue (src/World.cpp:268-274), the update is ordered behind everything
-    //    issued before it - the device is drained first.
-    HIP_TRY(hipSetDevice(w->device));
-    HIP_TRY(hipDeviceSynchronize());
-    DevChunk &e = w->table[(size_t)chunk];
-    const bool tree_fits = c.tree.size() <= w->tree_slot[(size_t)chunk];
-    const bool twig_fits = c.twig_count() <= w->twig_slot[(size_t)chunk];
-    bool table_dirty = e.levels != c.depth - TWIG_LEVELS || e.bmin[0] != c.position[0] || e.bmin[1] != c.position[1] || e.bmin[2] != c.position[2];
-    e.levels = c.depth - TWIG_LEVELS;
-    e.bmin[0] = c.position[0]; e.bmin[1] = c.position[1]; e.bmin[2] = c.position[2];
-    if (!tree_fits || !twig_fits) {
-        // move the outgrown pool(s) to the tail; no room there -> full re-upload
-        const uint64_t tbase = ((w->tree_pool_len + 8) & ~(uint64_t)7) - 1;
-        const uint64_t need_t = tree_fits ? 0 : c.tree_capacity, need_b = twig_fits ? 0 : c.twig_capacity;
-        if ((!tree_fits && tbase + need_t > w->tree_pool_cap) || (!twig_fits && w->twig_pool_len + need_b > w->twig_pool_cap))
-            return world_upload_impl(w, w->device, true);
-        if (!tree_fits) { e.tree_off = tbase; w->tree_slot[(size_t)chunk] = need_t; w->tree_pool_len = tbase + need_t; }
-        if (!twig_fits) { e.twig_off = w->twig_pool_len; w->twig_slot[(size_t)chunk] = need_b; w->twig_pool_len += need_b; }
-        table_dirty = true;
-        realloc_ = 1;
-        if (tree_fits) { /* tree stays, only its dirty range is re-sent below */ }
-    }
-    uint64_t tl = tree_left, tr = tree_right, bl = twig_left, br = twig_right;
-    if (realloc_ || !tree_fits) { tl = 0; tr = c.tree.size(); }
-    if (realloc_ || !twig_fits) { bl = 0; br = c.twig_count(); }
-    tr = std::min<uint64_t>(tr, c.tree.size()); br = std::min<uint64_t>(br, c.twig_count());
-    if (tl < tr) HIP_TRY(hipMemcpy(w->d_tree + e.tree_off + tl, c.tree.data() + tl, (tr - tl) * sizeof(uint32_t), hipMemcpyHostToDevice));
-    if (bl < br) {
-        HIP_TRY(hipMemcpy(w->d_twig + (e.twig_off + bl) * TWIG_WORDS, c.twig.data() + bl * TWIG_WORDS, (br - bl) * TWIG_WORDS * sizeof(uint16_t), hipMemcpyHostToDevice));
-        rc = launch_masks(*w, e.twig_off + bl, br - bl, nullptr);
-        if (rc != SVO_OK) return rc;
-    }
-    if (table_dirty) HIP_TRY(hipMemcpy(w->d_chunks + chunk, &e, sizeof(DevChunk), hipMemcpyHostToDevice));
-    // the stack kernel's view of the chunk: rebuilt from the node words now in the pool
-    // (the pools and the chunk table already hold the new chunk: a wide tree that cannot be rebuilt - rebuild_wide_chunk has dropped
-    // the wide pool then - leaves a world the literal kernel marches, and the caller is told so instead of being told "error"
-    // about a change that took effect)
-    rc = rebuild_wide_chunk(*w, chunk, nullptr);
-    HIP_TRY(hipDeviceSynchronize());
-    return rc == SVO_OK ? SVO_OK : SVO_OK_LITERAL_ONLY;
+    // 2. refresh HBM
+    return install_chunk(*w, chunk, cur.tree.data(), cur.twig.data(), hipMemcpyHostToDevice, tree_left, tree_right, twig_left, twig_right);
 }
 
-// nothing throws across the C ABI: host-side allocations of the two entry points above are fenced here
+} // namespace svo
+
+extern "C" {
+
+// nothing throws across the C ABI: host-side allocations of the two entry points below are fenced here
 int svo_world_upload(svo_world *w, int device)
 {
     try { return world_upload_impl(w, device); }
@@ -710,57 +728,6 @@ int svo_world_update(svo_world *w, int chunk, const svo_chunk_desc *desc,
 } // extern "C"
 
 namespace svo {
-
-// svo_world_update's device half for a chunk whose new pools already lie in HBM (World::shift on an uploaded world,
-// builder.hip): same ordering rule (the device is drained first), same slot logic - in place if it fits, at the pools' tails
-// if they have room; otherwise the chunk comes to the host and the whole world is packed again.
-int install_resident_chunk(svo_world &w, int chunk, const ChunkPools &meta, const uint32_t *tree_dev, const uint16_t *twig_dev)
-{
-    if (w.device < 0 || chunk < 0 || chunk >= (int)w.chunks.size()) return SVO_ERR_INVALID_ARG;
-    HIP_TRY(hipSetDevice(w.device));
-    HIP_TRY(hipDeviceSynchronize());
-    ChunkPools &c = w.chunks[(size_t)chunk];
-    const uint64_t trees = meta.trees_on_device, twigs = meta.twigs_on_device;
-    std::memcpy(c.position, meta.position, sizeof c.position);
-    c.size = meta.size; c.depth = meta.depth;
-    c.tree_capacity = std::max(c.tree_capacity, meta.tree_capacity);    // (svo_world_update keeps the slot's capacity as the floor too)
-    c.twig_capacity = std::max(c.twig_capacity, meta.twig_capacity);
-    std::vector<uint32_t>().swap(c.tree);
-    std::vector<uint16_t>().swap(c.twig);
-    c.trees_on_device = trees; c.twigs_on_device = twigs;
-    classify_world(w);
-    DevChunk &e = w.table[(size_t)chunk];
-    const bool tree_fits = trees <= w.tree_slot[(size_t)chunk], twig_fits = twigs <= w.twig_slot[(size_t)chunk];
-    const bool trace = std::getenv("SVO_BUILD_TIMING") != nullptr;
-    if (trace) std::fprintf(stderr, "[svo install] chunk %d: %s\n", chunk, tree_fits && twig_fits ? "in place" : "outgrew its slot");
-    if (!tree_fits || !twig_fits) {
-        const uint64_t tbase = ((w.tree_pool_len + 8) & ~(uint64_t)7) - 1;
-        const uint64_t need_t = tree_fits ? 0 : c.tree_capacity, need_b = twig_fits ? 0 : c.twig_capacity;
-        if ((!tree_fits && tbase + need_t > w.tree_pool_cap) || (!twig_fits && w.twig_pool_len + need_b > w.twig_pool_cap)) {
-            // no room: this chunk's pools come to the host, then everything is fetched and packed afresh
-            if (trace) std::fprintf(stderr, "[svo install] chunk %d: no room at the tails, packing the world again\n", chunk);
-            c.tree.resize(trees); c.twig.resize(twigs * TWIG_WORDS);
-            c.trees_on_device = c.twigs_on_device = 0;
-            HIP_TRY(hipMemcpy(c.tree.data(), tree_dev, trees * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            if (twigs) HIP_TRY(hipMemcpy(c.twig.data(), twig_dev, twigs * TWIG_WORDS * sizeof(uint16_t), hipMemcpyDeviceToHost));
-            return world_upload_impl(&w, w.device, true);
-        }
-        if (!tree_fits) { e.tree_off = tbase; w.tree_slot[(size_t)chunk] = need_t; w.tree_pool_len = tbase + need_t; }
-        if (!twig_fits) { e.twig_off = w.twig_pool_len; w.twig_slot[(size_t)chunk] = need_b; w.twig_pool_len += need_b; }
-    }
-    e.levels = c.depth - TWIG_LEVELS;
-    e.bmin[0] = c.position[0]; e.bmin[1] = c.position[1]; e.bmin[2] = c.position[2];
-    HIP_TRY(hipMemcpy(w.d_tree + e.tree_off, tree_dev, trees * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-    if (twigs) {
-        HIP_TRY(hipMemcpy(w.d_twig + e.twig_off * TWIG_WORDS, twig_dev, twigs * TWIG_WORDS * sizeof(uint16_t), hipMemcpyDeviceToDevice));
-        const int rc = launch_masks(w, e.twig_off, twigs, nullptr);
-        if (rc != SVO_OK) return rc;
-    }
-    HIP_TRY(hipMemcpy(w.d_chunks + chunk, &e, sizeof(DevChunk), hipMemcpyHostToDevice));
-    const int rc = rebuild_wide_chunk(w, chunk, nullptr);      // (failure: the wide pool is dropped, the installed chunk stays - see svo_world_update)
-    HIP_TRY(hipDeviceSynchronize());
-    return rc == SVO_OK ? SVO_OK : SVO_OK_LITERAL_ONLY;
-}
 
 // k_trace_stack's instantiations, by depth class, GLSL before CPU semantics: the large-world instantiation (BIG: 64-bit wide-tree and mask
 // addresses, where 32-bit offsets do not reach) in two depth classes - a world that large is built of deep chunks -, the default one in four

@@ -148,6 +148,12 @@ void ChunkPools::reserve_tree(uint64_t need)
     if (tree.capacity() < tree_capacity) tree.reserve(tree_capacity);
 }
 
+void ChunkPools::fit_capacity(uint64_t trees, uint64_t twigs)
+{
+    while (tree_capacity <= trees + 8) tree_capacity *= 2;
+    while (twig_capacity < twigs) twig_capacity *= 2;
+}
+
 void grow_chunk(ChunkPools &c, const float position[3], float size, uint32_t depth, const HeightPyramid &pyr,
                 const TerrainParams *sparse)
 {   // src/Octree.cpp:74-176, level-synchronous

@@ -29,6 +29,9 @@ struct ChunkPools {
     uint64_t trees_on_device = 0;
     uint64_t tree_count() const { return trees_on_device ? trees_on_device : tree.size(); }
     void reserve_tree(uint64_t need);
+    // the capacities of a chunk whose pools arrive whole (svo_world_create / _update, compact, coarsen): doubled until `trees` node
+    // words with a block of 8 to spare and `twigs` bricks fit
+    void fit_capacity(uint64_t trees, uint64_t twigs);
 };
 
 // BoundsPyramid (src/BoundsPyramid.h) as one flat array per bound.

@@ -163,8 +163,7 @@ int svo_world_create(const svo_chunk_desc *chunks, int n, int w, int h, int d, i
             c.size = s.size; c.depth = s.depth;
             c.tree.assign(s.tree, s.tree + s.trees);
             c.twig.assign(s.twig, s.twig + s.twigs * TWIG_WORDS);
-            while (c.tree_capacity <= c.tree.size() + 8) c.tree_capacity *= 2;
-            while (c.twig_capacity < c.twig_count()) c.twig_capacity *= 2;
+            c.fit_capacity(c.tree.size(), c.twig_count());
             std::string why;
             const int rc = validate_chunk(c, why);
             if (rc != SVO_OK) { delete world; set_error("svo_world_create: chunk " + std::to_string(i) + ": " + why); return rc; }

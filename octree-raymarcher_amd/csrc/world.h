@@ -2,6 +2,9 @@
 #pragma once
 #include <string>
 #include <vector>
+#ifdef __HIP__
+#include <hip/hip_runtime_api.h>
+#endif
 #include "../../include/svo.h"
 #include "svo_format.h"
 #include "terrain.h"
@@ -54,15 +57,21 @@ void set_error(const std::string &msg);
 int  validate_chunk(const ChunkPools &c, std::string &why);
 bool chunk_is_exact(const ChunkPools &c, int chunksize);
 void classify_world(svo_world &w);
-int  release_device(svo_world &w);
+// device.hip: frees the world's device copy; keep_builder keeps builder_ctx (a re-pack on the same device, maybe by one of the builders)
+int  release_device(svo_world &w, bool keep_builder = false);
 // device.hip: HBM residency building blocks shared by svo_world_upload and the device-resident generator
-int  plan_pools(svo_world &w);                    // slots, offsets and pool sizes from the chunks' capacities (host only)
+void plan_pools(svo_world &w);                    // slots, offsets and pool sizes from the chunks' capacities (host only)
 int  alloc_pools(svo_world &w, int device);       // hipMalloc + clear of the pools planned above; sets w.device
-int  launch_brick_masks(svo_world &w, uint64_t first, uint64_t count, void *stream);
+#ifdef __HIP__
+// node words [tl, tr) and bricks [bl, br) of chunk i from host vectors (hipMemcpyHostToDevice, synchronous) or device buffers
+// (hipMemcpyDeviceToDevice, on `stream`) into its slots, then the masks of those bricks
+int  copy_chunk(svo_world &w, int i, const uint32_t *tree, const uint16_t *twig, hipMemcpyKind kind,
+                uint64_t tl, uint64_t tr, uint64_t bl, uint64_t br, void *stream);
+#endif
 int  fetch_pools(svo_world &w, int chunk);        // node words / bricks that live only on the device -> host copy of that chunk
 int  build_wide_all(svo_world &w, void *stream);  // wide trees (wide_tree.hip.h) of all chunks from the node words in the tree pool
 // a chunk built on the device (its pools at tree_dev / twig_dev, meta.trees_on_device nodes / meta.twigs_on_device bricks) takes
-// slot `chunk` of an uploaded world: device-to-device, no host copy made
+// slot `chunk` of an uploaded world: device-to-device, no host copy made, through svo_world_update's install path
 int  install_resident_chunk(svo_world &w, int chunk, const ChunkPools &meta, const uint32_t *tree_dev, const uint16_t *twig_dev);
 int  rebuild_wide_chunk(svo_world &w, int chunk, void *stream);
 // builder.hip: World::init on the device, pools left in HBM (the world is uploaded to `device` when this returns)

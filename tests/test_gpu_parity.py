@@ -677,6 +677,44 @@ def test_update_replaces_a_chunk_by_one_of_another_depth(svo, oracle):
         g.destroy()
 
 
+def test_host_update_walks_in_place_tail_and_repack(svo, oracle, capfd, monkeypatch):
+    """svo_world_update from host pools through all three placements of the install path it shares with the device-built chunks
+    (shift, edit, compact): chunk 0, depth 4 among depth-7 chunks, is handed larger and larger versions of itself - another seed's
+    chunk of the same depth (fits its slot), the chunk at depth 5 (outgrows its slot, fits the pools' tails) and at depth 7 (no room
+    at the tails: the world is packed again).  The pools keep their size until the re-pack; svo_world_chunk returns what was sent
+    and both kernels match the oracle after every step."""
+    monkeypatch.setenv("SVO_BUILD_TIMING", "1")         # the install path names the placement it took on stderr
+    gen = {}
+    for depth, seed in ((4, 0), (4, 28), (5, 28), (7, 0)):
+        g = svo.World.generate(2, 1, 2, 128, depth, seed=seed)
+        gen[depth, seed] = chunks_of(g, 4)
+        g.destroy()
+    chunks = [gen[4, 0][0]] + gen[7, 0][1:]
+    W = svo.World.create(chunks, 2, 1, 2, 128)
+    W.upload(0)
+    capfd.readouterr()
+    o, d = random_rays(np.random.default_rng(17), 12000, (0, 0, 0), (256, 128, 256))
+    pool = W.info.tree_pool_bytes
+    for key, placement in (((4, 28), "in place"), ((5, 28), "tail"), ((7, 0), "re-pack")):
+        new = gen[key][0]
+        assert new["tree"].size > chunks[0]["tree"].size and new["twig"].size >= chunks[0]["twig"].size
+        chunks[0] = new
+        W.update(0, new, tree_range=(0, new["tree"].size), twig_range=(0, new["twig"].size // 64))
+        err = capfd.readouterr().err
+        assert ("chunk 0: in place" in err) == (placement == "in place"), (key, err)
+        assert ("chunk 0: outgrew its slot" in err) == (placement != "in place"), (key, err)
+        assert ("chunk 0: no room at the tails" in err) == (placement == "re-pack"), (key, err)
+        assert (W.info.tree_pool_bytes == pool) == (placement != "re-pack"), key
+        for i in range(4):
+            got = W.chunk(i)
+            assert np.array_equal(got["tree"], chunks[i]["tree"]) and np.array_equal(got["twig"], chunks[i]["twig"]), (key, i)
+        O = oracle.OracleWorld.from_chunks(chunks, 2, 1, 2, 128, (0, 0, 0))
+        want = O.trace_rays(o, d, params=oracle.make_params(shadow=True), threads=8)
+        for k in (svo.KERNEL_STACK, svo.KERNEL_LITERAL):
+            assert_gbuffer_equal(W.chunkmarch(o, d, shadow=True, kernel=k), want, f"after update {key}/{k}")
+    W.destroy()
+
+
 @pytest.mark.parametrize("kernel", KERNELS)
 @pytest.mark.parametrize("band,stride", [(1, 2), (3, 3), (5, 2), (16, 3), (120, 1)])
 def test_band_heights_other_than_the_tile_height(svo, oracle, worlds, kernel, band, stride):
