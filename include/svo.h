@@ -30,6 +30,9 @@
  *   svo_world_coarsen    <- Ocroot::lodmm + World::modify(realloc)        src/Octree.cpp:626-765, src/MisraGries.h
  *                           (the caller's pattern: key 'g', src/Main.cpp:438-448)
  *   svo_shade(_packed)   <- lighting of fragment main               shaders/World.Fragment.glsl:63-138,180-197
+ *   svo_trace_params.see_through <- the `ignore` material of treemarch / twigmarch   shaders/Chunkmarch.glsl:190-191,240-241,280
+ *   svo_trace_translucent <- the second march from a translucent hit   shaders/ParallaxAlpha.Fragment.glsl:141-199,276-335
+ *   svo_shade_translucent <- its blend by the path length through the liquid   shaders/ParallaxAlpha.Fragment.glsl:226-234,315-323
  *
  * Conventions
  *   - plain C, opaque handle, caller owns every buffer it passes in;
@@ -68,7 +71,9 @@ extern "C" {
 #define SVO_ABI_VERSION 4           /* 2: svo_trace_params.normal_mode, SVO_FACE_NORMAL, error bit in the packed record
                                        3: svo_trace_params.tile_cost_dev / tile_order_dev, svo_tile_order
                                        4: SVO_OK_LITERAL_ONLY, svo_device_cache_trim, svo_trace_params.semantics;
-                                          4 later gained svo_world_compact and svo_world_coarsen (functions added, nothing changed) */
+                                          4 later gained svo_world_compact and svo_world_coarsen (functions added, nothing changed),
+                                          svo_trace_params.see_through (was padding: zeroed structs keep their results),
+                                          svo_trace_translucent and svo_shade_translucent */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -197,7 +202,13 @@ typedef struct svo_trace_params {
                                        1 / dir, :116-126), no chunk containment re-check (:297-330), a LEAF hit is reported at t without the
                                        CPU code's back-off (:263-268; svo_hit.t is then the shader's sigma), brick cells are found by
                                        multiplying with 1 / leafsize (:201,212).  Both kernels, the oracle and its Python twin implement it */
-    int32_t  _pad_semantics;
+    uint32_t see_through;           /* 0 = off.  m in 1..0xFFFF: every ray (shadow rays too) is marched as if each LEAF node of material m
+                                       (offset & 0xFFFF == m) were EMPTY and each brick cell holding m were 0 - shaders/Chunkmarch.glsl's
+                                       `ignore` (:190-191,240-241,280), used by ParallaxAlpha.Fragment.glsl (:147,181).  The records equal,
+                                       bit for bit, those of the same world with those words rewritten to 0 (node, cell and chunk included).
+                                       Above 0xFFFF: SVO_ERR_INVALID_ARG.  The stack kernel marches a see-through copy of the world's wide
+                                       and mask pools, built on the device at the first such launch and kept for one material at a time
+                                       (svo_world_info does not count it; at most 1.4 GB at C3 size); every change to the pools drops it */
 } svo_trace_params;
 enum { SVO_NORMAL_CUBE = 0, SVO_NORMAL_FACE = 1 };
 enum { SVO_SEMANTICS_CPU = 0, SVO_SEMANTICS_GLSL = 1 };
@@ -208,6 +219,7 @@ enum {
     SVO_SHADOW_TRACED = 1u << 1,    /* a shadow ray was cast from this hit */
     SVO_SHADOWED      = 1u << 2,    /* ... and it hit something */
     SVO_FACE_NORMAL   = 1u << 3,    /* normal[] is the entered-face normal (svo_trace_params.normal_mode = SVO_NORMAL_FACE) */
+    SVO_SEE_THROUGH   = 1u << 4,    /* svo_trace_translucent: the surface hit is of the see-through material; the behind record is its continuation */
     SVO_ERR_FLAG      = 1u << 15    /* runaway ray: given up after 2^22 march steps of the kernel's own counting (only rays that
                                        creep through all three nested loops of the reference get there; the stack kernel
                                        takes creeping stretches in closed form and finishes rays the literal kernel gives
@@ -360,6 +372,19 @@ int svo_trace_rays(svo_world *, const float *origins_dev, const float *dirs_dev,
  * tile is skipped, its pixels stay unwritten) rather than read out of range. */
 int svo_tile_order(svo_world *, const uint32_t *cost_dev, uint32_t *order_dev, int ntiles, void *stream);
 
+/* See-through materials (shaders/ParallaxAlpha.Fragment.glsl:141-199,276-335): trace the rectangle like svo_trace, and march on
+ * past every surface hit of material m = params->see_through (1..0xFFFF; 0 is SVO_ERR_INVALID_ARG).
+ *   surface_dev  w*h records: exactly what svo_trace writes with see_through = 0 (shadow included), plus SVO_SEE_THROUGH on every
+ *                hit (SVO_HIT_FLAG without SVO_ERR_FLAG) whose material is m;
+ *   behind_dev   w*h records: for such a pixel, what svo_trace_rays(see_through = m) writes for the continuation ray - the pixel's
+ *                primary direction d from origin p1 = o + d * t1 (o the eye, t1 = surface.t; per component, separately rounded) -
+ *                shadow ray included, so behind.t is measured from p1: the path length through the liquid.  All-zero elsewhere.
+ * Asynchronous on `stream`; the continuation list lives in the world's scratch (calls of one world on different streams are
+ * ordered behind one another on the device).  counters_dev / tile_cost_dev / tile_order_dev apply to the surface launch only, and
+ * svo_trace_last_ray_count reports the continuation launch (w*h rays: pixels that are not continued get a ray that misses the world). */
+int svo_trace_translucent(svo_world *, const svo_camera *cam, const svo_trace_params *params,
+                          int x0, int y0, int w, int h, svo_hit *surface_dev, svo_hit *behind_dev, void *stream);
+
 /* ---- packed G-buffer (8 bytes / pixel) for the multi-GPU gather ------------------------------------------
  * { float t; uint32 w } with w = material (bits 0-15) | flags & 0xFF (bits 16-23) | normal code (bits 24-30) |
  * SVO_ERR_FLAG (bit 31): per axis 2 bits (0: -, 1: 0, 2: +) in bits 24-29, bit 30 = NaN normal.  cubeNormal only ever yields
@@ -395,6 +420,14 @@ int svo_shade(const svo_camera *cam, const svo_shade_params *p, int x0, int y0, 
  * written per pixel instead of 32 + 16; identical colours (the packed record carries t, normal, material, flags). */
 int svo_shade_packed(const svo_camera *cam, const svo_shade_params *p, int x0, int y0, int w, int h,
                      const uint64_t *packed_dev, float *rgba_dev, void *stream);
+
+/* ParallaxAlpha's blend (shaders/ParallaxAlpha.Fragment.glsl:226-234,315-323) over the two G-buffers of svo_trace_translucent:
+ * C_s = svo_shade of the surface record, C_b = svo_shade of the behind record with its t replaced by t1 + t2 (the distance from the
+ * eye, chunkmarch's own t += s), s = clamp(t2 * absorption, 0, 1) with absorption 0 meaning 0.5 (the reference's water alpha);
+ * rgb = C_b * (1 - s) + C_s * s, depth = C_b's.  The clamp departs from the reference, whose 1 - s goes negative past a path of
+ * 1 / absorption.  A pixel whose behind record misses is C_s; a pixel without SVO_SEE_THROUGH is exactly what svo_shade writes. */
+int svo_shade_translucent(const svo_camera *cam, const svo_shade_params *p, float absorption, int x0, int y0, int w, int h,
+                          const svo_hit *surface_dev, const svo_hit *behind_dev, float *rgba_dev, void *stream);
 
 /* Number of rays the last launch on this world actually marched (primary + shadow, all frames of a
  * svo_trace_frames launch; a multi-frame call served by a kernel other than SVO_KERNEL_STACK is one launch per

@@ -7,6 +7,7 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     World.upload(device)                      <- World::load_gpu        src/World.cpp:57-94
     World.draw(camera, ...)                   <- World::draw            src/World.cpp:205-266
     World.chunkmarch(origins, dirs)           <- chunkmarch             src/Traverse.cpp:127-171
+    World.draw_translucent(camera, m)         <- ParallaxAlpha's march past water   shaders/ParallaxAlpha.Fragment.glsl:141-199,276-335
     World.index / index_float                 <- World::index(_float)   src/World.cpp:288-293,323-332
 
 There is NO CPU fallback: if libsvo_amd.so is missing the import raises, and every device call
@@ -46,7 +47,7 @@ ERR_NAMES = {0: "SVO_OK", -1: "SVO_ERR_INVALID_ARG", -2: "SVO_ERR_NO_DEVICE", -3
 EMPTY, LEAF, BRANCH, TWIG = 0, 1, 2, 3
 KERNEL_AUTO, KERNEL_LITERAL, KERNEL_STACK = 0, 1, 2
 EDIT_BUILD, EDIT_DESTROY, EDIT_REPLACE = 0, 1, 2     # svo_world_edit_box
-HIT_FLAG, SHADOW_TRACED, SHADOWED, FACE_NORMAL, ERR_FLAG = 1, 2, 4, 8, 1 << 15
+HIT_FLAG, SHADOW_TRACED, SHADOWED, FACE_NORMAL, SEE_THROUGH, ERR_FLAG = 1, 2, 4, 8, 16, 1 << 15
 NORMAL_CUBE, NORMAL_FACE = 0, 1
 SEMANTICS_CPU, SEMANTICS_GLSL = 0, 1
 CELL_NONE = 0xFF
@@ -86,7 +87,7 @@ class TraceParams(C.Structure):
                 ("max_twig_steps", C.c_int32), ("shadow", C.c_int32), ("light_dir", C.c_float * 3),
                 ("kernel", C.c_int32), ("tiles_per_wave", C.c_int32), ("counters_dev", C.c_void_p),
                 ("normal_mode", C.c_int32), ("launches_in_flight", C.c_int32),
-                ("tile_cost_dev", C.c_void_p), ("tile_order_dev", C.c_void_p), ("semantics", C.c_int32), ("_pad_semantics", C.c_int32)]
+                ("tile_cost_dev", C.c_void_p), ("tile_order_dev", C.c_void_p), ("semantics", C.c_int32), ("see_through", C.c_uint32)]
 
 
 class Material(C.Structure):
@@ -129,8 +130,8 @@ MAX_FRAMES = 16                     # SVO_MAX_FRAMES
 ABI_SYMBOLS = [
     "svo_world_generate", "svo_world_create", "svo_world_info_get", "svo_world_chunk", "svo_world_destroy",
     "svo_world_index_float", "svo_world_index", "svo_world_upload", "svo_world_update",
-    "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
-    "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_last_ray_count",
+    "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
+    "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_translucent", "svo_trace_last_ray_count",
     "svo_device_count", "svo_device_alloc", "svo_device_free", "svo_device_cache_trim", "svo_memcpy_h2d", "svo_memcpy_d2h",
     "svo_stream_synchronize", "svo_last_error", "svo_abi_version",
 ]
@@ -162,6 +163,8 @@ lib.svo_shade_defaults.argtypes = [C.POINTER(ShadeParams)]
 lib.svo_shade_defaults.restype = None
 lib.svo_shade.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]
 lib.svo_shade_packed.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]
+lib.svo_shade_translucent.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams), C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
+lib.svo_trace_translucent.argtypes = [_P, C.POINTER(Camera), C.POINTER(TraceParams), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]
 lib.svo_world_upload.argtypes = [_P, C.c_int]
 lib.svo_world_update.argtypes = [_P, C.c_int, C.POINTER(ChunkDesc), C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int]
 lib.svo_trace.argtypes = [_P, C.POINTER(Camera), C.POINTER(TraceParams), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]
@@ -269,10 +272,12 @@ def c5_scene() -> dict:
 def trace_params(shadow: bool = False, kernel: int = KERNEL_AUTO, light_dir=(1.0, -1.0, 0.0), eps: float = 0.0,
                  caps=(0, 0, 0), counters_dev: Optional[int] = None, tiles_per_wave: int = 0, normal_mode: int = 0,
                  tile_cost_dev: Optional[int] = None, tile_order_dev: Optional[int] = None, launches_in_flight: int = 0,
-                 semantics: int = 0) -> TraceParams:
-    """semantics: SEMANTICS_CPU (src/Traverse.cpp) / SEMANTICS_GLSL (shaders/Chunkmarch.glsl); eps / caps 0 = that twin's own constants."""
+                 semantics: int = 0, see_through: int = 0) -> TraceParams:
+    """semantics: SEMANTICS_CPU (src/Traverse.cpp) / SEMANTICS_GLSL (shaders/Chunkmarch.glsl); eps / caps 0 = that twin's own constants.
+    see_through: a material (1..0xFFFF) every ray marches through as if it were empty; 0 = off."""
     p = TraceParams()
     p.semantics = semantics
+    p.see_through = see_through
     p.normal_mode = normal_mode
     p.eps = eps
     p.max_chunk_steps, p.max_tree_steps, p.max_twig_steps = caps
@@ -337,6 +342,26 @@ def shade_packed(cam: Camera, params: ShadeParams, rect, packed_ptr: int, rgba_p
     """svo_shade over the 8-byte records of gbuffer_pack."""
     x0, y0, w, h = rect
     _check(lib.svo_shade_packed(C.byref(cam), C.byref(params), x0, y0, w, h, packed_ptr, rgba_ptr, stream), "svo_shade_packed")
+
+
+def shade_translucent(cam: Camera, params: ShadeParams, rect, surface_ptr: int, behind_ptr: int, rgba_ptr: int,
+                      absorption: float = 0.0, stream: int = 0):
+    """svo_shade_translucent: ParallaxAlpha's blend of the two G-buffers of World.trace_translucent (absorption 0 = 0.5)."""
+    x0, y0, w, h = rect
+    _check(lib.svo_shade_translucent(C.byref(cam), C.byref(params), absorption, x0, y0, w, h, surface_ptr, behind_ptr, rgba_ptr, stream),
+           "svo_shade_translucent")
+
+
+def see_through_chunk(chunk: dict, material: int) -> dict:
+    """The chunk as a see-through march of `material` sees it: LEAF nodes of that material (offset & 0xFFFF) and brick cells
+    holding it set to 0, the tree's shape unchanged.  Host numpy; what svo_trace_params.see_through is defined against."""
+    tree = np.array(chunk["tree"], dtype=np.uint32, copy=True)
+    twig = np.array(chunk["twig"], dtype=np.uint16, copy=True)
+    tree[((tree >> 30) == LEAF) & ((tree & 0xFFFF) == material)] = 0
+    twig[twig == material] = 0
+    out = dict(chunk)
+    out["tree"], out["twig"] = tree, twig
+    return out
 
 
 class World:
@@ -480,6 +505,12 @@ class World:
     def trace_rays(self, origins_ptr: int, dirs_ptr: int, n: int, params: TraceParams, out_ptr: int, stream: int = 0):
         _check(lib.svo_trace_rays(self._h, origins_ptr, dirs_ptr, n, C.byref(params), out_ptr, stream), "svo_trace_rays")
 
+    def trace_translucent(self, cam: Camera, params: TraceParams, rect, surface_ptr: int, behind_ptr: int, stream: int = 0):
+        """svo_trace_translucent: the surface G-buffer and, behind every hit of material params.see_through, the continuation's."""
+        x0, y0, w, h = rect
+        _check(lib.svo_trace_translucent(self._h, C.byref(cam), C.byref(params), x0, y0, w, h, surface_ptr, behind_ptr, stream),
+               "svo_trace_translucent")
+
     def tile_order(self, cost_ptr: int, order_ptr: int, ntiles: int, stream: int = 0):
         """svo_tile_order: tile indices by descending cost (of one frame) into order_ptr."""
         _check(lib.svo_tile_order(self._h, cost_ptr, order_ptr, ntiles, stream), "svo_tile_order")
@@ -491,13 +522,13 @@ class World:
 
     # -- convenience: World::draw / chunkmarch returning numpy -------------------------------
     def draw(self, cam: Camera, rect=None, shadow: bool = False, kernel: int = KERNEL_AUTO, counters: bool = False,
-             light_dir=(1.0, -1.0, 0.0), normal_mode: int = 0, semantics: int = 0):
+             light_dir=(1.0, -1.0, 0.0), normal_mode: int = 0, semantics: int = 0, see_through: int = 0):
         """Trace a rectangle of the camera image; returns the G-buffer (HIT_DTYPE[h, w]) [+ counters]."""
         x0, y0, w, h = rect if rect is not None else (0, 0, cam.width, cam.height)
         out = DeviceBuffer(max(w * h, 1) * 32)
         cnt = DeviceBuffer(max(w * h, 1) * 16) if counters else None
         prm = trace_params(shadow=shadow, kernel=kernel, light_dir=light_dir, counters_dev=cnt.ptr if cnt else None, normal_mode=normal_mode,
-                           semantics=semantics)
+                           semantics=semantics, see_through=see_through)
         self.trace(cam, prm, (x0, y0, w, h), out.ptr)
         _check(lib.svo_stream_synchronize(None), "svo_stream_synchronize")
         g = out.to_numpy(HIT_DTYPE, w * h).reshape(h, w)
@@ -508,8 +539,23 @@ class World:
             return g, c
         return g
 
+    def draw_translucent(self, cam: Camera, see_through: int = 6, rect=None, shadow: bool = False, kernel: int = KERNEL_AUTO,
+                         light_dir=(1.0, -1.0, 0.0), normal_mode: int = 0, semantics: int = 0):
+        """svo_trace_translucent over a rectangle of the camera image; returns (surface, behind), HIT_DTYPE[h, w] each."""
+        x0, y0, w, h = rect if rect is not None else (0, 0, cam.width, cam.height)
+        surf, behind = DeviceBuffer(max(w * h, 1) * 32), DeviceBuffer(max(w * h, 1) * 32)
+        prm = trace_params(shadow=shadow, kernel=kernel, light_dir=light_dir, normal_mode=normal_mode, semantics=semantics,
+                           see_through=see_through)
+        self.trace_translucent(cam, prm, (x0, y0, w, h), surf.ptr, behind.ptr)
+        _check(lib.svo_stream_synchronize(None), "svo_stream_synchronize")
+        s, b = surf.to_numpy(HIT_DTYPE, w * h).reshape(h, w), behind.to_numpy(HIT_DTYPE, w * h).reshape(h, w)
+        surf.free()
+        behind.free()
+        return s, b
+
     def chunkmarch(self, origins, dirs, shadow: bool = False, kernel: int = KERNEL_AUTO, counters: bool = False,
-                   light_dir=(1.0, -1.0, 0.0), eps: float = 0.0, caps=(0, 0, 0), normal_mode: int = 0, semantics: int = 0):
+                   light_dir=(1.0, -1.0, 0.0), eps: float = 0.0, caps=(0, 0, 0), normal_mode: int = 0, semantics: int = 0,
+                   see_through: int = 0):
         """chunkmarch over a ray list (src/Traverse.cpp:127-171); returns HIT_DTYPE[n] [+ counters]."""
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
@@ -518,7 +564,7 @@ class World:
         out = DeviceBuffer(max(n, 1) * 32)
         cnt = DeviceBuffer(max(n, 1) * 16) if counters else None
         prm = trace_params(shadow=shadow, kernel=kernel, light_dir=light_dir, eps=eps, caps=caps,
-                           counters_dev=cnt.ptr if cnt else None, normal_mode=normal_mode, semantics=semantics)
+                           counters_dev=cnt.ptr if cnt else None, normal_mode=normal_mode, semantics=semantics, see_through=see_through)
         self.trace_rays(od.ptr, dd.ptr, n, prm, out.ptr)
         _check(lib.svo_stream_synchronize(None), "svo_stream_synchronize")
         g = out.to_numpy(HIT_DTYPE, n)

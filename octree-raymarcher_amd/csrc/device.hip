@@ -24,6 +24,7 @@
 
 #include "kernel_literal.hip.h"
 #include "kernel_stack.hip.h"
+#include "see_through.hip.h"
 #include "wide_tree.hip.h"
 #include "world.h"
 
@@ -148,10 +149,19 @@ static void pool_free(void *p)
     if (evict) (void)hipFree(evict);
 }
 
+// the see-through view (see_through.hip.h) and the continuation scratch: every change to the pools drops the view
+static void drop_view(svo_world &w)
+{
+    if (w.d_view_wide || w.d_view_mask) (void)hipDeviceSynchronize();
+    pool_free(w.d_view_wide); pool_free(w.d_view_mask);
+    w.d_view_wide = nullptr; w.d_view_mask = nullptr; w.view_material = 0;
+}
+
 int release_device(svo_world &w, bool keep_builder)
 {
     if (w.device >= 0) {
         (void)hipSetDevice(w.device);
+        drop_view(w);
         if (!keep_builder) free_builder_context(w);
         (void)hipDeviceSynchronize();                       // the large buffers may be handed to another world at once: nothing may still use them
         (void)hipFree(w.d_chunks); pool_free(w.d_tree); pool_free(w.d_twig);
@@ -159,7 +169,11 @@ int release_device(svo_world &w, bool keep_builder)
         pool_free(w.d_wide); pool_free(w.d_wbase); (void)hipFree(w.d_wchunks); pool_free(w.d_wscratch); (void)hipFree(w.d_sort);
         for (void *e : w.work_event) if (e) (void)hipEventDestroy((hipEvent_t)e);
         if (w.sort_event) (void)hipEventDestroy((hipEvent_t)w.sort_event);
+        (void)hipFree(w.d_cont);
+        if (w.view_event) (void)hipEventDestroy((hipEvent_t)w.view_event);
+        if (w.cont_event) (void)hipEventDestroy((hipEvent_t)w.cont_event);
     }
+    w.d_cont = nullptr; w.cont_rays = 0; w.view_event = nullptr; w.cont_event = nullptr;
     w.work_event.clear();
     w.d_chunks = nullptr; w.d_tree = nullptr; w.d_twig = nullptr; w.d_mask = nullptr; w.d_bmat = nullptr; w.d_work = nullptr;
     w.d_wide = nullptr; w.d_wbase = nullptr; w.d_wchunks = nullptr; w.d_wscratch = nullptr; w.wscratch_words = 0; w.wscan_words = 0;
@@ -377,6 +391,7 @@ static bool wide_fits(const svo_world &w, int chunk)
 
 static void drop_wide(svo_world &w)
 {
+    drop_view(w);
     if (w.d_wide || w.d_wbase) (void)hipDeviceSynchronize();
     pool_free(w.d_wide); pool_free(w.d_wbase); w.d_wide = w.d_wbase = nullptr;
     w.wide_ok = false;
@@ -580,6 +595,7 @@ static int install_chunk(svo_world &w, int chunk, const uint32_t *tree, const ui
 {
     HIP_TRY(hipSetDevice(w.device));
     HIP_TRY(hipDeviceSynchronize());
+    drop_view(w);                                                       // rebuilt from the new pools at the next see-through launch
     ChunkPools &c = w.chunks[(size_t)chunk];
     DevChunk &e = w.table[(size_t)chunk];
     const uint64_t trees = c.tree_count(), twigs = c.twig_count();
@@ -753,6 +769,7 @@ extern "C" {
 static int fill_common(svo_world *w, const svo_trace_params *prm, TraceArgs &A)
 {
     if (!w) return SVO_ERR_INVALID_ARG;
+    if (prm && prm->see_through > 0xFFFFu) { set_error("svo_trace: see_through is a 16-bit material"); return SVO_ERR_INVALID_ARG; }
     if (w->device < 0) { set_error("svo_trace: world is not uploaded"); return SVO_ERR_NOT_UPLOADED; }
     std::memset(&A, 0, sizeof A);
     // src/Traverse.cpp:129-133
@@ -852,11 +869,50 @@ static int launch_stack(svo_world *w, const TraceArgs &A, int tiles_per_wave, in
     return SVO_OK;
 }
 
+// The see-through view of material m (see_through.hip.h) for a stack-kernel launch on `s`: built on the device at the first such
+// launch after a change to the pools, rebuilt in place when m changes - on the device behind every launch of the world issued
+// before (the work-slot events), so that none still reading the old view sees the new one - and awaited by every launch that uses it.
+static int use_view(svo_world *w, uint32_t m, TraceArgs &A, hipStream_t s)
+{
+    hipEvent_t &built = reinterpret_cast<hipEvent_t &>(w->view_event);
+    if (w->view_material != m) {
+        const uint64_t n4 = w->wide_pool_len * 16, bricks = w->twig_pool_len;       // (64 entries = 16 uint4 per wide node)
+        if (!w->d_view_wide) {
+            if (pool_malloc((void **)&w->d_view_wide, std::max<uint64_t>(n4, 1) * sizeof(uint4), w->device) != hipSuccess ||
+                pool_malloc((void **)&w->d_view_mask, std::max<uint64_t>(bricks, 1) * sizeof(uint64_t), w->device) != hipSuccess) {
+                pool_free(w->d_view_wide); w->d_view_wide = nullptr; w->d_view_mask = nullptr;
+                set_error("svo_trace: hipMalloc of the see-through view failed"); return SVO_ERR_OUT_OF_MEMORY;
+            }
+        } else {
+            for (void *e : w->work_event) if (e) HIP_TRY(hipStreamWaitEvent(s, (hipEvent_t)e, 0));
+        }
+        w->view_material = 0;                                           // (until the build below is issued)
+        if ((n4 + 255) / 256 > 0x7FFFFFFFull || (bricks * 8 + 255) / 256 > 0x7FFFFFFFull) { set_error("svo_trace: pools too large for one view launch"); return SVO_ERR_UNSUPPORTED; }
+        if (n4) hipLaunchKernelGGL(k_view_wide, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const uint4 *>(w->d_wide),
+                                   reinterpret_cast<uint4 *>(w->d_view_wide), n4, m);
+        if (bricks) hipLaunchKernelGGL(k_view_mask, dim3((unsigned)((bricks * 8 + 255) / 256)), dim3(256), 0, s, w->d_twig, w->d_mask, w->d_view_mask, bricks, m);
+        HIP_TRY(hipGetLastError());
+        if (!built) HIP_TRY(hipEventCreateWithFlags(&built, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(built, s));
+        w->view_material = m;
+    } else {
+        HIP_TRY(hipStreamWaitEvent(s, built, 0));
+    }
+    A.wide = w->d_view_wide;
+    A.mask = w->d_view_mask;
+    return SVO_OK;
+}
+
 static int launch(svo_world *w, const svo_trace_params *prm, TraceArgs &A, hipStream_t s)
 {
     const int kernel = pick_kernel(w, prm, A);
     if (kernel < 0) return kernel;
     HIP_TRY(hipSetDevice(w->device));
+    const uint32_t see = prm ? prm->see_through : 0u;
+    if (see && kernel == SVO_KERNEL_STACK) {
+        const int rc = use_view(w, see, A, s);
+        if (rc != SVO_OK) return rc;
+    }
     // every launch gets its own {tile cursor, ray count} slot so that launches on different streams may overlap
     w->work_last = w->work_next;
     w->work_next = (w->work_next + 1) % WORK_SLOTS;
@@ -871,7 +927,8 @@ static int launch(svo_world *w, const svo_trace_params *prm, TraceArgs &A, hipSt
     if (kernel == SVO_KERNEL_LITERAL) {
         const int64_t blocks = (A.n + 255) / 256;
         if (blocks > 0x7FFFFFFF) { set_error("svo_trace: too many rays for one launch"); return SVO_ERR_UNSUPPORTED; }
-        hipLaunchKernelGGL(k_trace_literal, dim3((unsigned)blocks), dim3(256), 0, s, A);
+        if (see) hipLaunchKernelGGL(k_trace_literal_st, dim3((unsigned)blocks), dim3(256), 0, s, A, see);
+        else hipLaunchKernelGGL(k_trace_literal, dim3((unsigned)blocks), dim3(256), 0, s, A);
     } else {
         if (A.ntiles > (1 << 25)) { set_error("svo_trace: more than 2^31 rays in one stack-kernel launch"); return SVO_ERR_UNSUPPORTED; }
         if (A.tile_cost) HIP_TRY(hipMemsetAsync(A.tile_cost, 0, (size_t)A.ntiles * (size_t)(A.from_camera ? A.nframes : 1) * 2 * sizeof(uint32_t), s));
@@ -983,6 +1040,52 @@ int svo_trace_rays(svo_world *w, const float *origins_dev, const float *dirs_dev
     A.ntiles = (int32_t)tiles;
     A.out = out_dev;
     return launch(w, prm, A, (hipStream_t)stream);
+}
+
+// ParallaxAlpha's second march (shaders/ParallaxAlpha.Fragment.glsl:141-199,276-335): the surface, the continuation list of the
+// pixels that hit material m (see_through.hip.h k_continuation), one ray-list launch on the see-through world into behind_dev.
+int svo_trace_translucent(svo_world *w, const svo_camera *cam, const svo_trace_params *prm, int x0, int y0, int rw, int rh,
+                          svo_hit *surface_dev, svo_hit *behind_dev, void *stream)
+{
+    if (!w || !prm || !cam || !surface_dev || !behind_dev) { set_error("svo_trace_translucent: bad argument"); return SVO_ERR_INVALID_ARG; }
+    const uint32_t m = prm->see_through;
+    if (m == 0u || m > 0xFFFFu) { set_error("svo_trace_translucent: see_through must be a material in 1..0xFFFF"); return SVO_ERR_INVALID_ARG; }
+    if (w->device < 0) { set_error("svo_trace_translucent: world is not uploaded"); return SVO_ERR_NOT_UPLOADED; }
+    hipStream_t s = (hipStream_t)stream;
+    svo_trace_params surface = *prm;
+    surface.see_through = 0;
+    int rc = svo_trace(w, cam, &surface, x0, y0, rw, rh, surface_dev, stream);
+    if (rc != SVO_OK) return rc;
+    const int64_t n = (int64_t)rw * rh;
+    if (n == 0) return SVO_OK;
+    HIP_TRY(hipSetDevice(w->device));
+    // the list lives in the world's scratch: calls on different streams are ordered behind one another (as svo_tile_order's sort)
+    hipEvent_t &done = reinterpret_cast<hipEvent_t &>(w->cont_event);
+    if (n > w->cont_rays) {
+        if (w->d_cont) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(w->d_cont); w->d_cont = nullptr; w->cont_rays = 0; }
+        if (hipMalloc((void **)&w->d_cont, (size_t)n * 6 * sizeof(float)) != hipSuccess) { set_error("svo_trace_translucent: hipMalloc failed"); return SVO_ERR_OUT_OF_MEMORY; }
+        w->cont_rays = n;
+    }
+    if (done) HIP_TRY(hipStreamWaitEvent(s, done, 0));
+    else HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+    float *origins = w->d_cont, *dirs = w->d_cont + 3 * n;
+    FrameCam fc;
+    std::memcpy(fc.eye, cam->eye, sizeof fc.eye); std::memcpy(fc.fwd, cam->forward, sizeof fc.fwd);
+    std::memcpy(fc.right, cam->right, sizeof fc.right); std::memcpy(fc.up, cam->up, sizeof fc.up);
+    fc.tanx = cam->tan_half_x; fc.tany = cam->tan_half_y;
+    // the miss ray's origin: below the world box on y and z (by the box's extent), so that its line never meets the box
+    const float cs = (float)w->chunksize;
+    const float miny = (float)(w->chunkcoordmin[1] * (int)cs), minz = (float)(w->chunkcoordmin[2] * (int)cs);
+    const float oy = miny - (float)w->height * cs - cs, oz = minz - (float)w->depth * cs - cs;
+    hipLaunchKernelGGL(k_continuation, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, fc, cam->width, cam->height, x0, y0, rw, n, m,
+                       (float)(w->chunkcoordmin[0] * (int)cs), oy, oz, reinterpret_cast<uint4 *>(surface_dev), origins, dirs);
+    HIP_TRY(hipGetLastError());
+    svo_trace_params behind = *prm;                                     // (the caller's per-ray and per-tile buffers are sized for the surface)
+    behind.counters_dev = nullptr; behind.tile_cost_dev = nullptr; behind.tile_order_dev = nullptr;
+    rc = svo_trace_rays(w, origins, dirs, n, &behind, behind_dev, stream);
+    if (rc != SVO_OK) return rc;
+    HIP_TRY(hipEventRecord(done, s));
+    return SVO_OK;
 }
 
 int svo_tile_order(svo_world *w, const uint32_t *cost_dev, uint32_t *order_dev, int ntiles, void *stream)

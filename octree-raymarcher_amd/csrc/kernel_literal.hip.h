@@ -6,6 +6,10 @@
 //
 //   traverse   src/Traverse.cpp:34-48      twigmarch  src/Traverse.cpp:50-72
 //   treemarch  src/Traverse.cpp:74-113     chunkmarch src/Traverse.cpp:127-171
+//
+// ST: the see-through instantiation (svo_trace_params.see_through): a LEAF of material `ignore` is stepped over as an EMPTY node
+// and a brick cell holding it as an empty cell, like Chunkmarch.glsl's `ignore` (:190-191,240-241,280).  k_trace_literal is the
+// ST = false one (its device code is unchanged by the template), k_trace_literal_st the other.
 #pragma once
 #include "march.hip.h"
 
@@ -65,8 +69,9 @@ __device__ inline int lit_creep_run(V3 a, V3 b, V3 g, float t0, V3 lo, float siz
     return K;
 }
 
+template <bool ST>
 __device__ inline bool lit_brick(const TraceArgs &A, V3 a, V3 b, V3 g, V3 lo, float size, float voxel,
-                                 const uint16_t *cells, float &s, Voxel &vox, LitCounters &cnt, uint32_t &guard)
+                                 const uint16_t *cells, float &s, Voxel &vox, LitCounters &cnt, uint32_t &guard, uint32_t ignore)
 {
     const V3 hi = lo + size;
     float t = 0.0f;
@@ -81,7 +86,7 @@ __device__ inline bool lit_brick(const TraceArgs &A, V3 a, V3 b, V3 g, V3 lo, fl
         cnt.brick_cells++;
         const V3 vlo = lo + mk((float)ox, (float)oy, (float)oz) * voxel;
         const uint32_t m = cells[word];
-        if (m != 0) {
+        if (m != 0 && (!ST || m != ignore)) {
             s = t;
             vox.lo = vlo; vox.size = voxel; vox.material = m; vox.cell = word;
             return true;
@@ -97,8 +102,9 @@ __device__ inline bool lit_brick(const TraceArgs &A, V3 a, V3 b, V3 g, V3 lo, fl
     return false;
 }
 
+template <bool ST>
 __device__ inline bool lit_tree(const TraceArgs &A, V3 a, V3 b, V3 g, const DevChunk &ch, float rootsize,
-                                float &s, Voxel &vox, LitCounters &cnt, uint32_t &guard)
+                                float &s, Voxel &vox, LitCounters &cnt, uint32_t &guard, uint32_t ignore)
 {
     const uint32_t *tree = A.tree + ch.tree_off;
     const V3 rlo = ld3(ch.bmin), rhi = rlo + rootsize;
@@ -125,7 +131,8 @@ __device__ inline bool lit_tree(const TraceArgs &A, V3 a, V3 b, V3 g, const DevC
             size = half;
         }
         const uint32_t type = node_type(word);
-        if (type == LEAF) {
+        const bool ignored = ST && type == LEAF && (node_offset(word) & 0xFFFFu) == ignore;      // stepped over as an EMPTY node
+        if (type == LEAF && !ignored) {
             s = t - A.leaf_back;                                // src/Traverse.cpp:93 (t - EPS) / shaders/Chunkmarch.glsl:266 (t)
             vox.lo = lo; vox.size = size; vox.material = node_offset(word) & 0xFFFFu; vox.node = node; vox.cell = SVO_CELL_NONE;
             return true;
@@ -133,7 +140,7 @@ __device__ inline bool lit_tree(const TraceArgs &A, V3 a, V3 b, V3 g, const DevC
         if (type == TWIG) {
             const float voxel = size / 4.0f;
             const uint16_t *cells = A.twig + (ch.twig_off + node_offset(word)) * TWIG_WORDS;
-            if (lit_brick(A, p, b, g, lo, size, voxel, cells, s, vox, cnt, guard)) {
+            if (lit_brick<ST>(A, p, b, g, lo, size, voxel, cells, s, vox, cnt, guard, ignore)) {
                 s += t;
                 vox.node = node;
                 return true;
@@ -143,7 +150,7 @@ __device__ inline bool lit_tree(const TraceArgs &A, V3 a, V3 b, V3 g, const DevC
         }
         const float e = guarded(escape(p, g, lo, lo + size), A.guard_eps) + A.eps;
         t += e;
-        if (A.exact_geometry && type == EMPTY && e < 2.0f * A.eps) {   // a pinned step over an EMPTY node: the following ones in closed form
+        if (A.exact_geometry && (type == EMPTY || ignored) && e < 2.0f * A.eps) {   // a pinned step over an EMPTY node: the following ones in closed form
             const int K = lit_creep_run(a, b, g, t, lo, size, A.eps, min(A.cap_tree - 1 - i, (int)(STEP_GUARD - guard)), false, lo, size);
             t += (float)K * A.eps;
             i += K; guard += (uint32_t)K; cnt.tree_steps += (uint32_t)K; cnt.node_words += (uint32_t)K * words;
@@ -154,8 +161,9 @@ __device__ inline bool lit_tree(const TraceArgs &A, V3 a, V3 b, V3 g, const DevC
 
 // `runaway` is set when the ray used up STEP_GUARD march steps (the kernels' bound on a single ray; the reference itself
 // would keep going): the caller flags the record with SVO_ERR_FLAG, as the stack kernel does.
+template <bool ST>
 __device__ inline bool lit_world(const TraceArgs &A, V3 alpha, V3 beta, float &tout, Voxel &vox, uint32_t &chunk,
-                                 LitCounters &cnt, bool &runaway)
+                                 LitCounters &cnt, bool &runaway, uint32_t ignore)
 {
     const V3 wlo = ld3(A.worldmin), whi = ld3(A.worldmax);
     const V3 g = recip(beta);
@@ -175,7 +183,7 @@ __device__ inline bool lit_world(const TraceArgs &A, V3 alpha, V3 beta, float &t
         if (!A.glsl && !inside(p, clo, chi)) return false;      // (src/Traverse.cpp:154-155; the shader has no such check: its treemarch just fails)
         float s = 0.0f;
         const float rootsize = A.chunksize;             // Ocroot::size == chunksize (checked on create)
-        if (lit_tree(A, p, beta, g, ch, rootsize, s, vox, cnt, guard)) {
+        if (lit_tree<ST>(A, p, beta, g, ch, rootsize, s, vox, cnt, guard, ignore)) {
             t += s;
             tout = t;
             chunk = (uint32_t)ci;
@@ -211,14 +219,14 @@ __global__ __launch_bounds__(256) void k_trace_literal(TraceArgs A)
         uint32_t chunk = 0;
         rays = 1;
         bool runaway = false;
-        if (lit_world(A, o, d, t, vox, chunk, cnt, runaway)) {
+        if (lit_world<false>(A, o, d, t, vox, chunk, cnt, runaway, 0u)) {
             const V3 point = o + d * (t - A.eps);
             const bool face = A.normal_mode == SVO_NORMAL_FACE;
             const V3 n = face ? face_normal(point, vox.lo, vox.lo + vox.size, d) : cube_normal(point, vox.lo, vox.lo + vox.size, A.eps);
             uint32_t flags = SVO_HIT_FLAG | (face ? (uint32_t)SVO_FACE_NORMAL : 0u);
             if (A.shadow) {
                 Voxel sv; float st; uint32_t sc;
-                const bool occluded = lit_world(A, point, ld3(A.sdir), st, sv, sc, cnt, runaway);
+                const bool occluded = lit_world<false>(A, point, ld3(A.sdir), st, sv, sc, cnt, runaway, 0u);
                 flags |= SVO_SHADOW_TRACED | (occluded ? SVO_SHADOWED : 0u) | (runaway ? (uint32_t)SVO_ERR_FLAG : 0u);
                 rays = 2;
             }
@@ -236,5 +244,58 @@ __global__ __launch_bounds__(256) void k_trace_literal(TraceArgs A)
     for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off, 64);
     if ((threadIdx.x & 63) == 0 && total) atomicAdd(&A.work[1], (unsigned long long)total);
 }
+
+// The see-through instantiation: the same body with lit_world<true>.  (It is not shared through a device function: a kernel that
+// calls one is scheduled differently, and k_trace_literal is kept as it was, instruction for instruction.)
+__global__ __launch_bounds__(256) void k_trace_literal_st(TraceArgs A, uint32_t ignore)
+{
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned rays = 0;
+    bool live = k < A.n;
+    V3 o = mk(0, 0, 0), d = mk(0, 0, 1);
+    if (live) {
+        if (A.from_camera) {
+            int px, py;
+            local_to_pixel(A, (int)(k % A.w), (int)(k / A.w), px, py);
+            if (py >= A.imgh || px >= A.imgw) { store_miss(A.out, k, 0); live = false; }
+            else camera_ray(A.cams[0], A.imgw, A.imgh, px, py, o, d);
+        } else {
+            o = ld3(A.origins + 3 * k);
+            d = ld3(A.dirs + 3 * k);
+        }
+    }
+    if (live) {
+        LitCounters cnt = { 0, 0, 0, 0 };
+        Voxel vox; vox.lo = mk(0, 0, 0); vox.size = 0; vox.material = 0; vox.node = 0; vox.cell = 0;
+        float t = 0.0f;
+        uint32_t chunk = 0;
+        rays = 1;
+        bool runaway = false;
+        if (lit_world<true>(A, o, d, t, vox, chunk, cnt, runaway, ignore)) {
+            const V3 point = o + d * (t - A.eps);
+            const bool face = A.normal_mode == SVO_NORMAL_FACE;
+            const V3 n = face ? face_normal(point, vox.lo, vox.lo + vox.size, d) : cube_normal(point, vox.lo, vox.lo + vox.size, A.eps);
+            uint32_t flags = SVO_HIT_FLAG | (face ? (uint32_t)SVO_FACE_NORMAL : 0u);
+            if (A.shadow) {
+                Voxel sv; float st; uint32_t sc;
+                const bool occluded = lit_world<true>(A, point, ld3(A.sdir), st, sv, sc, cnt, runaway, ignore);
+                flags |= SVO_SHADOW_TRACED | (occluded ? SVO_SHADOWED : 0u) | (runaway ? (uint32_t)SVO_ERR_FLAG : 0u);
+                rays = 2;
+            }
+            store_hit(A.out, k, t, n, vox.material, flags, chunk, vox.node, vox.cell);
+        } else {
+            store_miss(A.out, k, runaway ? (uint32_t)SVO_ERR_FLAG : 0u);
+        }
+        if (A.counters) {
+            uint4 c; c.x = cnt.node_words; c.y = cnt.brick_cells; c.z = cnt.chunk_descs; c.w = cnt.tree_steps;
+            reinterpret_cast<uint4 *>(A.counters)[k] = c;
+        }
+    }
+    // rays marched: one atomic per wave (all 64 lanes reach this point)
+    unsigned total = rays;
+    for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off, 64);
+    if ((threadIdx.x & 63) == 0 && total) atomicAdd(&A.work[1], (unsigned long long)total);
+}
+
 
 } // namespace svo

@@ -58,26 +58,9 @@ __device__ __forceinline__ V3 normal_from_code(uint32_t code)
     return mk(ix * inv, iy * inv, iz * inv);
 }
 
-// PACKED: the G-buffer is the 8-byte form of svo_gbuffer_pack (8 B read + 16 B written per pixel instead of 32 + 16)
-template <bool PACKED>
-__global__ __launch_bounds__(256) void k_shade(ShadeArgs A)
+// One pixel's {r, g, b, depth} from its record (a hit: SVO_HIT_FLAG) - the body of k_shade, shared with k_shade_translucent
+__device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, uint32_t flags, uint32_t material, float t, V3 n)
 {
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= (int64_t)A.w * A.h) return;
-    uint32_t flags, material;
-    float t;
-    V3 n;
-    if (PACKED) {
-        const uint2 r = reinterpret_cast<const uint2 *>(A.gbuffer)[k];
-        t = __uint_as_float(r.x); material = r.y & 0xFFFFu; flags = (r.y >> 16) & 0xFFu;
-        n = normal_from_code((r.y >> 24) & 0x7Fu);
-    } else {
-        const uint4 r0 = A.gbuffer[2 * k], r1 = A.gbuffer[2 * k + 1];
-        flags = r1.x >> 16; material = r1.x & 0xFFFFu;
-        t = __uint_as_float(r0.x);
-        n = mk(__uint_as_float(r0.y), __uint_as_float(r0.z), __uint_as_float(r0.w));
-    }
-    if (!(flags & SVO_HIT_FLAG)) { A.rgba[k] = make_float4(0.0f, 0.0f, 0.0f, 1.0f); return; }       // discard
     const svo_shade_params &P = A.P;
     // the ray of this pixel (same generation as the march) and the shaded point alpha + beta * (sigma - EPS), :174
     const int px = A.x0 + (int)(k % A.w), py = A.y0 + (int)(k / A.w);
@@ -137,7 +120,54 @@ __global__ __launch_bounds__(256) void k_shade(ShadeArgs A)
         const V3 spe = ((ld3(P.spot.specular) * s) * specular) * lit;
         color = color + (amb + (dif + spe) * intensity) * att;
     }
-    A.rgba[k] = make_float4(color.x, color.y, color.z, (rcp_fast(zdist) - A.inv_near) * A.inv_depth_range);     // :193-197
+    return make_float4(color.x, color.y, color.z, (rcp_fast(zdist) - A.inv_near) * A.inv_depth_range);     // :193-197
+}
+
+// PACKED: the G-buffer is the 8-byte form of svo_gbuffer_pack (8 B read + 16 B written per pixel instead of 32 + 16)
+template <bool PACKED>
+__global__ __launch_bounds__(256) void k_shade(ShadeArgs A)
+{
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= (int64_t)A.w * A.h) return;
+    uint32_t flags, material;
+    float t;
+    V3 n;
+    if (PACKED) {
+        const uint2 r = reinterpret_cast<const uint2 *>(A.gbuffer)[k];
+        t = __uint_as_float(r.x); material = r.y & 0xFFFFu; flags = (r.y >> 16) & 0xFFu;
+        n = normal_from_code((r.y >> 24) & 0x7Fu);
+    } else {
+        const uint4 r0 = A.gbuffer[2 * k], r1 = A.gbuffer[2 * k + 1];
+        flags = r1.x >> 16; material = r1.x & 0xFFFFu;
+        t = __uint_as_float(r0.x);
+        n = mk(__uint_as_float(r0.y), __uint_as_float(r0.z), __uint_as_float(r0.w));
+    }
+    if (!(flags & SVO_HIT_FLAG)) { A.rgba[k] = make_float4(0.0f, 0.0f, 0.0f, 1.0f); return; }       // discard
+    A.rgba[k] = shade_hit(A, k, flags, material, t, n);
+}
+
+// svo_shade_translucent (shaders/ParallaxAlpha.Fragment.glsl:315-323): surface colour C_s, colour C_b of the behind record at the
+// eye distance t1 + t2, blended by s = clamp(t2 * absorption, 0, 1); depth is C_b's.  A.gbuffer is the surface, `behind` the
+// continuation records.
+__global__ __launch_bounds__(256) void k_shade_translucent(ShadeArgs A, const uint4 *behind, float absorption)
+{
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= (int64_t)A.w * A.h) return;
+    const uint4 r0 = A.gbuffer[2 * k], r1 = A.gbuffer[2 * k + 1];
+    const uint32_t flags = r1.x >> 16;
+    if (!(flags & SVO_HIT_FLAG)) { A.rgba[k] = make_float4(0.0f, 0.0f, 0.0f, 1.0f); return; }
+    const float t1 = __uint_as_float(r0.x);
+    const float4 cs = shade_hit(A, k, flags, r1.x & 0xFFFFu, t1, mk(__uint_as_float(r0.y), __uint_as_float(r0.z), __uint_as_float(r0.w)));
+    const uint4 b0 = behind[2 * k], b1 = behind[2 * k + 1];
+    const uint32_t bflags = b1.x >> 16;
+    if (!(flags & SVO_SEE_THROUGH) || !(bflags & SVO_HIT_FLAG)) { A.rgba[k] = cs; return; }
+    const float t2 = __uint_as_float(b0.x);
+    const float4 cb = shade_hit(A, k, bflags, b1.x & 0xFFFFu, t1 + t2, mk(__uint_as_float(b0.y), __uint_as_float(b0.z), __uint_as_float(b0.w)));
+    float s = t2 * absorption;
+    s = (s < 0.0f) ? 0.0f : s;
+    s = (1.0f < s) ? 1.0f : s;
+    const float r = 1.0f - s;
+    A.rgba[k] = make_float4(cb.x * r + cs.x * s, cb.y * r + cs.y * s, cb.z * r + cs.z * s, cb.w);
 }
 
 // ---- packed G-buffer -------------------------------------------------------------------------------------------
@@ -235,8 +265,9 @@ static int pack_common(const void *in, void *out, int64_t n, void *stream, bool 
 int svo_gbuffer_pack(const svo_hit *gbuffer_dev, uint64_t *packed_dev, int64_t n, void *stream) { return pack_common(gbuffer_dev, packed_dev, n, stream, true); }
 int svo_gbuffer_unpack(const uint64_t *packed_dev, svo_hit *gbuffer_dev, int64_t n, void *stream) { return pack_common(packed_dev, gbuffer_dev, n, stream, false); }
 
+// kind: 0 = svo_shade, 1 = svo_shade_packed, 2 = svo_shade_translucent (behind_dev, absorption)
 static int shade_impl(const svo_camera *cam, const svo_shade_params *p, int x0, int y0, int w, int h,
-                      const void *gbuffer_dev, float *rgba_dev, void *stream, bool packed)
+                      const void *gbuffer_dev, float *rgba_dev, void *stream, int kind, const void *behind_dev = nullptr, float absorption = 0.0f)
 {
     if (!cam || !p || !gbuffer_dev || !rgba_dev || w < 0 || h < 0 || x0 < 0 || y0 < 0 || cam->width <= 0 || cam->height <= 0) {
         set_error("svo_shade: bad argument"); return SVO_ERR_INVALID_ARG;
@@ -270,8 +301,11 @@ static int shade_impl(const svo_camera *cam, const svo_shade_params *p, int x0, 
     A.rgba = reinterpret_cast<float4 *>(rgba_dev);
     const int64_t n = (int64_t)w * h;
     if (n == 0) return SVO_OK;
-    if (packed) hipLaunchKernelGGL(k_shade<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
-    else hipLaunchKernelGGL(k_shade<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (kind == 1) hipLaunchKernelGGL(k_shade<true>, grid, dim3(256), 0, (hipStream_t)stream, A);
+    else if (kind == 0) hipLaunchKernelGGL(k_shade<false>, grid, dim3(256), 0, (hipStream_t)stream, A);
+    else hipLaunchKernelGGL(k_shade_translucent, grid, dim3(256), 0, (hipStream_t)stream, A, reinterpret_cast<const uint4 *>(behind_dev),
+                            absorption == 0.0f ? 0.5f : absorption);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error(std::string("svo_shade: ") + hipGetErrorString(e)); return e == hipErrorNoDevice ? SVO_ERR_NO_DEVICE : SVO_ERR_HIP; }
     return SVO_OK;
@@ -280,13 +314,20 @@ static int shade_impl(const svo_camera *cam, const svo_shade_params *p, int x0, 
 int svo_shade(const svo_camera *cam, const svo_shade_params *p, int x0, int y0, int w, int h,
               const svo_hit *gbuffer_dev, float *rgba_dev, void *stream)
 {
-    return shade_impl(cam, p, x0, y0, w, h, gbuffer_dev, rgba_dev, stream, false);
+    return shade_impl(cam, p, x0, y0, w, h, gbuffer_dev, rgba_dev, stream, 0);
 }
 
 int svo_shade_packed(const svo_camera *cam, const svo_shade_params *p, int x0, int y0, int w, int h,
                      const uint64_t *packed_dev, float *rgba_dev, void *stream)
 {
-    return shade_impl(cam, p, x0, y0, w, h, packed_dev, rgba_dev, stream, true);
+    return shade_impl(cam, p, x0, y0, w, h, packed_dev, rgba_dev, stream, 1);
+}
+
+int svo_shade_translucent(const svo_camera *cam, const svo_shade_params *p, float absorption, int x0, int y0, int w, int h,
+                          const svo_hit *surface_dev, const svo_hit *behind_dev, float *rgba_dev, void *stream)
+{
+    if (!behind_dev || !(absorption >= 0.0f)) { set_error("svo_shade_translucent: bad argument"); return SVO_ERR_INVALID_ARG; }
+    return shade_impl(cam, p, x0, y0, w, h, surface_dev, rgba_dev, stream, 2, behind_dev, absorption);
 }
 
 } // extern "C"

@@ -48,6 +48,15 @@ struct svo_world {
     std::vector<uint64_t> tree_slot, twig_slot;   // capacity of each chunk's slot (nodes / bricks)
     uint64_t tree_pool_len = 0, twig_pool_len = 0;    // elements in use (incl. alignment padding)
     uint64_t tree_pool_cap = 0, twig_pool_cap = 0;    // elements allocated
+    // see-through view (svo_trace_params.see_through, see_through.hip.h): the wide and mask pools with one material taken out, built
+    // on the device at the first launch that asks for it, dropped by every change to the pools
+    uint32_t *d_view_wide = nullptr;
+    uint64_t *d_view_mask = nullptr;
+    uint32_t view_material = 0;                   // material the view holds; 0 = no view
+    void *view_event = nullptr;                   // hipEvent_t behind the view's build: launches on other streams wait for it
+    float *d_cont = nullptr;                      // svo_trace_translucent: continuation origins and directions, [2][cont_rays][3]
+    int64_t cont_rays = 0;
+    void *cont_event = nullptr;                   // hipEvent_t behind the last continuation launch (the next call waits before reusing d_cont)
     int stack_blocks[12] = {};                    // persistent-grid size per k_trace_stack instantiation (device.hip: STACK_KERNELS); 0 = not queried yet
 };
 
