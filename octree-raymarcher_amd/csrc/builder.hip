@@ -307,15 +307,15 @@ inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + pe
 struct DevicePyramidBuilder {
     DevBuf<float> lo, hi;
     DevPyramid view{};
-    int build(uint32_t res, float ampl, float period, float xshift, float yshift, float zshift, hipStream_t s)
+    int build(const ColumnPyramid &a, hipStream_t s)
     {
         uint32_t levels = 0;
-        while ((1u << levels) < res) ++levels;
+        while ((1u << levels) < a.res) ++levels;
         const size_t total = HeightPyramid::level_offset(levels + 1);
         int rc;
         if ((rc = lo.reserve(total, false, s)) != SVO_OK || (rc = hi.reserve(total, false, s)) != SVO_OK) return rc;
         float *blo = lo.p + HeightPyramid::level_offset(levels), *bhi = hi.p + HeightPyramid::level_offset(levels);
-        hipLaunchKernelGGL(k_noise_base, dim3(blocks_for((uint64_t)res * res, 256)), dim3(256), 0, s, blo, bhi, res, period, xshift, zshift);
+        hipLaunchKernelGGL(k_noise_base, dim3(blocks_for((uint64_t)a.res * a.res, 256)), dim3(256), 0, s, blo, bhi, a.res, a.period, a.xshift, a.zshift);
         for (uint32_t lv = levels; lv > 0; --lv) {
             const uint32_t sdim = 1u << lv;
             hipLaunchKernelGGL(k_mip_level, dim3(blocks_for((uint64_t)(sdim / 2) * (sdim / 2), 256)), dim3(256), 0, s,
@@ -323,7 +323,7 @@ struct DevicePyramidBuilder {
                                lo.p + HeightPyramid::level_offset(lv - 1), hi.p + HeightPyramid::level_offset(lv - 1), sdim);
         }
         BUILD_TRY(hipGetLastError());
-        view.lo = lo.p; view.hi = hi.p; view.size = res; view.levels = levels; view.amplitude = ampl; view.shift = yshift;
+        view.lo = lo.p; view.hi = hi.p; view.size = a.res; view.levels = levels; view.amplitude = a.amplitude; view.shift = a.yshift;
         return SVO_OK;
     }
 };
@@ -656,7 +656,31 @@ struct DeviceGrower {
     }
 };
 
-static int positive_mod_b(int n, int m) { return (m + (n % m)) % m; }
+// The chunks of a terrain window grown on the device, in walk order.  Owns each chunk's device arrays (node words, bricks) until
+// release(), which its destructor calls too: a failure on the way frees whatever was grown.
+struct GrownWindow {
+    struct Chunk { ChunkPools meta; int index = 0; uint32_t *tree_dev = nullptr; uint16_t *twig_dev = nullptr; };
+    std::vector<Chunk> chunks;
+    GrownWindow() = default;
+    GrownWindow(const GrownWindow &) = delete;
+    ~GrownWindow() { release(); }
+    void release() { for (Chunk &e : chunks) { (void)hipFree(e.tree_dev); (void)hipFree(e.twig_dev); } chunks.clear(); }
+};
+
+// World::g_pyramid + g_chunk (src/World.cpp:296-321) on the device for every chunk of `win`, a column's pyramid built once.
+static int grow_window(const TerrainWindow &win, const TerrainParams &tp, DevicePyramidBuilder &pyr, DeviceGrower &grower,
+                       DeviceFiller &filler, hipStream_t s, GrownWindow &out)
+{
+    for (int k = 0; k < win.size(); ++k) {
+        const TerrainWindow::Chunk at = win.chunk(k);
+        int rc;
+        if (k % win.column_height() == 0 && (rc = pyr.build(column_pyramid(tp, at.x, at.z), s)) != SVO_OK) return rc;
+        GrownWindow::Chunk &e = out.chunks.emplace_back();
+        e.index = at.index;
+        if ((rc = grower.grow(e.meta, at.position, (float)win.chunksize, tp.depth, pyr.view, tp, s, filler, &e.tree_dev, &e.twig_dev)) != SVO_OK) return rc;
+    }
+    return SVO_OK;
+}
 
 // World::init on the device, pools left in HBM: noise, mips, grow() and the water fill (Ocroot::build) as kernels (above).
 // Neither node words nor bricks visit the host (fetched on request: device.hip, fetch_pools).  The pools are packed exactly as
@@ -667,57 +691,33 @@ static int generate_world_resident_impl(svo_world &w, int device)
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     double t0 = now();
     auto lapt = [&](const char *what) { if (timing) { (void)hipDeviceSynchronize(); const double t1 = now(); std::fprintf(stderr, "[svo build] %-28s %.1f ms\n", what, (t1 - t0) * 1e3); t0 = t1; } };
-    const TerrainParams &tp = w.terrain;
-    const int gw = w.width, gh = w.height, gd = w.depth, chunksize = w.chunksize;
-    const int *ccm = w.chunkcoordmin;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("svo_world_generate: no HIP device for the device builder"); return SVO_ERR_NO_DEVICE; }
     if (device < 0 || device >= ndev) { set_error("svo_world_generate: build_device out of range"); return SVO_ERR_INVALID_ARG; }
     BUILD_TRY(hipSetDevice(device));
-    std::vector<ChunkPools> &chunks = w.chunks;
-    chunks.assign((size_t)gw * gh * gd, ChunkPools());
-    std::vector<uint16_t *> bricks(chunks.size(), nullptr);             // per chunk: its pools as the builder left them in HBM
-    std::vector<uint32_t *> trees(chunks.size(), nullptr);
-    struct Cleanup {
-        std::vector<uint16_t *> &b; std::vector<uint32_t *> &t;
-        ~Cleanup() { for (uint16_t *p : b) if (p) (void)hipFree(p); for (uint32_t *p : t) if (p) (void)hipFree(p); }
-    } cleanup{ bricks, trees };
-    const uint32_t res = tp.pyramid_resolution ? tp.pyramid_resolution : (1u << tp.depth);
+    w.chunks.assign((size_t)w.width * w.height * w.depth, ChunkPools());
+    GrownWindow grown;
     hipStream_t s = nullptr;
     {
         DevicePyramidBuilder pyr;
         DeviceGrower grower;
         DeviceFiller filler;
-        for (int zi = 0; zi < gd; ++zi)
-            for (int xi = 0; xi < gw; ++xi) {
-                const int cx = ccm[0] + xi, cz = ccm[2] + zi;
-                int rc = pyr.build(res, tp.amplitude, 1.0f / (float)res, (float)cx * (float)res + (float)tp.seed, tp.yshift,
-                                   (float)cz * (float)res + (float)tp.seed, s);
-                if (rc != SVO_OK) return rc;
-                for (int yi = 0; yi < gh; ++yi) {
-                    const int cy = ccm[1] + yi;
-                    const int idx = positive_mod_b(cy, gh) * gw * gd + positive_mod_b(cz, gd) * gw + positive_mod_b(cx, gw);
-                    ChunkPools &c = chunks[(size_t)idx];
-                    const float pos[3] = { (float)cx * (float)chunksize, (float)cy * (float)chunksize, (float)cz * (float)chunksize };
-                    rc = grower.grow(c, pos, (float)chunksize, tp.depth, pyr.view, tp, s, filler, &trees[(size_t)idx], &bricks[(size_t)idx]);
-                    if (rc != SVO_OK) return rc;
-                }
-            }
+        const int rc = grow_window(TerrainWindow::whole(w.width, w.height, w.depth, w.chunksize, w.chunkcoordmin), w.terrain,
+                                   pyr, grower, filler, s, grown);
+        if (rc != SVO_OK) return rc;
         lapt("noise + mips + grow + fill");
     }
+    for (const GrownWindow::Chunk &e : grown.chunks) w.chunks[(size_t)e.index] = e.meta;
     // pack: the layout of svo_world_upload
     plan_pools(w);
     int rc = alloc_pools(w, device);
     if (rc != SVO_OK) return rc;
     lapt("alloc pools");
-    for (size_t i = 0; i < chunks.size(); ++i)
-        if ((rc = copy_chunk(w, (int)i, trees[i], bricks[i], hipMemcpyDeviceToDevice, 0, chunks[i].trees_on_device, 0, chunks[i].twigs_on_device, s)) != SVO_OK) return rc;
-    BUILD_TRY(hipMemcpyAsync(w.d_chunks, w.table.data(), chunks.size() * sizeof(DevChunk), hipMemcpyHostToDevice, s));
+    for (const GrownWindow::Chunk &e : grown.chunks)
+        if ((rc = copy_chunk(w, e.index, e.tree_dev, e.twig_dev, hipMemcpyDeviceToDevice, 0, e.meta.trees_on_device, 0, e.meta.twigs_on_device, s)) != SVO_OK) return rc;
+    BUILD_TRY(hipMemcpyAsync(w.d_chunks, w.table.data(), w.chunks.size() * sizeof(DevChunk), hipMemcpyHostToDevice, s));
     BUILD_TRY(hipStreamSynchronize(s));
-    for (size_t i = 0; i < chunks.size(); ++i) {
-        (void)hipFree(bricks[i]); bricks[i] = nullptr;
-        (void)hipFree(trees[i]); trees[i] = nullptr;
-    }
+    grown.release();
     lapt("pack + masks");
     const bool literal_only = build_wide_all(w, s) != SVO_OK;         // (a complete world either way: see svo_world_upload)
     lapt("wide trees");
@@ -766,51 +766,26 @@ void free_builder_context(svo_world &w)
 }
 
 // World::shift (src/World.cpp:334-378) on an uploaded world: the plane of chunks entering the grid is generated on the device
-// the pools live on (g_pyramid + g_chunk as in generate_world_resident_impl) and takes the slots of the plane that leaves -
+// the pools live on (grow_window, with the builders the world keeps) and takes the slots of the plane that leaves -
 // the toroidal index of a chunk coordinate does not depend on chunkcoordmin -, then chunkcoordmin moves.
 static int shift_world_resident_impl(svo_world &w, int axis, int sign)
 {
-    const TerrainParams &tp = w.terrain;
-    const int dims[3] = { w.width, w.height, w.depth };
-    const int u = sign < 0 ? w.chunkcoordmin[axis] - 1 : w.chunkcoordmin[axis] + dims[axis];
-    const uint32_t res = tp.pyramid_resolution ? tp.pyramid_resolution : (1u << tp.depth);
-    int lo[3], hi[3];
-    for (int a = 0; a < 3; ++a) { lo[a] = w.chunkcoordmin[a]; hi[a] = w.chunkcoordmin[a] + dims[a]; }
-    lo[axis] = u; hi[axis] = u + 1;
     BUILD_TRY(hipSetDevice(w.device));
-    hipStream_t s = nullptr;
     BuilderContext &ctx = builder_context(w);
-    DevicePyramidBuilder &pyr = ctx.pyr;
-    DeviceGrower &grower = ctx.grower;
-    DeviceFiller &filler = ctx.filler;
     // The whole entering plane is generated before any of it is installed: a failure on the way (device memory, mostly) leaves
     // the world as it was.  Once the installs have begun they all happen and chunkcoordmin moves - no launch sees a grid whose
     // slots hold chunks of two positions of the window ("none sees a mixture", svo.h); a wide tree that could not be rebuilt on
     // the way only takes the stack kernel away (SVO_OK_LITERAL_ONLY).
-    struct Entering { ChunkPools c; uint32_t *tree_dev = nullptr; uint16_t *twig_dev = nullptr; int index = 0; };
-    std::vector<Entering> plane;
-    auto release = [&plane]() { for (Entering &e : plane) { (void)hipFree(e.tree_dev); (void)hipFree(e.twig_dev); } plane.clear(); };
-    for (int cz = lo[2]; cz < hi[2]; ++cz)
-        for (int cx = lo[0]; cx < hi[0]; ++cx) {
-            int rc = pyr.build(res, tp.amplitude, 1.0f / (float)res, (float)cx * (float)res + (float)tp.seed, tp.yshift,
-                               (float)cz * (float)res + (float)tp.seed, s);
-            if (rc != SVO_OK) { release(); return rc; }
-            for (int cy = lo[1]; cy < hi[1]; ++cy) {
-                plane.emplace_back();
-                Entering &e = plane.back();
-                const float pos[3] = { (float)cx * (float)w.chunksize, (float)cy * (float)w.chunksize, (float)cz * (float)w.chunksize };
-                e.index = svo_world_index(&w, cx, cy, cz);
-                rc = grower.grow(e.c, pos, (float)w.chunksize, tp.depth, pyr.view, tp, s, filler, &e.tree_dev, &e.twig_dev);
-                if (rc != SVO_OK) { release(); return rc; }
-            }
-        }
+    GrownWindow plane;
+    int rc = grow_window(TerrainWindow::whole(w.width, w.height, w.depth, w.chunksize, w.chunkcoordmin).entering(axis, sign), w.terrain,
+                         ctx.pyr, ctx.grower, ctx.filler, nullptr, plane);
+    if (rc != SVO_OK) return rc;
     int status = SVO_OK;
-    for (Entering &e : plane) {
-        const int rc = install_resident_chunk(w, e.index, e.c, e.tree_dev, e.twig_dev);
-        if (rc < 0) { release(); return rc; }       // a HIP failure in the middle of the copies: the device is in no state to go on with
+    for (const GrownWindow::Chunk &e : plane.chunks) {
+        rc = install_resident_chunk(w, e.index, e.meta, e.tree_dev, e.twig_dev);
+        if (rc < 0) return rc;                      // a HIP failure in the middle of the copies: the device is in no state to go on with
         if (rc != SVO_OK) status = rc;
     }
-    release();
     w.chunkcoordmin[axis] += sign;
     return status;
 }

@@ -785,7 +785,7 @@ static int fill_common(svo_world *w, const svo_trace_params *prm, TraceArgs &A)
     A.dimw = w->width; A.dimh = w->height; A.dimd = w->depth;
     for (int a = 0; a < 3; ++a) {
         A.ccm[a] = w->chunkcoordmin[a];
-        A.cbase[a] = (dims[a] + (w->chunkcoordmin[a] % dims[a])) % dims[a];
+        A.cbase[a] = positive_mod(w->chunkcoordmin[a], dims[a]);
     }
     A.chunks = w->d_chunks; A.tree = w->d_tree; A.twig = w->d_twig; A.mask = w->d_mask;
     A.wchunks = w->d_wchunks; A.wide = w->d_wide; A.wbase = w->d_wbase; A.bmat = w->d_bmat;

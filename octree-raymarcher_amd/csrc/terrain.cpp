@@ -74,13 +74,13 @@ struct Noise2 {
 float simplex2(float x, float y) { return Noise2::eval(x, y); }
 
 // ---------------------------------------------------------------------------------------------
-void HeightPyramid::build(uint32_t res, float ampl, float period, float xshift, float yshift, float zshift)
+void HeightPyramid::build(const ColumnPyramid &a)
 {
-    size = res;
+    size = a.res;
     levels = 0;
-    while ((1u << levels) < res) ++levels;
-    amplitude = ampl;
-    shift = yshift;
+    while ((1u << levels) < a.res) ++levels;
+    amplitude = a.amplitude;
+    shift = a.yshift;
     const size_t total = level_offset(levels + 1);
     lo.assign(total, 1.0f);             // reference initial values, src/BoundsPyramid.cpp:60-69
     hi.assign(total, -1.0f);
@@ -89,7 +89,7 @@ void HeightPyramid::build(uint32_t res, float ampl, float period, float xshift, 
     float *blo = lo.data() + level_offset(levels), *bhi = hi.data() + level_offset(levels);
     for (size_t z = 0; z < size; ++z)
         for (size_t x = 0; x < size; ++x) {
-            const float n = simplex2(((float)x + xshift) * period, ((float)z + zshift) * period);
+            const float n = simplex2(((float)x + a.xshift) * a.period, ((float)z + a.zshift) * a.period);
             blo[z * size + x] = n;
             bhi[z * size + x] = n;
         }
@@ -310,14 +310,31 @@ void fill_box(ChunkPools &c, const float lo[3], const float hi[3], uint16_t mate
 }
 
 // ---------------------------------------------------------------------------------------------
-static int positive_mod(int n, int m) { return (m + (n % m)) % m; }   // src/World.cpp:276-279
+ColumnPyramid column_pyramid(const TerrainParams &tp, int cx, int cz)
+{
+    const uint32_t res = pyramid_resolution_or_default(tp.pyramid_resolution, tp.depth);
+    return { res, tp.amplitude, 1.0f / (float)res, (float)cx * (float)res + (float)tp.seed, tp.yshift, (float)cz * (float)res + (float)tp.seed };
+}
 
-int generate_world(int w, int h, int d, int chunksize, const int ccm[3], const TerrainParams &tp,
-                   std::vector<ChunkPools> &chunks)
+TerrainWindow TerrainWindow::entering(int axis, int sign) const
+{   // World::shift, src/World.cpp:334-378
+    TerrainWindow plane = *this;
+    plane.lo[axis] = sign < 0 ? lo[axis] - 1 : hi[axis];
+    plane.hi[axis] = plane.lo[axis] + 1;
+    return plane;
+}
+
+TerrainWindow::Chunk TerrainWindow::chunk(int k) const
+{
+    const int column = k / column_height(), columns_x = hi[0] - lo[0];
+    const int x = lo[0] + column % columns_x, y = lo[1] + k % column_height(), z = lo[2] + column / columns_x;
+    return { x, y, z, chunk_index(x, y, z, grid[0], grid[1], grid[2]), { (float)x * (float)chunksize, (float)y * (float)chunksize, (float)z * (float)chunksize } };
+}
+
+int generate_window(const TerrainWindow &win, const TerrainParams &tp, std::vector<ChunkPools> &chunks)
 {   // World::init, src/World.cpp:19-43; g_pyramid :296-306; g_chunk :308-321
-    chunks.assign((size_t)w * h * d, ChunkPools());
-    const uint32_t res = tp.pyramid_resolution ? tp.pyramid_resolution : (1u << tp.depth);
-    const int columns = w * d;
+    chunks.assign((size_t)win.size(), ChunkPools());
+    const int height = win.column_height(), columns = win.size() / height;
     int nthreads = tp.threads > 0 ? tp.threads : (int)std::thread::hardware_concurrency();
     nthreads = std::max(1, std::min(nthreads, columns));
 
@@ -329,18 +346,11 @@ int generate_world(int w, int h, int d, int chunksize, const int ccm[3], const T
         for (;;) {
             const int col = cursor.fetch_add(1);
             if (col >= columns) break;
-            const int xi = col % w, zi = col / w;
-            const int cx = ccm[0] + xi, cz = ccm[2] + zi;
-            const float period = 1.0f / (float)res;
-            pyr.build(res, tp.amplitude, period,
-                      (float)cx * (float)res + (float)tp.seed, tp.yshift,
-                      (float)cz * (float)res + (float)tp.seed);
-            for (int yi = 0; yi < h; ++yi) {
-                const int cy = ccm[1] + yi;
-                const int idx = positive_mod(cy, h) * w * d + positive_mod(cz, d) * w + positive_mod(cx, w);
-                ChunkPools &c = chunks[(size_t)idx];
-                const float pos[3] = { (float)cx * (float)chunksize, (float)cy * (float)chunksize, (float)cz * (float)chunksize };
-                grow_chunk(c, pos, (float)chunksize, tp.depth, pyr, &tp);
+            for (int k = col * height; k < (col + 1) * height; ++k) {
+                const TerrainWindow::Chunk e = win.chunk(k);
+                if (k == col * height) pyr.build(column_pyramid(tp, e.x, e.z));
+                ChunkPools &c = chunks[(size_t)k];
+                grow_chunk(c, e.position, (float)win.chunksize, tp.depth, pyr, &tp);
                 if (tp.water) {
                     const float hi[3] = { c.position[0] + c.size, tp.water_level, c.position[2] + c.size };
                     DirtyRange a, b;

@@ -34,13 +34,16 @@ struct ChunkPools {
     void fit_capacity(uint64_t trees, uint64_t twigs);
 };
 
+// What one height pyramid is built from (column_pyramid below).
+struct ColumnPyramid { uint32_t res; float amplitude, period, xshift, yshift, zshift; };
+
 // BoundsPyramid (src/BoundsPyramid.h) as one flat array per bound.
 struct HeightPyramid {
     uint32_t size = 0, levels = 0;
     float amplitude = 0, shift = 0;
     std::vector<float> lo, hi;                         // level lv at level_offset(lv), (2^lv)^2 entries
     static size_t level_offset(uint32_t lv) { return (((size_t)1 << (2 * lv)) - 1) / 3; }
-    void  build(uint32_t res, float ampl, float period, float xshift, float yshift, float zshift);
+    void  build(const ColumnPyramid &a);
     float bound(const std::vector<float> &q, float x, float z, uint32_t lv) const;
     float min(float x, float z, uint32_t lv) const { return bound(lo, x, z, lv); }
     float max(float x, float z, uint32_t lv) const { return bound(hi, x, z, lv); }
@@ -61,8 +64,35 @@ float simplex2(float x, float y);
 void  grow_chunk(ChunkPools &c, const float position[3], float size, uint32_t depth, const HeightPyramid &pyr,
                  const TerrainParams *sparse = nullptr);
 void  fill_box(ChunkPools &c, const float lo[3], const float hi[3], uint16_t material, DirtyRange &dtree, DirtyRange &dtwig);
-int   generate_world(int w, int h, int d, int chunksize, const int chunkcoordmin[3], const TerrainParams &tp,
-                     std::vector<ChunkPools> &chunks);
 
+// ---- the terrain window walk: which chunks a terrain world holds and how each is grown (World::init, World::shift) ----
+inline int positive_mod(int n, int m) { return (m + (n % m)) % m; }   // src/World.cpp:276-279
+// World::index (src/World.cpp:288-293): the slot of chunk (x, y, z) in a w x h x d toroidal grid
+inline int chunk_index(int x, int y, int z, int w, int h, int d) { return positive_mod(y, h) * w * d + positive_mod(z, d) * w + positive_mod(x, w); }
+// the base resolution of a column's height pyramid: one texel per voxel column of a chunk unless `requested` says otherwise
+inline uint32_t pyramid_resolution_or_default(uint32_t requested, uint32_t depth) { return requested ? requested : (1u << depth); }
+
+// World::g_pyramid (src/World.cpp:296-306): the height pyramid of chunk column (cx, cz)
+ColumnPyramid column_pyramid(const TerrainParams &tp, int cx, int cz);
+
+// A box [lo, hi) of chunk coordinates in a world's toroidal grid, walked column by column - z outer, x inner, y innermost -
+// because the chunks of one (x, z) column share one height pyramid.  World::init's window is the whole grid at chunkcoordmin,
+// World::shift's the plane that enters the grid.
+struct TerrainWindow {
+    int lo[3], hi[3];
+    int grid[3];                                       // the world's width, height, depth
+    int chunksize;
+    struct Chunk { int x, y, z, index; float position[3]; };
+
+    static TerrainWindow whole(int w, int h, int d, int chunksize, const int ccm[3])
+    { return { { ccm[0], ccm[1], ccm[2] }, { ccm[0] + w, ccm[1] + h, ccm[2] + d }, { w, h, d }, chunksize }; }
+    TerrainWindow entering(int axis, int sign) const;  // the plane that enters when the window steps by `sign` (+-1) along `axis`
+    int   column_height() const { return hi[1] - lo[1]; }
+    int   size() const { return (hi[0] - lo[0]) * column_height() * (hi[2] - lo[2]); }
+    Chunk chunk(int k) const;                          // k-th of the walk; a column's first at k % column_height() == 0
+};
+// World::g_chunk (src/World.cpp:308-321) for every chunk of `win`: grown, then the water filled in, in walk order; the columns
+// are spread over tp.threads host threads.  -1: a thread ran out of host memory.
+int generate_window(const TerrainWindow &win, const TerrainParams &tp, std::vector<ChunkPools> &chunks);
 
 } // namespace svo

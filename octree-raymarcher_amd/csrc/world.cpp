@@ -90,8 +90,6 @@ void classify_world(svo_world &w)
     }
 }
 
-static int positive_mod(int n, int m) { return (m + (n % m)) % m; }
-
 } // namespace svo
 
 using namespace svo;
@@ -107,7 +105,7 @@ int svo_world_generate(int w, int h, int d, int chunksize, const int ccm[3],
     if (!out || !tp || w <= 0 || h <= 0 || d <= 0 || chunksize <= 0) { set_error("svo_world_generate: bad argument"); return SVO_ERR_INVALID_ARG; }
     if (tp->depth < TWIG_LEVELS || tp->depth > 20) { set_error("svo_world_generate: depth must be in [2,20]"); return SVO_ERR_INVALID_ARG; }
     if (tp->coarse_depth != 0 && (tp->coarse_depth < TWIG_LEVELS || tp->coarse_depth >= tp->depth)) { set_error("svo_world_generate: coarse_depth must be in [2, depth)"); return SVO_ERR_INVALID_ARG; }
-    const uint32_t res = tp->pyramid_resolution ? tp->pyramid_resolution : (1u << tp->depth);
+    const uint32_t res = pyramid_resolution_or_default(tp->pyramid_resolution, tp->depth);
     if (res & (res - 1)) { set_error("svo_world_generate: pyramid_resolution must be a power of two"); return SVO_ERR_INVALID_ARG; }
     int status = SVO_OK;            // (SVO_OK_LITERAL_ONLY: generated on the device, resident there, but without the stack kernel's wide trees)
     try {
@@ -126,11 +124,15 @@ int svo_world_generate(int w, int h, int d, int chunksize, const int ccm[3],
             status = generate_world_resident(*world, tp->build_device_plus1 - 1);
             if (status < 0) { svo_world_destroy(world); return status; }
         } else {
-            if (generate_world(w, h, d, chunksize, world->chunkcoordmin, p, world->chunks) != 0) {
+            const TerrainWindow win = TerrainWindow::whole(w, h, d, chunksize, world->chunkcoordmin);
+            std::vector<ChunkPools> grown;
+            if (generate_window(win, p, grown) != 0) {
                 delete world;
                 set_error("svo_world_generate: out of host memory in a generator thread");
                 return SVO_ERR_OUT_OF_MEMORY;
             }
+            world->chunks.resize(grown.size());
+            for (int k = 0; k < win.size(); ++k) world->chunks[(size_t)win.chunk(k).index] = std::move(grown[(size_t)k]);
         }
         world->terrain = p;
         world->has_terrain = true;
@@ -177,9 +179,9 @@ int svo_world_create(const svo_chunk_desc *chunks, int n, int w, int h, int d, i
     }
 }
 
-// World::shift, src/World.cpp:334-378: slide the grid one chunk along one axis.  The plane of chunks entering
-// the grid is generated (g_pyramid + g_chunk) and stored at its toroidal index — where the plane leaving on the
-// opposite side used to live — then chunkcoordmin moves.  Device copies are refreshed through svo_world_update.
+// World::shift, src/World.cpp:334-378: slide the grid one chunk along one axis.  The whole plane of chunks entering the grid is
+// generated (g_pyramid + g_chunk) before any of it is stored at its toroidal index - where the plane leaving on the opposite side
+// used to live -, so a failure to generate it changes nothing; then chunkcoordmin moves.
 int svo_world_shift(svo_world *w, const int offset[3])
 {
     if (!w || !offset) return SVO_ERR_INVALID_ARG;
@@ -191,38 +193,20 @@ int svo_world_shift(svo_world *w, const int offset[3])
     const int sign = offset[axis];
     // an uploaded world: the entering plane is generated where the pools live (builder.hip), nothing visits the host
     if (w->device >= 0) return shift_world_resident(*w, axis, sign);
-    const int dims[3] = { w->width, w->height, w->depth };
-    const int u = sign < 0 ? w->chunkcoordmin[axis] - 1 : w->chunkcoordmin[axis] + dims[axis];
-    const TerrainParams &tp = w->terrain;
-    const uint32_t res = tp.pyramid_resolution ? tp.pyramid_resolution : (1u << tp.depth);
+    const TerrainWindow plane = TerrainWindow::whole(w->width, w->height, w->depth, w->chunksize, w->chunkcoordmin).entering(axis, sign);
     try {
-        // entering plane: all chunk coordinates with coordinate[axis] == u; columns (cx, cz) share a pyramid
-        int lo[3], hi[3];
-        for (int a = 0; a < 3; ++a) { lo[a] = w->chunkcoordmin[a]; hi[a] = w->chunkcoordmin[a] + dims[a]; }
-        lo[axis] = u; hi[axis] = u + 1;
-        HeightPyramid pyr;
-        for (int cz = lo[2]; cz < hi[2]; ++cz)
-            for (int cx = lo[0]; cx < hi[0]; ++cx) {
-                pyr.build(res, tp.amplitude, 1.0f / (float)res, (float)cx * (float)res + (float)tp.seed, tp.yshift, (float)cz * (float)res + (float)tp.seed);
-                for (int cy = lo[1]; cy < hi[1]; ++cy) {
-                    ChunkPools c;
-                    const float pos[3] = { (float)cx * (float)w->chunksize, (float)cy * (float)w->chunksize, (float)cz * (float)w->chunksize };
-                    grow_chunk(c, pos, (float)w->chunksize, tp.depth, pyr, &tp);
-                    if (tp.water) {
-                        const float top[3] = { c.position[0] + c.size, tp.water_level, c.position[2] + c.size };
-                        DirtyRange a, b;
-                        fill_box(c, c.position, top, (uint16_t)tp.water_material, a, b);
-                    }
-                    svo_chunk_desc d;
-                    std::memcpy(d.position, c.position, sizeof d.position);
-                    d.size = c.size; d.depth = c.depth; d._pad = 0;
-                    d.tree = c.tree.data(); d.trees = c.tree.size();
-                    d.twig = c.twig.data(); d.twigs = c.twig_count();
-                    const int idx = svo_world_index(w, cx, cy, cz);
-                    const int rc = svo_world_update(w, idx, &d, 0, d.trees, 0, d.twigs, 1);
-                    if (rc < 0) return rc;
-                }
-            }
+        std::vector<ChunkPools> grown;
+        if (generate_window(plane, w->terrain, grown) != 0) { set_error("svo_world_shift: out of host memory in a generator thread"); return SVO_ERR_OUT_OF_MEMORY; }
+        for (int k = 0; k < plane.size(); ++k) {
+            const ChunkPools &c = grown[(size_t)k];
+            svo_chunk_desc d;
+            std::memcpy(d.position, c.position, sizeof d.position);
+            d.size = c.size; d.depth = c.depth; d._pad = 0;
+            d.tree = c.tree.data(); d.trees = c.tree.size();
+            d.twig = c.twig.data(); d.twigs = c.twig_count();
+            const int rc = svo_world_update(w, plane.chunk(k).index, &d, 0, d.trees, 0, d.twigs, 1);
+            if (rc < 0) return rc;
+        }
     } catch (const std::bad_alloc &) {
         set_error("svo_world_shift: out of host memory");
         return SVO_ERR_OUT_OF_MEMORY;
@@ -374,7 +358,7 @@ int svo_world_index_float(const svo_world *w, const float p[3], int q[3])
 int svo_world_index(const svo_world *w, int x, int y, int z)
 {   // src/World.cpp:288-293
     if (!w) return SVO_ERR_INVALID_ARG;
-    return positive_mod(y, w->height) * w->width * w->depth + positive_mod(z, w->depth) * w->width + positive_mod(x, w->width);
+    return chunk_index(x, y, z, w->width, w->height, w->depth);
 }
 
 } // extern "C"
