@@ -29,18 +29,12 @@
 #include <thread>
 #include <vector>
 
+#include "hip_own.h"
 #include "terrain.h"
-#include "world.h"
 
 namespace svo {
 
 namespace {
-
-#define BUILD_TRY(expr)                                                                   \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) { set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); return e_ == hipErrorOutOfMemory ? SVO_ERR_OUT_OF_MEMORY : SVO_ERR_HIP; } \
-    } while (0)
 
 // ---- 2-D simplex noise, the same sequence of float operations as terrain.cpp's Noise2::eval ------------
 __device__ __forceinline__ float d_wrap289(float x) { return x - floorf(x * (1.0f / 289.0f)) * 289.0f; }
@@ -151,28 +145,7 @@ __device__ __forceinline__ uint32_t d_height_material(float y)
 
 struct Cell { float x, y, z; uint32_t slot; };
 
-// Consecutive values from *ctr for the threads of a block that raise `pred` - ONE global atomic per block.  The level-synchronous
-// sweeps number millions of nodes through a handful of counters, and same-address atomics are served one after the other (≈ 5.7 ns
-// each here, even at the one per wave the compiler already folds a uniform atomicAdd to: a sweep over 4.8 M nodes took 0.86 ms).
-// Every thread of the block calls this (no early return before it); sh holds FILL_BLOCK / 64 + 1 words.
-constexpr unsigned FILL_BLOCK = 1024;
-__device__ __forceinline__ uint32_t block_take(uint32_t *ctr, bool pred, uint32_t *sh)
-{
-    constexpr unsigned WAVES = FILL_BLOCK / 64;
-    const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(pred);
-    if (lane == 0u) sh[wv] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-        uint32_t tot = 0u;
-        for (unsigned w = 0; w < WAVES; ++w) { const uint32_t c = sh[w]; sh[w] = tot; tot += c; }
-        sh[WAVES] = tot ? atomicAdd(ctr, tot) : 0u;
-    }
-    __syncthreads();
-    const uint32_t r = sh[WAVES] + sh[wv] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    __syncthreads();                                        // (sh may serve a second call)
-    return r;
-}
+constexpr unsigned FILL_BLOCK = 1024;     // threads per block of the sweeps that number nodes through block_take (hip_own.h)
 
 struct GrowArgs {
     float px, py, pz, size;     // chunk position / edge
@@ -281,26 +254,6 @@ __global__ __launch_bounds__(256) void k_bricks_rows(const Cell *jobs, uint32_t 
     dst[1] = make_uint4(w[4], w[5], w[6], w[7]);
 }
 
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int reserve(size_t n, bool keep, hipStream_t s)
-    {
-        if (n <= cap) return SVO_OK;
-        size_t nc = std::max(n, cap * 2);
-        T *q = nullptr;
-        if (hipMalloc((void **)&q, nc * sizeof(T)) != hipSuccess) { set_error("device builder: hipMalloc failed"); return SVO_ERR_OUT_OF_MEMORY; }
-        if (keep && p && cap) { if (hipMemcpyAsync(q, p, cap * sizeof(T), hipMemcpyDeviceToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { (void)hipFree(q); return SVO_ERR_HIP; } }
-        if (p) (void)hipFree(p);
-        p = q; cap = nc;
-        return SVO_OK;
-    }
-};
-
-inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
-
 } // namespace
 
 // One chunk column's pyramid on the device.
@@ -322,7 +275,7 @@ struct DevicePyramidBuilder {
                                lo.p + HeightPyramid::level_offset(lv), hi.p + HeightPyramid::level_offset(lv),
                                lo.p + HeightPyramid::level_offset(lv - 1), hi.p + HeightPyramid::level_offset(lv - 1), sdim);
         }
-        BUILD_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         view.lo = lo.p; view.hi = hi.p; view.size = a.res; view.levels = levels; view.amplitude = a.amplitude; view.shift = a.yshift;
         return SVO_OK;
     }
@@ -384,7 +337,7 @@ __global__ __launch_bounds__(FILL_BLOCK) void k_fill_classify(const Cell *cells,
         }
     }
     const bool has_kids = a == FILL_SPLIT || a == FILL_DESCEND;
-    const uint32_t kids = block_take(&counters[0], has_kids, sh);
+    const uint32_t kids = block_take<FILL_BLOCK>(&counters[0], has_kids, sh);
     if (has_kids) {
         const float half = F.edge * 0.5f;
         const uint32_t first = node_offset(word);
@@ -397,7 +350,7 @@ __global__ __launch_bounds__(FILL_BLOCK) void k_fill_classify(const Cell *cells,
             next[8 * (uint64_t)kids + c] = ch;
         }
     }
-    (void)block_take(&counters[1], a == FILL_NEW_BRICK || a == FILL_BRICK, sh);
+    (void)block_take<FILL_BLOCK>(&counters[1], a == FILL_NEW_BRICK || a == FILL_BRICK, sh);
     if (live) act[i] = fill_pack(a, has_kids ? kids : 0u);
 }
 
@@ -427,7 +380,7 @@ __global__ __launch_bounds__(FILL_BLOCK) void k_fill_number(Cell *cells, uint32_
     const uint32_t i = blockIdx.x * FILL_BLOCK + threadIdx.x;
     const bool live = i < n;
     const uint32_t a = live ? fill_action(act[i]) : (uint32_t)FILL_NONE, kids = live ? fill_kids(act[i]) : 0u;
-    const uint32_t op_slot = block_take(op_cursor, a == FILL_NEW_BRICK || a == FILL_BRICK, sh);     // (any order: k_brick_edit treats the ops alike)
+    const uint32_t op_slot = block_take<FILL_BLOCK>(op_cursor, a == FILL_NEW_BRICK || a == FILL_BRICK, sh);     // (any order: k_brick_edit treats the ops alike)
     if (a == FILL_NONE) return;
     const Cell e = cells[i];                // (its slot is a real one by now: the parent's turn came a launch earlier)
     const uint2 base = cnt[i];
@@ -494,8 +447,7 @@ struct DeviceFiller {
     std::vector<Level> lv;
     DevBuf<uint32_t> counters;      // [2 * level + {0, 1}] of sweep A, [64] the op cursor of sweep C
     DevBuf<DevBrickOp> ops;
-    uint32_t *h_counters = nullptr; // pinned
-    ~DeviceFiller() { if (h_counters) (void)hipHostFree(h_counters); }
+    Pinned<uint32_t> h_counters;
 
     // Ocroot::build (edit = EDIT_BUILD: region [lo, hi] filled with `material`) or Ocroot::destroy (EDIT_DESTROY: emptied) applied
     // to the chunk in `tree` (trees nodes) and `twig` (twigs bricks); both buffers grow as needed, c's capacities follow the
@@ -507,15 +459,15 @@ struct DeviceFiller {
         const uint32_t maxlevel = c.depth - TWIG_LEVELS;
         if (lv.size() < maxlevel + 2) lv.resize(maxlevel + 2);
         if ((rc = counters.reserve(80, false, s)) != SVO_OK) return rc;
-        if (!h_counters) BUILD_TRY(hipHostMalloc((void **)&h_counters, 80 * sizeof(uint32_t)));
-        BUILD_TRY(hipMemsetAsync(counters.p, 0, 80 * sizeof(uint32_t), s));
+        if ((rc = h_counters.alloc(80)) != SVO_OK) return rc;
+        HIP_TRY(hipMemsetAsync(counters.p, 0, 80 * sizeof(uint32_t), s));
         FillArgs F{};
         for (int a = 0; a < 3; ++a) { F.rlo[a] = lo[a]; F.rhi[a] = hi[a]; }
         F.maxlevel = maxlevel; F.material = material; F.op = edit;
         // sweep A
         if ((rc = lv[0].cells.reserve(1, false, s)) != SVO_OK) return rc;
         const Cell root = { c.position[0], c.position[1], c.position[2], 0u };
-        BUILD_TRY(hipMemcpyAsync(lv[0].cells.p, &root, sizeof root, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(lv[0].cells.p, &root, sizeof root, hipMemcpyHostToDevice, s));
         lv[0].n = 1;
         float edge = c.size;
         uint32_t last = 0, brick_edits = 0;
@@ -529,13 +481,13 @@ struct DeviceFiller {
                 (rc = N.cells.reserve((uint64_t)n * 8, false, s)) != SVO_OK) return rc;
             F.level = level; F.edge = edge;
             hipLaunchKernelGGL(k_fill_classify, dim3(blocks_for(n, FILL_BLOCK)), dim3(FILL_BLOCK), 0, s, L.cells.p, n, F, tree.p, L.act.p, N.cells.p, counters.p + 2 * level);
-            BUILD_TRY(hipGetLastError());
-            BUILD_TRY(hipMemcpyAsync(h_counters, counters.p + 2 * level, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            BUILD_TRY(hipStreamSynchronize(s));
-            brick_edits += h_counters[1];
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(h_counters.p, counters.p + 2 * level, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            brick_edits += h_counters.p[1];
             // (also what fill_pack can hold: child-block indices stay below FILL_KIDS_LIMIT = 2^28)
-            if ((uint64_t)h_counters[0] >= FILL_KIDS_LIMIT) { set_error("device builder: the fill's frontier exceeds 2^31 nodes"); return SVO_ERR_UNSUPPORTED; }
-            N.n = h_counters[0] * 8u;
+            if ((uint64_t)h_counters.p[0] >= FILL_KIDS_LIMIT) { set_error("device builder: the fill's frontier exceeds 2^31 nodes"); return SVO_ERR_UNSUPPORTED; }
+            N.n = h_counters.p[0] * 8u;
             edge = edge * 0.5f;
             if (N.n == 0) break;
             // a node at maxlevel is never split and grow() puts no BRANCH there
@@ -546,17 +498,17 @@ struct DeviceFiller {
             Level &L = lv[(size_t)level], &N = lv[(size_t)level + 1];
             hipLaunchKernelGGL(k_fill_count, dim3(blocks_for(L.n, 256)), dim3(256), 0, s, L.act.p, L.n, N.cnt.p, L.cnt.p);
         }
-        BUILD_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         uint2 total;
-        BUILD_TRY(hipMemcpyAsync(h_counters, lv[0].cnt.p, sizeof(uint2), hipMemcpyDeviceToHost, s));
-        BUILD_TRY(hipStreamSynchronize(s));
-        total.x = h_counters[0]; total.y = h_counters[1];
+        HIP_TRY(hipMemcpyAsync(h_counters.p, lv[0].cnt.p, sizeof(uint2), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        total.x = h_counters.p[0]; total.y = h_counters.p[1];
         const uint64_t trees1 = trees + 8ull * total.x, twigs1 = twigs + total.y;
         if (trees1 >= (1ull << 30) || twigs1 >= (1ull << 30)) { set_error("device builder: chunk exceeds the 30-bit node offset"); return SVO_ERR_UNSUPPORTED; }
         if ((rc = tree.reserve(trees1, true, s)) != SVO_OK || (rc = twig.reserve(std::max<uint64_t>(twigs1, 1) * TWIG_WORDS, true, s)) != SVO_OK ||
             (rc = ops.reserve(std::max<uint32_t>(brick_edits, 1u), false, s)) != SVO_OK) return rc;
-        if (total.y) BUILD_TRY(hipMemsetAsync(twig.p + twigs * TWIG_WORDS, 0, (size_t)total.y * TWIG_WORDS * sizeof(uint16_t), s));
-        BUILD_TRY(hipMemsetAsync(lv[0].cnt.p, 0, sizeof(uint2), s));
+        if (total.y) HIP_TRY(hipMemsetAsync(twig.p + twigs * TWIG_WORDS, 0, (size_t)total.y * TWIG_WORDS * sizeof(uint16_t), s));
+        HIP_TRY(hipMemsetAsync(lv[0].cnt.p, 0, sizeof(uint2), s));
         // sweep C
         for (uint32_t level = 0; level <= last; ++level) {
             Level &L = lv[level], &N = lv[level + 1];
@@ -567,7 +519,7 @@ struct DeviceFiller {
         if (brick_edits)
             hipLaunchKernelGGL(k_brick_edit, dim3(blocks_for((uint64_t)brick_edits * 64, 256)), dim3(256), 0, s, twig.p, ops.p, brick_edits, edit,
                                F.rlo[0], F.rlo[1], F.rlo[2], F.rhi[0], F.rhi[1], F.rhi[2], material);
-        BUILD_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         // capacity bookkeeping of the reference's appends (src/Octree.cpp:349-351,365-368; terrain.cpp's Filler)
         if (total.x) while (trees1 >= c.tree_capacity) c.tree_capacity *= 2;
         while (twigs1 > c.twig_capacity) c.twig_capacity *= 2;
@@ -582,16 +534,15 @@ struct DeviceGrower {
     DevBuf<unsigned long long> flags, rank;
     DevBuf<uint16_t> twig;
     DevBuf<unsigned char> scan_tmp;
-    uint32_t *h_totals = nullptr;               // pinned
-    ~DeviceGrower() { if (h_totals) (void)hipHostFree(h_totals); }
+    Pinned<uint32_t> h_totals;
 
     uint64_t hint_tree = 1024, hint_twig = 0;   // what the previous chunk needed: the next one starts there instead of doubling its way up
 
     // grow() and - if the terrain has water - Ocroot::build behind it, both on the device.  Node words and bricks stay in HBM:
-    // *tree_dev / *bricks_dev receive the device arrays (caller owns them, hipFree), c.trees_on_device / c.twigs_on_device
-    // their lengths; the host copies are fetched on request (device.hip: fetch_pools).
+    // tree_dev / bricks_dev receive the device arrays, c.trees_on_device / c.twigs_on_device their lengths; the host copies are
+    // fetched on request (device.hip: fetch_pools).
     int grow(ChunkPools &c, const float position[3], float size, uint32_t depth, const DevPyramid &P, const TerrainParams &tp, hipStream_t s,
-             DeviceFiller &filler, uint32_t **tree_dev, uint16_t **bricks_dev)
+             DeviceFiller &filler, DevBuf<uint32_t> &tree_dev, DevBuf<uint16_t> &bricks_dev)
     {
         c.position[0] = position[0]; c.position[1] = position[1]; c.position[2] = position[2];
         c.size = size; c.depth = depth;
@@ -600,10 +551,10 @@ struct DeviceGrower {
         int rc;
         if ((rc = frontier.reserve(1, false, s)) != SVO_OK || (rc = tree.reserve(hint_tree, false, s)) != SVO_OK ||
             (hint_twig && (rc = twig.reserve(hint_twig, false, s)) != SVO_OK) || (rc = totals.reserve(64, false, s)) != SVO_OK) return rc;
-        if (!h_totals) BUILD_TRY(hipHostMalloc((void **)&h_totals, 2 * sizeof(uint32_t)));
-        BUILD_TRY(hipMemsetAsync(totals.p, 0, 64 * sizeof(uint32_t), s));
+        if ((rc = h_totals.alloc(2)) != SVO_OK) return rc;
+        HIP_TRY(hipMemsetAsync(totals.p, 0, 64 * sizeof(uint32_t), s));
         const Cell root = { position[0], position[1], position[2], 0u };
-        BUILD_TRY(hipMemcpyAsync(frontier.p, &root, sizeof root, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(frontier.p, &root, sizeof root, hipMemcpyHostToDevice, s));
         uint32_t n = 1;
         float edge = size;
         GrowArgs G{};
@@ -619,25 +570,25 @@ struct DeviceGrower {
             if ((rc = word.reserve(n, false, s)) != SVO_OK || (rc = flags.reserve(n, false, s)) != SVO_OK || (rc = rank.reserve(n, false, s)) != SVO_OK) return rc;
             hipLaunchKernelGGL(k_classify, dim3(blocks_for(n, 256)), dim3(256), 0, s, frontier.p, n, G, P, word.p, flags.p);
             size_t need = 0;
-            BUILD_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, flags.p, rank.p, (int)n, s));
+            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, flags.p, rank.p, (int)n, s));
             if ((rc = scan_tmp.reserve(need + 16, false, s)) != SVO_OK) return rc;
-            BUILD_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp.p, need, flags.p, rank.p, (int)n, s));
+            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp.p, need, flags.p, rank.p, (int)n, s));
             hipLaunchKernelGGL(k_level_totals, dim3(1), dim3(1), 0, s, flags.p, rank.p, n, totals.p + 2 * level);
-            BUILD_TRY(hipMemcpyAsync(h_totals, totals.p + 2 * level, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            BUILD_TRY(hipStreamSynchronize(s));
-            const uint64_t nb = h_totals[0], nt = h_totals[1];
+            HIP_TRY(hipMemcpyAsync(h_totals.p, totals.p + 2 * level, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipStreamSynchronize(s));
+            const uint64_t nb = h_totals.p[0], nt = h_totals.p[1];
             if (trees + 8 * nb >= (1ull << 30) || twigs + nt >= (1ull << 30)) { set_error("device builder: chunk exceeds the 30-bit node offset"); return SVO_ERR_UNSUPPORTED; }
             if ((rc = tree.reserve(trees + 8 * nb, true, s)) != SVO_OK || (rc = twig.reserve((twigs + nt) * TWIG_WORDS, true, s)) != SVO_OK ||
                 (rc = next.reserve(std::max<uint64_t>(8 * nb, 1), false, s)) != SVO_OK || (rc = jobs.reserve(std::max<uint64_t>(nt, 1), false, s)) != SVO_OK) return rc;
             hipLaunchKernelGGL(k_emit, dim3(blocks_for(n, 256)), dim3(256), 0, s, frontier.p, n, half, word.p, rank.p,
                                (uint32_t)trees, (uint32_t)twigs, tree.p, next.p, jobs.p);
             if (nt) hipLaunchKernelGGL(k_bricks_rows, dim3(blocks_for(nt * 4, 256)), dim3(256), 0, s, jobs.p, (uint32_t)nt, G, P, twig.p);
-            BUILD_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             // capacity bookkeeping exactly as the host builder (src/Octree.cpp:149-150,160-161)
             if (nb) while (trees + 8 * nb >= c.tree_capacity) c.tree_capacity *= 2;
             while (twigs + nt > c.twig_capacity) c.twig_capacity *= 2;
             trees += 8 * nb; twigs += nt;
-            std::swap(frontier.p, next.p); std::swap(frontier.cap, next.cap);
+            std::swap(frontier, next);
             n = (uint32_t)(8 * nb);
             edge = half;
         }
@@ -649,23 +600,15 @@ struct DeviceGrower {
         c.trees_on_device = trees;
         c.twigs_on_device = twigs;
         hint_tree = std::max<uint64_t>(hint_tree, tree.cap); hint_twig = std::max<uint64_t>(hint_twig, twig.cap);
-        *tree_dev = tree.p; *bricks_dev = twig.p;   // hand the arrays over; the next chunk gets fresh ones
-        tree.p = nullptr; tree.cap = 0;
-        twig.p = nullptr; twig.cap = 0;
+        tree_dev = std::move(tree); bricks_dev = std::move(twig);   // hand the arrays over; the next chunk gets fresh ones
         return SVO_OK;
     }
 };
 
-// The chunks of a terrain window grown on the device, in walk order.  Owns each chunk's device arrays (node words, bricks) until
-// release(), which its destructor calls too: a failure on the way frees whatever was grown.
-struct GrownWindow {
-    struct Chunk { ChunkPools meta; int index = 0; uint32_t *tree_dev = nullptr; uint16_t *twig_dev = nullptr; };
-    std::vector<Chunk> chunks;
-    GrownWindow() = default;
-    GrownWindow(const GrownWindow &) = delete;
-    ~GrownWindow() { release(); }
-    void release() { for (Chunk &e : chunks) { (void)hipFree(e.tree_dev); (void)hipFree(e.twig_dev); } chunks.clear(); }
-};
+// A chunk of a terrain window grown on the device with its device arrays (node words, bricks); a GrownWindow lists them in walk
+// order, and a failure on the way frees whatever was grown.
+struct GrownChunk { ChunkPools meta; int index = 0; DevBuf<uint32_t> tree_dev; DevBuf<uint16_t> twig_dev; };
+using GrownWindow = std::vector<GrownChunk>;
 
 // World::g_pyramid + g_chunk (src/World.cpp:296-321) on the device for every chunk of `win`, a column's pyramid built once.
 static int grow_window(const TerrainWindow &win, const TerrainParams &tp, DevicePyramidBuilder &pyr, DeviceGrower &grower,
@@ -675,9 +618,9 @@ static int grow_window(const TerrainWindow &win, const TerrainParams &tp, Device
         const TerrainWindow::Chunk at = win.chunk(k);
         int rc;
         if (k % win.column_height() == 0 && (rc = pyr.build(column_pyramid(tp, at.x, at.z), s)) != SVO_OK) return rc;
-        GrownWindow::Chunk &e = out.chunks.emplace_back();
+        GrownChunk &e = out.emplace_back();
         e.index = at.index;
-        if ((rc = grower.grow(e.meta, at.position, (float)win.chunksize, tp.depth, pyr.view, tp, s, filler, &e.tree_dev, &e.twig_dev)) != SVO_OK) return rc;
+        if ((rc = grower.grow(e.meta, at.position, (float)win.chunksize, tp.depth, pyr.view, tp, s, filler, e.tree_dev, e.twig_dev)) != SVO_OK) return rc;
     }
     return SVO_OK;
 }
@@ -694,7 +637,7 @@ static int generate_world_resident_impl(svo_world &w, int device)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("svo_world_generate: no HIP device for the device builder"); return SVO_ERR_NO_DEVICE; }
     if (device < 0 || device >= ndev) { set_error("svo_world_generate: build_device out of range"); return SVO_ERR_INVALID_ARG; }
-    BUILD_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     w.chunks.assign((size_t)w.width * w.height * w.depth, ChunkPools());
     GrownWindow grown;
     hipStream_t s = nullptr;
@@ -707,21 +650,21 @@ static int generate_world_resident_impl(svo_world &w, int device)
         if (rc != SVO_OK) return rc;
         lapt("noise + mips + grow + fill");
     }
-    for (const GrownWindow::Chunk &e : grown.chunks) w.chunks[(size_t)e.index] = e.meta;
+    for (const GrownChunk &e : grown) w.chunks[(size_t)e.index] = e.meta;
     // pack: the layout of svo_world_upload
     plan_pools(w);
     int rc = alloc_pools(w, device);
     if (rc != SVO_OK) return rc;
     lapt("alloc pools");
-    for (const GrownWindow::Chunk &e : grown.chunks)
-        if ((rc = copy_chunk(w, e.index, e.tree_dev, e.twig_dev, hipMemcpyDeviceToDevice, 0, e.meta.trees_on_device, 0, e.meta.twigs_on_device, s)) != SVO_OK) return rc;
-    BUILD_TRY(hipMemcpyAsync(w.d_chunks, w.table.data(), w.chunks.size() * sizeof(DevChunk), hipMemcpyHostToDevice, s));
-    BUILD_TRY(hipStreamSynchronize(s));
-    grown.release();
+    for (const GrownChunk &e : grown)
+        if ((rc = copy_chunk(w, e.index, e.tree_dev.p, e.twig_dev.p, hipMemcpyDeviceToDevice, 0, e.meta.trees_on_device, 0, e.meta.twigs_on_device, s)) != SVO_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(w.hbm->chunks.p, w.table.data(), w.chunks.size() * sizeof(DevChunk), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    grown.clear();
     lapt("pack + masks");
     const bool literal_only = build_wide_all(w, s) != SVO_OK;         // (a complete world either way: see svo_world_upload)
     lapt("wide trees");
-    BUILD_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipDeviceSynchronize());
     return literal_only ? SVO_OK_LITERAL_ONLY : SVO_OK;
 }
 
@@ -770,7 +713,7 @@ void free_builder_context(svo_world &w)
 // the toroidal index of a chunk coordinate does not depend on chunkcoordmin -, then chunkcoordmin moves.
 static int shift_world_resident_impl(svo_world &w, int axis, int sign)
 {
-    BUILD_TRY(hipSetDevice(w.device));
+    HIP_TRY(hipSetDevice(w.device));
     BuilderContext &ctx = builder_context(w);
     // The whole entering plane is generated before any of it is installed: a failure on the way (device memory, mostly) leaves
     // the world as it was.  Once the installs have begun they all happen and chunkcoordmin moves - no launch sees a grid whose
@@ -781,8 +724,8 @@ static int shift_world_resident_impl(svo_world &w, int axis, int sign)
                          ctx.pyr, ctx.grower, ctx.filler, nullptr, plane);
     if (rc != SVO_OK) return rc;
     int status = SVO_OK;
-    for (const GrownWindow::Chunk &e : plane.chunks) {
-        rc = install_resident_chunk(w, e.index, e.meta, e.tree_dev, e.twig_dev);
+    for (const GrownChunk &e : plane) {
+        rc = install_resident_chunk(w, e.index, e.meta, e.tree_dev.p, e.twig_dev.p);
         if (rc < 0) return rc;                      // a HIP failure in the middle of the copies: the device is in no state to go on with
         if (rc != SVO_OK) status = rc;
     }
@@ -802,8 +745,8 @@ int shift_world_resident(svo_world &w, int axis, int sign)
 // is dropped (svo_world_chunk fetches the edited pools on request).
 static int edit_box_resident_impl(svo_world &w, int chunk, int op, const float lo[3], const float hi[3], uint32_t material)
 {
-    BUILD_TRY(hipSetDevice(w.device));
-    BUILD_TRY(hipDeviceSynchronize());              // ordered behind every launch issued before it, like svo_world_update
+    HIP_TRY(hipSetDevice(w.device));
+    HIP_TRY(hipDeviceSynchronize());              // ordered behind every launch issued before it, like svo_world_update
     hipStream_t s = nullptr;
     const ChunkPools &c = w.chunks[(size_t)chunk];
     const DevChunk &e = w.table[(size_t)chunk];
@@ -813,8 +756,8 @@ static int edit_box_resident_impl(svo_world &w, int chunk, int op, const float l
     DevBuf<uint16_t> &twig = ctx.edit_twig;
     int rc;
     if ((rc = tree.reserve(trees + 1024, false, s)) != SVO_OK || (rc = twig.reserve((twigs + 16) * TWIG_WORDS, false, s)) != SVO_OK) return rc;
-    BUILD_TRY(hipMemcpyAsync(tree.p, w.d_tree + e.tree_off, trees * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-    if (twigs) BUILD_TRY(hipMemcpyAsync(twig.p, w.d_twig + e.twig_off * TWIG_WORDS, twigs * TWIG_WORDS * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(hipMemcpyAsync(tree.p, w.hbm->tree.p + e.tree_off, trees * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+    if (twigs) HIP_TRY(hipMemcpyAsync(twig.p, w.hbm->twig.p + e.twig_off * TWIG_WORDS, twigs * TWIG_WORDS * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
     ChunkPools meta;
     std::memcpy(meta.position, c.position, sizeof meta.position);
     meta.size = c.size; meta.depth = c.depth;

@@ -22,17 +22,11 @@
 #include <string>
 #include <vector>
 
-#include "world.h"
+#include "hip_own.h"
 
 namespace svo {
 
 namespace {
-
-#define LOD_TRY(expr)                                                                     \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess) { set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); return e_ == hipErrorOutOfMemory ? SVO_ERR_OUT_OF_MEMORY : SVO_ERR_HIP; } \
-    } while (0)
 
 constexpr unsigned LOD_BLOCK = 256;                 // 4 waves: sweep B / C brick kernels give one wave to each candidate
 constexpr uint32_t NO_KIDS = 0xFFFFFFFFu, DEAD = 0xFFFFFFFFu;
@@ -50,25 +44,6 @@ __device__ __forceinline__ uint32_t res_depth(uint2 r) { return r.y & 0xFFu; }
 __device__ __forceinline__ uint32_t res_kind(uint2 r) { return r.y >> 8; }
 __device__ __forceinline__ uint32_t leaf_value(uint32_t word) { return node_type(word) == LEAF ? node_offset(word) & 0xFFFFu : 0u; }
 __device__ __forceinline__ uint32_t octant(uint32_t x, uint32_t y, uint32_t z) { return (x & 1u) | (y & 1u) << 1 | (z & 1u) << 2; }
-
-// Consecutive values from *ctr for the threads of a block that raise `pred`, one atomic per block (every thread calls it).
-__device__ __forceinline__ uint32_t block_take(uint32_t *ctr, bool pred, uint32_t *sh)
-{
-    constexpr unsigned WAVES = LOD_BLOCK / 64;
-    const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(pred);
-    if (lane == 0u) sh[wv] = (uint32_t)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0u) {
-        uint32_t tot = 0u;
-        for (unsigned k = 0; k < WAVES; ++k) { const uint32_t c = sh[k]; sh[k] = tot; tot += c; }
-        sh[WAVES] = tot ? atomicAdd(ctr, tot) : 0u;
-    }
-    __syncthreads();
-    const uint32_t r = sh[WAVES] + sh[wv] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-    __syncthreads();
-    return r;
-}
 
 // One level's arrays (sweep_scratch).  old: the node's index in the old pool; kids: index of its child block in the next level's
 // list (NO_KIDS unless the recursion descends into it); res / cnt: sweep B's result and {blocks, bricks} of the subtree - in sweep
@@ -95,8 +70,8 @@ __global__ __launch_bounds__(LOD_BLOCK) void k_lod_gather(LodArgs A, uint32_t le
     const uint32_t type = node_type(word);
     const bool descend = live && type == BRANCH && level != A.coarse_level;
     const bool cand = live && (type == BRANCH || type == TWIG);
-    const uint32_t kids = block_take(&ctr[0], descend, sh);
-    const uint32_t c = block_take(&ctr[1], cand, sh);
+    const uint32_t kids = block_take<LOD_BLOCK>(&ctr[0], descend, sh);
+    const uint32_t c = block_take<LOD_BLOCK>(&ctr[1], cand, sh);
     if (!live) return;
     if (descend)
         for (uint32_t k = 0; k < 8; ++k) next_old[8 * (uint64_t)kids + k] = node_offset(word) + k;
@@ -236,19 +211,17 @@ __global__ __launch_bounds__(LOD_BLOCK) void k_lod_bricks(LodArgs A, LodLevel L,
     twig[(uint64_t)dst * TWIG_WORDS + lane] = (uint16_t)brick_cell(lane, r, L.kids[i], A, N.res, N.kids, res2);
 }
 
-inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
-
 int rebuild_resident_impl(svo_world &w, int chunk, bool lod)
 {
-    LOD_TRY(hipSetDevice(w.device));
-    LOD_TRY(hipDeviceSynchronize());                    // ordered behind every launch issued before it, like svo_world_edit_box
+    HIP_TRY(hipSetDevice(w.device));
+    HIP_TRY(hipDeviceSynchronize());                    // ordered behind every launch issued before it, like svo_world_edit_box
     hipStream_t s = nullptr;
     const ChunkPools &c = w.chunks[(size_t)chunk];
     const DevChunk &e = w.table[(size_t)chunk];
     const uint32_t maxlevel = c.depth - TWIG_LEVELS;
     LodArgs A;
-    A.tree = w.d_tree + e.tree_off;
-    A.twig = w.d_twig + e.twig_off * TWIG_WORDS;
+    A.tree = w.hbm->tree.p + e.tree_off;
+    A.twig = w.hbm->twig.p + e.twig_off * TWIG_WORDS;
     A.coarse_level = lod ? c.depth - 1 - TWIG_LEVELS : UINT32_MAX;
     const uint32_t last_level = lod ? A.coarse_level : maxlevel;        // no BRANCH below it is descended into
     int rc;
@@ -264,11 +237,11 @@ int rebuild_resident_impl(svo_world &w, int chunk, bool lod)
     };
     uint32_t *ctr = nullptr;
     if ((rc = sweep_scratch(w, 8 * 32, 2 * 32 * sizeof(uint32_t), (void **)&ctr)) != SVO_OK) return rc;
-    LOD_TRY(hipMemsetAsync(ctr, 0, 2 * 32 * sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(ctr, 0, 2 * 32 * sizeof(uint32_t), s));
     std::vector<LodLevel> lv(last_level + 2);
     if ((rc = level_arrays(0, 1, lv[0])) != SVO_OK) return rc;
     const uint32_t zero = 0;
-    LOD_TRY(hipMemcpyAsync(lv[0].old, &zero, sizeof zero, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(lv[0].old, &zero, sizeof zero, hipMemcpyHostToDevice, s));
     // sweep A
     uint32_t last = 0;
     for (uint32_t level = 0;; ++level) {
@@ -278,10 +251,10 @@ int rebuild_resident_impl(svo_world &w, int chunk, bool lod)
         // (level last_level descends into nothing: its children's list is never written; a one-entry dummy stands in)
         if ((rc = sweep_scratch(w, 8 * (level + 1), (level < last_level ? (size_t)L.n * 8 : 1) * 4, (void **)&next_old)) != SVO_OK) return rc;
         hipLaunchKernelGGL(k_lod_gather, dim3(blocks_for(L.n, LOD_BLOCK)), dim3(LOD_BLOCK), 0, s, A, level, L, next_old, ctr + 2 * level);
-        LOD_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
         uint32_t h[2];
-        LOD_TRY(hipMemcpyAsync(h, ctr + 2 * level, sizeof h, hipMemcpyDeviceToHost, s));
-        LOD_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpyAsync(h, ctr + 2 * level, sizeof h, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
         L.ncand = h[1];
         if (h[0] == 0) break;
         if (level >= last_level || (uint64_t)h[0] * 8 >= (1ull << 31)) {
@@ -297,10 +270,10 @@ int rebuild_resident_impl(svo_world &w, int chunk, bool lod)
         const uint2 *res2 = (size_t)level + 2 < lv.size() ? lv[(size_t)level + 2].res : nullptr;
         if (L.ncand) hipLaunchKernelGGL(k_lod_reduce, dim3(blocks_for(L.ncand, LOD_BLOCK / 64)), dim3(LOD_BLOCK), 0, s, A, (uint32_t)level, L, N, res2);
     }
-    LOD_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     uint32_t total[2];
-    LOD_TRY(hipMemcpyAsync(total, lv[0].cnt, sizeof total, hipMemcpyDeviceToHost, s));
-    LOD_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpyAsync(total, lv[0].cnt, sizeof total, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     const uint64_t trees = 1 + 8ull * total[0], twigs = total[1];
     if (trees >= (1ull << 30) || twigs >= (1ull << 30)) { set_error("svo_world_compact: chunk exceeds the 30-bit node offset"); return SVO_ERR_UNSUPPORTED; }
     uint32_t *tree = nullptr;
@@ -308,16 +281,16 @@ int rebuild_resident_impl(svo_world &w, int chunk, bool lod)
     if ((rc = edit_scratch(w, trees, twigs, &tree, &twig)) != SVO_OK) return rc;
     // sweep C: the root sits at slot 0 with nothing before it
     const uint32_t root[3] = { 0u, 0u, 0u };
-    LOD_TRY(hipMemcpyAsync(lv[0].slot, &root[0], sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    LOD_TRY(hipMemcpyAsync(lv[0].cnt, &root[1], sizeof(uint2), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(lv[0].slot, &root[0], sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(lv[0].cnt, &root[1], sizeof(uint2), hipMemcpyHostToDevice, s));
     for (uint32_t level = 0; level <= last; ++level) {
         const LodLevel &L = lv[level], &N = lv[level + 1];
         const uint2 *res2 = level + 2 < lv.size() ? lv[level + 2].res : nullptr;
         hipLaunchKernelGGL(k_lod_number, dim3(blocks_for(L.n, LOD_BLOCK)), dim3(LOD_BLOCK), 0, s, L, N, tree, trees);
         if (L.ncand) hipLaunchKernelGGL(k_lod_bricks, dim3(blocks_for(L.ncand, LOD_BLOCK / 64)), dim3(LOD_BLOCK), 0, s, A, L, N, res2, twig, twigs);
     }
-    LOD_TRY(hipGetLastError());
-    LOD_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
     ChunkPools meta;
     std::memcpy(meta.position, c.position, sizeof meta.position);
     meta.size = c.size; meta.depth = lod ? c.depth - 1 : c.depth;

@@ -25,21 +25,10 @@
 #include "kernel_literal.hip.h"
 #include "kernel_stack.hip.h"
 #include "see_through.hip.h"
+#include "hip_own.h"
 #include "wide_tree.hip.h"
-#include "world.h"
 
 using namespace svo;
-
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess) {                                                                    \
-            set_error(std::string(#expr) + ": " + hipGetErrorString(e_));                          \
-            return (e_ == hipErrorOutOfMemory) ? SVO_ERR_OUT_OF_MEMORY                             \
-                 : (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice) ? SVO_ERR_NO_DEVICE     \
-                 : SVO_ERR_HIP;                                                                    \
-        }                                                                                          \
-    } while (0)
 
 namespace svo {
 
@@ -87,7 +76,7 @@ static int launch_brick_masks(svo_world &w, uint64_t first, uint64_t count, hipS
 {
     const uint64_t blocks = (count * 8 + 255) / 256;
     if (blocks > 0x7FFFFFFFull) { set_error("brick pool too large for one mask launch"); return SVO_ERR_UNSUPPORTED; }
-    hipLaunchKernelGGL(k_brick_masks, dim3((unsigned)blocks), dim3(256), 0, s, w.d_twig, w.d_mask, w.d_bmat, first, count);
+    hipLaunchKernelGGL(k_brick_masks, dim3((unsigned)blocks), dim3(256), 0, s, w.hbm->twig.p, w.hbm->mask.p, w.hbm->bmat.p, first, count);
     HIP_TRY(hipGetLastError());
     return SVO_OK;
 }
@@ -101,11 +90,12 @@ static int launch_brick_masks(svo_world &w, uint64_t first, uint64_t count, hipS
 constexpr size_t POOL_CACHE_SLOTS = 8, POOL_CACHE_MIN = 1u << 20;
 struct PoolBuf { void *p; size_t bytes; int device; };
 static std::mutex g_pool_mutex;
-static std::vector<PoolBuf> g_pool_live, g_pool_cache;      // what pool_malloc has handed out / what pool_free has kept
+static std::vector<PoolBuf> g_pool_cache;                   // what pool_free has kept
 
-static hipError_t pool_malloc(void **out, size_t bytes, int device)
+hipError_t pool_malloc(void **out, size_t *asked, int device)
 {
-    if (bytes == 0) bytes = 1;
+    const size_t bytes = *asked ? *asked : 1;
+    *asked = bytes;
     {
         std::lock_guard<std::mutex> lock(g_pool_mutex);
         size_t best = g_pool_cache.size();
@@ -115,7 +105,7 @@ static hipError_t pool_malloc(void **out, size_t bytes, int device)
         }
         if (best != g_pool_cache.size()) {
             *out = g_pool_cache[best].p;
-            g_pool_live.push_back(g_pool_cache[best]);
+            *asked = g_pool_cache[best].bytes;
             g_pool_cache.erase(g_pool_cache.begin() + (long)best);
             return hipSuccess;
         }
@@ -125,18 +115,16 @@ static hipError_t pool_malloc(void **out, size_t bytes, int device)
         svo_device_cache_trim();
         e = hipMalloc(out, bytes);
     }
-    if (e == hipSuccess) { std::lock_guard<std::mutex> lock(g_pool_mutex); g_pool_live.push_back({ *out, bytes, device }); }
+    if (e != hipSuccess) *out = nullptr;
     return e;
 }
-static void pool_free(void *p)
+void pool_free(void *p, size_t bytes, int device)
 {
     if (!p) return;
-    PoolBuf b{ p, 0, -1 };
+    const PoolBuf b{ p, bytes, device };
     void *evict = nullptr;
     {
         std::lock_guard<std::mutex> lock(g_pool_mutex);
-        for (size_t i = 0; i < g_pool_live.size(); ++i)
-            if (g_pool_live[i].p == p) { b = g_pool_live[i]; g_pool_live.erase(g_pool_live.begin() + (long)i); break; }
         if (b.bytes >= POOL_CACHE_MIN) {
             if (g_pool_cache.size() >= POOL_CACHE_SLOTS) {  // full: the smallest buffer makes room (the large ones are the expensive ones)
                 size_t small = 0;
@@ -152,33 +140,20 @@ static void pool_free(void *p)
 // the see-through view (see_through.hip.h) and the continuation scratch: every change to the pools drops the view
 static void drop_view(svo_world &w)
 {
-    if (w.d_view_wide || w.d_view_mask) (void)hipDeviceSynchronize();
-    pool_free(w.d_view_wide); pool_free(w.d_view_mask);
-    w.d_view_wide = nullptr; w.d_view_mask = nullptr; w.view_material = 0;
+    if (w.hbm->view_wide.p || w.hbm->view_mask.p) (void)hipDeviceSynchronize();
+    w.hbm->view_wide = Pooled<uint32_t>(); w.hbm->view_mask = Pooled<uint64_t>(); w.hbm->view_material = 0;
 }
 
 int release_device(svo_world &w, bool keep_builder)
 {
-    if (w.device >= 0) {
+    if (w.hbm) {
         (void)hipSetDevice(w.device);
         drop_view(w);
         if (!keep_builder) free_builder_context(w);
         (void)hipDeviceSynchronize();                       // the large buffers may be handed to another world at once: nothing may still use them
-        (void)hipFree(w.d_chunks); pool_free(w.d_tree); pool_free(w.d_twig);
-        pool_free(w.d_mask); pool_free(w.d_bmat); (void)hipFree(w.d_work);
-        pool_free(w.d_wide); pool_free(w.d_wbase); (void)hipFree(w.d_wchunks); pool_free(w.d_wscratch); (void)hipFree(w.d_sort);
-        for (void *e : w.work_event) if (e) (void)hipEventDestroy((hipEvent_t)e);
-        if (w.sort_event) (void)hipEventDestroy((hipEvent_t)w.sort_event);
-        (void)hipFree(w.d_cont);
-        if (w.view_event) (void)hipEventDestroy((hipEvent_t)w.view_event);
-        if (w.cont_event) (void)hipEventDestroy((hipEvent_t)w.cont_event);
+        delete w.hbm;
+        w.hbm = nullptr;
     }
-    w.d_cont = nullptr; w.cont_rays = 0; w.view_event = nullptr; w.cont_event = nullptr;
-    w.work_event.clear();
-    w.d_chunks = nullptr; w.d_tree = nullptr; w.d_twig = nullptr; w.d_mask = nullptr; w.d_bmat = nullptr; w.d_work = nullptr;
-    w.d_wide = nullptr; w.d_wbase = nullptr; w.d_wchunks = nullptr; w.d_wscratch = nullptr; w.wscratch_words = 0; w.wscan_words = 0;
-    w.d_sort = nullptr; w.sort_bytes = 0; w.sort_event = nullptr;
-    if (w.h_wide_tail) { (void)hipHostFree(w.h_wide_tail); w.h_wide_tail = nullptr; }
     w.device = -1;
     w.table.clear(); w.tree_slot.clear(); w.twig_slot.clear(); w.wtable.clear(); w.wide_slot.clear();
     w.tree_pool_len = w.twig_pool_len = w.tree_pool_cap = w.twig_pool_cap = 0;
@@ -255,22 +230,22 @@ void plan_pools(svo_world &w)
 int alloc_pools(svo_world &w, int device)
 {
     if (hipSetDevice(device) != hipSuccess) { set_error("svo_world_upload: hipSetDevice failed"); return SVO_ERR_NO_DEVICE; }
+    Hbm &d = *(w.hbm = new Hbm());                                     // (both callers start from a released world: nothing is replaced)
     w.device = device;
     const size_t n = w.chunks.size();
-    if (pool_malloc((void **)&w.d_tree, w.tree_pool_cap * sizeof(uint32_t), device) != hipSuccess ||
-        pool_malloc((void **)&w.d_twig, w.twig_pool_cap * TWIG_WORDS * sizeof(uint16_t), device) != hipSuccess ||
-        pool_malloc((void **)&w.d_mask, w.twig_pool_cap * sizeof(uint64_t), device) != hipSuccess ||
-        pool_malloc((void **)&w.d_bmat, w.twig_pool_cap * sizeof(uint16_t), device) != hipSuccess ||
-        hipMalloc((void **)&w.d_chunks, n * sizeof(DevChunk)) != hipSuccess ||
-        hipMalloc((void **)&w.d_wchunks, n * sizeof(DevWide)) != hipSuccess ||
-        hipMalloc((void **)&w.d_work, WORK_SLOTS * WORK_SLOT_WORDS * sizeof(unsigned long long)) != hipSuccess) {
+    if (d.tree.alloc(w.tree_pool_cap, device) != hipSuccess ||
+        d.twig.alloc(w.twig_pool_cap * TWIG_WORDS, device) != hipSuccess ||
+        d.mask.alloc(w.twig_pool_cap, device) != hipSuccess ||
+        d.bmat.alloc(w.twig_pool_cap, device) != hipSuccess ||
+        d.chunks.reserve(n, false, nullptr) != SVO_OK ||
+        d.wchunks.reserve(n, false, nullptr) != SVO_OK ||
+        d.work.reserve(WORK_SLOTS * WORK_SLOT_WORDS, false, nullptr) != SVO_OK) {
         set_error("svo_world_upload: hipMalloc failed"); return SVO_ERR_OUT_OF_MEMORY;
     }
-    if (hipMemset(w.d_tree, 0, w.tree_pool_cap * sizeof(uint32_t)) != hipSuccess ||
-        hipMemset(w.d_mask, 0, w.twig_pool_cap * sizeof(uint64_t)) != hipSuccess ||
-        hipMemset(w.d_bmat, 0, w.twig_pool_cap * sizeof(uint16_t)) != hipSuccess ||
-        hipMemset(w.d_work, 0, WORK_SLOTS * WORK_SLOT_WORDS * sizeof(unsigned long long)) != hipSuccess) { set_error("svo_world_upload: hipMemset failed"); return SVO_ERR_HIP; }
-    std::fill(std::begin(w.stack_blocks), std::end(w.stack_blocks), 0);
+    if (hipMemset(d.tree.p, 0, w.tree_pool_cap * sizeof(uint32_t)) != hipSuccess ||
+        hipMemset(d.mask.p, 0, w.twig_pool_cap * sizeof(uint64_t)) != hipSuccess ||
+        hipMemset(d.bmat.p, 0, w.twig_pool_cap * sizeof(uint16_t)) != hipSuccess ||
+        hipMemset(d.work.p, 0, WORK_SLOTS * WORK_SLOT_WORDS * sizeof(unsigned long long)) != hipSuccess) { set_error("svo_world_upload: hipMemset failed"); return SVO_ERR_HIP; }
     w.wide_ok = false;                                                  // until build_wide_all has run
     return SVO_OK;
 }
@@ -284,9 +259,9 @@ int copy_chunk(svo_world &w, int i, const uint32_t *tree, const uint16_t *twig, 
     auto copy = [&](void *dst, const void *src, size_t bytes) {
         return kind == hipMemcpyDeviceToDevice ? hipMemcpyAsync(dst, src, bytes, kind, s) : hipMemcpy(dst, src, bytes, kind);
     };
-    if (tl < tr) HIP_TRY(copy(w.d_tree + e.tree_off + tl, tree + tl, (tr - tl) * sizeof(uint32_t)));
+    if (tl < tr) HIP_TRY(copy(w.hbm->tree.p + e.tree_off + tl, tree + tl, (tr - tl) * sizeof(uint32_t)));
     if (bl >= br) return SVO_OK;
-    HIP_TRY(copy(w.d_twig + (e.twig_off + bl) * TWIG_WORDS, twig + bl * TWIG_WORDS, (br - bl) * TWIG_WORDS * sizeof(uint16_t)));
+    HIP_TRY(copy(w.hbm->twig.p + (e.twig_off + bl) * TWIG_WORDS, twig + bl * TWIG_WORDS, (br - bl) * TWIG_WORDS * sizeof(uint16_t)));
     return launch_brick_masks(w, e.twig_off + bl, br - bl, s);
 }
 
@@ -295,45 +270,61 @@ int fetch_pools(svo_world &w, int chunk)
 {
     ChunkPools &c = w.chunks[(size_t)chunk];
     if (!c.twigs_on_device && !c.trees_on_device) return SVO_OK;
-    if (w.device < 0 || !w.d_twig || !w.d_tree) { set_error("fetch_pools: the device copy is gone"); return SVO_ERR_NOT_UPLOADED; }
+    if (!w.hbm || !w.hbm->twig.p || !w.hbm->tree.p) { set_error("fetch_pools: the device copy is gone"); return SVO_ERR_NOT_UPLOADED; }
     HIP_TRY(hipSetDevice(w.device));
     if (c.trees_on_device) {
         const uint64_t n = c.trees_on_device;
         c.tree.resize(n);
-        HIP_TRY(hipMemcpy(c.tree.data(), w.d_tree + w.table[(size_t)chunk].tree_off, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c.tree.data(), w.hbm->tree.p + w.table[(size_t)chunk].tree_off, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
         c.trees_on_device = 0;
     }
     if (c.twigs_on_device) {
         const uint64_t n = c.twigs_on_device;
         c.twig.resize(n * TWIG_WORDS);
-        HIP_TRY(hipMemcpy(c.twig.data(), w.d_twig + w.table[(size_t)chunk].twig_off * TWIG_WORDS, n * TWIG_WORDS * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(c.twig.data(), w.hbm->twig.p + w.table[(size_t)chunk].twig_off * TWIG_WORDS, n * TWIG_WORDS * sizeof(uint16_t), hipMemcpyDeviceToHost));
         c.twigs_on_device = 0;
     }
     return SVO_OK;
 }
 
+// The wide-tree builder's scratch for a chunk of at most B BRANCH nodes (= wide nodes a level can have): the two fronts, the flags and
+// ranks of a level's entries (64 per wide node), the entry references, a throw-away wide tree of B nodes and its bases (the count
+// pass of expand_into_scratch), then the scan's own scratch - kept 256-byte aligned: what precedes it is rounded up to 64 words.
+// Every offset grows with B: a scratch laid out for a larger chunk serves a smaller one as it is (reserve_wide_scratch).
+static WideLayout wide_layout(uint64_t B, size_t scan_bytes)
+{
+    WideLayout L;
+    L.next = B; L.flag = L.next + B; L.rank = L.flag + 64 * B; L.wref = L.rank + 64 * B; L.wide = L.wref + 64 * B; L.wbase = L.wide + 64 * B;
+    L.scan = ((L.wbase + WIDE_BASE_WORDS * B + 1024 + 63) / 64) * 64;
+    L.scan_words = (scan_bytes + 3) / 4 + 64; L.total = L.scan + L.scan_words;
+    return L;
+}
+
 // The wide tree of chunk `chunk` (wide_tree.hip.h) from its node words in the tree pool, level by level, into
 // wide_dst / wbase_dst (room for slot_cap wide nodes); *count = wide nodes written.  The per-entry reference indices that link
-// one level to the next live in the builder's scratch.
+// one level to the next live in the builder's scratch, which reserve_wide_scratch has laid out for this chunk or a larger one.
 // (results of this file's wide-tree helpers that are not svo_status values: they never leave this file)
 constexpr int WIDE_SLOT_FULL = 100;     // expand_wide_chunk: the chunk's wide tree does not fit slot_cap
 constexpr int WIDE_POOL_LIMIT = 101;    // build_wide_all's grow_pool: the pool would need 2^32 wide nodes or more (the literal kernel marches)
 static int expand_wide_chunk(svo_world &w, int chunk, hipStream_t s, uint32_t *wide_dst, uint32_t *wbase_dst, uint64_t slot_cap, uint64_t *count_out)
 {
+    Hbm &d = *w.hbm;
     const ChunkPools &c = w.chunks[(size_t)chunk];
     const DevChunk &e = w.table[(size_t)chunk];
     const uint32_t levels = c.depth - TWIG_LEVELS;
     const uint32_t nw = levels == 0 ? 1u : (levels + 1u) / 2u;
     const int pad = (int)(2u * nw - levels);
     const uint64_t B = c.tree_count() / 8 + 1;                          // most BRANCH nodes (= wide nodes) a level can have
-    uint32_t *front = w.d_wscratch, *next = front + B, *flag = next + B, *rank = flag + 64 * B, *wref_dst = rank + 64 * B;
-    const uint32_t *tree = w.d_tree + e.tree_off;
+    const WideLayout &L = d.wlayout;
+    uint32_t *const ws = d.wscratch.p;
+    uint32_t *front = ws, *next = ws + L.next, *flag = ws + L.flag, *rank = ws + L.rank, *wref_dst = ws + L.wref;
+    const uint32_t *tree = d.tree.p + e.tree_off;
     HIP_TRY(hipMemsetAsync(front, 0, sizeof(uint32_t), s));             // the top wide node expands reference node 0
-    if (!w.h_wide_tail && hipHostMalloc((void **)&w.h_wide_tail, 2 * sizeof(uint32_t)) != hipSuccess) { set_error("wide tree: hipHostMalloc failed"); return SVO_ERR_OUT_OF_MEMORY; }
+    if (d.wide_tail.alloc(2) != SVO_OK) { set_error("wide tree: hipHostMalloc failed"); return SVO_ERR_OUT_OF_MEMORY; }
     uint32_t count = 1, first = 0;
-    // the scan's own scratch lies behind the builder's (reserve_wide_scratch sized it for the largest level): no hipMalloc / hipFree per chunk
-    void *tmp = w.d_wscratch + (w.wscratch_words - w.wscan_words);
-    const size_t tmp_bytes = w.wscan_words * sizeof(uint32_t);
+    // the scan's own scratch lies behind the builder's (sized for the largest level): no hipMalloc / hipFree per chunk
+    void *tmp = ws + L.scan;
+    const size_t tmp_bytes = L.scan_words * sizeof(uint32_t);
     int rc = SVO_OK;
     for (uint32_t k = 0; k < nw && count > 0; ++k) {
         if ((uint64_t)first + count > slot_cap) { rc = WIDE_SLOT_FULL; break; }      // (the callers turn this into a larger slot, or into an error)
@@ -345,7 +336,7 @@ static int expand_wide_chunk(svo_world &w, int chunk, hipStream_t s, uint32_t *w
         size_t bytes = 0;
         if (hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, flag, rank, (int)n, s) != hipSuccess) { rc = SVO_ERR_HIP; break; }
         if (bytes > tmp_bytes) { set_error("wide tree: the scan asks for more scratch than was reserved"); rc = SVO_ERR_HIP; break; }
-        uint32_t *tail = w.h_wide_tail;                                 // pinned: a pageable destination stages every 4-byte copy
+        uint32_t *tail = d.wide_tail.p;                                 // pinned: a pageable destination stages every 4-byte copy
         if (hipcub::DeviceScan::ExclusiveSum(tmp, bytes, flag, rank, (int)n, s) != hipSuccess ||
             hipMemcpyAsync(&tail[0], rank + (n - 1), 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
             hipMemcpyAsync(&tail[1], flag + (n - 1), 4, hipMemcpyDeviceToHost, s) != hipSuccess ||
@@ -364,21 +355,19 @@ static int expand_wide_chunk(svo_world &w, int chunk, hipStream_t s, uint32_t *w
     return rc;
 }
 
-// scratch for the builder: fronts, flags, ranks of the largest chunk, and (count pass) a throw-away wide tree of its bound
-static int reserve_wide_scratch(svo_world &w, uint64_t largest_tree)
+// scratch for the builder (wide_layout) of a chunk of `trees` node words; one that is large enough already is kept as it is laid out
+static int reserve_wide_scratch(svo_world &w, uint64_t trees)
 {
-    const uint64_t B = largest_tree / 8 + 1;
+    Hbm &d = *w.hbm;
+    const uint64_t B = trees / 8 + 1;
     size_t scan_bytes = 0;
     uint32_t *nul = nullptr;
     if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, nul, nul, (int)(64 * B), (hipStream_t)nullptr) != hipSuccess) { set_error("wide tree: scan size query failed"); return SVO_ERR_HIP; }
-    const uint64_t scan_words = (scan_bytes + 3) / 4 + 64;
-    // fronts, flags + ranks, entry references + a throw-away tree, its bases; the scan's scratch (kept 256-byte aligned: everything before it is a multiple of 64 words)
-    const uint64_t body = ((2 * B + 2 * 64 * B + 2 * 64 * B + WIDE_BASE_WORDS * B + 1024 + 63) / 64) * 64;
-    const uint64_t need = body + scan_words;
-    if (scan_words <= w.wscan_words && body <= w.wscratch_words - w.wscan_words) return SVO_OK;
-    if (w.d_wscratch) { (void)hipDeviceSynchronize(); pool_free(w.d_wscratch); w.d_wscratch = nullptr; w.wscratch_words = 0; w.wscan_words = 0; }
-    if (pool_malloc((void **)&w.d_wscratch, need * sizeof(uint32_t), w.device) != hipSuccess) { set_error("wide tree: hipMalloc of the builder scratch failed"); return SVO_ERR_OUT_OF_MEMORY; }
-    w.wscratch_words = need; w.wscan_words = scan_words;
+    const WideLayout L = wide_layout(B, scan_bytes);
+    if (L.scan_words <= d.wlayout.scan_words && L.scan <= d.wlayout.scan) return SVO_OK;
+    if (d.wscratch.p) { (void)hipDeviceSynchronize(); d.wscratch = Pooled<uint32_t>(); d.wlayout = WideLayout(); }
+    if (d.wscratch.alloc(L.total, w.device) != hipSuccess) { set_error("wide tree: hipMalloc of the builder scratch failed"); return SVO_ERR_OUT_OF_MEMORY; }
+    d.wlayout = L;
     return SVO_OK;
 }
 static bool wide_fits(const svo_world &w, int chunk)
@@ -392,8 +381,8 @@ static bool wide_fits(const svo_world &w, int chunk)
 static void drop_wide(svo_world &w)
 {
     drop_view(w);
-    if (w.d_wide || w.d_wbase) (void)hipDeviceSynchronize();
-    pool_free(w.d_wide); pool_free(w.d_wbase); w.d_wide = w.d_wbase = nullptr;
+    if (w.hbm->wide.p || w.hbm->wbase.p) (void)hipDeviceSynchronize();
+    w.hbm->wide = Pooled<uint32_t>(); w.hbm->wbase = Pooled<uint32_t>();
     w.wide_ok = false;
     w.wide_pool_len = w.wide_pool_cap = w.wide_nodes_used = 0;
 }
@@ -402,8 +391,8 @@ static void drop_wide_scratch(svo_world &w, bool failed = true)
     // after a successful rebuild an interactive caller (one that has edited or slid the world: builder_ctx) keeps the scratch for
     // the next one; everybody else gets the ~1 GB back
     if (!failed && w.builder_ctx) return;
-    if (w.d_wscratch) { (void)hipDeviceSynchronize(); pool_free(w.d_wscratch); w.d_wscratch = nullptr; }
-    w.wscratch_words = 0; w.wscan_words = 0;
+    if (w.hbm->wscratch.p) { (void)hipDeviceSynchronize(); w.hbm->wscratch = Pooled<uint32_t>(); }
+    w.hbm->wlayout = WideLayout();
 }
 // the failure exit of a wide-tree build: no wide pool (the literal kernel marches the world) and no scratch
 static int wide_failed(svo_world &w, int rc, const char *why = nullptr)
@@ -413,7 +402,7 @@ static int wide_failed(svo_world &w, int rc, const char *why = nullptr)
     return rc;
 }
 
-// Chunk `chunk`'s wide tree into the throw-away tree at the end of the builder's scratch, reserved for this chunk first (room for all
+// Chunk `chunk`'s wide tree into the throw-away tree of the builder's scratch, reserved for this chunk first (room for all
 // its BRANCH nodes: *wide / *wbase, *count wide nodes)
 static int expand_into_scratch(svo_world &w, int chunk, hipStream_t s, uint32_t **wide, uint32_t **wbase, uint64_t *count)
 {
@@ -425,10 +414,16 @@ static int expand_into_scratch(svo_world &w, int chunk, hipStream_t s, uint32_t 
     if (rc == SVO_OK && fail && fail[0] == '1') { set_error("wide tree: injected allocation failure"); rc = SVO_ERR_OUT_OF_MEMORY; }
 #endif
     if (rc != SVO_OK) return rc;
-    *wide = w.d_wscratch + 2 * B + 3 * 64 * B; *wbase = *wide + 64 * B;
+    *wide = w.hbm->wscratch.p + w.hbm->wlayout.wide; *wbase = w.hbm->wscratch.p + w.hbm->wlayout.wbase;
     rc = expand_wide_chunk(w, chunk, s, *wide, *wbase, B, count);
     if (rc == WIDE_SLOT_FULL) { set_error("wide tree: more wide nodes than BRANCH nodes"); rc = SVO_ERR_MALFORMED_TREE; }
     return rc;
+}
+
+// a chunk's entry of the stack kernel's table: its frame from the chunk table, its top wide node at wide_off
+static DevWide wide_entry(const DevChunk &e, uint32_t wide_off)
+{
+    return DevWide{ { e.bmin[0], e.bmin[1], e.bmin[2] }, e.levels, wide_off, 0u, e.twig_off };
 }
 
 // Wide trees of every chunk from the node words, which must already be in the tree pool.
@@ -456,6 +451,7 @@ int build_wide_all(svo_world &w, void *stream)
     uint32_t *tmp_wide, *tmp_wbase;
     int rc = expand_into_scratch(w, (int)sample, s, &tmp_wide, &tmp_wbase, &count0);
     if (rc != SVO_OK) return wide_failed(w, rc);
+    Hbm &d = *w.hbm;
     uint64_t branches = 0;
     for (size_t i = 0; i < n; ++i) branches += w.chunks[i].tree_count() / 8 + 1;
     const double per_branch = (double)count0 / (double)(w.chunks[sample].tree_count() / 8 + 1);
@@ -465,31 +461,29 @@ int build_wide_all(svo_world &w, void *stream)
     // (the `hooks` variant only) SVO_TEST_WIDE_ESTIMATE=<factor> scales the estimate, so that the tests reach the growth path
     if (const char *e = std::getenv("SVO_TEST_WIDE_ESTIMATE")) cap = std::max<uint64_t>(64, (uint64_t)((double)cap * std::atof(e)));
 #endif
-    auto alloc_pool = [&](uint64_t nodes, uint32_t **wide, uint32_t **wbase) {
-        *wide = *wbase = nullptr;
+    auto alloc_pool = [&](uint64_t nodes, Pooled<uint32_t> &wide, Pooled<uint32_t> &wbase) {
         if (nodes >= (1ull << 32)) return false;
-        if (pool_malloc((void **)wide, nodes * 64 * sizeof(uint32_t), w.device) != hipSuccess) return false;
-        if (pool_malloc((void **)wbase, nodes * WIDE_BASE_WORDS * sizeof(uint32_t), w.device) != hipSuccess) { pool_free(*wide); *wide = nullptr; return false; }
+        if (wide.alloc(nodes * 64, w.device) != hipSuccess) return false;
+        if (wbase.alloc(nodes * WIDE_BASE_WORDS, w.device) != hipSuccess) { wide = Pooled<uint32_t>(); return false; }
         return true;
     };
     if (cap >= (1ull << 32)) return wide_failed(w, SVO_OK);                   // wide node indices are 32-bit (1 TiB of wide nodes): literal kernel
-    if (!alloc_pool(cap, &w.d_wide, &w.d_wbase)) return wide_failed(w, SVO_ERR_OUT_OF_MEMORY, "wide tree: hipMalloc of the pool failed");
+    if (!alloc_pool(cap, d.wide, d.wbase)) return wide_failed(w, SVO_ERR_OUT_OF_MEMORY, "wide tree: hipMalloc of the pool failed");
     uint64_t cur = 0, used = 0;
     auto grow_pool = [&](uint64_t at_least) -> int {
         uint64_t bigger = std::max<uint64_t>(cap + cap / 2, at_least + at_least / 16 + 64);
         if (bigger >= (1ull << 32)) return WIDE_POOL_LIMIT;
-        uint32_t *nw = nullptr, *nb = nullptr;
-        if (!alloc_pool(bigger, &nw, &nb)) return SVO_ERR_OUT_OF_MEMORY;
-        if (hipMemcpyAsync(nw, w.d_wide, cur * 64 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(nb, w.d_wbase, cur * WIDE_BASE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) { pool_free(nw); pool_free(nb); return SVO_ERR_HIP; }
-        pool_free(w.d_wide); pool_free(w.d_wbase);
-        w.d_wide = nw; w.d_wbase = nb; cap = bigger;
+        Pooled<uint32_t> nw, nb;
+        if (!alloc_pool(bigger, nw, nb)) return SVO_ERR_OUT_OF_MEMORY;
+        if (hipMemcpyAsync(nw.p, d.wide.p, cur * 64 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+            hipMemcpyAsync(nb.p, d.wbase.p, cur * WIDE_BASE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess) return SVO_ERR_HIP;
+        d.wide = std::move(nw); d.wbase = std::move(nb); cap = bigger;      // (nw / nb take the old pools back to the cache)
         return SVO_OK;
     };
     for (size_t i = 0; i < n; ) {
         uint64_t count = 0;
-        rc = expand_wide_chunk(w, (int)i, s, w.d_wide + cur * 64, w.d_wbase + cur * WIDE_BASE_WORDS, cap - cur, &count);
+        rc = expand_wide_chunk(w, (int)i, s, d.wide.p + cur * 64, d.wbase.p + cur * WIDE_BASE_WORDS, cap - cur, &count);
         const uint64_t slot = count + count / 8 + 16;
         if (rc == WIDE_SLOT_FULL || (rc == SVO_OK && cur + slot > cap)) {        // (grow, then this chunk again)
             const uint64_t bound = w.chunks[i].tree_count() / 8 + 1;
@@ -499,16 +493,13 @@ int build_wide_all(svo_world &w, void *stream)
             continue;
         }
         if (rc != SVO_OK) return wide_failed(w, rc);
-        const DevChunk &e = w.table[i];
-        DevWide &v = w.wtable[i];
-        v.bmin[0] = e.bmin[0]; v.bmin[1] = e.bmin[1]; v.bmin[2] = e.bmin[2];
-        v.levels = e.levels; v.wide_off = (uint32_t)cur; v._pad = 0; v.twig_off = e.twig_off;
+        w.wtable[i] = wide_entry(w.table[i], (uint32_t)cur);
         w.wide_slot[i] = slot;
         cur += slot;
         used += count;
         ++i;
     }
-    if (hipMemcpy(w.d_wchunks, w.wtable.data(), n * sizeof(DevWide), hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(d.wchunks.p, w.wtable.data(), n * sizeof(DevWide), hipMemcpyHostToDevice) != hipSuccess)
         return wide_failed(w, SVO_ERR_HIP, "wide tree: chunk table copy failed");
     w.wide_pool_len = cur; w.wide_pool_cap = cap; w.wide_nodes_used = used;
     w.wide_ok = true;
@@ -532,7 +523,6 @@ int rebuild_wide_chunk(svo_world &w, int chunk, void *stream)
     const int rc = expand_into_scratch(w, chunk, s, &tmp_wide, &tmp_wbase, &count);
     if (rc != SVO_OK) return wide_failed(w, rc);
     DevWide &v = w.wtable[(size_t)chunk];
-    const DevChunk &e = w.table[(size_t)chunk];
     if (count > w.wide_slot[(size_t)chunk]) {
         const uint64_t want = count + count / 4 + 16;
         if (w.wide_pool_len + want > w.wide_pool_cap) { drop_wide_scratch(w); return build_wide_all(w, stream); }
@@ -540,11 +530,10 @@ int rebuild_wide_chunk(svo_world &w, int chunk, void *stream)
         w.wide_slot[(size_t)chunk] = want;
         w.wide_pool_len += want;
     }
-    v.bmin[0] = e.bmin[0]; v.bmin[1] = e.bmin[1]; v.bmin[2] = e.bmin[2];
-    v.levels = e.levels; v.twig_off = e.twig_off;
-    if (hipMemcpyAsync(w.d_wide + (uint64_t)v.wide_off * 64, tmp_wide, count * 64 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(w.d_wbase + (uint64_t)v.wide_off * WIDE_BASE_WORDS, tmp_wbase, count * WIDE_BASE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-        hipMemcpyAsync(w.d_wchunks + chunk, &v, sizeof(DevWide), hipMemcpyHostToDevice, s) != hipSuccess ||
+    v = wide_entry(w.table[(size_t)chunk], v.wide_off);
+    if (hipMemcpyAsync(w.hbm->wide.p + (uint64_t)v.wide_off * 64, tmp_wide, count * 64 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(w.hbm->wbase.p + (uint64_t)v.wide_off * WIDE_BASE_WORDS, tmp_wbase, count * WIDE_BASE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(w.hbm->wchunks.p + chunk, &v, sizeof(DevWide), hipMemcpyHostToDevice, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) return wide_failed(w, SVO_ERR_HIP, "wide tree: copy of the rebuilt chunk failed");
     drop_wide_scratch(w, false);
     return SVO_OK;
@@ -579,7 +568,7 @@ static int world_upload_impl(svo_world *w, int device, bool force = false)
     // the stack kernel's wide trees: a failure here (device memory, mostly) leaves a complete world for the literal kernel
     // (build_wide_all has dropped whatever it had begun), and the caller is told so
     const bool literal_only = build_wide_all(*w, nullptr) != SVO_OK;
-    if (hipMemcpy(w->d_chunks, w->table.data(), n * sizeof(DevChunk), hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
+    if (hipMemcpy(w->hbm->chunks.p, w->table.data(), n * sizeof(DevChunk), hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
         set_error("svo_world_upload: chunk table copy failed"); release_device(*w); return SVO_ERR_HIP;
     }
     return literal_only ? SVO_OK_LITERAL_ONLY : SVO_OK;
@@ -626,7 +615,7 @@ static int install_chunk(svo_world &w, int chunk, const uint32_t *tree, const ui
     e.bmin[0] = c.position[0]; e.bmin[1] = c.position[1]; e.bmin[2] = c.position[2];
     int rc = copy_chunk(w, chunk, tree, twig, kind, tl, std::min(tr, trees), bl, std::min(br, twigs), nullptr);
     if (rc != SVO_OK) return rc;
-    if (table_dirty) HIP_TRY(hipMemcpy(w.d_chunks + chunk, &e, sizeof(DevChunk), hipMemcpyHostToDevice));
+    if (table_dirty) HIP_TRY(hipMemcpy(w.hbm->chunks.p + chunk, &e, sizeof(DevChunk), hipMemcpyHostToDevice));
     // the stack kernel's view of the chunk: rebuilt from the node words now in the pool
     // (the pools and the chunk table already hold the new chunk: a wide tree that cannot be rebuilt - rebuild_wide_chunk has dropped
     // the wide pool then - leaves a world the literal kernel marches, and the caller is told so instead of being told "error"
@@ -759,25 +748,26 @@ static const StackKernel STACK_KERNELS[] = {
     stack_kernel<16, false, true>, stack_kernel<16, false, false>,
     stack_kernel<22, false, true>, stack_kernel<22, false, false>,
 };
-static_assert(sizeof(STACK_KERNELS) / sizeof(StackKernel) == sizeof(svo_world::stack_blocks) / sizeof(int), "one grid size per instantiation");
+static_assert(sizeof(STACK_KERNELS) / sizeof(StackKernel) == sizeof(Hbm::stack_blocks) / sizeof(int), "one grid size per instantiation");
 
 } // namespace svo
 
 extern "C" {
 
 // ---------------------------------------------------------------------------------------------
+// the world box's minimum on axis a (src/Traverse.cpp:129-133)
+static float world_min(const svo_world *w, int a) { return (float)(w->chunkcoordmin[a] * (int)(float)w->chunksize); }
+
 static int fill_common(svo_world *w, const svo_trace_params *prm, TraceArgs &A)
 {
     if (!w) return SVO_ERR_INVALID_ARG;
     if (prm && prm->see_through > 0xFFFFu) { set_error("svo_trace: see_through is a 16-bit material"); return SVO_ERR_INVALID_ARG; }
     if (w->device < 0) { set_error("svo_trace: world is not uploaded"); return SVO_ERR_NOT_UPLOADED; }
     std::memset(&A, 0, sizeof A);
-    // src/Traverse.cpp:129-133
     const float cs = (float)w->chunksize;
-    const int ics = (int)cs;
     const int dims[3] = { w->width, w->height, w->depth };
     for (int a = 0; a < 3; ++a) {
-        A.worldmin[a] = (float)(w->chunkcoordmin[a] * ics);
+        A.worldmin[a] = world_min(w, a);
         A.worldmax[a] = (float)(w->chunkcoordmin[a] + dims[a]) * cs;
     }
     A.chunksize = cs;
@@ -787,8 +777,8 @@ static int fill_common(svo_world *w, const svo_trace_params *prm, TraceArgs &A)
         A.ccm[a] = w->chunkcoordmin[a];
         A.cbase[a] = positive_mod(w->chunkcoordmin[a], dims[a]);
     }
-    A.chunks = w->d_chunks; A.tree = w->d_tree; A.twig = w->d_twig; A.mask = w->d_mask;
-    A.wchunks = w->d_wchunks; A.wide = w->d_wide; A.wbase = w->d_wbase; A.bmat = w->d_bmat;
+    A.chunks = w->hbm->chunks.p; A.tree = w->hbm->tree.p; A.twig = w->hbm->twig.p; A.mask = w->hbm->mask.p;
+    A.wchunks = w->hbm->wchunks.p; A.wide = w->hbm->wide.p; A.wbase = w->hbm->wbase.p; A.bmat = w->hbm->bmat.p;
     if (prm && prm->semantics != SVO_SEMANTICS_CPU && prm->semantics != SVO_SEMANTICS_GLSL) { set_error("svo_trace: unknown semantics"); return SVO_ERR_INVALID_ARG; }
     const bool glsl = prm && prm->semantics == SVO_SEMANTICS_GLSL;      // defaults: src/Traverse.cpp:8,54,79,142 / shaders/Chunkmarch.glsl:1-3,17
     A.glsl = glsl ? 1 : 0;
@@ -811,7 +801,7 @@ static int fill_common(svo_world *w, const svo_trace_params *prm, TraceArgs &A)
     A.exact_geometry = w->exact_geometry ? 1 : 0;
     A.tile_cost = prm ? prm->tile_cost_dev : nullptr;
     A.tile_order = prm ? prm->tile_order_dev : nullptr;
-    A.work = w->d_work;                 // the launch picks its slot
+    A.work = w->hbm->work.p;                 // the launch picks its slot
     return SVO_OK;
 }
 
@@ -849,7 +839,7 @@ static int launch_stack(svo_world *w, const TraceArgs &A, int tiles_per_wave, in
     const int depth = stack_needs_big(w) ? (lv <= 10 ? 0 : 1) : lv <= 6 ? 2 : lv <= 10 ? 3 : lv <= 16 ? 4 : 5;
     const int which = 2 * depth + (A.glsl ? 0 : 1);
     const StackKernel kernel = STACK_KERNELS[which];
-    int &resident = w->stack_blocks[which];
+    int &resident = w->hbm->stack_blocks[which];
     if (resident <= 0) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, w->device) != hipSuccess) return SVO_ERR_HIP;
@@ -874,32 +864,31 @@ static int launch_stack(svo_world *w, const TraceArgs &A, int tiles_per_wave, in
 // before (the work-slot events), so that none still reading the old view sees the new one - and awaited by every launch that uses it.
 static int use_view(svo_world *w, uint32_t m, TraceArgs &A, hipStream_t s)
 {
-    hipEvent_t &built = reinterpret_cast<hipEvent_t &>(w->view_event);
-    if (w->view_material != m) {
+    Hbm &d = *w->hbm;
+    if (d.view_material != m) {
         const uint64_t n4 = w->wide_pool_len * 16, bricks = w->twig_pool_len;       // (64 entries = 16 uint4 per wide node)
-        if (!w->d_view_wide) {
-            if (pool_malloc((void **)&w->d_view_wide, std::max<uint64_t>(n4, 1) * sizeof(uint4), w->device) != hipSuccess ||
-                pool_malloc((void **)&w->d_view_mask, std::max<uint64_t>(bricks, 1) * sizeof(uint64_t), w->device) != hipSuccess) {
-                pool_free(w->d_view_wide); w->d_view_wide = nullptr; w->d_view_mask = nullptr;
+        if (!d.view_wide.p) {
+            if (d.view_wide.alloc(std::max<uint64_t>(n4, 1) * 4, w->device) != hipSuccess ||
+                d.view_mask.alloc(std::max<uint64_t>(bricks, 1), w->device) != hipSuccess) {
+                d.view_wide = Pooled<uint32_t>();
                 set_error("svo_trace: hipMalloc of the see-through view failed"); return SVO_ERR_OUT_OF_MEMORY;
             }
         } else {
-            for (void *e : w->work_event) if (e) HIP_TRY(hipStreamWaitEvent(s, (hipEvent_t)e, 0));
+            for (Event &e : d.work_done) if (e.e) if (const int rc = e.wait(s)) return rc;
         }
-        w->view_material = 0;                                           // (until the build below is issued)
+        d.view_material = 0;                                            // (until the build below is issued)
         if ((n4 + 255) / 256 > 0x7FFFFFFFull || (bricks * 8 + 255) / 256 > 0x7FFFFFFFull) { set_error("svo_trace: pools too large for one view launch"); return SVO_ERR_UNSUPPORTED; }
-        if (n4) hipLaunchKernelGGL(k_view_wide, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const uint4 *>(w->d_wide),
-                                   reinterpret_cast<uint4 *>(w->d_view_wide), n4, m);
-        if (bricks) hipLaunchKernelGGL(k_view_mask, dim3((unsigned)((bricks * 8 + 255) / 256)), dim3(256), 0, s, w->d_twig, w->d_mask, w->d_view_mask, bricks, m);
+        if (n4) hipLaunchKernelGGL(k_view_wide, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const uint4 *>(d.wide.p),
+                                   reinterpret_cast<uint4 *>(d.view_wide.p), n4, m);
+        if (bricks) hipLaunchKernelGGL(k_view_mask, dim3((unsigned)((bricks * 8 + 255) / 256)), dim3(256), 0, s, d.twig.p, d.mask.p, d.view_mask.p, bricks, m);
         HIP_TRY(hipGetLastError());
-        if (!built) HIP_TRY(hipEventCreateWithFlags(&built, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(built, s));
-        w->view_material = m;
+        if (const int rc = d.view_built.record(s)) return rc;
+        d.view_material = m;
     } else {
-        HIP_TRY(hipStreamWaitEvent(s, built, 0));
+        if (const int rc = d.view_built.wait(s)) return rc;
     }
-    A.wide = w->d_view_wide;
-    A.mask = w->d_view_mask;
+    A.wide = d.view_wide.p;
+    A.mask = d.view_mask.p;
     return SVO_OK;
 }
 
@@ -914,16 +903,15 @@ static int launch(svo_world *w, const svo_trace_params *prm, TraceArgs &A, hipSt
         if (rc != SVO_OK) return rc;
     }
     // every launch gets its own {tile cursor, ray count} slot so that launches on different streams may overlap
-    w->work_last = w->work_next;
-    w->work_next = (w->work_next + 1) % WORK_SLOTS;
-    A.work = w->d_work + WORK_SLOT_WORDS * w->work_last;
+    Hbm &d = *w->hbm;
+    d.work_last = d.work_next;
+    d.work_next = (d.work_next + 1) % WORK_SLOTS;
+    A.work = d.work.p + WORK_SLOT_WORDS * d.work_last;
     // a slot coming round again must not be reset under a launch that still reads it: order behind that launch
-    if (w->work_event.size() != WORK_SLOTS) w->work_event.assign(WORK_SLOTS, nullptr);
-    hipEvent_t &ev = reinterpret_cast<hipEvent_t &>(w->work_event[w->work_last]);
-    if (ev) HIP_TRY(hipStreamWaitEvent(s, ev, 0));
-    else HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    Event &ev = d.work_done[d.work_last];
+    if (const int rc = ev.wait(s)) return rc;
     HIP_TRY(hipMemsetAsync(A.work, 0, WORK_SLOT_WORDS * sizeof(unsigned long long), s));
-    if (A.n <= 0) return hipEventRecord(ev, s) == hipSuccess ? SVO_OK : SVO_ERR_HIP;
+    if (A.n <= 0) return ev.record(s) == SVO_OK ? SVO_OK : SVO_ERR_HIP;
     if (kernel == SVO_KERNEL_LITERAL) {
         const int64_t blocks = (A.n + 255) / 256;
         if (blocks > 0x7FFFFFFF) { set_error("svo_trace: too many rays for one launch"); return SVO_ERR_UNSUPPORTED; }
@@ -936,8 +924,16 @@ static int launch(svo_world *w, const svo_trace_params *prm, TraceArgs &A, hipSt
         if (rc != SVO_OK) { set_error("svo_trace: device query failed"); return rc; }
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev, s));
-    return SVO_OK;
+    return ev.record(s);
+}
+
+static FrameCam frame_cam(const svo_camera &c)
+{
+    FrameCam d;
+    std::memcpy(d.eye, c.eye, sizeof d.eye); std::memcpy(d.fwd, c.forward, sizeof d.fwd);
+    std::memcpy(d.right, c.right, sizeof d.right); std::memcpy(d.up, c.up, sizeof d.up);
+    d.tanx = c.tan_half_x; d.tany = c.tan_half_y;
+    return d;
 }
 
 static int fill_cameras(const svo_camera *cams, int nframes, TraceArgs &A)
@@ -947,10 +943,7 @@ static int fill_cameras(const svo_camera *cams, int nframes, TraceArgs &A)
         const svo_camera &c = cams[f];
         if (c.width <= 0 || c.height <= 0) { set_error("svo_trace: bad camera"); return SVO_ERR_INVALID_ARG; }
         if (c.width != cams[0].width || c.height != cams[0].height) { set_error("svo_trace_frames: the cameras of one launch share one image size"); return SVO_ERR_INVALID_ARG; }
-        FrameCam &d = A.cams[f];
-        std::memcpy(d.eye, c.eye, sizeof d.eye); std::memcpy(d.fwd, c.forward, sizeof d.fwd);
-        std::memcpy(d.right, c.right, sizeof d.right); std::memcpy(d.up, c.up, sizeof d.up);
-        d.tanx = c.tan_half_x; d.tany = c.tan_half_y;
+        A.cams[f] = frame_cam(c);
     }
     A.from_camera = 1;
     A.nframes = nframes;
@@ -1060,32 +1053,21 @@ int svo_trace_translucent(svo_world *w, const svo_camera *cam, const svo_trace_p
     if (n == 0) return SVO_OK;
     HIP_TRY(hipSetDevice(w->device));
     // the list lives in the world's scratch: calls on different streams are ordered behind one another (as svo_tile_order's sort)
-    hipEvent_t &done = reinterpret_cast<hipEvent_t &>(w->cont_event);
-    if (n > w->cont_rays) {
-        if (w->d_cont) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(w->d_cont); w->d_cont = nullptr; w->cont_rays = 0; }
-        if (hipMalloc((void **)&w->d_cont, (size_t)n * 6 * sizeof(float)) != hipSuccess) { set_error("svo_trace_translucent: hipMalloc failed"); return SVO_ERR_OUT_OF_MEMORY; }
-        w->cont_rays = n;
-    }
-    if (done) HIP_TRY(hipStreamWaitEvent(s, done, 0));
-    else HIP_TRY(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-    float *origins = w->d_cont, *dirs = w->d_cont + 3 * n;
-    FrameCam fc;
-    std::memcpy(fc.eye, cam->eye, sizeof fc.eye); std::memcpy(fc.fwd, cam->forward, sizeof fc.fwd);
-    std::memcpy(fc.right, cam->right, sizeof fc.right); std::memcpy(fc.up, cam->up, sizeof fc.up);
-    fc.tanx = cam->tan_half_x; fc.tany = cam->tan_half_y;
+    OrderedScratch<float> &list = w->hbm->cont;
+    if ((rc = list.reserve((size_t)n * 6, "svo_trace_translucent")) != SVO_OK) return rc;
+    if ((rc = list.done.wait(s)) != SVO_OK) return rc;
+    float *origins = list.buf.p, *dirs = list.buf.p + 3 * n;
     // the miss ray's origin: below the world box on y and z (by the box's extent), so that its line never meets the box
     const float cs = (float)w->chunksize;
-    const float miny = (float)(w->chunkcoordmin[1] * (int)cs), minz = (float)(w->chunkcoordmin[2] * (int)cs);
-    const float oy = miny - (float)w->height * cs - cs, oz = minz - (float)w->depth * cs - cs;
-    hipLaunchKernelGGL(k_continuation, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, fc, cam->width, cam->height, x0, y0, rw, n, m,
-                       (float)(w->chunkcoordmin[0] * (int)cs), oy, oz, reinterpret_cast<uint4 *>(surface_dev), origins, dirs);
+    const float oy = world_min(w, 1) - (float)w->height * cs - cs, oz = world_min(w, 2) - (float)w->depth * cs - cs;
+    hipLaunchKernelGGL(k_continuation, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, frame_cam(*cam), cam->width, cam->height, x0, y0, rw, n, m,
+                       world_min(w, 0), oy, oz, reinterpret_cast<uint4 *>(surface_dev), origins, dirs);
     HIP_TRY(hipGetLastError());
     svo_trace_params behind = *prm;                                     // (the caller's per-ray and per-tile buffers are sized for the surface)
     behind.counters_dev = nullptr; behind.tile_cost_dev = nullptr; behind.tile_order_dev = nullptr;
     rc = svo_trace_rays(w, origins, dirs, n, &behind, behind_dev, stream);
     if (rc != SVO_OK) return rc;
-    HIP_TRY(hipEventRecord(done, s));
-    return SVO_OK;
+    return list.done.record(s);
 }
 
 int svo_tile_order(svo_world *w, const uint32_t *cost_dev, uint32_t *order_dev, int ntiles, void *stream)
@@ -1100,24 +1082,16 @@ int svo_tile_order(svo_world *w, const uint32_t *cost_dev, uint32_t *order_dev, 
     uint32_t *nul = nullptr;
     if (hipcub::DeviceRadixSort::SortPairsDescending(nullptr, cub_bytes, nul, nul, nul, nul, ntiles, 0, 32, s) != hipSuccess) return SVO_ERR_HIP;
     const size_t need = (size_t)ntiles * 3 * sizeof(uint32_t) + cub_bytes + 256;
-    if (need > w->sort_bytes) {
-        if (w->d_sort) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(w->d_sort); w->d_sort = nullptr; w->sort_bytes = 0; }
-        if (hipMalloc(&w->d_sort, need) != hipSuccess) { set_error("svo_tile_order: hipMalloc failed"); return SVO_ERR_OUT_OF_MEMORY; }
-        w->sort_bytes = need;
-    }
-    // One scratch per world: calls on different streams (one cost / order pair per launch in flight is the intended use) are
-    // ordered behind one another here, like the work slots of the launches - a sort that shared its keys with another need not
-    // even yield a permutation.
-    hipEvent_t &sorted = reinterpret_cast<hipEvent_t &>(w->sort_event);
-    if (sorted) HIP_TRY(hipStreamWaitEvent(s, sorted, 0));
-    else HIP_TRY(hipEventCreateWithFlags(&sorted, hipEventDisableTiming));
-    uint32_t *keys = static_cast<uint32_t *>(w->d_sort), *keys_out = keys + ntiles, *idx = keys_out + ntiles;
+    OrderedScratch<unsigned char> &sort = w->hbm->sort;
+    if (const int rc = sort.reserve(need, "svo_tile_order")) return rc;
+    // calls on different streams (one cost / order pair per launch in flight) share it: a sort that shared its keys need not even yield a permutation
+    if (const int rc = sort.done.wait(s)) return rc;
+    uint32_t *keys = reinterpret_cast<uint32_t *>(sort.buf.p), *keys_out = keys + ntiles, *idx = keys_out + ntiles;
     void *tmp = reinterpret_cast<char *>(idx + ntiles) + ((256 - ((size_t)ntiles * 12) % 256) % 256);
     hipLaunchKernelGGL(k_tile_keys, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, s, cost_dev, keys, idx, ntiles);
     HIP_TRY(hipGetLastError());
     if (hipcub::DeviceRadixSort::SortPairsDescending(tmp, cub_bytes, keys, keys_out, idx, order_dev, ntiles, 0, 32, s) != hipSuccess) { set_error("svo_tile_order: sort failed"); return SVO_ERR_HIP; }
-    HIP_TRY(hipEventRecord(sorted, s));
-    return SVO_OK;
+    return sort.done.record(s);
 }
 
 int svo_trace_last_ray_count(svo_world *w, void *stream, uint64_t *rays)
@@ -1127,7 +1101,7 @@ int svo_trace_last_ray_count(svo_world *w, void *stream, uint64_t *rays)
     HIP_TRY(hipSetDevice(w->device));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     unsigned long long v[2] = { 0, 0 };
-    HIP_TRY(hipMemcpy(v, w->d_work + WORK_SLOT_WORDS * w->work_last, sizeof v, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(v, w->hbm->work.p + WORK_SLOT_WORDS * w->hbm->work_last, sizeof v, hipMemcpyDeviceToHost));
     *rays = v[1];
     return SVO_OK;
 }

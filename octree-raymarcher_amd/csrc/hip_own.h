@@ -1,0 +1,131 @@
+// hip_own.h — what the .hip files share: the HIP status mapping, block_take for the numbering kernels, the owners of HIP resources
+// and svo::Hbm, the device half of a world (the struct behind svo_world::hbm).  HIP only: world.h stays free of it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <utility>
+
+#include "world.h"
+
+namespace svo {
+
+inline int hip_status(hipError_t e)
+{
+    return e == hipErrorOutOfMemory ? SVO_ERR_OUT_OF_MEMORY : (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? SVO_ERR_NO_DEVICE : SVO_ERR_HIP;
+}
+#define HIP_TRY(expr)                                                                              \
+    do { if (hipError_t e_ = (expr); e_ != hipSuccess) { svo::set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); return svo::hip_status(e_); } } while (0)
+
+inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
+
+// Consecutive values from *ctr for the threads of a block of BLOCK threads that raise `pred` - ONE global atomic per block.  The
+// level-synchronous sweeps number millions of nodes through a handful of counters, and same-address atomics are served one after the
+// other (≈ 5.7 ns each here, even at the one per wave the compiler already folds a uniform atomicAdd to: a sweep over 4.8 M nodes took
+// 0.86 ms).  Every thread of the block calls this (no early return before it); sh holds BLOCK / 64 + 1 words.
+template <unsigned BLOCK> __device__ __forceinline__ uint32_t block_take(uint32_t *ctr, bool pred, uint32_t *sh)
+{
+    constexpr unsigned WAVES = BLOCK / 64;
+    const unsigned lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(pred);
+    if (lane == 0u) sh[wv] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        uint32_t tot = 0u;
+        for (unsigned w = 0; w < WAVES; ++w) { const uint32_t c = sh[w]; sh[w] = tot; tot += c; }
+        sh[WAVES] = tot ? atomicAdd(ctr, tot) : 0u;
+    }
+    __syncthreads();
+    const uint32_t r = sh[WAVES] + sh[wv] + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    __syncthreads();                                        // (sh may serve a second call)
+    return r;
+}
+
+// ---- owners: each frees what it holds, none can be copied; the two that change hands can be moved --------------------------------
+struct NoCopy { NoCopy() = default; NoCopy(const NoCopy &) = delete; NoCopy &operator=(const NoCopy &) = delete; };
+
+template <typename T> struct DevBuf {                       // cap elements of device memory
+    T *p = nullptr; size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }     // (o frees what this held)
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int reserve(size_t n, bool keep, hipStream_t s)         // at least n elements (an empty one: exactly n; else doubling), the old contents copied if `keep`
+    {
+        if (n <= cap) return SVO_OK;
+        DevBuf q; q.cap = std::max(n, cap * 2);
+        if (hipMalloc((void **)&q.p, q.cap * sizeof(T)) != hipSuccess) { q.p = nullptr; set_error("device builder: hipMalloc failed"); return SVO_ERR_OUT_OF_MEMORY; }
+        if (keep && p && cap) { if (hipMemcpyAsync(q.p, p, cap * sizeof(T), hipMemcpyDeviceToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return SVO_ERR_HIP; }
+        *this = std::move(q);
+        return SVO_OK;
+    }
+};
+
+// device memory of the pool cache (device.hip: the large buffers of a world); the handle knows what the cache needs to take it back
+hipError_t pool_malloc(void **out, size_t *bytes, int device);      // *bytes: asked for -> handed out (a cached buffer may be larger); *out = null if it fails
+void pool_free(void *p, size_t bytes, int device);
+template <typename T> struct Pooled {
+    T *p = nullptr; size_t bytes = 0; int device = -1;
+    Pooled() = default;
+    Pooled(Pooled &&o) noexcept : p(o.p), bytes(o.bytes), device(o.device) { o.p = nullptr; o.bytes = 0; }
+    Pooled &operator=(Pooled &&o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); std::swap(device, o.device); return *this; }
+    ~Pooled() { if (p) pool_free(p, bytes, device); }
+    // n elements on `dev`, whatever it held goes back to the cache first
+    hipError_t alloc(size_t n, int dev) { *this = Pooled(); bytes = n * sizeof(T); device = dev; return pool_malloc((void **)&p, &bytes, dev); }
+};
+
+template <typename T> struct Pinned : NoCopy {              // n elements of pinned host memory, allocated once
+    T *p = nullptr;
+    ~Pinned() { if (p) (void)hipHostFree(p); }
+    int alloc(size_t n) { if (!p) HIP_TRY(hipHostMalloc((void **)&p, n * sizeof(T))); return SVO_OK; }
+};
+
+// An event that orders the streams of a world's callers behind one another: created by its first use, destroyed with its owner.
+struct Event : NoCopy {
+    hipEvent_t e = nullptr;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    // `s` goes on behind the last record(); before the first one there is nothing to wait for (the event is created instead)
+    int wait(hipStream_t s) { if (e) HIP_TRY(hipStreamWaitEvent(s, e, 0)); else HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); return SVO_OK; }
+    int record(hipStream_t s) { if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); HIP_TRY(hipEventRecord(e, s)); return SVO_OK; }
+};
+
+// A scratch buffer of the world that calls on any stream use one after the other: reserve(), done.wait(s), the work, done.record(s).
+template <typename T> struct OrderedScratch {
+    DevBuf<T> buf; Event done;
+    int reserve(size_t n, const char *who)                  // too small: replaced by one of n elements, once the device is through with the old one
+    {
+        if (n <= buf.cap) return SVO_OK;
+        if (buf.p) HIP_TRY(hipDeviceSynchronize());
+        buf = DevBuf<T>();
+        if (buf.reserve(n, false, nullptr) != SVO_OK) { set_error(std::string(who) + ": hipMalloc failed"); return SVO_ERR_OUT_OF_MEMORY; }
+        return SVO_OK;
+    }
+};
+
+// The wide-tree builder's scratch in uint32 words from its start (device.hip: wide_layout is the one place that knows it); the
+// fronts begin at 0, the scan's own scratch is the tail
+struct WideLayout { uint64_t next = 0, flag = 0, rank = 0, wref = 0, wide = 0, wbase = 0, scan = 0, scan_words = 0, total = 0; };
+
+// What an uploaded world keeps on the device.  release_device (device.hip) lets go of it as a whole.
+struct Hbm {
+    DevBuf<DevChunk> chunks; DevBuf<DevWide> wchunks;       // the chunk tables (host mirrors: svo_world::table / wtable)
+    Pooled<uint32_t> tree; Pooled<uint64_t> mask;
+    Pooled<uint16_t> twig, bmat;                            // bmat: per brick its one material / 0 (empty) / 0xFFFF (several), written with the masks
+    Pooled<uint32_t> wide, wbase;                           // wide tree of every chunk (wide_tree.hip.h) and, per wide node, the reference blocks it expands
+    Pooled<uint32_t> wscratch; WideLayout wlayout;          // the wide builder's scratch and how it is laid out
+    Pinned<uint32_t> wide_tail;                             // the wide builder's per-level read-back
+    DevBuf<unsigned long long> work;                        // WORK_SLOTS x {tile cursor, rays marched}: one slot per launch in flight
+    unsigned work_next = 0, work_last = 0;                  // ring cursor; slot of the most recent launch
+    Event work_done[WORK_SLOTS];                            // recorded behind the launch that used the slot
+    OrderedScratch<unsigned char> sort;                     // svo_tile_order
+    OrderedScratch<float> cont;                             // svo_trace_translucent: continuation origins and directions, [2][rays][3]
+    // see-through view (svo_trace_params.see_through, see_through.hip.h): the wide and mask pools with one material taken out, built
+    // on the device at the first launch that asks for it, dropped by every change to the pools
+    Pooled<uint32_t> view_wide; Pooled<uint64_t> view_mask;
+    uint32_t view_material = 0;                             // material the view holds; 0 = no view
+    Event view_built;                                       // launches on other streams wait for it
+    int stack_blocks[12] = {};                              // persistent-grid size per k_trace_stack instantiation (device.hip: STACK_KERNELS); 0 = not queried yet
+};
+
+} // namespace svo

@@ -8,7 +8,7 @@
 #include <string>
 
 #include "march.hip.h"
-#include "world.h"
+#include "hip_own.h"
 
 namespace svo {
 namespace {
@@ -258,7 +258,7 @@ static int pack_common(const void *in, void *out, int64_t n, void *stream, bool 
     if (pack) hipLaunchKernelGGL(k_gbuffer_pack, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint4 *)in, (uint2 *)out, n);
     else hipLaunchKernelGGL(k_gbuffer_unpack, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint2 *)in, (uint4 *)out, n);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("svo_gbuffer_pack/unpack: ") + hipGetErrorString(e)); return e == hipErrorNoDevice ? SVO_ERR_NO_DEVICE : SVO_ERR_HIP; }
+    if (e != hipSuccess) { set_error(std::string("svo_gbuffer_pack/unpack: ") + hipGetErrorString(e)); return hip_status(e); }
     return SVO_OK;
 }
 
@@ -307,7 +307,7 @@ static int shade_impl(const svo_camera *cam, const svo_shade_params *p, int x0, 
     else hipLaunchKernelGGL(k_shade_translucent, grid, dim3(256), 0, (hipStream_t)stream, A, reinterpret_cast<const uint4 *>(behind_dev),
                             absorption == 0.0f ? 0.5f : absorption);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("svo_shade: ") + hipGetErrorString(e)); return e == hipErrorNoDevice ? SVO_ERR_NO_DEVICE : SVO_ERR_HIP; }
+    if (e != hipSuccess) { set_error(std::string("svo_shade: ") + hipGetErrorString(e)); return hip_status(e); }
     return SVO_OK;
 }
 

@@ -9,6 +9,8 @@
 #include "svo_format.h"
 #include "terrain.h"
 
+namespace svo { struct Hbm; }
+
 struct svo_world {
     // World (src/World.h:44-57)
     int width = 0, height = 0, depth = 0, chunksize = 0;
@@ -21,43 +23,16 @@ struct svo_world {
     bool exact_geometry = false;                  // every voxel corner is an exact float
     int  max_levels = 0;                          // max over chunks of depth - TWIG_LEVELS
 
-    // device residency
+    // device residency: the numbers the host half reads; everything HIP owns is behind `hbm` (hip_own.h), which only the .hip files see
     int device = -1;
-    svo::DevChunk *d_chunks = nullptr;
-    uint32_t *d_tree = nullptr;
-    uint16_t *d_twig = nullptr;
-    uint64_t *d_mask = nullptr;
-    uint16_t *d_bmat = nullptr;                   // per brick: its one material / 0 (empty) / 0xFFFF (several), written with the masks
-    uint32_t *d_wide = nullptr, *d_wbase = nullptr; // wide tree of every chunk (wide_tree.hip.h) and, per wide node, the reference blocks it expands
-    svo::DevWide *d_wchunks = nullptr;
-    std::vector<svo::DevWide> wtable;             // host mirror of d_wchunks
-    std::vector<uint64_t> wide_slot;              // capacity of each chunk's wide slot (wide nodes)
-    uint64_t wide_pool_len = 0, wide_pool_cap = 0, wide_nodes_used = 0;
-    uint32_t *d_wscratch = nullptr;               // builder scratch: fronts, flags, ranks
-    uint32_t *h_wide_tail = nullptr;              // pinned: the wide builder's per-level read-back
-    uint64_t wscratch_words = 0, wscan_words = 0;  // its size; the tail of it that is the scan's own scratch
-    void *builder_ctx = nullptr;                  // builder.hip: working buffers svo_world_shift / svo_world_edit_box keep between calls
-    void *d_sort = nullptr;                       // svo_tile_order scratch
-    size_t sort_bytes = 0;
-    void *sort_event = nullptr;                   // hipEvent_t behind the last svo_tile_order: the next one (any stream) waits for it before it reuses the scratch
-    bool wide_ok = false;                         // every chunk's bricks fit the 26-bit payload
-    unsigned long long *d_work = nullptr;         // WORK_SLOTS x {tile cursor, rays marched}: one slot per launch in flight
-    unsigned work_next = 0, work_last = 0;        // ring cursor; slot of the most recent launch
-    std::vector<void *> work_event;               // hipEvent_t per slot, recorded behind the launch that used it
-    std::vector<svo::DevChunk> table;             // host mirror of d_chunks
-    std::vector<uint64_t> tree_slot, twig_slot;   // capacity of each chunk's slot (nodes / bricks)
+    svo::Hbm *hbm = nullptr;                      // non-null exactly while device >= 0 (alloc_pools / release_device)
+    std::vector<svo::DevChunk> table; std::vector<svo::DevWide> wtable;    // host mirrors of hbm->chunks / wchunks
+    std::vector<uint64_t> tree_slot, twig_slot, wide_slot;   // capacity of each chunk's slots (nodes / bricks / wide nodes)
     uint64_t tree_pool_len = 0, twig_pool_len = 0;    // elements in use (incl. alignment padding)
     uint64_t tree_pool_cap = 0, twig_pool_cap = 0;    // elements allocated
-    // see-through view (svo_trace_params.see_through, see_through.hip.h): the wide and mask pools with one material taken out, built
-    // on the device at the first launch that asks for it, dropped by every change to the pools
-    uint32_t *d_view_wide = nullptr;
-    uint64_t *d_view_mask = nullptr;
-    uint32_t view_material = 0;                   // material the view holds; 0 = no view
-    void *view_event = nullptr;                   // hipEvent_t behind the view's build: launches on other streams wait for it
-    float *d_cont = nullptr;                      // svo_trace_translucent: continuation origins and directions, [2][cont_rays][3]
-    int64_t cont_rays = 0;
-    void *cont_event = nullptr;                   // hipEvent_t behind the last continuation launch (the next call waits before reusing d_cont)
-    int stack_blocks[12] = {};                    // persistent-grid size per k_trace_stack instantiation (device.hip: STACK_KERNELS); 0 = not queried yet
+    uint64_t wide_pool_len = 0, wide_pool_cap = 0, wide_nodes_used = 0;
+    bool wide_ok = false;                         // the wide pool is complete: every chunk's bricks fit the 26-bit payload and the build succeeded
+    void *builder_ctx = nullptr;                  // builder.hip: working buffers svo_world_shift / svo_world_edit_box keep between calls
 };
 
 namespace svo {
@@ -70,7 +45,7 @@ void classify_world(svo_world &w);
 int  release_device(svo_world &w, bool keep_builder = false);
 // device.hip: HBM residency building blocks shared by svo_world_upload and the device-resident generator
 void plan_pools(svo_world &w);                    // slots, offsets and pool sizes from the chunks' capacities (host only)
-int  alloc_pools(svo_world &w, int device);       // hipMalloc + clear of the pools planned above; sets w.device
+int  alloc_pools(svo_world &w, int device);       // hipMalloc + clear of the pools planned above; sets w.device and w.hbm
 #ifdef __HIP__
 // node words [tl, tr) and bricks [bl, br) of chunk i from host vectors (hipMemcpyHostToDevice, synchronous) or device buffers
 // (hipMemcpyDeviceToDevice, on `stream`) into its slots, then the masks of those bricks
