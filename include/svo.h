@@ -33,6 +33,8 @@
  *   svo_trace_params.see_through <- the `ignore` material of treemarch / twigmarch   shaders/Chunkmarch.glsl:190-191,240-241,280
  *   svo_trace_translucent <- the second march from a translucent hit   shaders/ParallaxAlpha.Fragment.glsl:141-199,276-335
  *   svo_shade_translucent <- its blend by the path length through the liquid   shaders/ParallaxAlpha.Fragment.glsl:226-234,315-323
+ *   svo_trace_local_shadows <- (a departure: the reference gives the directional light's shadow term to all three lights,
+ *                           shaders/World.Fragment.glsl:186-190) one occlusion ray per hit towards the point light and the spotlight
  *
  * Conventions
  *   - plain C, opaque handle, caller owns every buffer it passes in;
@@ -73,7 +75,8 @@ extern "C" {
                                        4: SVO_OK_LITERAL_ONLY, svo_device_cache_trim, svo_trace_params.semantics;
                                           4 later gained svo_world_compact and svo_world_coarsen (functions added, nothing changed),
                                           svo_trace_params.see_through (was padding: zeroed structs keep their results),
-                                          svo_trace_translucent and svo_shade_translucent */
+                                          svo_trace_translucent and svo_shade_translucent,
+                                          svo_trace_local_shadows and SVO_LOCAL_SHADOWS / SVO_SHADOWED_POINT / SVO_SHADOWED_SPOT */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -220,6 +223,9 @@ enum {
     SVO_SHADOWED      = 1u << 2,    /* ... and it hit something */
     SVO_FACE_NORMAL   = 1u << 3,    /* normal[] is the entered-face normal (svo_trace_params.normal_mode = SVO_NORMAL_FACE) */
     SVO_SEE_THROUGH   = 1u << 4,    /* svo_trace_translucent: the surface hit is of the see-through material; the behind record is its continuation */
+    SVO_LOCAL_SHADOWS  = 1u << 5,   /* svo_trace_local_shadows has been through this record: bits 6 and 7 are valid for it */
+    SVO_SHADOWED_POINT = 1u << 6,   /* ... the point light is occluded (or, not asked for, a copy of SVO_SHADOWED) */
+    SVO_SHADOWED_SPOT  = 1u << 7,   /* ... the spotlight is */
     SVO_ERR_FLAG      = 1u << 15    /* runaway ray: given up after 2^22 march steps of the kernel's own counting (only rays that
                                        creep through all three nested loops of the reference get there; the stack kernel
                                        takes creeping stretches in closed form and finishes rays the literal kernel gives
@@ -385,6 +391,28 @@ int svo_tile_order(svo_world *, const uint32_t *cost_dev, uint32_t *order_dev, i
 int svo_trace_translucent(svo_world *, const svo_camera *cam, const svo_trace_params *params,
                           int x0, int y0, int w, int h, svo_hit *surface_dev, svo_hit *behind_dev, void *stream);
 
+/* Shadows from the point light and the spotlight, one flag per light.  The reference hands the directional light's shadow term to
+ * all three light functions (shaders/World.Fragment.glsl:186-190), and so does svo_shade on a record without SVO_LOCAL_SHADOWS;
+ * this call is the opt-in departure.  gbuffer_dev holds the w*h records that svo_trace(cam, params, x0, y0, w, h) wrote (or the
+ * surface records of svo_trace_translucent).  For every record with SVO_HIT_FLAG and without SVO_ERR_FLAG, and every light asked
+ * for (position L; NULL = not asked for, both NULL is SVO_ERR_INVALID_ARG):
+ *   P = o + d * (t - eps)   (o, d) the pixel's camera ray, eps the launch's (0 = 1/8192, 1/4096 under SVO_SEMANTICS_GLSL): the point
+ *                           the directional shadow ray starts from; every operation separately rounded;
+ *   v = L - P, q = v.x*v.x + v.y*v.y + v.z*v.z (left to right), direction v * (1 / sqrt(q)), dist = sqrt(q);
+ *   the ray (P, direction) is marched as svo_trace_rays marches it with `params` and shadow = 0 (eps, caps, semantics, kernel and
+ *   see_through are honoured); the light is OCCLUDED iff that ray's record has SVO_HIT_FLAG, has no SVO_ERR_FLAG and its t < dist -
+ *   terrain behind the light does not shadow it, a runaway ray is "traced, not occluded".  q == 0 or not finite: no ray, not occluded.
+ * The record then gets SVO_LOCAL_SHADOWS, and SVO_SHADOWED_POINT / SVO_SHADOWED_SPOT are written: the occlusion of a light asked for,
+ * a copy of the record's SVO_SHADOWED for a light that was not (it keeps the reference's behaviour).  No other byte of the record
+ * changes; records without a hit or with SVO_ERR_FLAG stay exactly as they were.  The three bits lie in the low flag byte, so
+ * svo_gbuffer_pack carries them and svo_shade(_packed / _translucent) uses them: one shadow factor per light.
+ * All the lights' rays go through ONE ray-list launch (svo_trace_last_ray_count then reports lights * w * h: pixels without a usable
+ * hit get a ray that misses the world); the list and its records live in the world's scratch, 56 bytes per ray.  Asynchronous on
+ * `stream`; calls of one world on different streams are ordered behind one another on the device. */
+int svo_trace_local_shadows(svo_world *, const svo_camera *cam, const svo_trace_params *params,
+                            const float point_position[3], const float spot_position[3],
+                            int x0, int y0, int w, int h, svo_hit *gbuffer_dev, void *stream);
+
 /* ---- packed G-buffer (8 bytes / pixel) for the multi-GPU gather ------------------------------------------
  * { float t; uint32 w } with w = material (bits 0-15) | flags & 0xFF (bits 16-23) | normal code (bits 24-30) |
  * SVO_ERR_FLAG (bit 31): per axis 2 bits (0: -, 1: 0, 2: +) in bits 24-29, bit 30 = NaN normal.  cubeNormal only ever yields
@@ -396,7 +424,9 @@ int svo_gbuffer_unpack(const uint64_t *packed_dev, svo_hit *gbuffer_dev, int64_t
 /* ---- shading stage: Blinn-Phong x 3 lights over the G-buffer --------------------
  * shaders/World.Fragment.glsl:63-138,180-197.  The reference multiplies the lights with gamma-decoded samples of
  * its Diffuse / Specular texture atlas, which is not part of the repository; here the albedo comes from the
- * material table's diffuse / specular colours instead (pow(colour, gamma)), the shadow term from SVO_SHADOWED.
+ * material table's diffuse / specular colours instead (pow(colour, gamma)), the shadow term from SVO_SHADOWED
+ * for all three lights - or, on a record that carries SVO_LOCAL_SHADOWS, from SVO_SHADOWED_POINT for the point light, SVO_SHADOWED_SPOT
+ * for the spotlight and SVO_SHADOWED for the directional light.
  * Output per pixel: float4 {r, g, b, depth} with depth = (1/dist - 1/near) / (1/far - 1/near) (gl_FragDepth,
  * World.Fragment.glsl:193-197); misses give {0,0,0,1}. */
 typedef struct svo_material { float ambient[3], diffuse[3], specular[3]; float shininess; } svo_material;

@@ -8,6 +8,7 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     World.draw(camera, ...)                   <- World::draw            src/World.cpp:205-266
     World.chunkmarch(origins, dirs)           <- chunkmarch             src/Traverse.cpp:127-171
     World.draw_translucent(camera, m)         <- ParallaxAlpha's march past water   shaders/ParallaxAlpha.Fragment.glsl:141-199,276-335
+    World.trace_local_shadows(camera, ...)    <- (none: the reference's three lights share the directional light's shadow term)
     World.index / index_float                 <- World::index(_float)   src/World.cpp:288-293,323-332
 
 There is NO CPU fallback: if libsvo_amd.so is missing the import raises, and every device call
@@ -48,6 +49,7 @@ EMPTY, LEAF, BRANCH, TWIG = 0, 1, 2, 3
 KERNEL_AUTO, KERNEL_LITERAL, KERNEL_STACK = 0, 1, 2
 EDIT_BUILD, EDIT_DESTROY, EDIT_REPLACE = 0, 1, 2     # svo_world_edit_box
 HIT_FLAG, SHADOW_TRACED, SHADOWED, FACE_NORMAL, SEE_THROUGH, ERR_FLAG = 1, 2, 4, 8, 16, 1 << 15
+LOCAL_SHADOWS, SHADOWED_POINT, SHADOWED_SPOT = 1 << 5, 1 << 6, 1 << 7     # svo_trace_local_shadows
 NORMAL_CUBE, NORMAL_FACE = 0, 1
 SEMANTICS_CPU, SEMANTICS_GLSL = 0, 1
 CELL_NONE = 0xFF
@@ -131,7 +133,7 @@ ABI_SYMBOLS = [
     "svo_world_generate", "svo_world_create", "svo_world_info_get", "svo_world_chunk", "svo_world_destroy",
     "svo_world_index_float", "svo_world_index", "svo_world_upload", "svo_world_update",
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
-    "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_translucent", "svo_trace_last_ray_count",
+    "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_device_count", "svo_device_alloc", "svo_device_free", "svo_device_cache_trim", "svo_memcpy_h2d", "svo_memcpy_d2h",
     "svo_stream_synchronize", "svo_last_error", "svo_abi_version",
 ]
@@ -165,6 +167,8 @@ lib.svo_shade.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams), C.c_int, C.
 lib.svo_shade_packed.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]
 lib.svo_shade_translucent.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams), C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
 lib.svo_trace_translucent.argtypes = [_P, C.POINTER(Camera), C.POINTER(TraceParams), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]
+lib.svo_trace_local_shadows.argtypes = [_P, C.POINTER(Camera), C.POINTER(TraceParams), C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                        C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]
 lib.svo_world_upload.argtypes = [_P, C.c_int]
 lib.svo_world_update.argtypes = [_P, C.c_int, C.POINTER(ChunkDesc), C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int]
 lib.svo_trace.argtypes = [_P, C.POINTER(Camera), C.POINTER(TraceParams), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]
@@ -511,6 +515,14 @@ class World:
         _check(lib.svo_trace_translucent(self._h, C.byref(cam), C.byref(params), x0, y0, w, h, surface_ptr, behind_ptr, stream),
                "svo_trace_translucent")
 
+    def trace_local_shadows(self, cam: Camera, params: TraceParams, rect, gbuffer_ptr: int, point=None, spot=None, stream: int = 0):
+        """svo_trace_local_shadows on the G-buffer svo_trace(cam, params, rect) filled: SHADOWED_POINT / SHADOWED_SPOT from one occlusion
+        ray per hit towards `point` / `spot` (positions; None = that light keeps the record's SHADOWED), LOCAL_SHADOWS on every hit."""
+        x0, y0, w, h = rect
+        vec = [None if v is None else (C.c_float * 3)(*[float(c) for c in v]) for v in (point, spot)]
+        _check(lib.svo_trace_local_shadows(self._h, C.byref(cam) if cam is not None else None, C.byref(params) if params is not None else None,
+                                           vec[0], vec[1], x0, y0, w, h, gbuffer_ptr, stream), "svo_trace_local_shadows")
+
     def tile_order(self, cost_ptr: int, order_ptr: int, ntiles: int, stream: int = 0):
         """svo_tile_order: tile indices by descending cost (of one frame) into order_ptr."""
         _check(lib.svo_tile_order(self._h, cost_ptr, order_ptr, ntiles, stream), "svo_tile_order")
@@ -522,14 +534,17 @@ class World:
 
     # -- convenience: World::draw / chunkmarch returning numpy -------------------------------
     def draw(self, cam: Camera, rect=None, shadow: bool = False, kernel: int = KERNEL_AUTO, counters: bool = False,
-             light_dir=(1.0, -1.0, 0.0), normal_mode: int = 0, semantics: int = 0, see_through: int = 0):
-        """Trace a rectangle of the camera image; returns the G-buffer (HIT_DTYPE[h, w]) [+ counters]."""
+             light_dir=(1.0, -1.0, 0.0), normal_mode: int = 0, semantics: int = 0, see_through: int = 0, local_shadows=None):
+        """Trace a rectangle of the camera image; returns the G-buffer (HIT_DTYPE[h, w]) [+ counters].
+        local_shadows=(point, spot): positions (or None) handed to trace_local_shadows behind the trace."""
         x0, y0, w, h = rect if rect is not None else (0, 0, cam.width, cam.height)
         out = DeviceBuffer(max(w * h, 1) * 32)
         cnt = DeviceBuffer(max(w * h, 1) * 16) if counters else None
         prm = trace_params(shadow=shadow, kernel=kernel, light_dir=light_dir, counters_dev=cnt.ptr if cnt else None, normal_mode=normal_mode,
                            semantics=semantics, see_through=see_through)
         self.trace(cam, prm, (x0, y0, w, h), out.ptr)
+        if local_shadows is not None:
+            self.trace_local_shadows(cam, prm, (x0, y0, w, h), out.ptr, point=local_shadows[0], spot=local_shadows[1])
         _check(lib.svo_stream_synchronize(None), "svo_stream_synchronize")
         g = out.to_numpy(HIT_DTYPE, w * h).reshape(h, w)
         out.free()

@@ -25,6 +25,7 @@
 #include "kernel_literal.hip.h"
 #include "kernel_stack.hip.h"
 #include "see_through.hip.h"
+#include "local_shadows.hip.h"
 #include "hip_own.h"
 #include "wide_tree.hip.h"
 
@@ -1067,6 +1068,48 @@ int svo_trace_translucent(svo_world *w, const svo_camera *cam, const svo_trace_p
     behind.counters_dev = nullptr; behind.tile_cost_dev = nullptr; behind.tile_order_dev = nullptr;
     rc = svo_trace_rays(w, origins, dirs, n, &behind, behind_dev, stream);
     if (rc != SVO_OK) return rc;
+    return list.done.record(s);
+}
+
+// Shadows from the point light and the spotlight (local_shadows.hip.h): the ray list of every light asked for, ONE ray-list launch
+// for all of them (the stack kernel's persistent waves drain once, not once per light), the fold into gbuffer_dev's flag words.
+int svo_trace_local_shadows(svo_world *w, const svo_camera *cam, const svo_trace_params *prm, const float *point_position, const float *spot_position,
+                            int x0, int y0, int rw, int rh, svo_hit *gbuffer_dev, void *stream)
+{
+    if (!w || !cam || !prm || !gbuffer_dev || (!point_position && !spot_position) || rw < 0 || rh < 0 || x0 < 0 || y0 < 0 || cam->width <= 0 || cam->height <= 0) {
+        set_error("svo_trace_local_shadows: bad argument"); return SVO_ERR_INVALID_ARG;
+    }
+    TraceArgs A;                                                        // (for the launch's resolved eps; checks see_through, semantics and residency)
+    int rc = fill_common(w, prm, A);
+    if (rc != SVO_OK) return rc;
+    LocalLights L;
+    std::memset(&L, 0, sizeof L);
+    if (point_position) { std::memcpy(L.pos[L.count], point_position, 12); L.bit[L.count++] = SVO_SHADOWED_POINT; }
+    if (spot_position) { std::memcpy(L.pos[L.count], spot_position, 12); L.bit[L.count++] = SVO_SHADOWED_SPOT; }
+    const int64_t n = (int64_t)rw * rh, rays = n * L.count;
+    if (n == 0) return SVO_OK;
+    if (rays > 0x7FFFFFFF) { set_error("svo_trace_local_shadows: image too large"); return SVO_ERR_UNSUPPORTED; }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(w->device));
+    // the records and the list live in the world's scratch: calls on different streams are ordered behind one another (as svo_trace_translucent's)
+    OrderedScratch<float> &list = w->hbm->local;
+    if ((rc = list.reserve((size_t)rays * 14, "svo_trace_local_shadows")) != SVO_OK) return rc;
+    if ((rc = list.done.wait(s)) != SVO_OK) return rc;
+    float *records = list.buf.p, *origins = records + 8 * rays, *dirs = origins + 3 * rays;
+    const float cs = (float)w->chunksize;                               // the miss ray of svo_trace_translucent
+    const float oy = world_min(w, 1) - (float)w->height * cs - cs, oz = world_min(w, 2) - (float)w->depth * cs - cs;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    hipLaunchKernelGGL(k_local_rays, grid, dim3(256), 0, s, frame_cam(*cam), cam->width, cam->height, x0, y0, rw, n, A.eps, L,
+                       world_min(w, 0), oy, oz, reinterpret_cast<const uint4 *>(gbuffer_dev), origins, dirs);
+    HIP_TRY(hipGetLastError());
+    svo_trace_params march = *prm;                                      // (the caller's per-ray and per-tile buffers are sized for the frame)
+    march.shadow = 0;
+    march.counters_dev = nullptr; march.tile_cost_dev = nullptr; march.tile_order_dev = nullptr;
+    rc = svo_trace_rays(w, origins, dirs, rays, &march, reinterpret_cast<svo_hit *>(records), stream);
+    if (rc != SVO_OK) return rc;
+    hipLaunchKernelGGL(k_local_resolve, grid, dim3(256), 0, s, frame_cam(*cam), cam->width, cam->height, x0, y0, rw, n, A.eps, L,
+                       reinterpret_cast<const uint4 *>(records), reinterpret_cast<uint4 *>(gbuffer_dev));
+    HIP_TRY(hipGetLastError());
     return list.done.record(s);
 }
 

@@ -74,7 +74,11 @@ __device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, uint3
     const int mi = material < 8 ? (int)material : 0;
     const float shininess = P.materials[mi].shininess;
     const V3 diffuse = ld3(A.gdiffuse[mi]), specular = ld3(A.gspecular[mi]);                          // :183-184
-    const float lit = (flags & SVO_SHADOWED) ? 0.0f : 1.0f;                                          // (1.0 - shadow)
+    // (1.0 - shadow): the directional light's term for all three (:186-190), unless svo_trace_local_shadows gave each local light its own
+    const float lit = (flags & SVO_SHADOWED) ? 0.0f : 1.0f;
+    const bool local = (flags & SVO_LOCAL_SHADOWS) != 0u;
+    const float lit_point = local ? ((flags & SVO_SHADOWED_POINT) ? 0.0f : 1.0f) : lit;
+    const float lit_spot = local ? ((flags & SVO_SHADOWED_SPOT) ? 0.0f : 1.0f) : lit;
     // normalize(eye - p) = -beta and |p - eye| = sigma - EPS (beta is a unit vector) while the hit lies in front of the eye
     const bool front = sdist > 1.0e-3f;
     const V3 vdir = front ? mk(-beta.x, -beta.y, -beta.z) : normalize_fast(eye - p);
@@ -89,8 +93,8 @@ __device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, uint3
         const float s = pow_shiny(maxf0(dot3(vdir, hv)), shininess);
         const float att = attenuation(P.point.constant, P.point.linear, P.point.quadratic, l2 * il);     // |p - position| = l2 / sqrt(l2)
         const V3 amb = ld3(P.point.ambient) * diffuse;
-        const V3 dif = ((ld3(P.point.diffuse) * d) * diffuse) * lit;
-        const V3 spe = ((ld3(P.point.specular) * s) * specular) * lit;
+        const V3 dif = ((ld3(P.point.diffuse) * d) * diffuse) * lit_point;
+        const V3 spe = ((ld3(P.point.specular) * s) * specular) * lit_point;
         color = color + ((amb + dif) + spe) * att;
     }
     {   // computeDirectionalLight_BlinnPhong, :99-114
@@ -116,8 +120,8 @@ __device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, uint3
         intensity = (intensity < 0.0f) ? 0.0f : intensity;                      // clamp = min(max(x, 0), 1)
         intensity = (1.0f < intensity) ? 1.0f : intensity;
         const V3 amb = ld3(P.spot.ambient) * diffuse;
-        const V3 dif = ((ld3(P.spot.diffuse) * d) * diffuse) * lit;
-        const V3 spe = ((ld3(P.spot.specular) * s) * specular) * lit;
+        const V3 dif = ((ld3(P.spot.diffuse) * d) * diffuse) * lit_spot;
+        const V3 spe = ((ld3(P.spot.specular) * s) * specular) * lit_spot;
         color = color + (amb + (dif + spe) * intensity) * att;
     }
     return make_float4(color.x, color.y, color.z, (rcp_fast(zdist) - A.inv_near) * A.inv_depth_range);     // :193-197

@@ -8,6 +8,7 @@
 //   svo::World::init(w,h,d,s)        <- World::init            src/World.cpp:19-43
 //   svo::World::load_gpu()           <- World::load_gpu        src/World.cpp:57-94
 //   svo::World::draw(camera, ...)    <- World::draw (+ draw_shadowmap as the fused shadow ray)  src/World.cpp:162-266
+//   svo::World::local_shadows(...)   <- (none: per-light shadows of the point light and the spotlight, svo_trace_local_shadows)
 //   svo::World::modify(i, ...)       <- World::modify          src/World.cpp:268-274
 //   svo::World::index / index_float  <- src/World.cpp:288-293,323-332
 //   svo::World::deinit()             <- World::deinit          src/World.cpp:129-151
@@ -146,6 +147,21 @@ public:
         if (light_dir) std::memcpy(p.light_dir, light_dir, sizeof p.light_dir);
         std::vector<svo_camera> plain(cams.begin(), cams.end());
         check(svo_trace_frames(world_, plain.data(), (int)plain.size(), &p, 0, 0, w, h, out.device(), stream), "World::draw_frames");
+    }
+
+    // Shadows from the point light and the spotlight on a G-buffer that draw() filled with the same camera, shadow flag and light
+    // direction (svo_trace_local_shadows): one flag per light, a null position leaves that light with the directional light's term.
+    // Not in the reference, whose three lights share one shadow term (shaders/World.Fragment.glsl:186-190).
+    void local_shadows(const Camera &cam, GBuffer &gbuffer, const float point_position[3], const float spot_position[3],
+                       bool shadow = false, const float light_dir[3] = nullptr, void *stream = nullptr)
+    {
+        svo_trace_params p;
+        std::memset(&p, 0, sizeof p);
+        p.semantics = semantics;
+        p.shadow = shadow ? 1 : 0;
+        if (light_dir) std::memcpy(p.light_dir, light_dir, sizeof p.light_dir);
+        check(svo_trace_local_shadows(world_, &cam, &p, point_position, spot_position, 0, 0, cam.width, cam.height, gbuffer.device(), stream),
+              "World::local_shadows");
     }
 
     // World::modify(i, tree delta, twig delta): re-send an edited chunk (Ocdelta ranges, src/Octree.h:47-54).

@@ -1,0 +1,102 @@
+"""Shadows from the point light and the spotlight on the benchmark's C3 world: ms per frame of svo_trace(shadow=1)
+alone, followed by svo_trace_local_shadows with one light and with both (the reference's light rig, svo_shade_defaults), and of
+svo_shade, over bench.py's 32-camera path at 1920x1080 - one launch per frame, best of --reps passes, the variants interleaved
+within each pass - plus the share of pixels that got rays and the scratch the call holds.  Prints one JSON line.
+
+    python scripts/local_shadows_timing.py [--reps 3] [--out FILE] [--root CHECKOUT] [--baseline]
+
+--root measures another checkout's package and library (default: this one); --baseline measures svo_trace and svo_shade only, for a
+checkout that predates the call.
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    ap.add_argument("--baseline", action="store_true")
+    a = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(a.root))
+    import bench  # noqa: E402  (its camera path)
+    svo = importlib.import_module("octree-raymarcher_amd")
+
+    def sync():
+        svo.lib.svo_stream_synchronize(None)
+
+    gw, gh, gd, depth, iw, ih = 4, 1, 4, 12, 1920, 1080
+    W = svo.World.generate(gw, gh, gd, 128, depth, build_device=0)
+    cams = bench.camera_path(svo, "c3_1080p_depth12_4x1x4_shadow", gw, gd, iw, ih)
+    n = iw * ih
+    rect = (0, 0, iw, ih)
+    g, rgba = svo.DeviceBuffer(n * 32), svo.DeviceBuffer(n * 16)
+    sp = svo.shade_defaults()
+    point, spot = tuple(sp.point.position), tuple(sp.spot.position)
+    prm = svo.trace_params(shadow=True)
+
+    def pass_ms(lights):
+        """One pass over the camera path: svo_trace, then the local shadows of `lights` (None: none), one sync at the end."""
+        sync()
+        t0 = time.perf_counter()
+        for c in cams:
+            W.trace(c, prm, rect, g.ptr)
+            if lights is not None:
+                W.trace_local_shadows(c, prm, rect, g.ptr, point=lights[0], spot=lights[1])
+        sync()
+        return (time.perf_counter() - t0) * 1e3 / len(cams)
+
+    def shade_ms():
+        sync()
+        t0 = time.perf_counter()
+        for c in cams:
+            svo.shade(c, sp, rect, g.ptr, rgba.ptr)
+        sync()
+        return (time.perf_counter() - t0) * 1e3 / len(cams)
+
+    variants = {"trace_ms": None}
+    if not a.baseline:
+        variants.update({"trace_point_ms": (point, None), "trace_spot_ms": (None, spot), "trace_both_ms": (point, spot)})
+    for lights in variants.values():                                # warm-up (scratch allocated, occupancy queried)
+        pass_ms(lights)
+    shade_ms()
+    times = {k: [] for k in list(variants) + ["shade_ms"]}
+    for _ in range(a.reps):
+        for k, lights in variants.items():
+            times[k].append(pass_ms(lights))
+        times["shade_ms"].append(shade_ms())                        # (on the last camera's G-buffer, local-shadow flags included)
+    res = {"world": [gw, gh, gd, depth], "image": [iw, ih], "cameras": len(cams), "reps": a.reps, "baseline": bool(a.baseline)}
+    for k, v in times.items():
+        res[k] = round(min(v), 4)
+        res[k + "_passes"] = [round(x, 4) for x in v]
+    if not a.baseline:
+        fr = []
+        for c in cams:
+            W.trace(c, prm, rect, g.ptr)
+            sync()
+            fl = g.to_numpy(svo.HIT_DTYPE, n)["flags"]
+            fr.append(float(np.count_nonzero(((fl & svo.HIT_FLAG) != 0) & ((fl & svo.ERR_FLAG) == 0))) / n)
+        res["pixels_with_rays_mean"] = round(float(np.mean(fr)), 4)
+        res["pixels_with_rays_min_max"] = [round(min(fr), 4), round(max(fr), 4)]
+        res["scratch_bytes_per_light"] = n * 56                     # 32 B record + 24 B origin and direction per ray of the padded list
+        res["scratch_bytes_both"] = 2 * n * 56
+    g.free()
+    rgba.free()
+    W.destroy()
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
