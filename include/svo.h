@@ -18,6 +18,8 @@
  *                           src/Main.cpp:190-222; stereo / split-screen views; a pipelined renderer's next frames)
  *   svo_trace_rows(_frames) <- the same over the interleaved row bands of one rank (multi-GPU partition)
  *   svo_trace_rays       <- chunkmarch over a ray list             src/Traverse.cpp:127-171
+ *   svo_trace_segments   <- (no counterpart: chunkmarch has no far end) the same list with a far end per ray: line of sight,
+ *                           picking with a reach, short occlusion rays, a light inside the world
  *   svo_tile_order       <- (no counterpart: the GL rasteriser schedules fragments itself) longest-first tile order of the
  *                           next World::draw from the previous one's per-tile step counts
  *   svo_world_destroy    <- World::deinit                          src/World.cpp:129-151
@@ -76,7 +78,8 @@ extern "C" {
                                           4 later gained svo_world_compact and svo_world_coarsen (functions added, nothing changed),
                                           svo_trace_params.see_through (was padding: zeroed structs keep their results),
                                           svo_trace_translucent and svo_shade_translucent,
-                                          svo_trace_local_shadows and SVO_LOCAL_SHADOWS / SVO_SHADOWED_POINT / SVO_SHADOWED_SPOT */
+                                          svo_trace_local_shadows and SVO_LOCAL_SHADOWS / SVO_SHADOWED_POINT / SVO_SHADOWED_SPOT,
+                                          svo_trace_segments */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -370,6 +373,20 @@ int svo_trace_rows_frames(svo_world *, const svo_camera *cams, int nframes, cons
 /* chunkmarch over an explicit list: origins_dev/dirs_dev are [n][3] float on the device. */
 int svo_trace_rays(svo_world *, const float *origins_dev, const float *dirs_dev, int64_t n,
                    const svo_trace_params *params, svo_hit *out_dev, void *stream);
+
+/* Bounded rays: svo_trace_rays with a far end per ray, tmax_dev[n] float on the device.  With R[k] the record svo_trace_rays
+ * writes for ray k under the same params:
+ *   out[k] = R[k], byte for byte (shadow bits included when params->shadow != 0), if R[k] has SVO_HIT_FLAG, has no SVO_ERR_FLAG
+ *            and R[k].t < tmax_dev[k] (one float compare, strict);
+ *   out[k] = the miss record (all zero) otherwise; no shadow ray is cast from a dropped hit.
+ * So tmax = +inf reproduces svo_trace_rays, and tmax <= 0 or NaN (the compare is false) gives a miss.  The march ENDS at the far
+ * end, it is not filtered afterwards: a ray stops as soon as no later hit can have t < tmax.  A ray is given up with SVO_ERR_FLAG
+ * only where its march has not yet passed tmax; such records stay outside the equality above, as they do between the two kernels.
+ * Every field of params means what it means for svo_trace_rays.  counters_dev (literal kernel) counts what the BOUNDED march
+ * read - never more than the unbounded one, in any word of any ray; it has no CPU-oracle counterpart.  svo_trace_last_ray_count
+ * reports n, plus one per kept hit when params->shadow != 0.  tmax_dev == NULL with n > 0 is SVO_ERR_INVALID_ARG; n == 0 is SVO_OK. */
+int svo_trace_segments(svo_world *, const float *origins_dev, const float *dirs_dev, const float *tmax_dev, int64_t n,
+                       const svo_trace_params *params, svo_hit *out_dev, void *stream);
 
 /* order_dev[0..ntiles) = the tile indices sorted by descending cost[i][0] + cost[i][1] (a stable device sort; cost_dev as
  * svo_trace_params.tile_cost_dev of ONE frame wrote it).  Asynchronous on `stream`; calls of one world on different streams are

@@ -133,7 +133,7 @@ ABI_SYMBOLS = [
     "svo_world_generate", "svo_world_create", "svo_world_info_get", "svo_world_chunk", "svo_world_destroy",
     "svo_world_index_float", "svo_world_index", "svo_world_upload", "svo_world_update",
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
-    "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
+    "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_device_count", "svo_device_alloc", "svo_device_free", "svo_device_cache_trim", "svo_memcpy_h2d", "svo_memcpy_d2h",
     "svo_stream_synchronize", "svo_last_error", "svo_abi_version",
 ]
@@ -177,6 +177,7 @@ lib.svo_trace_frames.argtypes = [_P, C.POINTER(Camera), C.c_int, C.POINTER(Trace
 lib.svo_trace_rows_frames.argtypes = [_P, C.POINTER(Camera), C.c_int, C.POINTER(TraceParams), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]
 lib.svo_tile_order.argtypes = [_P, _P, _P, C.c_int, _P]
 lib.svo_trace_rays.argtypes = [_P, _P, _P, C.c_int64, C.POINTER(TraceParams), _P, _P]
+lib.svo_trace_segments.argtypes = [_P, _P, _P, _P, C.c_int64, C.POINTER(TraceParams), _P, _P]
 lib.svo_trace_last_ray_count.argtypes = [_P, _P, C.POINTER(C.c_uint64)]
 lib.svo_device_count.restype = C.c_int
 lib.svo_device_alloc.argtypes = [C.c_size_t]
@@ -509,6 +510,10 @@ class World:
     def trace_rays(self, origins_ptr: int, dirs_ptr: int, n: int, params: TraceParams, out_ptr: int, stream: int = 0):
         _check(lib.svo_trace_rays(self._h, origins_ptr, dirs_ptr, n, C.byref(params), out_ptr, stream), "svo_trace_rays")
 
+    def trace_segments(self, origins_ptr: int, dirs_ptr: int, tmax_ptr: int, n: int, params: TraceParams, out_ptr: int, stream: int = 0):
+        """svo_trace_segments: trace_rays with a far end per ray (tmax_ptr: [n] float on the device); a hit counts only if t < tmax."""
+        _check(lib.svo_trace_segments(self._h, origins_ptr, dirs_ptr, tmax_ptr, n, C.byref(params), out_ptr, stream), "svo_trace_segments")
+
     def trace_translucent(self, cam: Camera, params: TraceParams, rect, surface_ptr: int, behind_ptr: int, stream: int = 0):
         """svo_trace_translucent: the surface G-buffer and, behind every hit of material params.see_through, the continuation's."""
         x0, y0, w, h = rect
@@ -570,20 +575,25 @@ class World:
 
     def chunkmarch(self, origins, dirs, shadow: bool = False, kernel: int = KERNEL_AUTO, counters: bool = False,
                    light_dir=(1.0, -1.0, 0.0), eps: float = 0.0, caps=(0, 0, 0), normal_mode: int = 0, semantics: int = 0,
-                   see_through: int = 0):
-        """chunkmarch over a ray list (src/Traverse.cpp:127-171); returns HIT_DTYPE[n] [+ counters]."""
+                   see_through: int = 0, tmax=None):
+        """chunkmarch over a ray list (src/Traverse.cpp:127-171); returns HIT_DTYPE[n] [+ counters].
+        tmax: a far end per ray (a scalar or [n] floats): the rays are marched as segments (svo_trace_segments)."""
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
         n = o.shape[0]
         od, dd = DeviceBuffer.from_numpy(o), DeviceBuffer.from_numpy(d)
+        td = None if tmax is None else DeviceBuffer.from_numpy(np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,))))
         out = DeviceBuffer(max(n, 1) * 32)
         cnt = DeviceBuffer(max(n, 1) * 16) if counters else None
         prm = trace_params(shadow=shadow, kernel=kernel, light_dir=light_dir, eps=eps, caps=caps,
                            counters_dev=cnt.ptr if cnt else None, normal_mode=normal_mode, semantics=semantics, see_through=see_through)
-        self.trace_rays(od.ptr, dd.ptr, n, prm, out.ptr)
+        if td is None:
+            self.trace_rays(od.ptr, dd.ptr, n, prm, out.ptr)
+        else:
+            self.trace_segments(od.ptr, dd.ptr, td.ptr, n, prm, out.ptr)
         _check(lib.svo_stream_synchronize(None), "svo_stream_synchronize")
         g = out.to_numpy(HIT_DTYPE, n)
-        for b in (od, dd, out):
+        for b in (od, dd, out) + (() if td is None else (td,)):
             b.free()
         if counters:
             c = cnt.to_numpy(np.uint32, n * 4).reshape(n, 4)

@@ -740,7 +740,8 @@ namespace svo {
 constexpr int STACK_REFILL = 8;         // retired lanes per wave that trigger a refill (cheap: rays are staged in LDS)
 constexpr int STACK_WAVES = 6;          // waves per SIMD the stack kernel is register-budgeted for: 80 VGPRs (the asm step holds 63; spills sit in the rare blocks)
 using StackKernel = void (*)(TraceArgs);
-template <int MAXLV, bool BIG, bool GLSL> constexpr StackKernel stack_kernel = k_trace_stack<MAXLV, STACK_REFILL, STACK_WAVES, BIG, GLSL>;
+template <int MAXLV, bool BIG, bool GLSL, bool SEG = false> constexpr StackKernel stack_kernel = k_trace_stack<MAXLV, STACK_REFILL, STACK_WAVES, BIG, GLSL, SEG>;
+constexpr int STACK_CLASSES = 12;       // depth class x semantics; the bounded set (svo_trace_segments) follows in the same order
 static const StackKernel STACK_KERNELS[] = {
     stack_kernel<10, true, true>, stack_kernel<10, true, false>,
     stack_kernel<22, true, true>, stack_kernel<22, true, false>,
@@ -748,7 +749,14 @@ static const StackKernel STACK_KERNELS[] = {
     stack_kernel<10, false, true>, stack_kernel<10, false, false>,
     stack_kernel<16, false, true>, stack_kernel<16, false, false>,
     stack_kernel<22, false, true>, stack_kernel<22, false, false>,
+    stack_kernel<10, true, true, true>, stack_kernel<10, true, false, true>,
+    stack_kernel<22, true, true, true>, stack_kernel<22, true, false, true>,
+    stack_kernel<6, false, true, true>, stack_kernel<6, false, false, true>,
+    stack_kernel<10, false, true, true>, stack_kernel<10, false, false, true>,
+    stack_kernel<16, false, true, true>, stack_kernel<16, false, false, true>,
+    stack_kernel<22, false, true, true>, stack_kernel<22, false, false, true>,
 };
+static_assert(sizeof(STACK_KERNELS) / sizeof(StackKernel) == 2 * STACK_CLASSES, "an unbounded and a bounded instantiation per class");
 static_assert(sizeof(STACK_KERNELS) / sizeof(StackKernel) == sizeof(Hbm::stack_blocks) / sizeof(int), "one grid size per instantiation");
 
 } // namespace svo
@@ -838,7 +846,7 @@ static int launch_stack(svo_world *w, const TraceArgs &A, int tiles_per_wave, in
 {
     const int lv = w->max_levels;
     const int depth = stack_needs_big(w) ? (lv <= 10 ? 0 : 1) : lv <= 6 ? 2 : lv <= 10 ? 3 : lv <= 16 ? 4 : 5;
-    const int which = 2 * depth + (A.glsl ? 0 : 1);
+    const int which = 2 * depth + (A.glsl ? 0 : 1) + (A.tmax ? STACK_CLASSES : 0);
     const StackKernel kernel = STACK_KERNELS[which];
     int &resident = w->hbm->stack_blocks[which];
     if (resident <= 0) {
@@ -916,7 +924,9 @@ static int launch(svo_world *w, const svo_trace_params *prm, TraceArgs &A, hipSt
     if (kernel == SVO_KERNEL_LITERAL) {
         const int64_t blocks = (A.n + 255) / 256;
         if (blocks > 0x7FFFFFFF) { set_error("svo_trace: too many rays for one launch"); return SVO_ERR_UNSUPPORTED; }
-        if (see) hipLaunchKernelGGL(k_trace_literal_st, dim3((unsigned)blocks), dim3(256), 0, s, A, see);
+        if (A.tmax && see) hipLaunchKernelGGL(k_trace_literal_seg<true>, dim3((unsigned)blocks), dim3(256), 0, s, A, see);
+        else if (A.tmax) hipLaunchKernelGGL(k_trace_literal_seg<false>, dim3((unsigned)blocks), dim3(256), 0, s, A, 0u);
+        else if (see) hipLaunchKernelGGL(k_trace_literal_st, dim3((unsigned)blocks), dim3(256), 0, s, A, see);
         else hipLaunchKernelGGL(k_trace_literal, dim3((unsigned)blocks), dim3(256), 0, s, A);
     } else {
         if (A.ntiles > (1 << 25)) { set_error("svo_trace: more than 2^31 rays in one stack-kernel launch"); return SVO_ERR_UNSUPPORTED; }
@@ -1018,15 +1028,16 @@ int svo_trace_rows(svo_world *w, const svo_camera *cam, const svo_trace_params *
     return svo_trace_rows_frames(w, cam, 1, prm, band0, band_stride, nbands, band_height, out_dev, stream);
 }
 
-int svo_trace_rays(svo_world *w, const float *origins_dev, const float *dirs_dev, int64_t n,
-                   const svo_trace_params *prm, svo_hit *out_dev, void *stream)
+// the ray-list launch of svo_trace_rays (tmax_dev == nullptr) and svo_trace_segments (the bounded kernels)
+static int trace_list(svo_world *w, const float *origins_dev, const float *dirs_dev, const float *tmax_dev, int64_t n,
+                      const svo_trace_params *prm, svo_hit *out_dev, void *stream)
 {
     TraceArgs A;
     int rc = fill_common(w, prm, A);
     if (rc != SVO_OK) return rc;
     if (n < 0 || (n > 0 && (!origins_dev || !dirs_dev || !out_dev))) { set_error("svo_trace_rays: bad ray list"); return SVO_ERR_INVALID_ARG; }
     A.from_camera = 0; A.nframes = 1;
-    A.origins = origins_dev; A.dirs = dirs_dev;
+    A.origins = origins_dev; A.dirs = dirs_dev; A.tmax = tmax_dev;
     A.n = n;
     A.w = 64; A.h = 1; A.bh = 1; A.tiles_per_row = 1;
     const int64_t tiles = (n + 63) / 64;
@@ -1034,6 +1045,20 @@ int svo_trace_rays(svo_world *w, const float *origins_dev, const float *dirs_dev
     A.ntiles = (int32_t)tiles;
     A.out = out_dev;
     return launch(w, prm, A, (hipStream_t)stream);
+}
+
+int svo_trace_rays(svo_world *w, const float *origins_dev, const float *dirs_dev, int64_t n,
+                   const svo_trace_params *prm, svo_hit *out_dev, void *stream)
+{
+    return trace_list(w, origins_dev, dirs_dev, nullptr, n, prm, out_dev, stream);
+}
+
+int svo_trace_segments(svo_world *w, const float *origins_dev, const float *dirs_dev, const float *tmax_dev, int64_t n,
+                       const svo_trace_params *prm, svo_hit *out_dev, void *stream)
+{
+    if (n > 0 && !tmax_dev) { set_error("svo_trace_segments: tmax_dev is NULL"); return SVO_ERR_INVALID_ARG; }
+    if (n == 0) tmax_dev = nullptr;                                     // (nothing is launched: the work slot is reset as svo_trace_rays resets it)
+    return trace_list(w, origins_dev, dirs_dev, tmax_dev, n, prm, out_dev, stream);
 }
 
 // ParallaxAlpha's second march (shaders/ParallaxAlpha.Fragment.glsl:141-199,276-335): the surface, the continuation list of the
@@ -1105,6 +1130,7 @@ int svo_trace_local_shadows(svo_world *w, const svo_camera *cam, const svo_trace
     svo_trace_params march = *prm;                                      // (the caller's per-ray and per-tile buffers are sized for the frame)
     march.shadow = 0;
     march.counters_dev = nullptr; march.tile_cost_dev = nullptr; march.tile_order_dev = nullptr;
+    // (unbounded on purpose: ending each ray at its light through svo_trace_segments was measured and is slower)
     rc = svo_trace_rays(w, origins, dirs, rays, &march, reinterpret_cast<svo_hit *>(records), stream);
     if (rc != SVO_OK) return rc;
     hipLaunchKernelGGL(k_local_resolve, grid, dim3(256), 0, s, frame_cam(*cam), cam->width, cam->height, x0, y0, rw, n, A.eps, L,

@@ -126,7 +126,7 @@ struct Hbm {
     Pooled<uint32_t> view_wide; Pooled<uint64_t> view_mask;
     uint32_t view_material = 0;                             // material the view holds; 0 = no view
     Event view_built;                                       // launches on other streams wait for it
-    int stack_blocks[12] = {};                              // persistent-grid size per k_trace_stack instantiation (device.hip: STACK_KERNELS); 0 = not queried yet
+    int stack_blocks[24] = {};                              // persistent-grid size per k_trace_stack instantiation (device.hip: STACK_KERNELS); 0 = not queried yet
 };
 
 } // namespace svo

@@ -10,6 +10,16 @@
 // ST: the see-through instantiation (svo_trace_params.see_through): a LEAF of material `ignore` is stepped over as an EMPTY node
 // and a brick cell holding it as an empty cell, like Chunkmarch.glsl's `ignore` (:190-191,240-241,280).  k_trace_literal is the
 // ST = false one (its device code is unchanged by the template), k_trace_literal_st the other.
+//
+// SEG: the bounded instantiations (svo_trace_segments, k_trace_literal_seg<ST>): ray k ends at far = A.tmax[k].  A hit counts only
+// if its t < far (strict; the compare sits before store_hit and before the shadow ray), and the march ends as soon as no later hit
+// can pass that compare (DESIGN.md 6g has the argument):
+//   tree loop   every later hit of THIS tree march lies at tw + s with s >= t - leaf_back (t never decreases while p stays inside
+//               the root box, a brick hit adds u >= 0, float addition is monotone): tw + (t - leaf_back) >= far abandons the tree
+//               march - as a march that left the chunk, so the chunk loop takes its usual step;
+//   chunk loop  every later hit lies at t + s with s >= -leaf_back and t does not decrease from chunk to chunk (the escape out of a
+//               box that holds p is >= -0): t - leaf_back >= far ends the ray.
+// A NaN on either side fails the compare and the march goes on as the unbounded one.  SEG = false compiles to the kernels as they were.
 #pragma once
 #include "march.hip.h"
 
@@ -102,14 +112,15 @@ __device__ inline bool lit_brick(const TraceArgs &A, V3 a, V3 b, V3 g, V3 lo, fl
     return false;
 }
 
-template <bool ST>
+template <bool ST, bool SEG>
 __device__ inline bool lit_tree(const TraceArgs &A, V3 a, V3 b, V3 g, const DevChunk &ch, float rootsize,
-                                float &s, Voxel &vox, LitCounters &cnt, uint32_t &guard, uint32_t ignore)
+                                float &s, Voxel &vox, LitCounters &cnt, uint32_t &guard, uint32_t ignore, float tw, float far)
 {
     const uint32_t *tree = A.tree + ch.tree_off;
     const V3 rlo = ld3(ch.bmin), rhi = rlo + rootsize;
     float t = 0.0f;
     for (int i = 0; i < A.cap_tree; ++i) {
+        if constexpr (SEG) if (tw + (t - A.leaf_back) >= far) return false;       // no hit of this tree march can lie in front of the far end
         if (++guard > STEP_GUARD) return false;
         const V3 p = a + b * t;
         if (!inside(p, rlo, rhi)) return false;
@@ -161,9 +172,9 @@ __device__ inline bool lit_tree(const TraceArgs &A, V3 a, V3 b, V3 g, const DevC
 
 // `runaway` is set when the ray used up STEP_GUARD march steps (the kernels' bound on a single ray; the reference itself
 // would keep going): the caller flags the record with SVO_ERR_FLAG, as the stack kernel does.
-template <bool ST>
+template <bool ST, bool SEG = false>
 __device__ inline bool lit_world(const TraceArgs &A, V3 alpha, V3 beta, float &tout, Voxel &vox, uint32_t &chunk,
-                                 LitCounters &cnt, bool &runaway, uint32_t ignore)
+                                 LitCounters &cnt, bool &runaway, uint32_t ignore, float far = 0.0f)
 {
     const V3 wlo = ld3(A.worldmin), whi = ld3(A.worldmax);
     const V3 g = recip(beta);
@@ -173,6 +184,7 @@ __device__ inline bool lit_world(const TraceArgs &A, V3 alpha, V3 beta, float &t
     if (!hit) return false;
     uint32_t guard = 0;
     for (int c = 0; c < A.cap_chunk; ++c) {
+        if constexpr (SEG) if (t - A.leaf_back >= far) return false;              // the ray has passed its far end
         if (++guard > STEP_GUARD) { runaway = true; return false; }
         const V3 p = alpha + beta * t;
         if (!inside(p, wlo, whi)) return false;
@@ -183,7 +195,7 @@ __device__ inline bool lit_world(const TraceArgs &A, V3 alpha, V3 beta, float &t
         if (!A.glsl && !inside(p, clo, chi)) return false;      // (src/Traverse.cpp:154-155; the shader has no such check: its treemarch just fails)
         float s = 0.0f;
         const float rootsize = A.chunksize;             // Ocroot::size == chunksize (checked on create)
-        if (lit_tree<ST>(A, p, beta, g, ch, rootsize, s, vox, cnt, guard, ignore)) {
+        if (lit_tree<ST, SEG>(A, p, beta, g, ch, rootsize, s, vox, cnt, guard, ignore, t, far)) {
             t += s;
             tout = t;
             chunk = (uint32_t)ci;
@@ -297,5 +309,44 @@ __global__ __launch_bounds__(256) void k_trace_literal_st(TraceArgs A, uint32_t 
     if ((threadIdx.x & 63) == 0 && total) atomicAdd(&A.work[1], (unsigned long long)total);
 }
 
+// The bounded instantiations (svo_trace_segments): ray k of the list ends at A.tmax[k].  List mode only.
+template <bool ST>
+__global__ __launch_bounds__(256) void k_trace_literal_seg(TraceArgs A, uint32_t ignore)
+{
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned rays = 0;
+    if (k < A.n) {
+        const V3 o = ld3(A.origins + 3 * k), d = ld3(A.dirs + 3 * k);
+        const float far = A.tmax[k];
+        LitCounters cnt = { 0, 0, 0, 0 };
+        Voxel vox; vox.lo = mk(0, 0, 0); vox.size = 0; vox.material = 0; vox.node = 0; vox.cell = 0;
+        float t = 0.0f;
+        uint32_t chunk = 0;
+        rays = 1;
+        bool runaway = false;
+        if (lit_world<ST, true>(A, o, d, t, vox, chunk, cnt, runaway, ignore, far) && t < far) {     // the strict compare decides the record
+            const V3 point = o + d * (t - A.eps);
+            const bool face = A.normal_mode == SVO_NORMAL_FACE;
+            const V3 n = face ? face_normal(point, vox.lo, vox.lo + vox.size, d) : cube_normal(point, vox.lo, vox.lo + vox.size, A.eps);
+            uint32_t flags = SVO_HIT_FLAG | (face ? (uint32_t)SVO_FACE_NORMAL : 0u);
+            if (A.shadow) {                                         // (unbounded: the light is a direction)
+                Voxel sv; float st; uint32_t sc;
+                const bool occluded = lit_world<ST>(A, point, ld3(A.sdir), st, sv, sc, cnt, runaway, ignore);
+                flags |= SVO_SHADOW_TRACED | (occluded ? SVO_SHADOWED : 0u) | (runaway ? (uint32_t)SVO_ERR_FLAG : 0u);
+                rays = 2;
+            }
+            store_hit(A.out, k, t, n, vox.material, flags, chunk, vox.node, vox.cell);
+        } else {
+            store_miss(A.out, k, runaway ? (uint32_t)SVO_ERR_FLAG : 0u);
+        }
+        if (A.counters) {
+            uint4 c; c.x = cnt.node_words; c.y = cnt.brick_cells; c.z = cnt.chunk_descs; c.w = cnt.tree_steps;
+            reinterpret_cast<uint4 *>(A.counters)[k] = c;
+        }
+    }
+    unsigned total = rays;
+    for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off, 64);
+    if ((threadIdx.x & 63) == 0 && total) atomicAdd(&A.work[1], (unsigned long long)total);
+}
 
 } // namespace svo

@@ -237,16 +237,31 @@ __device__ __forceinline__ void note_tile_cost(int outk, uint32_t steps)
     atomicMax(&T.tile_cost[((size_t)frame * (size_t)T.ntiles + (size_t)tile) * 2 + (outk < 0 ? 1 : 0)], steps);
 }
 
+// (the bounded instantiations) no hit of the lane's tree march can lie in front of its far end any more: the smallest t a later hit of
+// this chunk can report is tw + (tree-level t - leaf_back); inside a brick the tree level's t is the one the brick was entered at
+template <bool GLSL>
+__device__ __forceinline__ bool past_far_end(int mode, float t, float tt_saved, float tw, float eps, float far)
+{
+    const float tt = mode == M_TWIG ? tt_saved : t;
+    return (mode == M_TREE || mode == M_TWIG) && tw + (GLSL ? tt : tt - eps) >= far;
+}
+
 // BIG: the large-world instantiation - the chunk's wide tree is a 64-bit address per lane and the brick masks are addressed with
 // 64 bits (step_asm.hip.h: march_steps_asm<true, GLSL>), for wide pools of 4 GiB and more and mask pools of 2^29 bricks and more; the same
 // kernel otherwise, the same results.
 // GLSL: the shader twin's march (svo_trace_params.semantics = SVO_SEMANTICS_GLSL; shaders/Chunkmarch.glsl): the guarded escape
 // distance and the LEAF hit at t inside the step (step_asm.hip.h), the entry condition and the missing containment re-check here.
-template <int MAXLV, int REFILL, int WAVES_PER_SIMD, bool BIG, bool GLSL>
+// SEG: the bounded instantiations (svo_trace_segments; ray lists only): ray k ends at `far` = A.tmax[k], one more lane value, loaded with
+// the ray at refill (+inf once the lane turns into a shadow ray).  The step itself is untouched.  Between two statements a marching lane
+// whose tree march can no longer hit in front of the far end - tw + (t - leaf_back) >= far with the TREE level's t, which never decreases
+// inside the chunk; see kernel_literal.hip.h and DESIGN.md 6g - gives its chunk up the way a lane that marched out of it does (M_WORLD,
+// escape pending): so a ray ends INSIDE a chunk, a statement late at the most.  The chunk step, where tw changes, ends the ray once
+// tw - leaf_back >= far, and the hit blocks apply the strict compare t < far (a dropped hit writes the miss record and casts no shadow ray).
+template <int MAXLV, int REFILL, int WAVES_PER_SIMD, bool BIG, bool GLSL, bool SEG = false>
 __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
 {
     __shared__ uint32_t stk[MAXLV / 2 + 1][64];     // wide node index per wide level of the current path (level 0 is node 0)
-    __shared__ float tile_ray[11][64];
+    __shared__ float tile_ray[SEG ? 12 : 11][64];
     // the chunk table (bmin, levels, wide offset, brick offset) of worlds of up to 64 chunks - the reference's default is 4x4x4 -
     // staged in LDS: the chunk step then reads it there instead of waiting for a 32-byte global load per lane (the block runs
     // in six of ten passes and a wave waits out the slowest lane's load each time)
@@ -305,6 +320,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
     int outk = 0;                   // output record of the ray; bit 31 set: the lane marches that pixel's shadow ray
     V3 alpha = mk(0, 0, 0), beta = mk(0, 0, 1), g = mk(0, 0, 0);
     float tw = 0.0f;                // chunkmarch's t (src/Traverse.cpp:135)
+    [[maybe_unused]] float far = __uint_as_float(0x7F800000u);     // (SEG) the ray's far end
     int cw = 0;
     uint32_t guard = 0;
     // The level being marched (tree: src/Traverse.cpp:74-113, brick: :50-72) as one "frame": p = O + beta*t is
@@ -342,7 +358,6 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
     // creeping rays: |creepn| = consecutive advances of this ray by less than 2 EPS (kept across level changes: a ray pinned
     // on a chunk face creeps at every level); > 0 only while the cell located last is known to be empty (creep block armed)
     int creepn = 0;
-
     for (;;) {
         // ==== refill retired lanes =============================================================
         unsigned long long dead = __ballot(mode == M_DONE);
@@ -407,6 +422,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
                         ok = id < T.n && tframe >= 0;
                         k = id;
                         if (ok) { o = ld3(T.origins + 3 * (long long)id); d = ld3(T.dirs + 3 * (long long)id); }
+                        if constexpr (SEG) tile_ray[11][lane] = ok ? T.tmax[id] : 0.0f;
                     }
                     const V3 gg = recip(d);
                     float t0 = 0.0f;
@@ -438,6 +454,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
                     beta = mk(tile_ray[3][slot], tile_ray[4][slot], tile_ray[5][slot]);
                     g = mk(tile_ray[6][slot], tile_ray[7][slot], tile_ray[8][slot]);
                     tw = tile_ray[9][slot];
+                    if constexpr (SEG) far = tile_ray[11][slot];
                     cw = 0; guard = 0; creepn = 0;
                     mode = M_WORLD;
                 }
@@ -479,6 +496,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
                 else tw += escape(O, g, clo, clo + csize) + eps;
             }
             bool miss = cw >= A.cap_chunk;
+            if constexpr (SEG) miss |= (GLSL ? tw : tw - eps) >= far;          // every later hit lies at tw + s, s >= -leaf_back: the ray has passed its far end
             if (!miss) {
                 cw++;
                 const V3 p = alpha + beta * tw;
@@ -676,8 +694,17 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
         if (more || pass >= 256) break;
         const unsigned long long marching = __ballot(mode == M_TREE || mode == M_TWIG);
         if (marching == 0ull || marching != __ballot(mode != M_DONE) || __ballot(creepn > 0 || creepn <= -4 * CREEP_SERIOUS) != 0ull) break;
+        if constexpr (SEG) if (__ballot(past_far_end<GLSL>(mode, t, tt_saved, tw, eps, far)) != 0ull) break;       // a lane of the draining wave has reached its far end
         }
         guard += pass - 1;
+        if constexpr (SEG) {
+            if (past_far_end<GLSL>(mode, t, tt_saved, tw, eps, far)) {                               // leave the chunk as the step does (its S_LEAVE out of a brick, then out of the tree)
+                if (mode == M_TWIG) O = alpha + beta * tw;  // the chunk march's p: what the chunk step takes the escape from
+                creepn = creepn > 0 ? -creepn : creepn;     // (disarmed: the lane marches no cell)
+                cw |= CW_ESCAPE_PENDING;
+                mode = M_WORLD;
+            }
+        }
 
 #include "creep_block.inc"
 
@@ -687,6 +714,13 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
             store_flags(A.out, outk & 0x7FFFFFFF, SVO_HIT_FLAG | SVO_SHADOW_TRACED | SVO_SHADOWED | (A.normal_mode == SVO_NORMAL_FACE ? (uint32_t)SVO_FACE_NORMAL : 0u));
             if (want_cost) note_tile_cost(outk, guard);
             mode = M_DONE;
+        }
+        if constexpr (SEG) {
+            if (mode == M_HIT && !(tw < far)) {             // a hit at or behind the far end: the miss record, no shadow ray (no vote needed)
+                store_miss(A.out, outk, 0);
+                if (want_cost) note_tile_cost(outk, guard);
+                mode = M_DONE;
+            }
         }
         if (run_hit && mode == M_HIT) {
             // which voxel: the node comes from the descent cache; the frame still describes the level that hit
@@ -734,6 +768,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
             if (A.shadow) {                             // the lane becomes its own shadow ray
                 alpha = point; beta = sdir; g = sg;
                 outk |= (int)0x80000000;
+                if constexpr (SEG) far = __uint_as_float(0x7F800000u);    // (the light is a direction: its ray has no far end)
                 tw = 0.0f; cw = 0; guard = 0; creepn = 0;
                 bool hit = true;
                 if (!inside(alpha, wlo, whi)) tw = (GLSL ? enter_glsl(alpha, g, wlo, whi, hit) : enter(alpha, beta, wlo, whi, hit)) + eps;

@@ -28,6 +28,15 @@ int main(int argc, char **argv)
         svo::vec3 sigma = { 0.0f, 0.0f, 0.0f };
         const bool hit = svo::chunkmarch({ 250.3f, 150.0f, -40.0f }, { 0.0f, -0.5f, 0.866f }, &world, &sigma);
         std::printf("hits %zu shadowed %zu cursor %s (%.3f %.3f %.3f)\n", hits, shadowed, hit ? "hit" : "miss", sigma.x, sigma.y, sigma.z);
+        // a cursor with a reach (svo_trace_segments): the terrain is out of reach at half its distance, within reach at twice
+        if (hit) {
+            svo_hit far_hit;
+            svo::chunkmarch({ 250.3f, 150.0f, -40.0f }, { 0.0f, -0.5f, 0.866f }, &world, nullptr, &far_hit);
+            svo::vec3 near = { 0.0f, 0.0f, 0.0f };
+            const bool short_arm = svo::chunkmarch({ 250.3f, 150.0f, -40.0f }, { 0.0f, -0.5f, 0.866f }, &world, nullptr, nullptr, 0.5f * far_hit.t);
+            const bool long_arm = svo::chunkmarch({ 250.3f, 150.0f, -40.0f }, { 0.0f, -0.5f, 0.866f }, &world, &near, nullptr, 2.0f * far_hit.t);
+            if (short_arm || !long_arm || near.y != sigma.y) { std::fprintf(stderr, "chunkmarch: the reach does not bound the cursor ray\n"); return 6; }
+        }
         // Main.cpp:350-357 build(): a cube of material 5 at the cursor, in every chunk it overlaps; then the edit cursor again
         if (hit) {
             const svo::vec3 cmin = { sigma.x - 4.0f, sigma.y, sigma.z - 4.0f }, cmax = { sigma.x + 4.0f, sigma.y + 8.0f, sigma.z + 4.0f };

@@ -164,6 +164,19 @@ public:
               "World::local_shadows");
     }
 
+    // Rays with a far end (svo_trace_segments): n rays (origins / dirs [n][3], tmax [n], all on the device) into out_dev; a hit counts only
+    // if its t < tmax and the march ends there.  Line of sight, picking with a reach, short occlusion rays.  Not in the reference.
+    void segments(const float *origins_dev, const float *dirs_dev, const float *tmax_dev, int64_t n, svo_hit *out_dev,
+                  bool shadow = false, const float light_dir[3] = nullptr, void *stream = nullptr)
+    {
+        svo_trace_params p;
+        std::memset(&p, 0, sizeof p);
+        p.semantics = semantics;
+        p.shadow = shadow ? 1 : 0;
+        if (light_dir) std::memcpy(p.light_dir, light_dir, sizeof p.light_dir);
+        check(svo_trace_segments(world_, origins_dev, dirs_dev, tmax_dev, n, &p, out_dev, stream), "World::segments");
+    }
+
     // World::modify(i, tree delta, twig delta): re-send an edited chunk (Ocdelta ranges, src/Octree.h:47-54).
     void modify(int i, const svo_chunk_desc &edited, uint64_t tree_left, uint64_t tree_right, uint64_t twig_left, uint64_t twig_right, bool realloc_)
     {
@@ -209,17 +222,22 @@ private:
 // bool chunkmarch(vec3 alpha, vec3 beta, const World *world, vec3 *sigma) — src/Traverse.cpp:127-171.
 // One ray through the device kernel (the reference uses this for the edit cursor, src/Main.cpp:314-319).
 // sigma is written only on a hit, exactly like the reference; `hit_out` optionally receives the voxel record.
-inline bool chunkmarch(vec3 alpha, vec3 beta, const World *world, vec3 *sigma, svo_hit *hit_out = nullptr)
+// `reach` (not in the reference): the ray ends there - a hit counts only if its t < reach (svo_trace_segments); the default is chunkmarch itself.
+inline bool chunkmarch(vec3 alpha, vec3 beta, const World *world, vec3 *sigma, svo_hit *hit_out = nullptr, float reach = INFINITY)
 {
     struct Scratch {
-        float *o = nullptr, *d = nullptr; svo_hit *h = nullptr;
-        Scratch() { o = (float *)svo_device_alloc(12); d = (float *)svo_device_alloc(12); h = (svo_hit *)svo_device_alloc(sizeof(svo_hit)); }
-        ~Scratch() { svo_device_free(o); svo_device_free(d); svo_device_free(h); }
+        float *o = nullptr, *d = nullptr, *far = nullptr; svo_hit *h = nullptr;
+        Scratch() { o = (float *)svo_device_alloc(12); d = (float *)svo_device_alloc(12); far = (float *)svo_device_alloc(4); h = (svo_hit *)svo_device_alloc(sizeof(svo_hit)); }
+        ~Scratch() { svo_device_free(o); svo_device_free(d); svo_device_free(far); svo_device_free(h); }
     };
     static thread_local Scratch s;
     const float a[3] = { alpha.x, alpha.y, alpha.z }, b[3] = { beta.x, beta.y, beta.z };
     check(svo_memcpy_h2d(s.o, a, sizeof a), "chunkmarch"); check(svo_memcpy_h2d(s.d, b, sizeof b), "chunkmarch");
-    check(svo_trace_rays(world->handle(), s.o, s.d, 1, nullptr, s.h, nullptr), "chunkmarch");
+    if (reach == INFINITY) check(svo_trace_rays(world->handle(), s.o, s.d, 1, nullptr, s.h, nullptr), "chunkmarch");
+    else {
+        check(svo_memcpy_h2d(s.far, &reach, sizeof reach), "chunkmarch");
+        check(svo_trace_segments(world->handle(), s.o, s.d, s.far, 1, nullptr, s.h, nullptr), "chunkmarch");
+    }
     svo_hit h;
     check(svo_memcpy_d2h(&h, s.h, sizeof h), "chunkmarch");
     if (hit_out) *hit_out = h;

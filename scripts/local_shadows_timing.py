@@ -3,10 +3,12 @@ alone, followed by svo_trace_local_shadows with one light and with both (the ref
 svo_shade, over bench.py's 32-camera path at 1920x1080 - one launch per frame, best of --reps passes, the variants interleaved
 within each pass - plus the share of pixels that got rays and the scratch the call holds.  Prints one JSON line.
 
-    python scripts/local_shadows_timing.py [--reps 3] [--out FILE] [--root CHECKOUT] [--baseline]
+    python scripts/local_shadows_timing.py [--reps 3] [--out FILE] [--root CHECKOUT] [--baseline] [--segments]
 
 --root measures another checkout's package and library (default: this one); --baseline measures svo_trace and svo_shade only, for a
-checkout that predates the call.
+checkout that predates the call.  --segments adds the price of the far end itself: the point light's rays of four
+cameras of the path as an explicit list, ms per launch of svo_trace_rays, of svo_trace_segments with tmax = +inf (the same march, bounded
+kernels) and of svo_trace_segments with tmax = the distance to the light, on both kernels.
 """
 import argparse
 import importlib
@@ -24,6 +26,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--baseline", action="store_true")
+    ap.add_argument("--segments", action="store_true")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.root))
     import bench  # noqa: E402  (its camera path)
@@ -87,6 +90,50 @@ def main():
         res["pixels_with_rays_min_max"] = [round(min(fr), 4), round(max(fr), 4)]
         res["scratch_bytes_per_light"] = n * 56                     # 32 B record + 24 B origin and direction per ray of the padded list
         res["scratch_bytes_both"] = 2 * n * 56
+    if a.segments:
+        F = np.float32
+        res["segments"] = {}
+        for ci in (0, 8, 16, 24):
+            c = cams[ci]
+            W.trace(c, prm, rect, g.ptr)
+            sync()
+            rec = g.to_numpy(svo.HIT_DTYPE, n)
+            # the pixel's camera ray and the occlusion ray towards the point light (include/svo.h), in float32; the list keeps hit pixels only
+            px, py = (np.arange(n) % iw).astype(F) + F(0.5), (np.arange(n) // iw).astype(F) + F(0.5)
+            u = ((px / F(iw)) * F(2) - F(1)) * F(c.tan_half_x)
+            v = (F(1) - (py / F(ih)) * F(2)) * F(c.tan_half_y)
+            d = np.array(c.forward, F)[None, :] + np.array(c.right, F)[None, :] * u[:, None] + np.array(c.up, F)[None, :] * v[:, None]
+            d = (d / np.sqrt((d * d).sum(axis=1, dtype=F))[:, None]).astype(F)
+            P = (np.array(c.eye, F)[None, :] + d * (rec["t"] - F(1.0 / 8192.0))[:, None]).astype(F)
+            sel = ((rec["flags"] & svo.HIT_FLAG) != 0) & ((rec["flags"] & svo.ERR_FLAG) == 0)
+            vec = (np.array(point, F)[None, :] - P[sel]).astype(F)
+            dist = np.sqrt((vec * vec).sum(axis=1, dtype=F)).astype(F)
+            ok = np.isfinite(dist) & (dist > 0)
+            o, dirs, dist = np.ascontiguousarray(P[sel][ok]), np.ascontiguousarray((vec[ok] / dist[ok][:, None]).astype(F)), np.ascontiguousarray(dist[ok])
+            m = o.shape[0]
+            od, dd, out = svo.DeviceBuffer.from_numpy(o), svo.DeviceBuffer.from_numpy(dirs), svo.DeviceBuffer(m * 32)
+            ends = {"rays_ms": None, "segments_inf_ms": svo.DeviceBuffer.from_numpy(np.full(m, np.inf, F)), "segments_dist_ms": svo.DeviceBuffer.from_numpy(dist)}
+            cam_res = {"rays": int(m)}
+            for kname, kernel in (("stack", svo.KERNEL_STACK), ("literal", svo.KERNEL_LITERAL)):
+                p2 = svo.trace_params(shadow=False, kernel=kernel)
+                best = {k: [] for k in ends}
+                for rep_ in range(a.reps + 1):                          # (the first pass warms up)
+                    for k, td in ends.items():
+                        sync()
+                        t0 = time.perf_counter()
+                        for _ in range(4):
+                            if td is None:
+                                W.trace_rays(od.ptr, dd.ptr, m, p2, out.ptr)
+                            else:
+                                W.trace_segments(od.ptr, dd.ptr, td.ptr, m, p2, out.ptr)
+                        sync()
+                        if rep_:
+                            best[k].append((time.perf_counter() - t0) * 1e3 / 4)
+                cam_res[kname] = {k: round(min(x), 4) for k, x in best.items()}
+                cam_res[kname + "_passes"] = {k: [round(y, 4) for y in x] for k, x in best.items()}
+            res["segments"][f"camera_{ci}"] = cam_res
+            for b in [od, dd, out] + [b for b in ends.values() if b is not None]:
+                b.free()
     g.free()
     rgba.free()
     W.destroy()
