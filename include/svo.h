@@ -24,6 +24,8 @@
  *                           next World::draw from the previous one's per-tile step counts
  *   svo_world_destroy    <- World::deinit                          src/World.cpp:129-151
  *   svo_world_index*     <- World::index / index_float             src/World.cpp:276-293,323-332
+ *   svo_world_locate     <- World::index_float + World::index (src/World.cpp:288-293,323-332) + traverse (src/Traverse.cpp:34-48)
+ *                           + the cell lookup of twigmarch (:58-67) over a device point list
  *   svo_chunk_write/read <- Ocroot::write / Ocroot::read           src/Octree.cpp:178-201
  *   svo_world_shift      <- World::shift                           src/World.cpp:334-378
  *   svo_world_edit_box   <- Ocroot::build / destroy / replace + World::modify   src/Octree.cpp:203-443, src/World.cpp:268-274
@@ -79,7 +81,8 @@ extern "C" {
                                           svo_trace_params.see_through (was padding: zeroed structs keep their results),
                                           svo_trace_translucent and svo_shade_translucent,
                                           svo_trace_local_shadows and SVO_LOCAL_SHADOWS / SVO_SHADOWED_POINT / SVO_SHADOWED_SPOT,
-                                          svo_trace_segments */
+                                          svo_trace_segments,
+                                          svo_world_locate and svo_voxel */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -387,6 +390,47 @@ int svo_trace_rays(svo_world *, const float *origins_dev, const float *dirs_dev,
  * reports n, plus one per kept hit when params->shadow != 0.  tmax_dev == NULL with n > 0 is SVO_ERR_INVALID_ARG; n == 0 is SVO_OK. */
 int svo_trace_segments(svo_world *, const float *origins_dev, const float *dirs_dev, const float *tmax_dev, int64_t n,
                        const svo_trace_params *params, svo_hit *out_dev, void *stream);
+
+/* Point queries: which node, which box, what material lies at each point - traverse() (src/Traverse.cpp:34-48), which the reference
+ * calls once per march step, over a device list: points_dev is [n][3] float, out_dev receives n records.  Collision and "is this
+ * position solid", standing a body on the terrain, free space for particles, the voxel under an edit cursor - and the voxel box
+ * that svo_hit does not carry.  For p = points_dev[3k..3k+2], every operation in float, separately rounded, in the reference's order:
+ *   1. the world box of chunkmarch (:129-133): !isInsideCube(p, chunkmin, chunkmax) - closed; NaN and +-inf fail - gives out[k] all zero;
+ *   2. i = index(index_float(p)), cmin = chunk[i].position: !isInsideCube(p, cmin, cmin + chunksize) (the check of :154) gives out[k]
+ *      all zero - on the world's max faces, where the toroidal index wraps to a chunk that does not hold p;
+ *   3. (bmin, size, node) = traverse(p, chunk[i]): the child is chosen by p >= bmin + halfsize per axis;
+ *   4. an EMPTY node: { bmin, size, material 0, SVO_LOCATE_INSIDE, i, node, SVO_CELL_NONE };
+ *   5. a LEAF node: the same with material = offset & 0xFFFF and SVO_LOCATE_INSIDE | SVO_LOCATE_SOLID (whatever the material: the
+ *      march hits every LEAF);
+ *   6. a TWIG node: leafsize = size / 4, off = ivec3((p - bmin) / leafsize) - under SVO_SEMANTICS_GLSL ivec3((p - bmin) * (1 / leafsize)).
+ *      off outside [0,3]^3 (a point on the chunk's max face; twigmarch returns "no hit" there, :59): the TWIG node's own box,
+ *      material 0, SVO_CELL_NONE, SVO_LOCATE_INSIDE.  Otherwise cell = z*16 + y*4 + x, bmin = node bmin + vec3(off) * leafsize,
+ *      size = leafsize, material = the brick's cell, SVO_LOCATE_SOLID iff it is not 0;
+ *   7. params->see_through = m: a LEAF or a cell of material m is reported with material 0 and without SVO_LOCATE_SOLID; node, cell
+ *      and box are unchanged - the records of the same world with those words rewritten to 0.
+ * params == NULL means defaults; only kernel, semantics and see_through are read.  SVO_KERNEL_LITERAL walks the tree pool, one load
+ * per level, on any geometry; SVO_KERNEL_STACK walks the stack kernel's wide trees, two levels per load, and is refused with
+ * SVO_ERR_UNSUPPORTED where svo_trace refuses that kernel (no wide trees, exact_geometry == 0); SVO_KERNEL_AUTO takes the wide walk
+ * where it is allowed.  Both write the same records, byte for byte.
+ * n < 0, a NULL points_dev / out_dev with n > 0, see_through > 0xFFFF, an unknown semantics or kernel: SVO_ERR_INVALID_ARG; then a world
+ * that is not resident: SVO_ERR_NOT_UPLOADED; then n == 0: SVO_OK.  All of these are settled before any device work.
+ * Asynchronous on `stream` and ordered against updates, edits and shifts like svo_trace_rays.  The call takes no launch slot and no
+ * scratch: calls on different streams are independent, and svo_trace_last_ray_count does not see it. */
+enum {
+    SVO_LOCATE_INSIDE = 1u << 0,    /* the point lies in the world box and in its chunk's box: every other field is valid */
+    SVO_LOCATE_SOLID  = 1u << 1     /* a LEAF node or a brick cell that is not 0 (after see_through) */
+};
+typedef struct svo_voxel {          /* 32 bytes, laid out like svo_hit */
+    float    bmin[3];               /* Tree::bmin of traverse(), or the brick cell's leafmin (src/Traverse.cpp:66) */
+    float    size;                  /* Tree::size, or leafsize for a brick cell */
+    uint16_t material;              /* 0 for EMPTY / an empty cell; LEAF offset & 0xFFFF; brick cell value */
+    uint16_t flags;                 /* SVO_LOCATE_* */
+    uint32_t chunk;                 /* World::index() linear chunk index */
+    uint32_t node;                  /* index in that chunk's tree[] of the EMPTY / LEAF / TWIG node traverse() ends in */
+    uint32_t cell;                  /* brick cell word z*16+y*4+x, or SVO_CELL_NONE */
+} svo_voxel;
+int svo_world_locate(svo_world *, const float *points_dev, int64_t n,
+                     const svo_trace_params *params, svo_voxel *out_dev, void *stream);
 
 /* order_dev[0..ntiles) = the tile indices sorted by descending cost[i][0] + cost[i][1] (a stable device sort; cost_dev as
  * svo_trace_params.tile_cost_dev of ONE frame wrote it).  Asynchronous on `stream`; calls of one world on different streams are

@@ -10,6 +10,7 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     World.draw_translucent(camera, m)         <- ParallaxAlpha's march past water   shaders/ParallaxAlpha.Fragment.glsl:141-199,276-335
     World.trace_local_shadows(camera, ...)    <- (none: the reference's three lights share the directional light's shadow term)
     World.index / index_float                 <- World::index(_float)   src/World.cpp:288-293,323-332
+    World.locate / locate_points              <- traverse               src/Traverse.cpp:34-48 (the voxel under each point)
 
 There is NO CPU fallback: if libsvo_amd.so is missing the import raises, and every device call
 raises SvoError when HIP reports no device.
@@ -57,6 +58,10 @@ CELL_NONE = 0xFF
 HIT_DTYPE = np.dtype([("t", "<f4"), ("normal", "<f4", (3,)), ("material", "<u2"), ("flags", "<u2"),
                       ("chunk", "<u4"), ("node", "<u4"), ("cell", "<u4")])
 assert HIT_DTYPE.itemsize == 32
+LOCATE_INSIDE, LOCATE_SOLID = 1, 2                       # svo_voxel.flags (svo_world_locate)
+VOXEL_DTYPE = np.dtype([("bmin", "<f4", (3,)), ("size", "<f4"), ("material", "<u2"), ("flags", "<u2"),
+                        ("chunk", "<u4"), ("node", "<u4"), ("cell", "<u4")])
+assert VOXEL_DTYPE.itemsize == 32
 
 
 class SvoError(RuntimeError):
@@ -131,7 +136,7 @@ MAX_FRAMES = 16                     # SVO_MAX_FRAMES
 
 ABI_SYMBOLS = [
     "svo_world_generate", "svo_world_create", "svo_world_info_get", "svo_world_chunk", "svo_world_destroy",
-    "svo_world_index_float", "svo_world_index", "svo_world_upload", "svo_world_update",
+    "svo_world_index_float", "svo_world_index", "svo_world_locate", "svo_world_upload", "svo_world_update",
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_device_count", "svo_device_alloc", "svo_device_free", "svo_device_cache_trim", "svo_memcpy_h2d", "svo_memcpy_d2h",
@@ -178,6 +183,7 @@ lib.svo_trace_rows_frames.argtypes = [_P, C.POINTER(Camera), C.c_int, C.POINTER(
 lib.svo_tile_order.argtypes = [_P, _P, _P, C.c_int, _P]
 lib.svo_trace_rays.argtypes = [_P, _P, _P, C.c_int64, C.POINTER(TraceParams), _P, _P]
 lib.svo_trace_segments.argtypes = [_P, _P, _P, _P, C.c_int64, C.POINTER(TraceParams), _P, _P]
+lib.svo_world_locate.argtypes = [_P, _P, C.c_int64, C.POINTER(TraceParams), _P, _P]
 lib.svo_trace_last_ray_count.argtypes = [_P, _P, C.POINTER(C.c_uint64)]
 lib.svo_device_count.restype = C.c_int
 lib.svo_device_alloc.argtypes = [C.c_size_t]
@@ -514,6 +520,11 @@ class World:
         """svo_trace_segments: trace_rays with a far end per ray (tmax_ptr: [n] float on the device); a hit counts only if t < tmax."""
         _check(lib.svo_trace_segments(self._h, origins_ptr, dirs_ptr, tmax_ptr, n, C.byref(params), out_ptr, stream), "svo_trace_segments")
 
+    def locate(self, points_ptr: int, n: int, params: Optional[TraceParams], out_ptr: int, stream: int = 0):
+        """svo_world_locate: the voxel under each of n points ([n][3] float on the device) into out_ptr (n VOXEL_DTYPE records).
+        Only kernel, semantics and see_through of params are read; None = defaults."""
+        _check(lib.svo_world_locate(self._h, points_ptr, n, C.byref(params) if params is not None else None, out_ptr, stream), "svo_world_locate")
+
     def trace_translucent(self, cam: Camera, params: TraceParams, rect, surface_ptr: int, behind_ptr: int, stream: int = 0):
         """svo_trace_translucent: the surface G-buffer and, behind every hit of material params.see_through, the continuation's."""
         x0, y0, w, h = rect
@@ -600,3 +611,15 @@ class World:
             cnt.free()
             return g, c
         return g
+
+    def locate_points(self, points, kernel: int = KERNEL_AUTO, semantics: int = 0, see_through: int = 0):
+        """traverse (src/Traverse.cpp:34-48) and twigmarch's cell lookup over a point list; returns VOXEL_DTYPE[n]."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = p.shape[0]
+        pd, out = DeviceBuffer.from_numpy(p), DeviceBuffer(max(n, 1) * 32)
+        self.locate(pd.ptr, n, trace_params(kernel=kernel, semantics=semantics, see_through=see_through), out.ptr)
+        _check(lib.svo_stream_synchronize(None), "svo_stream_synchronize")
+        v = out.to_numpy(VOXEL_DTYPE, n)
+        pd.free()
+        out.free()
+        return v

@@ -3,6 +3,7 @@
 //   svo_world_upload  <- World::load_gpu + RootAllocator::alloc   src/World.cpp:57-94, src/Allocator.cpp:28-35
 //   svo_world_update  <- World::modify + RootAllocator::subst     src/World.cpp:268-274, src/Allocator.cpp:37-55
 //   svo_trace*        <- World::draw / draw_shadowmap             src/World.cpp:162-266
+//   svo_world_locate  <- traverse over a point list               src/Traverse.cpp:34-48 (locate.hip.h)
 //
 // The reference's first-fit free-list allocator over GL buffers is not reproduced: a world is
 // packed into one flat pool per kind with per-chunk slots sized by the chunk's host capacity
@@ -26,6 +27,7 @@
 #include "kernel_stack.hip.h"
 #include "see_through.hip.h"
 #include "local_shadows.hip.h"
+#include "locate.hip.h"
 #include "hip_own.h"
 #include "wide_tree.hip.h"
 
@@ -1137,6 +1139,33 @@ int svo_trace_local_shadows(svo_world *w, const svo_camera *cam, const svo_trace
                        reinterpret_cast<const uint4 *>(records), reinterpret_cast<uint4 *>(gbuffer_dev));
     HIP_TRY(hipGetLastError());
     return list.done.record(s);
+}
+
+// Point queries (locate.hip.h): one thread per point, the tree pool (SVO_KERNEL_LITERAL) or the wide pool (SVO_KERNEL_STACK; AUTO where
+// svo_trace would march with the stack kernel).  No launch slot, no scratch, no see-through view: the kernels compare the material read.
+int svo_world_locate(svo_world *w, const float *points_dev, int64_t n, const svo_trace_params *prm, svo_voxel *out_dev, void *stream)
+{
+    if (!w || n < 0 || (n > 0 && (!points_dev || !out_dev))) { set_error("svo_world_locate: bad point list or output"); return SVO_ERR_INVALID_ARG; }
+    if (prm && prm->see_through > 0xFFFFu) { set_error("svo_world_locate: see_through is a 16-bit material"); return SVO_ERR_INVALID_ARG; }
+    if (prm && prm->semantics != SVO_SEMANTICS_CPU && prm->semantics != SVO_SEMANTICS_GLSL) { set_error("svo_world_locate: unknown semantics"); return SVO_ERR_INVALID_ARG; }
+    if (prm && prm->kernel != SVO_KERNEL_AUTO && prm->kernel != SVO_KERNEL_LITERAL && prm->kernel != SVO_KERNEL_STACK) { set_error("svo_world_locate: unknown kernel id"); return SVO_ERR_INVALID_ARG; }
+    TraceArgs A;
+    const int rc = fill_common(w, prm, A);                              // (residency; the world box, the tables and the pools)
+    if (rc != SVO_OK) return rc;
+    A.counters = nullptr; A.tile_cost = nullptr; A.tile_order = nullptr;   // only kernel, semantics and see_through are read
+    const int kernel = pick_kernel(w, prm, A);
+    if (kernel < 0) return kernel;
+    if (n == 0) return SVO_OK;
+    const int64_t blocks = (n + 255) / 256;
+    if (blocks > 0x7FFFFFFF) { set_error("svo_world_locate: too many points for one launch"); return SVO_ERR_UNSUPPORTED; }
+    HIP_TRY(hipSetDevice(w->device));
+    A.from_camera = 0; A.nframes = 1;
+    A.origins = points_dev; A.n = n; A.out = out_dev;
+    const uint32_t see = prm ? prm->see_through : 0u;
+    if (kernel == SVO_KERNEL_STACK) hipLaunchKernelGGL(k_locate_wide, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A, see);
+    else hipLaunchKernelGGL(k_locate_literal, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A, see);
+    HIP_TRY(hipGetLastError());
+    return SVO_OK;
 }
 
 int svo_tile_order(svo_world *w, const uint32_t *cost_dev, uint32_t *order_dev, int ntiles, void *stream)

@@ -11,6 +11,7 @@
 //   svo::World::local_shadows(...)   <- (none: per-light shadows of the point light and the spotlight, svo_trace_local_shadows)
 //   svo::World::modify(i, ...)       <- World::modify          src/World.cpp:268-274
 //   svo::World::index / index_float  <- src/World.cpp:288-293,323-332
+//   svo::World::locate(points, ...)  <- traverse over a point list (svo_world_locate)   src/Traverse.cpp:34-48
 //   svo::World::deinit()             <- World::deinit          src/World.cpp:129-151
 //   svo::chunkmarch(alpha,beta,world,&sigma) <- chunkmarch     src/Traverse.cpp:127-171
 //
@@ -175,6 +176,17 @@ public:
         p.shadow = shadow ? 1 : 0;
         if (light_dir) std::memcpy(p.light_dir, light_dir, sizeof p.light_dir);
         check(svo_trace_segments(world_, origins_dev, dirs_dev, tmax_dev, n, &p, out_dev, stream), "World::segments");
+    }
+
+    // traverse(p, root) over a point list (svo_world_locate; src/Traverse.cpp:34-48): the node, the voxel box and the material under each
+    // of n points ([n][3] float on the device) into out_dev.  see_through: a material reported as empty (0 = off).
+    void locate(const float *points_dev, int64_t n, svo_voxel *out_dev, uint32_t see_through = 0, void *stream = nullptr)
+    {
+        svo_trace_params p;
+        std::memset(&p, 0, sizeof p);
+        p.semantics = semantics;
+        p.see_through = see_through;
+        check(svo_world_locate(world_, points_dev, n, &p, out_dev, stream), "World::locate");
     }
 
     // World::modify(i, tree delta, twig delta): re-send an edited chunk (Ocdelta ranges, src/Octree.h:47-54).
