@@ -1,6 +1,13 @@
-"""Shading stage (svo_shade): Blinn-Phong x 3 lights over the G-buffer, against the oracle's restatement
-of shaders/World.Fragment.glsl:75-138,180-197.  Float tolerance: powf / sqrtf-division chains differ in the last bits
-between glibc and the device, so colours are compared to 2e-5 relative (+1e-6 absolute); depth likewise."""
+"""Shading stage (svo_shade): Blinn-Phong x 3 lights over the G-buffer of a terrain frame, against the oracle's
+float32 restatement of shaders/World.Fragment.glsl:75-138,180-197, to 2e-5 relative (+1e-6 absolute); depth likewise.
+
+What that figure covers: the frames below, where nearly every voxel is material 4 (shininess 10000) and no camera sits within the
+0.03 rad of a perfect highlight, so every specular term is zero and the comparison is of the ambient and diffuse terms, the
+attenuation and the depth.  What it does not cover: any pixel with a visible highlight - x^y turns one float rounding of x into y
+roundings of the result, and there the correctly rounded oracle itself misses a float64 evaluation by 15 times this tolerance -
+and the materials, spot cone edges, near-eye points, shadow-bit combinations and packed-record patterns a terrain frame does not
+produce.  tests/test_shading_synthetic.py checks all of those against the float64 model of tests/shade_model.py, with a tolerance
+that grows with shininess * |specular term|; tests/test_shade_model_cpu.py checks that model and tolerance on a CPU."""
 import ctypes as C
 
 import numpy as np
