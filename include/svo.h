@@ -26,6 +26,11 @@
  *   svo_world_index*     <- World::index / index_float             src/World.cpp:276-293,323-332
  *   svo_world_locate     <- World::index_float + World::index (src/World.cpp:288-293,323-332) + traverse (src/Traverse.cpp:34-48)
  *                           + the cell lookup of twigmarch (:58-67) over a device point list
+ *   svo_hit_voxels       <- hit.bmin / hit.size, the Leaf that rootmarch hands to fragment main (shaders/World.Fragment.glsl:168-172): the box
+ *                           traverse() holds at the hit node (src/Traverse.cpp:34-48) and twigmarch's leafmin / leafsize (:66), from the
+ *                           record's ids; what the caller's edit cursor is placed from (src/Main.cpp:317,340-367)
+ *   svo_hit_uv           <- leafUV on cubeUV                        shaders/World.Fragment.glsl:5-15, shaders/Chunkmarch.glsl:138-149
+ *   svo_shade_textured   <- texture(Diffuse / Specular, uv) in fragment main   shaders/World.Fragment.glsl:178-190, src/Atlas.cpp:18-32
  *   svo_chunk_write/read <- Ocroot::write / Ocroot::read           src/Octree.cpp:178-201
  *   svo_world_shift      <- World::shift                           src/World.cpp:334-378
  *   svo_world_edit_box   <- Ocroot::build / destroy / replace + World::modify   src/Octree.cpp:203-443, src/World.cpp:268-274
@@ -82,7 +87,8 @@ extern "C" {
                                           svo_trace_translucent and svo_shade_translucent,
                                           svo_trace_local_shadows and SVO_LOCAL_SHADOWS / SVO_SHADOWED_POINT / SVO_SHADOWED_SPOT,
                                           svo_trace_segments,
-                                          svo_world_locate and svo_voxel */
+                                          svo_world_locate and svo_voxel,
+                                          svo_hit_voxels, svo_hit_uv, svo_shade_textured and svo_atlas */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -432,6 +438,45 @@ typedef struct svo_voxel {          /* 32 bytes, laid out like svo_hit */
 int svo_world_locate(svo_world *, const float *points_dev, int64_t n,
                      const svo_trace_params *params, svo_voxel *out_dev, void *stream);
 
+/* The box of every hit: out_dev[k] is the voxel that record k of gbuffer_dev names - what fragment main has as `hit` (hit.bmin, hit.size,
+ * shaders/World.Fragment.glsl:168-172) and svo_hit has no room for.  It cannot be rebuilt from t (chunkmarch, treemarch and twigmarch
+ * each restart t from their own entry point, src/Traverse.cpp:56,81,144,160) but follows from the ids, which every trace entry point
+ * writes: picking, the edit cursor (the box goes straight into svo_world_edit_box), leafUV.
+ * A record gets a box if it has SVO_HIT_FLAG, has no SVO_ERR_FLAG, chunk < the world's chunk count, node < that chunk's trees, the node
+ * is reachable from the chunk's root and is a LEAF (with cell == SVO_CELL_NONE) or a TWIG (with cell <= 63).  Then, every operation in
+ * float, separately rounded:
+ *   (bmin, size) = what traverse() (src/Traverse.cpp:34-48) holds on arriving at node: from (chunk.position, chunk.size), per level
+ *                  halfsize = size * 0.5f, bmin = bmin + vec3(ge) * halfsize with ge the bits of the child slot (x + 2y + 4z);
+ *   a brick cell:  leafsize = size / 4, bmin = bmin + vec3(cell & 3, (cell >> 2) & 3, cell >> 4) * leafsize, size = leafsize (:66);
+ *   out[k] = { bmin, size, the RECORD's material (a see-through launch's records keep theirs), SVO_LOCATE_INSIDE | SVO_LOCATE_SOLID,
+ *              chunk, node, cell }.
+ * Every other record - a miss, an error record, ids that name nothing reachable - gives an all-zero out[k]; nothing is read out of
+ * range whatever the ids hold.  A G-buffer that went through svo_gbuffer_pack / svo_gbuffer_unpack has lost its ids (unpack zeroes
+ * them): take the boxes before packing.
+ * The walk needs each node's parent, which the pools do not hold: a parent index - per 8-block of the tree pool the BRANCH that owns it
+ * and its level, reachable blocks only, so that a BRANCH word in a block an edit orphaned never counts; 5 bytes per 8 node words - is
+ * built on the device at the first call (level-synchronous sweeps, nothing read back) and dropped by every change to the pools
+ * (svo_world_update / _edit_box / _shift / _compact / _coarsen / _upload, destroy).  svo_world_info does not count it; if it cannot
+ * be allocated the call is SVO_ERR_OUT_OF_MEMORY and nothing is written.
+ * n < 0 or a NULL gbuffer_dev / out_dev with n > 0: SVO_ERR_INVALID_ARG; then a world that is not resident: SVO_ERR_NOT_UPLOADED; then
+ * n == 0: SVO_OK - all settled before any device work.  Asynchronous on `stream`, ordered against updates, edits and shifts like
+ * svo_world_locate; calls of one world on different streams are ordered behind one another only while the index is being built. */
+int svo_hit_voxels(svo_world *, const svo_hit *gbuffer_dev, int64_t n, svo_voxel *out_dev, void *stream);
+
+/* leafUV (shaders/World.Fragment.glsl:5-15) per pixel of the rectangle svo_trace(cam, x0, y0, w, h) filled: gbuffer_dev its w*h records,
+ * voxels_dev what svo_hit_voxels wrote for them, uv_dev w*h float2.  For a record with SVO_HIT_FLAG, without SVO_ERR_FLAG, whose voxel
+ * record has SVO_LOCATE_INSIDE - every float operation separately rounded, eps == 0 meaning 1/8192 (pass the launch's):
+ *   point = o + d * (t - eps)       (o, d) the pixel's camera ray as the march forms it;
+ *   iuv   = cubeUV(point, bmin, bmin + size)   (shaders/Chunkmarch.glsl:138-149): size = cmax.x - cmin.x, uv = (0, 0), then the six
+ *           tests abs(p.x - cmin.x) <= eps: uv = p.yz - cmin.yz; p.x, cmax: p.yz - cmax.yz; p.y, cmin: p.xz - cmin.xz; p.y, cmax;
+ *           p.z, cmin: p.xy - cmin.xy; p.z, cmax - in this order, a later one that holds winning; iuv = abs(uv) / size;
+ *   iuv  += (vec2(lessThan(iuv, 0.125)) - vec2(greaterThan(iuv, 0.125))) * eps * 2;
+ *   uv    = (vec2(m & 0xff, (m >> 8) & 0xff) + iuv) / 256, m the record's material.
+ * Every other pixel gets (0, 0).  Any sampler can texture from this.  A NULL pointer, a negative rectangle, a camera without an image
+ * size or eps < 0: SVO_ERR_INVALID_ARG.  Asynchronous on `stream`. */
+int svo_hit_uv(const svo_camera *cam, float eps, int x0, int y0, int w, int h,
+               const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, float *uv_dev, void *stream);
+
 /* order_dev[0..ntiles) = the tile indices sorted by descending cost[i][0] + cost[i][1] (a stable device sort; cost_dev as
  * svo_trace_params.tile_cost_dev of ONE frame wrote it).  Asynchronous on `stream`; calls of one world on different streams are
  * ordered behind one another on the device (they share the world's sort scratch), each call's order_dev is complete when the
@@ -484,8 +529,9 @@ int svo_gbuffer_unpack(const uint64_t *packed_dev, svo_hit *gbuffer_dev, int64_t
 
 /* ---- shading stage: Blinn-Phong x 3 lights over the G-buffer --------------------
  * shaders/World.Fragment.glsl:63-138,180-197.  The reference multiplies the lights with gamma-decoded samples of
- * its Diffuse / Specular texture atlas, which is not part of the repository; here the albedo comes from the
- * material table's diffuse / specular colours instead (pow(colour, gamma)), the shadow term from SVO_SHADOWED
+ * its Diffuse / Specular texture atlas, which is not part of the repository; in svo_shade the albedo comes from the
+ * material table's diffuse / specular colours instead (pow(colour, gamma)) - svo_shade_textured samples an atlas the caller supplies -,
+ * the shadow term from SVO_SHADOWED
  * for all three lights - or, on a record that carries SVO_LOCAL_SHADOWS, from SVO_SHADOWED_POINT for the point light, SVO_SHADOWED_SPOT
  * for the spotlight and SVO_SHADOWED for the directional light.
  * Output per pixel: float4 {r, g, b, depth} with depth = (1/dist - 1/near) / (1/far - 1/near) (gl_FragDepth,
@@ -511,6 +557,20 @@ int svo_shade(const svo_camera *cam, const svo_shade_params *p, int x0, int y0, 
  * written per pixel instead of 32 + 16; identical colours (the packed record carries t, normal, material, flags). */
 int svo_shade_packed(const svo_camera *cam, const svo_shade_params *p, int x0, int y0, int w, int h,
                      const uint64_t *packed_dev, float *rgba_dev, void *stream);
+
+/* svo_shade with the albedo the reference has (shaders/World.Fragment.glsl:178-182): diffuse = pow(texture(Diffuse, uv), gamma) and
+ * specular = pow(texture(Specular, uv), gamma) at uv = svo_hit_uv's, in the place of the material table's diffuse / specular colours.
+ * The atlas is the caller's: two RGB8 images of width x height texels on the device, rows tightly packed (GL_UNPACK_ALIGNMENT 1), row 0
+ * at v = 0, a 256 x 256 grid of tiles - tile (m & 0xff, (m >> 8) & 0xff) belongs to material m.  specular_dev == NULL means the diffuse
+ * image (src/Atlas.cpp:31-32).  Sampling is GL_NEAREST (src/Atlas.cpp:18-21) with GL's default repeat wrap:
+ *   x = min(int(floor((u - floor(u)) * width)), width - 1), y likewise with v and height; texel = image[(y * width + x) * 3 ..]
+ * and a texel byte b decodes to pow(b / 255.0f, gamma) in float, as the material table's colours do.  Everything else is svo_shade:
+ * p->eps is the eps of the UV, materials[m].shininess, the shadow bits, depth, misses give {0,0,0,1}.  voxels_dev holds the records
+ * svo_hit_voxels wrote for gbuffer_dev; a hit whose voxel record lacks SVO_LOCATE_INSIDE is shaded exactly as svo_shade shades it.
+ * So a flat atlas of byte value b gives, bit for bit, svo_shade's image with every material's diffuse and specular set to b / 255.0f. */
+typedef struct svo_atlas { const uint8_t *diffuse_dev, *specular_dev; int32_t width, height; } svo_atlas;
+int svo_shade_textured(const svo_camera *cam, const svo_shade_params *p, const svo_atlas *atlas, int x0, int y0, int w, int h,
+                       const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, float *rgba_dev, void *stream);
 
 /* ParallaxAlpha's blend (shaders/ParallaxAlpha.Fragment.glsl:226-234,315-323) over the two G-buffers of svo_trace_translucent:
  * C_s = svo_shade of the surface record, C_b = svo_shade of the behind record with its t replaced by t1 + t2 (the distance from the

@@ -11,6 +11,8 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     World.trace_local_shadows(camera, ...)    <- (none: the reference's three lights share the directional light's shadow term)
     World.index / index_float                 <- World::index(_float)   src/World.cpp:288-293,323-332
     World.locate / locate_points              <- traverse               src/Traverse.cpp:34-48 (the voxel under each point)
+    World.hit_voxels / hit_boxes              <- hit.bmin / hit.size of fragment main   shaders/World.Fragment.glsl:168-172
+    hit_uv, shade_textured, Atlas             <- leafUV, texture(Diffuse / Specular, uv)   shaders/World.Fragment.glsl:5-15,178-182
 
 There is NO CPU fallback: if libsvo_amd.so is missing the import raises, and every device call
 raises SvoError when HIP reports no device.
@@ -122,6 +124,11 @@ class ShadeParams(C.Structure):
                 ("eps", C.c_float), ("gamma", C.c_float), ("near_plane", C.c_float), ("far_plane", C.c_float)]
 
 
+class Atlas(C.Structure):
+    """svo_atlas: RGB8 images on the device, rows tightly packed, row 0 at v = 0; specular_dev None = the diffuse image."""
+    _fields_ = [("diffuse_dev", C.c_void_p), ("specular_dev", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
+
+
 class WorldInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("depth", C.c_int32), ("chunksize", C.c_int32),
                 ("chunkcoordmin", C.c_int32 * 3), ("uploaded_device", C.c_int32),
@@ -136,7 +143,7 @@ MAX_FRAMES = 16                     # SVO_MAX_FRAMES
 
 ABI_SYMBOLS = [
     "svo_world_generate", "svo_world_create", "svo_world_info_get", "svo_world_chunk", "svo_world_destroy",
-    "svo_world_index_float", "svo_world_index", "svo_world_locate", "svo_world_upload", "svo_world_update",
+    "svo_world_index_float", "svo_world_index", "svo_world_locate", "svo_hit_voxels", "svo_hit_uv", "svo_shade_textured", "svo_world_upload", "svo_world_update",
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_device_count", "svo_device_alloc", "svo_device_free", "svo_device_cache_trim", "svo_memcpy_h2d", "svo_memcpy_d2h",
@@ -184,6 +191,9 @@ lib.svo_tile_order.argtypes = [_P, _P, _P, C.c_int, _P]
 lib.svo_trace_rays.argtypes = [_P, _P, _P, C.c_int64, C.POINTER(TraceParams), _P, _P]
 lib.svo_trace_segments.argtypes = [_P, _P, _P, _P, C.c_int64, C.POINTER(TraceParams), _P, _P]
 lib.svo_world_locate.argtypes = [_P, _P, C.c_int64, C.POINTER(TraceParams), _P, _P]
+lib.svo_hit_voxels.argtypes = [_P, _P, C.c_int64, _P, _P]
+lib.svo_hit_uv.argtypes = [C.POINTER(Camera), C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
+lib.svo_shade_textured.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams), C.POINTER(Atlas), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
 lib.svo_trace_last_ray_count.argtypes = [_P, _P, C.POINTER(C.c_uint64)]
 lib.svo_device_count.restype = C.c_int
 lib.svo_device_alloc.argtypes = [C.c_size_t]
@@ -363,6 +373,20 @@ def shade_translucent(cam: Camera, params: ShadeParams, rect, surface_ptr: int, 
            "svo_shade_translucent")
 
 
+def hit_uv(cam: Camera, eps: float, rect, gbuffer_ptr: int, voxels_ptr: int, uv_ptr: int, stream: int = 0):
+    """svo_hit_uv: the reference's leafUV per pixel ([w*h][2] float) from the G-buffer and World.hit_voxels' records; eps 0 = 1/8192."""
+    x0, y0, w, h = rect
+    _check(lib.svo_hit_uv(C.byref(cam) if cam is not None else None, eps, x0, y0, w, h, gbuffer_ptr, voxels_ptr, uv_ptr, stream), "svo_hit_uv")
+
+
+def shade_textured(cam: Camera, params: ShadeParams, atlas: Atlas, rect, gbuffer_ptr: int, voxels_ptr: int, rgba_ptr: int, stream: int = 0):
+    """svo_shade_textured: svo_shade with the albedo sampled from the caller's atlas at the hit's leafUV."""
+    x0, y0, w, h = rect
+    _check(lib.svo_shade_textured(C.byref(cam) if cam is not None else None, C.byref(params) if params is not None else None,
+                                  C.byref(atlas) if atlas is not None else None, x0, y0, w, h, gbuffer_ptr, voxels_ptr, rgba_ptr, stream),
+           "svo_shade_textured")
+
+
 def see_through_chunk(chunk: dict, material: int) -> dict:
     """The chunk as a see-through march of `material` sees it: LEAF nodes of that material (offset & 0xFFFF) and brick cells
     holding it set to 0, the tree's shape unchanged.  Host numpy; what svo_trace_params.see_through is defined against."""
@@ -525,6 +549,11 @@ class World:
         Only kernel, semantics and see_through of params are read; None = defaults."""
         _check(lib.svo_world_locate(self._h, points_ptr, n, C.byref(params) if params is not None else None, out_ptr, stream), "svo_world_locate")
 
+    def hit_voxels(self, gbuffer_ptr: int, n: int, out_ptr: int, stream: int = 0):
+        """svo_hit_voxels: the voxel box of each of n G-buffer records (HIT_DTYPE on the device) into out_ptr (n VOXEL_DTYPE records);
+        all zero for a record without a usable hit or whose (chunk, node, cell) name nothing reachable."""
+        _check(lib.svo_hit_voxels(self._h, gbuffer_ptr, n, out_ptr, stream), "svo_hit_voxels")
+
     def trace_translucent(self, cam: Camera, params: TraceParams, rect, surface_ptr: int, behind_ptr: int, stream: int = 0):
         """svo_trace_translucent: the surface G-buffer and, behind every hit of material params.see_through, the continuation's."""
         x0, y0, w, h = rect
@@ -621,5 +650,17 @@ class World:
         _check(lib.svo_stream_synchronize(None), "svo_stream_synchronize")
         v = out.to_numpy(VOXEL_DTYPE, n)
         pd.free()
+        out.free()
+        return v
+
+    def hit_boxes(self, records):
+        """World.hit_voxels over host records (HIT_DTYPE, any shape); returns VOXEL_DTYPE[n]."""
+        g = np.ascontiguousarray(records, dtype=HIT_DTYPE).reshape(-1)
+        n = g.shape[0]
+        gd, out = DeviceBuffer.from_numpy(g), DeviceBuffer(max(n, 1) * 32)
+        self.hit_voxels(gd.ptr, n, out.ptr)
+        _check(lib.svo_stream_synchronize(None), "svo_stream_synchronize")
+        v = out.to_numpy(VOXEL_DTYPE, n)
+        gd.free()
         out.free()
         return v

@@ -28,6 +28,7 @@
 #include "see_through.hip.h"
 #include "local_shadows.hip.h"
 #include "locate.hip.h"
+#include "hit_voxels.hip.h"
 #include "hip_own.h"
 #include "wide_tree.hip.h"
 
@@ -147,11 +148,21 @@ static void drop_view(svo_world &w)
     w.hbm->view_wide = Pooled<uint32_t>(); w.hbm->view_mask = Pooled<uint64_t>(); w.hbm->view_material = 0;
 }
 
+// the parent index (hit_voxels.hip.h): every change to the pools drops it, the next svo_hit_voxels call builds it again
+static void drop_parents(svo_world &w)
+{
+    Hbm &d = *w.hbm;
+    if (d.parent.p || d.parent_level.p || d.chunk_trees.p) (void)hipDeviceSynchronize();
+    d.parent = Pooled<uint32_t>(); d.parent_level = Pooled<uint8_t>(); d.chunk_trees = DevBuf<uint32_t>();
+    d.parents_ok = false;
+}
+
 int release_device(svo_world &w, bool keep_builder)
 {
     if (w.hbm) {
         (void)hipSetDevice(w.device);
         drop_view(w);
+        drop_parents(w);
         if (!keep_builder) free_builder_context(w);
         (void)hipDeviceSynchronize();                       // the large buffers may be handed to another world at once: nothing may still use them
         delete w.hbm;
@@ -588,6 +599,7 @@ static int install_chunk(svo_world &w, int chunk, const uint32_t *tree, const ui
     HIP_TRY(hipSetDevice(w.device));
     HIP_TRY(hipDeviceSynchronize());
     drop_view(w);                                                       // rebuilt from the new pools at the next see-through launch
+    drop_parents(w);                                                    // ... and at the next svo_hit_voxels call
     ChunkPools &c = w.chunks[(size_t)chunk];
     DevChunk &e = w.table[(size_t)chunk];
     const uint64_t trees = c.tree_count(), twigs = c.twig_count();
@@ -1164,6 +1176,76 @@ int svo_world_locate(svo_world *w, const float *points_dev, int64_t n, const svo
     const uint32_t see = prm ? prm->see_through : 0u;
     if (kernel == SVO_KERNEL_STACK) hipLaunchKernelGGL(k_locate_wide, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A, see);
     else hipLaunchKernelGGL(k_locate_literal, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A, see);
+    HIP_TRY(hipGetLastError());
+    return SVO_OK;
+}
+
+// The parent index for a svo_hit_voxels call on `s`: built on the device at the first call after a change to the pools - level 0
+// everywhere, the roots' kernel, one sweep per further BRANCH level - and awaited by every call on another stream.
+static int use_parents(svo_world *w, hipStream_t s)
+{
+    Hbm &d = *w->hbm;
+    if (d.parents_ok) return d.parents_built.wait(s);
+    const size_t n = w->chunks.size(), blocks = (size_t)(w->tree_pool_cap >> 3) + 1;
+    std::vector<uint32_t> trees(n);
+    uint64_t most = 0;                                                  // most 8-blocks a chunk holds
+    for (size_t i = 0; i < n; ++i) {
+        trees[i] = (uint32_t)w->chunks[i].tree_count();                 // (< 2^30: offsets are 30-bit)
+        most = std::max<uint64_t>(most, (w->chunks[i].tree_count() - 1) / 8);
+    }
+    if (d.parent.alloc(blocks, w->device) != hipSuccess || d.parent_level.alloc(blocks, w->device) != hipSuccess ||
+        d.chunk_trees.reserve(n, false, nullptr) != SVO_OK) {
+        d.parent = Pooled<uint32_t>(); d.parent_level = Pooled<uint8_t>(); d.chunk_trees = DevBuf<uint32_t>();
+        set_error("svo_hit_voxels: hipMalloc of the parent index failed"); return SVO_ERR_OUT_OF_MEMORY;
+    }
+    HIP_TRY(hipMemcpy(d.chunk_trees.p, trees.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(d.parent_level.p, 0, blocks, s));
+    hipLaunchKernelGGL(k_parent_roots, dim3(blocks_for(n, 256)), dim3(256), 0, s, d.chunks.p, d.chunk_trees.p, (uint32_t)n, d.tree.p, d.parent.p, d.parent_level.p);
+    if (most) {
+        const dim3 grid(blocks_for(most, 256), (unsigned)std::min<size_t>(n, 65535));
+        for (int L = 1; L < w->max_levels; ++L)
+            hipLaunchKernelGGL(k_parent_sweep, grid, dim3(256), 0, s, d.chunks.p, d.chunk_trees.p, (uint32_t)n, d.tree.p, d.parent.p, d.parent_level.p, (uint32_t)L);
+    }
+    HIP_TRY(hipGetLastError());
+    if (const int rc = d.parents_built.record(s)) return rc;
+    d.parents_ok = true;
+    return SVO_OK;
+}
+
+// The box of every hit (hit_voxels.hip.h): one thread per record, the walk up through the parent index and the replay down.  No launch
+// slot and no scratch: calls on different streams are ordered behind one another only while the index is being built.
+int svo_hit_voxels(svo_world *w, const svo_hit *gbuffer_dev, int64_t n, svo_voxel *out_dev, void *stream)
+{
+    if (!w || n < 0 || (n > 0 && (!gbuffer_dev || !out_dev))) { set_error("svo_hit_voxels: bad G-buffer or output"); return SVO_ERR_INVALID_ARG; }
+    if (w->device < 0) { set_error("svo_hit_voxels: world is not uploaded"); return SVO_ERR_NOT_UPLOADED; }
+    if (n == 0) return SVO_OK;
+    const int64_t blocks = (n + 255) / 256;
+    if (blocks > 0x7FFFFFFF) { set_error("svo_hit_voxels: too many records for one launch"); return SVO_ERR_UNSUPPORTED; }
+    HIP_TRY(hipSetDevice(w->device));
+    hipStream_t s = (hipStream_t)stream;
+    try {
+        if (const int rc = use_parents(w, s)) return rc;
+    } catch (const std::bad_alloc &) { set_error("svo_hit_voxels: out of host memory"); return SVO_ERR_OUT_OF_MEMORY; }
+    const Hbm &d = *w->hbm;
+    hipLaunchKernelGGL(k_hit_voxels, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<const uint4 *>(gbuffer_dev), out_dev, n, d.chunks.p,
+                       d.chunk_trees.p, (uint32_t)w->chunks.size(), d.tree.p, d.parent.p, d.parent_level.p, (float)w->chunksize);
+    HIP_TRY(hipGetLastError());
+    return SVO_OK;
+}
+
+// leafUV per pixel (march.hip.h hit_uv) from the G-buffer and the records svo_hit_voxels wrote for it
+int svo_hit_uv(const svo_camera *cam, float eps, int x0, int y0, int rw, int rh, const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev,
+               float *uv_dev, void *stream)
+{
+    if (!cam || !gbuffer_dev || !voxels_dev || !uv_dev || rw < 0 || rh < 0 || x0 < 0 || y0 < 0 || cam->width <= 0 || cam->height <= 0 || !(eps >= 0.0f)) {
+        set_error("svo_hit_uv: bad argument"); return SVO_ERR_INVALID_ARG;
+    }
+    const int64_t n = (int64_t)rw * rh;
+    if (n == 0) return SVO_OK;
+    if ((n + 255) / 256 > 0x7FFFFFFF) { set_error("svo_hit_uv: image too large"); return SVO_ERR_UNSUPPORTED; }
+    hipLaunchKernelGGL(k_hit_uv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, frame_cam(*cam), cam->width, cam->height, x0, y0, rw, n,
+                       eps == 0.0f ? 1.0f / 8192.0f : eps, reinterpret_cast<const uint4 *>(gbuffer_dev), reinterpret_cast<const uint4 *>(voxels_dev),
+                       reinterpret_cast<float2 *>(uv_dev));
     HIP_TRY(hipGetLastError());
     return SVO_OK;
 }

@@ -126,6 +126,12 @@ struct Hbm {
     Pooled<uint32_t> view_wide; Pooled<uint64_t> view_mask;
     uint32_t view_material = 0;                             // material the view holds; 0 = no view
     Event view_built;                                       // launches on other streams wait for it
+    // parent index (svo_hit_voxels, hit_voxels.hip.h): per 8-block of the tree pool the chunk-relative index of the BRANCH that owns it
+    // and the block's level (0 = not reachable), and per chunk its node count; built on the device at the first svo_hit_voxels call,
+    // dropped by every change to the pools
+    Pooled<uint32_t> parent; Pooled<uint8_t> parent_level; DevBuf<uint32_t> chunk_trees;
+    bool parents_ok = false;                                // the build has been issued
+    Event parents_built;                                    // calls on other streams wait for it
     int stack_blocks[24] = {};                              // persistent-grid size per k_trace_stack instantiation (device.hip: STACK_KERNELS); 0 = not queried yet
 };
 

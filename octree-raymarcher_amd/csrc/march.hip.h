@@ -133,6 +133,41 @@ __device__ __forceinline__ void local_to_pixel(const TraceArgs &A, int lx, int l
     py = A.y0 + (ly / A.bh) * A.ystep + (ly % A.bh);
 }
 
+// cubeUV (shaders/Chunkmarch.glsl:138-149) and leafUV (shaders/World.Fragment.glsl:5-15) as written: six face tests in the
+// shader's order, the later one winning; abs(uv) / size; the nudge away from 0.125; the tile of material m in a 256 x 256 grid.
+__device__ __forceinline__ void leaf_uv(V3 p, V3 cmin, float bsize, uint32_t m, float eps, float &u, float &v)
+{
+    const V3 cmax = cmin + bsize;
+    const float size = cmax.x - cmin.x;
+    float a = 0.0f, b = 0.0f;
+    if (fabsf(p.x - cmin.x) <= eps) { a = p.y - cmin.y; b = p.z - cmin.z; }
+    if (fabsf(p.x - cmax.x) <= eps) { a = p.y - cmax.y; b = p.z - cmax.z; }
+    if (fabsf(p.y - cmin.y) <= eps) { a = p.x - cmin.x; b = p.z - cmin.z; }
+    if (fabsf(p.y - cmax.y) <= eps) { a = p.x - cmax.x; b = p.z - cmax.z; }
+    if (fabsf(p.z - cmin.z) <= eps) { a = p.x - cmin.x; b = p.y - cmin.y; }
+    if (fabsf(p.z - cmax.z) <= eps) { a = p.x - cmax.x; b = p.y - cmax.y; }
+    a = fabsf(a) / size; b = fabsf(b) / size;
+    a = a + (((a < 0.125f ? 1.0f : 0.0f) - (a > 0.125f ? 1.0f : 0.0f)) * eps) * 2.0f;
+    b = b + (((b < 0.125f ? 1.0f : 0.0f) - (b > 0.125f ? 1.0f : 0.0f)) * eps) * 2.0f;
+    u = ((float)(m & 0xFFu) + a) / 256.0f;
+    v = ((float)((m >> 8) & 0xFFu) + b) / 256.0f;
+}
+
+// leafUV of a pixel from its record (h0, h1) and its voxel record (v0, v1: svo_hit_voxels); false, and (0, 0), where there is none:
+// no hit, SVO_ERR_FLAG, or a voxel record without SVO_LOCATE_INSIDE
+__device__ __forceinline__ bool hit_uv(const FrameCam &cam, int imgw, int imgh, int px, int py, float eps, uint4 h0, uint4 h1, uint4 v0, uint4 v1,
+                                       float &u, float &v)
+{
+    u = v = 0.0f;
+    const uint32_t flags = h1.x >> 16;
+    if (!(flags & SVO_HIT_FLAG) || (flags & SVO_ERR_FLAG) || !((v1.x >> 16) & SVO_LOCATE_INSIDE)) return false;
+    V3 o, d;
+    camera_ray(cam, imgw, imgh, px, py, o, d);
+    const V3 p = o + d * (__uint_as_float(h0.x) - eps);     // the point cubeNormal is taken at, shaders/World.Fragment.glsl:174
+    leaf_uv(p, mk(__uint_as_float(v0.x), __uint_as_float(v0.y), __uint_as_float(v0.z)), __uint_as_float(v0.w), h1.x & 0xFFFFu, eps, u, v);
+    return true;
+}
+
 struct Voxel { V3 lo; float size; uint32_t material, node, cell; };
 
 // 32-byte record as two 16-byte stores.

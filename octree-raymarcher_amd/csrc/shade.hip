@@ -1,6 +1,7 @@
 // shade.hip — the shading stage over the G-buffer: Blinn-Phong x 3 lights,
 // shaders/World.Fragment.glsl:63-138,180-197, as one coalesced kernel (32 B read + 16 B written per pixel:
-// HBM-bound).  Albedo from the material table instead of the (unavailable) texture atlas — see include/svo.h.
+// HBM-bound).  Albedo from the material table (svo_shade) or from the caller's texture atlas at the hit's leafUV
+// (svo_shade_textured, :5-15,178-182) — see include/svo.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -59,8 +60,11 @@ __device__ __forceinline__ V3 normal_from_code(uint32_t code)
     return mk(ix * inv, iy * inv, iz * inv);
 }
 
-// One pixel's {r, g, b, depth} from its record (a hit: SVO_HIT_FLAG) - the body of k_shade, shared with k_shade_translucent
-__device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, uint32_t flags, uint32_t material, float t, V3 n)
+__device__ __forceinline__ int material_index(uint32_t material) { return material < 8 ? (int)material : 0; }
+
+// One pixel's {r, g, b, depth} from its record (a hit: SVO_HIT_FLAG) and its gamma-decoded albedo (:181-182) - the body of every
+// shading kernel
+__device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, uint32_t flags, uint32_t material, float t, V3 n, V3 diffuse, V3 specular)
 {
     const svo_shade_params &P = A.P;
     // the ray of this pixel (same generation as the march) and the shaded point alpha + beta * (sigma - EPS), :174
@@ -72,9 +76,7 @@ __device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, uint3
     const V3 beta = normalize_fast((ld3(A.fwd) + ld3(A.right) * u) + ld3(A.up) * v);
     const float sdist = t - P.eps;
     const V3 p = eye + beta * sdist;
-    const int mi = material < 8 ? (int)material : 0;
-    const float shininess = P.materials[mi].shininess;
-    const V3 diffuse = ld3(A.gdiffuse[mi]), specular = ld3(A.gspecular[mi]);                          // :183-184
+    const float shininess = P.materials[material_index(material)].shininess;
     // (1.0 - shadow): the directional light's term for all three (:186-190), unless svo_trace_local_shadows gave each local light its own
     const float lit = (flags & SVO_SHADOWED) ? 0.0f : 1.0f;
     const bool local = (flags & SVO_LOCAL_SHADOWS) != 0u;
@@ -128,6 +130,13 @@ __device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, uint3
     return make_float4(color.x, color.y, color.z, (rcp_fast(zdist) - A.inv_near) * A.inv_depth_range);     // :193-197
 }
 
+// svo_shade's albedo: the material table's (:183-184 with the table in the atlas's place)
+__device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, uint32_t flags, uint32_t material, float t, V3 n)
+{
+    const int mi = material_index(material);
+    return shade_hit(A, k, flags, material, t, n, ld3(A.gdiffuse[mi]), ld3(A.gspecular[mi]));
+}
+
 // PACKED: the G-buffer is the 8-byte form of svo_gbuffer_pack (8 B read + 16 B written per pixel instead of 32 + 16)
 template <bool PACKED>
 __global__ __launch_bounds__(256) void k_shade(ShadeArgs A)
@@ -173,6 +182,45 @@ __global__ __launch_bounds__(256) void k_shade_translucent(ShadeArgs A, const ui
     s = (1.0f < s) ? 1.0f : s;
     const float r = 1.0f - s;
     A.rgba[k] = make_float4(cb.x * r + cs.x * s, cb.y * r + cs.y * s, cb.z * r + cs.z * s, cb.w);
+}
+
+// svo_shade_textured: the caller's atlas (RGB8, rows tightly packed, row 0 at v = 0) and the 256 values a texel byte decodes to
+struct AtlasArgs {
+    const uint8_t *diffuse, *specular;
+    int32_t width, height;
+    float decode[256];                          // pow(byte / 255, gamma), made on the host like gdiffuse
+};
+
+// texture(sampler, uv) of a GL_NEAREST, GL_REPEAT sampler
+__device__ __forceinline__ V3 atlas_texel(const AtlasArgs &T, const uint8_t *image, float u, float v)
+{
+    const int x = max(min((int)floorf((u - floorf(u)) * (float)T.width), T.width - 1), 0);       // (the max: a NaN uv reads texel 0, never out of range)
+    const int y = max(min((int)floorf((v - floorf(v)) * (float)T.height), T.height - 1), 0);
+    const uint8_t *px = image + ((size_t)y * (size_t)T.width + (size_t)x) * 3;
+    return mk(T.decode[px[0]], T.decode[px[1]], T.decode[px[2]]);
+}
+
+// k_shade with the albedo of :178-182: the two atlases sampled at the hit's leafUV (march.hip.h hit_uv, separately rounded IEEE
+// operations: the texel is the reference's).  `voxels`: the records svo_hit_voxels wrote for A.gbuffer; a hit without a box gets
+// the material table's albedo.
+__global__ __launch_bounds__(256) void k_shade_textured(ShadeArgs A, const uint4 *voxels, AtlasArgs T)
+{
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= (int64_t)A.w * A.h) return;
+    const uint4 r0 = A.gbuffer[2 * k], r1 = A.gbuffer[2 * k + 1];
+    const uint32_t flags = r1.x >> 16, material = r1.x & 0xFFFFu;
+    if (!(flags & SVO_HIT_FLAG)) { A.rgba[k] = make_float4(0.0f, 0.0f, 0.0f, 1.0f); return; }
+    const float t = __uint_as_float(r0.x);
+    const V3 n = mk(__uint_as_float(r0.y), __uint_as_float(r0.z), __uint_as_float(r0.w));
+    FrameCam cam;
+    for (int a = 0; a < 3; ++a) { cam.eye[a] = A.eye[a]; cam.fwd[a] = A.fwd[a]; cam.right[a] = A.right[a]; cam.up[a] = A.up[a]; }
+    cam.tanx = A.tanx; cam.tany = A.tany;
+    float u, v;
+    if (!hit_uv(cam, A.imgw, A.imgh, A.x0 + (int)(k % A.w), A.y0 + (int)(k / A.w), A.P.eps, r0, r1, voxels[2 * k], voxels[2 * k + 1], u, v)) {
+        A.rgba[k] = shade_hit(A, k, flags, material, t, n);
+        return;
+    }
+    A.rgba[k] = shade_hit(A, k, flags, material, t, n, atlas_texel(T, T.diffuse, u, v), atlas_texel(T, T.specular, u, v));
 }
 
 // ---- packed G-buffer -------------------------------------------------------------------------------------------
@@ -270,9 +318,10 @@ static int pack_common(const void *in, void *out, int64_t n, void *stream, bool 
 int svo_gbuffer_pack(const svo_hit *gbuffer_dev, uint64_t *packed_dev, int64_t n, void *stream) { return pack_common(gbuffer_dev, packed_dev, n, stream, true); }
 int svo_gbuffer_unpack(const uint64_t *packed_dev, svo_hit *gbuffer_dev, int64_t n, void *stream) { return pack_common(packed_dev, gbuffer_dev, n, stream, false); }
 
-// kind: 0 = svo_shade, 1 = svo_shade_packed, 2 = svo_shade_translucent (behind_dev, absorption)
+// kind: 0 = svo_shade, 1 = svo_shade_packed, 2 = svo_shade_translucent (behind_dev, absorption), 3 = svo_shade_textured (behind_dev: the voxel records, atlas)
 static int shade_impl(const svo_camera *cam, const svo_shade_params *p, int x0, int y0, int w, int h,
-                      const void *gbuffer_dev, float *rgba_dev, void *stream, int kind, const void *behind_dev = nullptr, float absorption = 0.0f)
+                      const void *gbuffer_dev, float *rgba_dev, void *stream, int kind, const void *behind_dev = nullptr, float absorption = 0.0f,
+                      const svo_atlas *atlas = nullptr)
 {
     if (!cam || !p || !gbuffer_dev || !rgba_dev || w < 0 || h < 0 || x0 < 0 || y0 < 0 || cam->width <= 0 || cam->height <= 0) {
         set_error("svo_shade: bad argument"); return SVO_ERR_INVALID_ARG;
@@ -307,7 +356,14 @@ static int shade_impl(const svo_camera *cam, const svo_shade_params *p, int x0, 
     const int64_t n = (int64_t)w * h;
     if (n == 0) return SVO_OK;
     const dim3 grid((unsigned)((n + 255) / 256));
-    if (kind == 1) hipLaunchKernelGGL(k_shade<true>, grid, dim3(256), 0, (hipStream_t)stream, A);
+    if (kind == 3) {
+        AtlasArgs T;
+        T.diffuse = atlas->diffuse_dev; T.specular = atlas->specular_dev ? atlas->specular_dev : atlas->diffuse_dev;      // src/Atlas.cpp:31-32
+        T.width = atlas->width; T.height = atlas->height;
+        for (int v = 0; v < 256; ++v) T.decode[v] = std::pow((float)v / 255.0f, A.P.gamma);
+        hipLaunchKernelGGL(k_shade_textured, grid, dim3(256), 0, (hipStream_t)stream, A, reinterpret_cast<const uint4 *>(behind_dev), T);
+    }
+    else if (kind == 1) hipLaunchKernelGGL(k_shade<true>, grid, dim3(256), 0, (hipStream_t)stream, A);
     else if (kind == 0) hipLaunchKernelGGL(k_shade<false>, grid, dim3(256), 0, (hipStream_t)stream, A);
     else hipLaunchKernelGGL(k_shade_translucent, grid, dim3(256), 0, (hipStream_t)stream, A, reinterpret_cast<const uint4 *>(behind_dev),
                             absorption == 0.0f ? 0.5f : absorption);
@@ -333,6 +389,13 @@ int svo_shade_translucent(const svo_camera *cam, const svo_shade_params *p, floa
 {
     if (!behind_dev || !(absorption >= 0.0f)) { set_error("svo_shade_translucent: bad argument"); return SVO_ERR_INVALID_ARG; }
     return shade_impl(cam, p, x0, y0, w, h, surface_dev, rgba_dev, stream, 2, behind_dev, absorption);
+}
+
+int svo_shade_textured(const svo_camera *cam, const svo_shade_params *p, const svo_atlas *atlas, int x0, int y0, int w, int h,
+                       const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, float *rgba_dev, void *stream)
+{
+    if (!atlas || !atlas->diffuse_dev || atlas->width <= 0 || atlas->height <= 0 || !voxels_dev) { set_error("svo_shade_textured: bad argument"); return SVO_ERR_INVALID_ARG; }
+    return shade_impl(cam, p, x0, y0, w, h, gbuffer_dev, rgba_dev, stream, 3, voxels_dev, 0.0f, atlas);
 }
 
 } // extern "C"

@@ -12,6 +12,8 @@
 //   svo::World::modify(i, ...)       <- World::modify          src/World.cpp:268-274
 //   svo::World::index / index_float  <- src/World.cpp:288-293,323-332
 //   svo::World::locate(points, ...)  <- traverse over a point list (svo_world_locate)   src/Traverse.cpp:34-48
+//   svo::World::hit_voxels(...)      <- hit.bmin / hit.size of fragment main (svo_hit_voxels)   shaders/World.Fragment.glsl:168-172
+//   svo::World::hit_uv / shade_textured  <- leafUV, texture(Diffuse / Specular, uv) (svo_hit_uv, svo_shade_textured)   shaders/World.Fragment.glsl:5-15,178-182
 //   svo::World::deinit()             <- World::deinit          src/World.cpp:129-151
 //   svo::chunkmarch(alpha,beta,world,&sigma) <- chunkmarch     src/Traverse.cpp:127-171
 //
@@ -187,6 +189,27 @@ public:
         p.semantics = semantics;
         p.see_through = see_through;
         check(svo_world_locate(world_, points_dev, n, &p, out_dev, stream), "World::locate");
+    }
+
+    // The voxel box of each of n G-buffer records (svo_hit_voxels: hit.bmin / hit.size, shaders/World.Fragment.glsl:168-172) into out_dev;
+    // all zero for a record without a usable hit.  What the edit cursor is placed from (src/Main.cpp:317,340-367) and what leafUV needs.
+    void hit_voxels(const svo_hit *gbuffer_dev, int64_t n, svo_voxel *out_dev, void *stream = nullptr)
+    {
+        check(svo_hit_voxels(world_, gbuffer_dev, n, out_dev, stream), "World::hit_voxels");
+    }
+
+    // leafUV (svo_hit_uv; shaders/World.Fragment.glsl:5-15) of the rectangle draw() filled, from its records and their boxes; uv_dev is [w*h][2].
+    void hit_uv(const svo_camera &cam, int x0, int y0, int w, int h, const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, float *uv_dev,
+                void *stream = nullptr) const
+    {
+        check(svo_hit_uv(&cam, semantics == SVO_SEMANTICS_GLSL ? 1.0f / 4096.0f : 0.0f, x0, y0, w, h, gbuffer_dev, voxels_dev, uv_dev, stream), "World::hit_uv");
+    }
+
+    // The fragment shader's colour with the caller's atlas as albedo (svo_shade_textured; shaders/World.Fragment.glsl:178-190).
+    void shade_textured(const svo_camera &cam, const svo_shade_params &p, const svo_atlas &atlas, int x0, int y0, int w, int h,
+                        const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, float *rgba_dev, void *stream = nullptr) const
+    {
+        check(svo_shade_textured(&cam, &p, &atlas, x0, y0, w, h, gbuffer_dev, voxels_dev, rgba_dev, stream), "World::shade_textured");
     }
 
     // World::modify(i, tree delta, twig delta): re-send an edited chunk (Ocdelta ranges, src/Octree.h:47-54).
