@@ -42,6 +42,8 @@
  *   svo_trace_params.see_through <- the `ignore` material of treemarch / twigmarch   shaders/Chunkmarch.glsl:190-191,240-241,280
  *   svo_trace_translucent <- the second march from a translucent hit   shaders/ParallaxAlpha.Fragment.glsl:141-199,276-335
  *   svo_shade_translucent <- its blend by the path length through the liquid   shaders/ParallaxAlpha.Fragment.glsl:226-234,315-323
+ *   svo_shade_sky        <- Skybox::draw behind the world (src/Main.cpp:227)   src/Skybox.cpp, shaders/Skybox.*.glsl
+ *   svo_frame_rgba8      <- the RGBA8 colour attachment and its alpha of 1     src/GBuffer.cpp, shaders/GBuffer.Fragment.glsl
  *   svo_trace_local_shadows <- (a departure: the reference gives the directional light's shadow term to all three lights,
  *                           shaders/World.Fragment.glsl:186-190) one occlusion ray per hit towards the point light and the spotlight
  *
@@ -88,7 +90,8 @@ extern "C" {
                                           svo_trace_local_shadows and SVO_LOCAL_SHADOWS / SVO_SHADOWED_POINT / SVO_SHADOWED_SPOT,
                                           svo_trace_segments,
                                           svo_world_locate and svo_voxel,
-                                          svo_hit_voxels, svo_hit_uv, svo_shade_textured and svo_atlas */
+                                          svo_hit_voxels, svo_hit_uv, svo_shade_textured and svo_atlas,
+                                          svo_shade_sky, svo_sky and svo_frame_rgba8 */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -579,6 +582,49 @@ int svo_shade_textured(const svo_camera *cam, const svo_shade_params *p, const s
  * 1 / absorption.  A pixel whose behind record misses is C_s; a pixel without SVO_SEE_THROUGH is exactly what svo_shade writes. */
 int svo_shade_translucent(const svo_camera *cam, const svo_shade_params *p, float absorption, int x0, int y0, int w, int h,
                           const svo_hit *surface_dev, const svo_hit *behind_dev, float *rgba_dev, void *stream);
+
+/* The skybox behind the misses (src/Skybox.cpp, shaders/Skybox.*.glsl; drawn at depth 1 behind everything, src/Main.cpp:227), over an
+ * image that svo_shade, svo_shade_packed, svo_shade_translucent or svo_shade_textured has already written for the same rectangle.
+ * Exactly one of gbuffer_dev (the w*h 32-byte records) and packed_dev (svo_gbuffer_pack's 8-byte records) is non-NULL; for a
+ * translucent frame pass the surface records.  A pixel is a sky pixel iff its record lacks SVO_HIT_FLAG - exactly the set svo_shade
+ * writes as {0,0,0,1}.  A sky pixel gets its r, g and b replaced; its depth float is not written (it stays 1, the skybox's xyww
+ * depth); every other pixel, and everything outside w*h pixels, is not written at all.
+ * The cube map is the caller's: six size x size RGB8 images on the device, rows tightly packed, row 0 at t = 0 (as glTexImage2D takes
+ * them), in the order of GL_TEXTURE_CUBE_MAP_POSITIVE_X + i: +X, -X, +Y, -Y, +Z, -Z - the reference's right, left, top, bottom, front,
+ * back (src/Skybox.cpp:15-23,45).  Every operation below is in float and separately rounded, divisions are IEEE:
+ *   d        the pixel's direction exactly as the march forms it (svo_camera above).  The reference interpolates the normalised corners
+ *            of a rasterised cube instead: a departure a per-pixel renderer has to make.
+ *   axis     ax, ay, az = |d.x|, |d.y|, |d.z|; X is the major axis if ax >= ay && ax >= az, otherwise Y if ay >= az, otherwise Z; ma is
+ *            that magnitude.  !(ma > 0) - a zero or NaN direction - leaves the pixel as it is.
+ *   face     the OpenGL cube-map table; the positive face unless the major component is < 0:
+ *              +X: sc = -d.z, tc = -d.y    -X: sc =  d.z, tc = -d.y
+ *              +Y: sc =  d.x, tc =  d.z    -Y: sc =  d.x, tc = -d.z
+ *              +Z: sc =  d.x, tc = -d.y    -Z: sc = -d.x, tc = -d.y
+ *            s = (sc / ma + 1) * 0.5, t = (tc / ma + 1) * 0.5.
+ *   texel    T(x, y) = image[(y * size + x) * 3 ..] of the chosen face, a byte b decoding to (float)b / 255.0f - no gamma: the
+ *            reference draws the sky with GL_FRAMEBUFFER_SRGB off.
+ *   SVO_SKY_NEAREST   x = min(max((int)floor(s * size), 0), size - 1), y likewise from t; the colour is T(x, y).
+ *   SVO_SKY_LINEAR    (the reference, src/Skybox.cpp:49-50; CLAMP_TO_EDGE within the face - it does not enable seamless cube maps)
+ *            u = s * size - 0.5f, i = floor(u), a = u - i, xl = clamp((int)i, 0, size - 1), xr = clamp((int)i + 1, 0, size - 1);
+ *            v, j, b, yl, yr likewise from t; per channel top = T(xl,yl) + (T(xr,yl) - T(xl,yl)) * a,
+ *            bot = T(xl,yr) + (T(xr,yr) - T(xl,yr)) * a, c = top + (bot - top) * b - a face of one colour comes out as exactly that colour.
+ * A NULL cam, sky, rgba_dev or face pointer, size <= 0, an unknown filter, both record pointers given or neither, a negative
+ * rectangle, a camera without an image size: SVO_ERR_INVALID_ARG, settled before any device work.  w*h == 0 is SVO_OK.  Takes no
+ * world; asynchronous on `stream`. */
+enum { SVO_SKY_LINEAR = 0, SVO_SKY_NEAREST = 1 };
+typedef struct svo_sky {
+    const uint8_t *faces_dev[6];    /* +X, -X, +Y, -Y, +Z, -Z */
+    int32_t size;                   /* faces are size x size RGB8 */
+    int32_t filter;                 /* SVO_SKY_LINEAR: the reference */
+} svo_sky;
+int svo_shade_sky(const svo_camera *cam, const svo_sky *sky, int x0, int y0, int w, int h,
+                  const svo_hit *gbuffer_dev, const uint64_t *packed_dev, float *rgba_dev, void *stream);
+
+/* n float4 pixels {r, g, b, depth} to the RGBA8 of the reference's colour attachment (src/GBuffer.cpp): memory order R, G, B, A, one
+ * 4-byte store per pixel.  Per colour channel c: NaN or c <= 0 gives 0, c >= 1 gives 255, anything else (uint8_t)(int)(c * 255.0f + 0.5f).
+ * A is 255 for every pixel (shaders/GBuffer.Fragment.glsl:10); the depth float does not enter the colour.
+ * n < 0, or a NULL pointer with n > 0: SVO_ERR_INVALID_ARG; n == 0: SVO_OK.  Asynchronous on `stream`. */
+int svo_frame_rgba8(const float *rgba_dev, int64_t n, uint32_t *out_dev, void *stream);
 
 /* Number of rays the last launch on this world actually marched (primary + shadow, all frames of a
  * svo_trace_frames launch; a multi-frame call served by a kernel other than SVO_KERNEL_STACK is one launch per

@@ -13,6 +13,8 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     World.locate / locate_points              <- traverse               src/Traverse.cpp:34-48 (the voxel under each point)
     World.hit_voxels / hit_boxes              <- hit.bmin / hit.size of fragment main   shaders/World.Fragment.glsl:168-172
     hit_uv, shade_textured, Atlas             <- leafUV, texture(Diffuse / Specular, uv)   shaders/World.Fragment.glsl:5-15,178-182
+    shade_sky, Sky                            <- Skybox::draw behind the world             src/Skybox.cpp, shaders/Skybox.*.glsl
+    frame_rgba8                               <- the RGBA8 colour attachment               src/GBuffer.cpp, shaders/GBuffer.Fragment.glsl:10
 
 There is NO CPU fallback: if libsvo_amd.so is missing the import raises, and every device call
 raises SvoError when HIP reports no device.
@@ -56,6 +58,7 @@ LOCAL_SHADOWS, SHADOWED_POINT, SHADOWED_SPOT = 1 << 5, 1 << 6, 1 << 7     # svo_
 NORMAL_CUBE, NORMAL_FACE = 0, 1
 SEMANTICS_CPU, SEMANTICS_GLSL = 0, 1
 CELL_NONE = 0xFF
+SKY_LINEAR, SKY_NEAREST = 0, 1                           # svo_sky.filter
 
 HIT_DTYPE = np.dtype([("t", "<f4"), ("normal", "<f4", (3,)), ("material", "<u2"), ("flags", "<u2"),
                       ("chunk", "<u4"), ("node", "<u4"), ("cell", "<u4")])
@@ -129,6 +132,18 @@ class Atlas(C.Structure):
     _fields_ = [("diffuse_dev", C.c_void_p), ("specular_dev", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
 
 
+class Sky(C.Structure):
+    """svo_sky: six size x size RGB8 cube-map faces on the device (+X, -X, +Y, -Y, +Z, -Z; rows tightly packed, row 0 at t = 0).
+    Sky(face_ptrs, size, filter): face_ptrs are six device pointers (None = NULL)."""
+    _fields_ = [("faces_dev", C.c_void_p * 6), ("size", C.c_int32), ("filter", C.c_int32)]
+
+    def __init__(self, faces=(None,) * 6, size: int = 0, filter: int = SKY_LINEAR):
+        super().__init__()
+        for i, ptr in enumerate(faces):
+            self.faces_dev[i] = ptr
+        self.size, self.filter = int(size), int(filter)
+
+
 class WorldInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("depth", C.c_int32), ("chunksize", C.c_int32),
                 ("chunkcoordmin", C.c_int32 * 3), ("uploaded_device", C.c_int32),
@@ -144,7 +159,7 @@ MAX_FRAMES = 16                     # SVO_MAX_FRAMES
 ABI_SYMBOLS = [
     "svo_world_generate", "svo_world_create", "svo_world_info_get", "svo_world_chunk", "svo_world_destroy",
     "svo_world_index_float", "svo_world_index", "svo_world_locate", "svo_hit_voxels", "svo_hit_uv", "svo_shade_textured", "svo_world_upload", "svo_world_update",
-    "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
+    "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_device_count", "svo_device_alloc", "svo_device_free", "svo_device_cache_trim", "svo_memcpy_h2d", "svo_memcpy_d2h",
     "svo_stream_synchronize", "svo_last_error", "svo_abi_version",
@@ -194,6 +209,8 @@ lib.svo_world_locate.argtypes = [_P, _P, C.c_int64, C.POINTER(TraceParams), _P, 
 lib.svo_hit_voxels.argtypes = [_P, _P, C.c_int64, _P, _P]
 lib.svo_hit_uv.argtypes = [C.POINTER(Camera), C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
 lib.svo_shade_textured.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams), C.POINTER(Atlas), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
+lib.svo_shade_sky.argtypes = [C.POINTER(Camera), C.POINTER(Sky), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
+lib.svo_frame_rgba8.argtypes = [_P, C.c_int64, _P, _P]
 lib.svo_trace_last_ray_count.argtypes = [_P, _P, C.POINTER(C.c_uint64)]
 lib.svo_device_count.restype = C.c_int
 lib.svo_device_alloc.argtypes = [C.c_size_t]
@@ -385,6 +402,19 @@ def shade_textured(cam: Camera, params: ShadeParams, atlas: Atlas, rect, gbuffer
     _check(lib.svo_shade_textured(C.byref(cam) if cam is not None else None, C.byref(params) if params is not None else None,
                                   C.byref(atlas) if atlas is not None else None, x0, y0, w, h, gbuffer_ptr, voxels_ptr, rgba_ptr, stream),
            "svo_shade_textured")
+
+
+def shade_sky(cam: Camera, sky: Sky, rect, rgba_ptr: int, gbuffer_ptr: Optional[int] = None, packed_ptr: Optional[int] = None, stream: int = 0):
+    """svo_shade_sky: r, g, b of every pixel whose record lacks HIT_FLAG replaced by the cube map's colour along the pixel's ray, over an
+    image a shade call has written; the records are given as gbuffer_ptr (32-byte) or packed_ptr (gbuffer_pack's), exactly one of them."""
+    x0, y0, w, h = rect
+    _check(lib.svo_shade_sky(C.byref(cam) if cam is not None else None, C.byref(sky) if sky is not None else None, x0, y0, w, h,
+                             gbuffer_ptr, packed_ptr, rgba_ptr, stream), "svo_shade_sky")
+
+
+def frame_rgba8(rgba_ptr: int, n: int, out_ptr: int, stream: int = 0):
+    """svo_frame_rgba8: n float4 pixels to RGBA8 (4 bytes a pixel, memory order R, G, B, A; alpha 255)."""
+    _check(lib.svo_frame_rgba8(rgba_ptr, n, out_ptr, stream), "svo_frame_rgba8")
 
 
 def see_through_chunk(chunk: dict, material: int) -> dict:

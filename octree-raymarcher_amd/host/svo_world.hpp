@@ -14,6 +14,7 @@
 //   svo::World::locate(points, ...)  <- traverse over a point list (svo_world_locate)   src/Traverse.cpp:34-48
 //   svo::World::hit_voxels(...)      <- hit.bmin / hit.size of fragment main (svo_hit_voxels)   shaders/World.Fragment.glsl:168-172
 //   svo::World::hit_uv / shade_textured  <- leafUV, texture(Diffuse / Specular, uv) (svo_hit_uv, svo_shade_textured)   shaders/World.Fragment.glsl:5-15,178-182
+//   svo::World::shade_sky / frame_rgba8  <- Skybox::draw and the RGBA8 colour attachment (svo_shade_sky, svo_frame_rgba8)   src/Skybox.cpp, src/GBuffer.cpp
 //   svo::World::deinit()             <- World::deinit          src/World.cpp:129-151
 //   svo::chunkmarch(alpha,beta,world,&sigma) <- chunkmarch     src/Traverse.cpp:127-171
 //
@@ -210,6 +211,20 @@ public:
                         const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, float *rgba_dev, void *stream = nullptr) const
     {
         check(svo_shade_textured(&cam, &p, &atlas, x0, y0, w, h, gbuffer_dev, voxels_dev, rgba_dev, stream), "World::shade_textured");
+    }
+
+    // The skybox behind the misses (svo_shade_sky; src/Skybox.cpp, src/Main.cpp:227) over an image a shade call has written for the same
+    // rectangle: exactly one of gbuffer_dev and packed_dev names the rectangle's records.  Hit pixels and every depth are left alone.
+    void shade_sky(const svo_camera &cam, const svo_sky &sky, int x0, int y0, int w, int h, const svo_hit *gbuffer_dev, const uint64_t *packed_dev,
+                   float *rgba_dev, void *stream = nullptr) const
+    {
+        check(svo_shade_sky(&cam, &sky, x0, y0, w, h, gbuffer_dev, packed_dev, rgba_dev, stream), "World::shade_sky");
+    }
+
+    // n float4 pixels to the RGBA8 of the reference's colour attachment (svo_frame_rgba8; src/GBuffer.cpp, alpha 255).
+    void frame_rgba8(const float *rgba_dev, int64_t n, uint32_t *out_dev, void *stream = nullptr) const
+    {
+        check(svo_frame_rgba8(rgba_dev, n, out_dev, stream), "World::frame_rgba8");
     }
 
     // World::modify(i, tree delta, twig delta): re-send an edited chunk (Ocdelta ranges, src/Octree.h:47-54).
