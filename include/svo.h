@@ -44,6 +44,10 @@
  *   svo_shade_translucent <- its blend by the path length through the liquid   shaders/ParallaxAlpha.Fragment.glsl:226-234,315-323
  *   svo_shade_sky        <- Skybox::draw behind the world (src/Main.cpp:227)   src/Skybox.cpp, shaders/Skybox.*.glsl
  *   svo_frame_rgba8      <- the RGBA8 colour attachment and its alpha of 1     src/GBuffer.cpp, shaders/GBuffer.Fragment.glsl
+ *   svo_cursor_place     <- computeTarget + ImaginaryCube::position      src/Main.cpp:314-319, src/ImaginaryCube.cpp:59-62
+ *   svo_shade_boxes      <- ImaginaryCube::draw and the lights' marker cubes over the finished image (src/Main.cpp:223-225)
+ *                           src/ImaginaryCube.cpp:64-87, shaders/Imag.Fragment.glsl, src/Light.cpp:141-155, shaders/Light.Fragment.glsl
+ *   svo_world_edit_cube  <- modify(): one cube to every chunk that holds one of its corners   src/Main.cpp:321-368
  *   svo_trace_local_shadows <- (a departure: the reference gives the directional light's shadow term to all three lights,
  *                           shaders/World.Fragment.glsl:186-190) one occlusion ray per hit towards the point light and the spotlight
  *
@@ -91,7 +95,8 @@ extern "C" {
                                           svo_trace_segments,
                                           svo_world_locate and svo_voxel,
                                           svo_hit_voxels, svo_hit_uv, svo_shade_textured and svo_atlas,
-                                          svo_shade_sky, svo_sky and svo_frame_rgba8 */
+                                          svo_shade_sky, svo_sky and svo_frame_rgba8,
+                                          svo_cursor_place, svo_shade_boxes, svo_box and svo_world_edit_cube */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -338,6 +343,24 @@ int svo_world_shift(svo_world *, const int offset[3]);
  * SVO_ERR_NOT_UPLOADED on a world that is not resident. */
 enum { SVO_EDIT_BUILD = 0, SVO_EDIT_DESTROY = 1, SVO_EDIT_REPLACE = 2 };
 int svo_world_edit_box(svo_world *, int chunk, int op, const float lo[3], const float hi[3], uint16_t material);
+
+/* modify() (src/Main.cpp:321-338) with destroy / build / replace (:340-367): the cube [bmin, bmin + size] goes to every chunk that holds
+ * one of its eight corners - what pressing `x` / `z` / `c` does with the edit cursor (svo_cursor_place's box: bmin and size as read back
+ * from it).  For i = 0..7, every operation in float and separately rounded:
+ *   p = bmin + vec3(bool(i & 4), bool(i & 2), bool(i & 1)) * size;
+ *   j = World::index(World::index_float(p))   (src/World.cpp:288-293,323-332);
+ *   the corner is dropped unless isInsideCube(p, chunk[j].position, chunk[j].position + chunksize) (closed): a corner outside the
+ *   world wraps to a chunk that does not hold it;
+ *   otherwise chunk j takes svo_world_edit_box(j, op, bmin, bmin + size, material).
+ * Each distinct chunk is edited ONCE, in the order of its first appearance; the reference edits once per corner, up to eight times on
+ * one chunk.  The two are equal because a repeated Ocroot::build / destroy / replace of the same box leaves the pools as they are,
+ * index for index and in size (tests/test_boxes_cpu.py checks this against the CPU oracle for all three operations).
+ * chunks_out[0..*nchunks_out) receives those chunks in that order; both may be NULL.  They are written before the first edit.
+ * The corner rule's limitation is the reference's: a cube wider than a chunk skips the chunks that lie between its corners.
+ * Returns the largest positive status of the edits (SVO_OK_LITERAL_ONLY) or the first negative one; the edits stop at a failing chunk,
+ * and AN EDIT APPLIED BEFORE THE FAILING ONE STAYS APPLIED.  A NULL world or bmin, !(size > 0), a NaN or infinite bmin / size or an
+ * unknown op: SVO_ERR_INVALID_ARG; then a world that is not resident: SVO_ERR_NOT_UPLOADED - both before anything changes or is written. */
+int svo_world_edit_cube(svo_world *, int op, const float bmin[3], float size, uint16_t material, int chunks_out[8], int *nchunks_out);
 
 /* Ocroot::defragcopy (src/Octree.cpp:445-614) followed by World::modify with realloc (src/World.cpp:268-274) on chunk `chunk`:
  * the chunk is rebuilt from its root into fresh pools - depth-first, root at 0, blocks at 1 + 8k - so that what no BRANCH reaches
@@ -625,6 +648,68 @@ int svo_shade_sky(const svo_camera *cam, const svo_sky *sky, int x0, int y0, int
  * A is 255 for every pixel (shaders/GBuffer.Fragment.glsl:10); the depth float does not enter the colour.
  * n < 0, or a NULL pointer with n > 0: SVO_ERR_INVALID_ARG; n == 0: SVO_OK.  Asynchronous on `stream`. */
 int svo_frame_rgba8(const float *rgba_dev, int64_t n, uint32_t *out_dev, void *stream);
+
+/* ---- the edit cursor and the light markers: cubes over the finished image ----------------------------------
+ * One overlay record, 48 bytes, on the device.  The reference has four: the cursor cube (ImagCube: translucent grey, black edges) and one
+ * solid marker cube at each light (src/Main.cpp:223-225). */
+enum { SVO_BOX_SOLID = 0, SVO_BOX_CURSOR = 1, SVO_BOX_HIDDEN = 1u << 8 };
+#define SVO_MAX_BOXES 64
+typedef struct svo_box {
+    float    bmin[3];
+    float    size;        /* cube edge (ImaginaryCube's scale is a vec3 with three equal components) */
+    float    color[3];
+    float    alpha;
+    uint32_t style;       /* SVO_BOX_SOLID / SVO_BOX_CURSOR in bits 0-7, | SVO_BOX_HIDDEN */
+    uint32_t _pad[3];
+} svo_box;
+
+/* computeTarget (src/Main.cpp:314-319) + ImaginaryCube::position (src/ImaginaryCube.cpp:59-62) without a read-back: one tiny launch.
+ * record_dev is the record a march wrote for the ray (origin, dir): svo_trace_rays with one ray, or the address of a pixel's record
+ * together with that pixel's ray.  If the record has SVO_HIT_FLAG and no SVO_ERR_FLAG - every operation separately rounded:
+ *   sigma = origin + dir * t   per component (src/Traverse.cpp:161; under SVO_SEMANTICS_CPU svo_hit.t is that t),
+ *   box_dev->bmin = sigma - size * 0.5f, box_dev->size = size, SVO_BOX_HIDDEN is cleared.
+ * Otherwise SVO_BOX_HIDDEN is set (imag.real == false) and bmin / size are left alone.  color, alpha and the low style bits are never
+ * written: the caller sets them once.  A NULL pointer or !(size > 0): SVO_ERR_INVALID_ARG before any device work.  Asynchronous on
+ * `stream`: issue it behind the march on the same stream, and svo_shade_boxes behind it. */
+int svo_cursor_place(const float origin[3], const float dir[3], const svo_hit *record_dev,
+                     float size, svo_box *box_dev, void *stream);
+
+/* The boxes over the shaded image, depth-tested against the world (ImaginaryCube::draw, src/ImaginaryCube.cpp:64-87,
+ * shaders/Imag.Fragment.glsl; Light::draw, src/Light.cpp:141-155, shaders/Light.Fragment.glsl): over an image that svo_shade* has written
+ * for the same rectangle, whose fourth float is the depth buffer.  If the frame has a sky, call it AFTER svo_shade_sky: that call picks
+ * its pixels by the record's flag, not by depth, and would paint over a box drawn before it (the reference draws the sky at depth 1
+ * with GL_LEQUAL for the same effect).
+ * near_plane / far_plane of 0 mean 0.125 / 8192, as in svo_shade_params: pass the shade call's.  Per pixel, (o, d) is its ray exactly
+ * as the march and svo_shade_sky form it, D its depth float.  The boxes go in list order (GL draws in call order); a box with
+ * SVO_BOX_HIDDEN or !(size > 0) is skipped.  Every operation is in float and separately rounded, every division IEEE:
+ *   slabs     bmax = bmin + size.  Per axis a with d.a != 0: t0 = (bmin.a - o.a) / d.a, t1 = (bmax.a - o.a) / d.a; the near value is the
+ *             smaller and belongs to the min face if t0 <= t1 (to the max face otherwise), the far value is the other, on the other
+ *             face.  With d.a == 0 the box is missed if o.a < bmin.a || o.a > bmax.a, and the axis bounds nothing otherwise.
+ *             tnear = the largest near value, tfar = the smallest far value, in both the first axis in x, y, z order winning ties.
+ *             The box is missed unless tnear <= tfar.
+ *   fragments up to two: the entry face at tnear if tnear > 0, the exit face at tfar if tfar > 0 (culling is off,
+ *             src/ImaginaryCube.cpp:71), processed in the face order of the reference's index buffer (CUBE_INDICES,
+ *             src/Parallax.cpp:25-38): -Z, -X, +Z, +X, -Y, +Y.
+ *   depth     a fragment at t has f = (1 / t - 1 / near) / (1 / far - 1 / near): gl_FragDepth's form in the world shader with the
+ *             distance along the unit ray.  It passes iff f < D (GL_LESS; a NaN fails), and a passing fragment sets D = f (depth
+ *             writes are on).  So an exit face drawn before its entry face shows through it, one drawn after its entry face is
+ *             discarded - as in the reference.  There is no clipping against the planes.
+ *   colour    SVO_BOX_SOLID (and every other value of the low style byte): {color, alpha}.  SVO_BOX_CURSOR (Imag.Fragment.glsl): with
+ *             p = o + d * t the two in-face coordinates are c = (p - bmin) / size (the face axis' own coordinate is exactly 0 or 1 and
+ *             always counts as an edge): {0, 0, 0, 1} if either is <= 1/64 or >= 1 - 1/64, {color, alpha} otherwise (the reference: 0.8
+ *             and 0.2).
+ *   blend     rgb = src * a + dst * (1 - a) per channel: GL_SRC_ALPHA, GL_ONE_MINUS_SRC_ALPHA, the state src/Text.cpp:135 leaves for
+ *             every frame after the first; the reference's frame one has the GL default (GL_ONE, GL_ZERO) instead.
+ *   stores    a pixel no fragment passed on is not written at all, neither is anything outside the w*h pixels; a pixel a fragment
+ *             passed on gets all four floats (r, g, b, D) in one store.
+ * Two departures from the reference: the direction is the pinhole ray's, not a rasteriser's interpolant (as svo_shade_sky); and the
+ * rasterised cubes get GL's projective depth while the world shader writes the distance form - here both are in the world's form, so that
+ * a box and the terrain are compared in one measure.
+ * A NULL cam / rgba_dev, a NULL boxes_dev with nboxes > 0, nboxes < 0 or > SVO_MAX_BOXES, a negative rectangle, a camera without an
+ * image size, a negative (or NaN) plane: SVO_ERR_INVALID_ARG, settled before any device work.  nboxes == 0 or w*h == 0: SVO_OK, nothing
+ * written.  rgba_dev is 16-byte aligned, as for svo_shade.  Takes no world; asynchronous on `stream`. */
+int svo_shade_boxes(const svo_camera *cam, const svo_box *boxes_dev, int nboxes, float near_plane, float far_plane,
+                    int x0, int y0, int w, int h, float *rgba_dev, void *stream);
 
 /* Number of rays the last launch on this world actually marched (primary + shadow, all frames of a
  * svo_trace_frames launch; a multi-frame call served by a kernel other than SVO_KERNEL_STACK is one launch per

@@ -15,6 +15,8 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     hit_uv, shade_textured, Atlas             <- leafUV, texture(Diffuse / Specular, uv)   shaders/World.Fragment.glsl:5-15,178-182
     shade_sky, Sky                            <- Skybox::draw behind the world             src/Skybox.cpp, shaders/Skybox.*.glsl
     frame_rgba8                               <- the RGBA8 colour attachment               src/GBuffer.cpp, shaders/GBuffer.Fragment.glsl:10
+    cursor_place, shade_boxes, Box            <- computeTarget, ImaginaryCube / Light::draw   src/Main.cpp:314-319, src/ImaginaryCube.cpp:59-87
+    World.edit_cube                           <- modify()                                  src/Main.cpp:321-368
 
 There is NO CPU fallback: if libsvo_amd.so is missing the import raises, and every device call
 raises SvoError when HIP reports no device.
@@ -59,6 +61,10 @@ NORMAL_CUBE, NORMAL_FACE = 0, 1
 SEMANTICS_CPU, SEMANTICS_GLSL = 0, 1
 CELL_NONE = 0xFF
 SKY_LINEAR, SKY_NEAREST = 0, 1                           # svo_sky.filter
+BOX_SOLID, BOX_CURSOR, BOX_HIDDEN = 0, 1, 1 << 8         # svo_box.style
+MAX_BOXES = 64                                           # SVO_MAX_BOXES
+BOX_DTYPE = np.dtype([("bmin", "<f4", (3,)), ("size", "<f4"), ("color", "<f4", (3,)), ("alpha", "<f4"), ("style", "<u4"), ("_pad", "<u4", (3,))])
+assert BOX_DTYPE.itemsize == 48
 
 HIT_DTYPE = np.dtype([("t", "<f4"), ("normal", "<f4", (3,)), ("material", "<u2"), ("flags", "<u2"),
                       ("chunk", "<u4"), ("node", "<u4"), ("cell", "<u4")])
@@ -144,6 +150,12 @@ class Sky(C.Structure):
         self.size, self.filter = int(size), int(filter)
 
 
+class Box(C.Structure):
+    """svo_box: one overlay cube of svo_shade_boxes (48 bytes; BOX_DTYPE is its numpy twin)."""
+    _fields_ = [("bmin", C.c_float * 3), ("size", C.c_float), ("color", C.c_float * 3), ("alpha", C.c_float), ("style", C.c_uint32),
+                ("_pad", C.c_uint32 * 3)]
+
+
 class WorldInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("depth", C.c_int32), ("chunksize", C.c_int32),
                 ("chunkcoordmin", C.c_int32 * 3), ("uploaded_device", C.c_int32),
@@ -159,7 +171,7 @@ MAX_FRAMES = 16                     # SVO_MAX_FRAMES
 ABI_SYMBOLS = [
     "svo_world_generate", "svo_world_create", "svo_world_info_get", "svo_world_chunk", "svo_world_destroy",
     "svo_world_index_float", "svo_world_index", "svo_world_locate", "svo_hit_voxels", "svo_hit_uv", "svo_shade_textured", "svo_world_upload", "svo_world_update",
-    "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
+    "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_edit_cube", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_cursor_place", "svo_shade_boxes", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_device_count", "svo_device_alloc", "svo_device_free", "svo_device_cache_trim", "svo_memcpy_h2d", "svo_memcpy_d2h",
     "svo_stream_synchronize", "svo_last_error", "svo_abi_version",
@@ -169,6 +181,7 @@ _P = C.c_void_p
 lib.svo_last_error.restype = C.c_char_p
 lib.svo_abi_version.restype = C.c_int
 lib.svo_world_edit_box.argtypes = [_P, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint16]
+lib.svo_world_edit_cube.argtypes = [_P, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_uint16, C.POINTER(C.c_int), C.POINTER(C.c_int)]
 lib.svo_world_compact.argtypes = [_P, C.c_int]
 lib.svo_world_compact.restype = C.c_int
 lib.svo_world_coarsen.argtypes = [_P, C.c_int]
@@ -211,6 +224,8 @@ lib.svo_hit_uv.argtypes = [C.POINTER(Camera), C.c_float, C.c_int, C.c_int, C.c_i
 lib.svo_shade_textured.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams), C.POINTER(Atlas), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
 lib.svo_shade_sky.argtypes = [C.POINTER(Camera), C.POINTER(Sky), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
 lib.svo_frame_rgba8.argtypes = [_P, C.c_int64, _P, _P]
+lib.svo_cursor_place.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), _P, C.c_float, _P, _P]
+lib.svo_shade_boxes.argtypes = [C.POINTER(Camera), _P, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]
 lib.svo_trace_last_ray_count.argtypes = [_P, _P, C.POINTER(C.c_uint64)]
 lib.svo_device_count.restype = C.c_int
 lib.svo_device_alloc.argtypes = [C.c_size_t]
@@ -417,6 +432,21 @@ def frame_rgba8(rgba_ptr: int, n: int, out_ptr: int, stream: int = 0):
     _check(lib.svo_frame_rgba8(rgba_ptr, n, out_ptr, stream), "svo_frame_rgba8")
 
 
+def cursor_place(origin, direction, record_ptr: int, size: float, box_ptr: int, stream: int = 0):
+    """svo_cursor_place: the cursor cube of edge `size` centred on the hit of the ray (origin, direction) whose record the march wrote at
+    record_ptr, into the svo_box at box_ptr (bmin, size, BOX_HIDDEN only); a record without a usable hit hides the box."""
+    vec = [None if v is None else (C.c_float * 3)(*[float(c) for c in v]) for v in (origin, direction)]
+    _check(lib.svo_cursor_place(vec[0], vec[1], record_ptr, size, box_ptr, stream), "svo_cursor_place")
+
+
+def shade_boxes(cam: Camera, boxes_ptr: int, nboxes: int, rect, rgba_ptr: int, near_plane: float = 0.0, far_plane: float = 0.0, stream: int = 0):
+    """svo_shade_boxes: nboxes svo_box records (BOX_DTYPE on the device) blended in list order over the image a shade call (and
+    shade_sky) wrote, depth-tested against its depth floats; planes 0 = 0.125 / 8192."""
+    x0, y0, w, h = rect
+    _check(lib.svo_shade_boxes(C.byref(cam) if cam is not None else None, boxes_ptr, nboxes, near_plane, far_plane, x0, y0, w, h, rgba_ptr, stream),
+           "svo_shade_boxes")
+
+
 def see_through_chunk(chunk: dict, material: int) -> dict:
     """The chunk as a see-through march of `material` sees it: LEAF nodes of that material (offset & 0xFFFF) and brick cells
     holding it set to 0, the tree's shape unchanged.  Host numpy; what svo_trace_params.see_through is defined against."""
@@ -531,6 +561,14 @@ class World:
         """Ocroot::build / destroy / replace + World::modify on the device (svo_world_edit_box); op = EDIT_BUILD / EDIT_DESTROY / EDIT_REPLACE."""
         return _check(lib.svo_world_edit_box(self._h, int(chunk), int(op), (C.c_float * 3)(*[float(v) for v in lo]),
                                              (C.c_float * 3)(*[float(v) for v in hi]), C.c_uint16(int(material))), "svo_world_edit_box")
+
+    def edit_cube(self, op: int, bmin, size: float, material: int = 0):
+        """svo_world_edit_cube: the reference's modify() - the cube [bmin, bmin + size] to every chunk that holds one of its corners, each
+        once.  Returns (status, [chunks edited, in order])."""
+        chunks, n = (C.c_int * 8)(), C.c_int(0)
+        rc = _check(lib.svo_world_edit_cube(self._h, int(op), None if bmin is None else (C.c_float * 3)(*[float(v) for v in bmin]), float(size),
+                                            C.c_uint16(int(material)), chunks, C.byref(n)), "svo_world_edit_cube")
+        return rc, list(chunks[:n.value])
 
     def compact(self, chunk: int):
         """Ocroot::defragcopy + World::modify(realloc) (svo_world_compact): chunk rebuilt from its root, uniform bricks and blocks folded."""

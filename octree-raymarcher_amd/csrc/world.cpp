@@ -223,6 +223,45 @@ int svo_world_edit_box(svo_world *w, int chunk, int op, const float lo[3], const
     return edit_box_resident(*w, chunk, op, lo, hi, material);
 }
 
+int svo_world_edit_cube(svo_world *w, int op, const float bmin[3], float size, uint16_t material, int chunks_out[8], int *nchunks_out)
+{   // modify(), src/Main.cpp:321-338
+    bool ok = w && bmin && op >= SVO_EDIT_BUILD && op <= SVO_EDIT_REPLACE && size > 0.0f && std::isfinite(size);
+    for (int a = 0; ok && a < 3; ++a) ok = std::isfinite(bmin[a]) && std::isfinite(bmin[a] + size);
+    if (!ok) { set_error("svo_world_edit_cube: bad argument"); return SVO_ERR_INVALID_ARG; }
+    if (w->device < 0) { set_error("svo_world_edit_cube: the world is not uploaded"); return SVO_ERR_NOT_UPLOADED; }
+    const float cs = (float)w->chunksize;
+    int list[8], n = 0;
+    for (int i = 0; i < 8; ++i) {
+        const float p[3] = { bmin[0] + ((i & 4) ? 1.0f : 0.0f) * size, bmin[1] + ((i & 2) ? 1.0f : 0.0f) * size, bmin[2] + ((i & 1) ? 1.0f : 0.0f) * size };
+        int q[3];
+        bool held = true;
+        for (int a = 0; a < 3; ++a) {                       // World::index_float, src/World.cpp:323-332
+            float f = p[a] / cs;
+            if (f < 0.0f) f -= 1.0f;
+            if (!(std::fabs(f) < 2147483648.0f)) { held = false; f = 0.0f; }     // beyond every grid an int can place: no chunk holds it
+            q[a] = (int)f;
+        }
+        if (!held) continue;
+        const int j = chunk_index(q[0], q[1], q[2], w->width, w->height, w->depth);
+        const float *c = w->chunks[(size_t)j].position;
+        for (int a = 0; a < 3; ++a) held = held && p[a] >= c[a] && c[a] + cs >= p[a];      // isInsideCube, src/Traverse.cpp:18-23
+        if (!held) continue;
+        bool seen = false;
+        for (int k = 0; k < n; ++k) seen = seen || list[k] == j;
+        if (!seen) list[n++] = j;
+    }
+    if (chunks_out) for (int k = 0; k < n; ++k) chunks_out[k] = list[k];
+    if (nchunks_out) *nchunks_out = n;
+    const float hi[3] = { bmin[0] + size, bmin[1] + size, bmin[2] + size };
+    int status = SVO_OK;
+    for (int k = 0; k < n; ++k) {
+        const int rc = svo_world_edit_box(w, list[k], op, bmin, hi, material);
+        if (rc < 0) return rc;
+        if (rc > status) status = rc;
+    }
+    return status;
+}
+
 int svo_world_info_get(const svo_world *w, svo_world_info *o)
 {
     if (!w || !o) return SVO_ERR_INVALID_ARG;

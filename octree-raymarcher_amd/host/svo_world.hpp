@@ -15,6 +15,8 @@
 //   svo::World::hit_voxels(...)      <- hit.bmin / hit.size of fragment main (svo_hit_voxels)   shaders/World.Fragment.glsl:168-172
 //   svo::World::hit_uv / shade_textured  <- leafUV, texture(Diffuse / Specular, uv) (svo_hit_uv, svo_shade_textured)   shaders/World.Fragment.glsl:5-15,178-182
 //   svo::World::shade_sky / frame_rgba8  <- Skybox::draw and the RGBA8 colour attachment (svo_shade_sky, svo_frame_rgba8)   src/Skybox.cpp, src/GBuffer.cpp
+//   svo::World::cursor_place / shade_boxes / edit_cube  <- computeTarget, ImaginaryCube::draw, modify() (svo_cursor_place, svo_shade_boxes,
+//                                       svo_world_edit_cube)   src/Main.cpp:314-368, src/ImaginaryCube.cpp:59-87
 //   svo::World::deinit()             <- World::deinit          src/World.cpp:129-151
 //   svo::chunkmarch(alpha,beta,world,&sigma) <- chunkmarch     src/Traverse.cpp:127-171
 //
@@ -227,6 +229,19 @@ public:
         check(svo_frame_rgba8(rgba_dev, n, out_dev, stream), "World::frame_rgba8");
     }
 
+    // computeTarget + imag.position(sigma) (src/Main.cpp:314-319) from the record a march wrote for the ray (alpha, beta), on the device.
+    void cursor_place(vec3 alpha, vec3 beta, const svo_hit *record_dev, float size, svo_box *box_dev, void *stream = nullptr) const
+    {
+        const float a[3] = { alpha.x, alpha.y, alpha.z }, b[3] = { beta.x, beta.y, beta.z };
+        check(svo_cursor_place(a, b, record_dev, size, box_dev, stream), "World::cursor_place");
+    }
+    // imag.draw(mvp) and the lights' marker cubes (src/Main.cpp:223-225) over the shaded image, behind shade_sky.
+    void shade_boxes(const svo_camera &cam, const svo_box *boxes_dev, int nboxes, float near_plane, float far_plane, int x0, int y0, int w, int h,
+                     float *rgba_dev, void *stream = nullptr) const
+    {
+        check(svo_shade_boxes(&cam, boxes_dev, nboxes, near_plane, far_plane, x0, y0, w, h, rgba_dev, stream), "World::shade_boxes");
+    }
+
     // World::modify(i, tree delta, twig delta): re-send an edited chunk (Ocdelta ranges, src/Octree.h:47-54).
     void modify(int i, const svo_chunk_desc &edited, uint64_t tree_left, uint64_t tree_right, uint64_t twig_left, uint64_t twig_right, bool realloc_)
     {
@@ -238,6 +253,16 @@ public:
     void build(int i, vec3 cmin, vec3 cmax, uint16_t material) { edit(i, SVO_EDIT_BUILD, cmin, cmax, material, "World::build"); }
     void destroy(int i, vec3 cmin, vec3 cmax) { edit(i, SVO_EDIT_DESTROY, cmin, cmax, 0, "World::destroy"); }
     void replace(int i, vec3 cmin, vec3 cmax, uint16_t material) { edit(i, SVO_EDIT_REPLACE, cmin, cmax, material, "World::replace"); }
+
+    // destroy() / build() / replace() of src/Main.cpp:340-367 through modify() (:321-338): the cursor cube to every chunk that holds one of
+    // its corners (svo_world_edit_cube).  Returns the chunks edited.
+    std::vector<int> edit_cube(int op, vec3 bmin, float size, uint16_t material)
+    {
+        const float lo[3] = { bmin.x, bmin.y, bmin.z };
+        int chunks[8], n = 0;
+        check(svo_world_edit_cube(world_, op, lo, size, material, chunks, &n), "World::edit_cube");
+        return std::vector<int>(chunks, chunks + n);
+    }
 
     // World::shift(offset): slide the grid by one chunk (src/World.cpp:334-378).
     void shift(ivec3 offset)
