@@ -6,11 +6,7 @@
 // reciprocals: the face chosen at a box edge must not hang on 1 ulp).
 #include <hip/hip_runtime.h>
 
-#include <cstring>
-#include <string>
-
-#include "march.hip.h"
-#include "hip_own.h"
+#include "image_stage.hip.h"
 
 static_assert(sizeof(svo_box) == 48, "svo_box is 48 bytes");
 
@@ -20,8 +16,7 @@ namespace {
 constexpr int BOX_WORDS = sizeof(svo_box) / 4;
 
 struct BoxArgs {
-    FrameCam cam;
-    int32_t imgw, imgh, x0, y0, w, h;
+    PixelFrame frame;
     const uint32_t *boxes;                      // nboxes svo_box records
     int32_t nboxes;
     float inv_near, depth_range;                // 1 / near, 1 / far - 1 / near
@@ -45,9 +40,9 @@ __global__ __launch_bounds__(256) void k_shade_boxes(BoxArgs A)
     for (int i = (int)threadIdx.x; i < A.nboxes * BOX_WORDS; i += 256) list[i] = A.boxes[i];
     __syncthreads();
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= (int64_t)A.w * A.h) return;
+    if (k >= A.frame.count()) return;
     V3 o, d;
-    camera_ray(A.cam, A.imgw, A.imgh, A.x0 + (int)(k % A.w), A.y0 + (int)(k / A.w), o, d);
+    A.frame.ray(k, o, d);
     float4 px = A.rgba[k];
     bool written = false;
     const float oa[3] = { o.x, o.y, o.z }, da[3] = { d.x, d.y, d.z };
@@ -106,9 +101,8 @@ __global__ __launch_bounds__(256) void k_shade_boxes(BoxArgs A)
 __global__ void k_cursor_place(V3 o, V3 d, float size, const uint32_t *record, uint32_t *box)
 {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
-    const uint32_t flags = record[4] >> 16;
     uint32_t style = box[8];
-    if ((flags & SVO_HIT_FLAG) && !(flags & SVO_ERR_FLAG)) {
+    if (usable_hit(record[4] >> 16)) {
         const V3 sigma = o + d * __uint_as_float(record[0]);        // src/Traverse.cpp:161
         const float half = size * 0.5f;
         box[0] = __float_as_uint(sigma.x - half);
@@ -134,34 +128,25 @@ int svo_cursor_place(const float origin[3], const float dir[3], const svo_hit *r
     o.x = origin[0]; o.y = origin[1]; o.z = origin[2]; d.x = dir[0]; d.y = dir[1]; d.z = dir[2];
     hipLaunchKernelGGL(k_cursor_place, dim3(1), dim3(64), 0, (hipStream_t)stream, o, d, size,
                        reinterpret_cast<const uint32_t *>(record_dev), reinterpret_cast<uint32_t *>(box_dev));
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("svo_cursor_place: ") + hipGetErrorString(e)); return hip_status(e); }
-    return SVO_OK;
+    return launch_status("svo_cursor_place");
 }
 
 int svo_shade_boxes(const svo_camera *cam, const svo_box *boxes_dev, int nboxes, float near_plane, float far_plane,
                     int x0, int y0, int w, int h, float *rgba_dev, void *stream)
 {
-    bool ok = cam && rgba_dev && nboxes >= 0 && nboxes <= SVO_MAX_BOXES && (boxes_dev || nboxes == 0) && w >= 0 && h >= 0 && x0 >= 0 && y0 >= 0;
-    ok = ok && cam->width > 0 && cam->height > 0 && near_plane >= 0.0f && far_plane >= 0.0f;      // (a NaN plane fails the compare)
+    bool ok = rgba_dev && nboxes >= 0 && nboxes <= SVO_MAX_BOXES && (boxes_dev || nboxes == 0) && rect_ok(cam, x0, y0, w, h);
+    ok = ok && near_plane >= 0.0f && far_plane >= 0.0f;       // (a NaN plane fails the compare)
     if (!ok) { set_error("svo_shade_boxes: bad argument"); return SVO_ERR_INVALID_ARG; }
-    const int64_t n = (int64_t)w * h;
-    if (n == 0 || nboxes == 0) return SVO_OK;
-    if ((n + 255) / 256 > 0x7FFFFFFF) { set_error("svo_shade_boxes: image too large"); return SVO_ERR_UNSUPPORTED; }
+    if (nboxes == 0) return SVO_OK;
     if (near_plane == 0.0f) near_plane = 0.125f;
     if (far_plane == 0.0f) far_plane = 8192.0f;
     BoxArgs A;
-    std::memcpy(A.cam.eye, cam->eye, 12); std::memcpy(A.cam.fwd, cam->forward, 12); std::memcpy(A.cam.right, cam->right, 12); std::memcpy(A.cam.up, cam->up, 12);
-    A.cam.tanx = cam->tan_half_x; A.cam.tany = cam->tan_half_y;
-    A.imgw = cam->width; A.imgh = cam->height; A.x0 = x0; A.y0 = y0; A.w = w; A.h = h;
+    A.frame = make_frame(*cam, x0, y0, w, h);
     A.boxes = reinterpret_cast<const uint32_t *>(boxes_dev); A.nboxes = nboxes;
     A.inv_near = 1.0f / near_plane;
     A.depth_range = 1.0f / far_plane - A.inv_near;
     A.rgba = reinterpret_cast<float4 *>(rgba_dev);
-    hipLaunchKernelGGL(k_shade_boxes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("svo_shade_boxes: ") + hipGetErrorString(e)); return hip_status(e); }
-    return SVO_OK;
+    return launch_per_element("svo_shade_boxes", A.frame.count(), (hipStream_t)stream, k_shade_boxes, A);
 }
 
 } // extern "C"

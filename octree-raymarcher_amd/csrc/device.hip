@@ -780,6 +780,13 @@ extern "C" {
 // ---------------------------------------------------------------------------------------------
 // the world box's minimum on axis a (src/Traverse.cpp:129-133)
 static float world_min(const svo_world *w, int a) { return (float)(w->chunkcoordmin[a] * (int)(float)w->chunksize); }
+// Where the rays of pixels that have nothing to march start, along -x (k_continuation, k_local_rays): below the world box on y and z
+// (by the box's extent), so that the line never meets the box
+static V3 miss_ray_origin(const svo_world *w)
+{
+    const float cs = (float)w->chunksize;
+    return V3{ world_min(w, 0), world_min(w, 1) - (float)w->height * cs - cs, world_min(w, 2) - (float)w->depth * cs - cs };
+}
 
 static int fill_common(svo_world *w, const svo_trace_params *prm, TraceArgs &A)
 {
@@ -952,15 +959,6 @@ static int launch(svo_world *w, const svo_trace_params *prm, TraceArgs &A, hipSt
     return ev.record(s);
 }
 
-static FrameCam frame_cam(const svo_camera &c)
-{
-    FrameCam d;
-    std::memcpy(d.eye, c.eye, sizeof d.eye); std::memcpy(d.fwd, c.forward, sizeof d.fwd);
-    std::memcpy(d.right, c.right, sizeof d.right); std::memcpy(d.up, c.up, sizeof d.up);
-    d.tanx = c.tan_half_x; d.tany = c.tan_half_y;
-    return d;
-}
-
 static int fill_cameras(const svo_camera *cams, int nframes, TraceArgs &A)
 {
     if (!cams || nframes < 1 || nframes > MAX_FRAMES) { set_error("svo_trace: between 1 and 16 cameras per launch"); return SVO_ERR_INVALID_ARG; }
@@ -1097,12 +1095,9 @@ int svo_trace_translucent(svo_world *w, const svo_camera *cam, const svo_trace_p
     if ((rc = list.reserve((size_t)n * 6, "svo_trace_translucent")) != SVO_OK) return rc;
     if ((rc = list.done.wait(s)) != SVO_OK) return rc;
     float *origins = list.buf.p, *dirs = list.buf.p + 3 * n;
-    // the miss ray's origin: below the world box on y and z (by the box's extent), so that its line never meets the box
-    const float cs = (float)w->chunksize;
-    const float oy = world_min(w, 1) - (float)w->height * cs - cs, oz = world_min(w, 2) - (float)w->depth * cs - cs;
-    hipLaunchKernelGGL(k_continuation, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, frame_cam(*cam), cam->width, cam->height, x0, y0, rw, n, m,
-                       world_min(w, 0), oy, oz, reinterpret_cast<uint4 *>(surface_dev), origins, dirs);
-    HIP_TRY(hipGetLastError());
+    rc = launch_per_element("svo_trace_translucent", n, s, k_continuation, make_frame(*cam, x0, y0, rw, rh), m, miss_ray_origin(w),
+                            reinterpret_cast<uint4 *>(surface_dev), origins, dirs);
+    if (rc != SVO_OK) return rc;
     svo_trace_params behind = *prm;                                     // (the caller's per-ray and per-tile buffers are sized for the surface)
     behind.counters_dev = nullptr; behind.tile_cost_dev = nullptr; behind.tile_order_dev = nullptr;
     rc = svo_trace_rays(w, origins, dirs, n, &behind, behind_dev, stream);
@@ -1115,7 +1110,7 @@ int svo_trace_translucent(svo_world *w, const svo_camera *cam, const svo_trace_p
 int svo_trace_local_shadows(svo_world *w, const svo_camera *cam, const svo_trace_params *prm, const float *point_position, const float *spot_position,
                             int x0, int y0, int rw, int rh, svo_hit *gbuffer_dev, void *stream)
 {
-    if (!w || !cam || !prm || !gbuffer_dev || (!point_position && !spot_position) || rw < 0 || rh < 0 || x0 < 0 || y0 < 0 || cam->width <= 0 || cam->height <= 0) {
+    if (!w || !prm || !gbuffer_dev || (!point_position && !spot_position) || !rect_ok(cam, x0, y0, rw, rh)) {
         set_error("svo_trace_local_shadows: bad argument"); return SVO_ERR_INVALID_ARG;
     }
     TraceArgs A;                                                        // (for the launch's resolved eps; checks see_through, semantics and residency)
@@ -1135,21 +1130,19 @@ int svo_trace_local_shadows(svo_world *w, const svo_camera *cam, const svo_trace
     if ((rc = list.reserve((size_t)rays * 14, "svo_trace_local_shadows")) != SVO_OK) return rc;
     if ((rc = list.done.wait(s)) != SVO_OK) return rc;
     float *records = list.buf.p, *origins = records + 8 * rays, *dirs = origins + 3 * rays;
-    const float cs = (float)w->chunksize;                               // the miss ray of svo_trace_translucent
-    const float oy = world_min(w, 1) - (float)w->height * cs - cs, oz = world_min(w, 2) - (float)w->depth * cs - cs;
-    const dim3 grid((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(k_local_rays, grid, dim3(256), 0, s, frame_cam(*cam), cam->width, cam->height, x0, y0, rw, n, A.eps, L,
-                       world_min(w, 0), oy, oz, reinterpret_cast<const uint4 *>(gbuffer_dev), origins, dirs);
-    HIP_TRY(hipGetLastError());
+    const PixelFrame F = make_frame(*cam, x0, y0, rw, rh);
+    rc = launch_per_element("svo_trace_local_shadows", n, s, k_local_rays, F, A.eps, L, miss_ray_origin(w), reinterpret_cast<const uint4 *>(gbuffer_dev),
+                            origins, dirs);
+    if (rc != SVO_OK) return rc;
     svo_trace_params march = *prm;                                      // (the caller's per-ray and per-tile buffers are sized for the frame)
     march.shadow = 0;
     march.counters_dev = nullptr; march.tile_cost_dev = nullptr; march.tile_order_dev = nullptr;
     // (unbounded on purpose: ending each ray at its light through svo_trace_segments was measured and is slower)
     rc = svo_trace_rays(w, origins, dirs, rays, &march, reinterpret_cast<svo_hit *>(records), stream);
     if (rc != SVO_OK) return rc;
-    hipLaunchKernelGGL(k_local_resolve, grid, dim3(256), 0, s, frame_cam(*cam), cam->width, cam->height, x0, y0, rw, n, A.eps, L,
-                       reinterpret_cast<const uint4 *>(records), reinterpret_cast<uint4 *>(gbuffer_dev));
-    HIP_TRY(hipGetLastError());
+    rc = launch_per_element("svo_trace_local_shadows", n, s, k_local_resolve, F, A.eps, L, reinterpret_cast<const uint4 *>(records),
+                            reinterpret_cast<uint4 *>(gbuffer_dev));
+    if (rc != SVO_OK) return rc;
     return list.done.record(s);
 }
 
@@ -1229,23 +1222,6 @@ int svo_hit_voxels(svo_world *w, const svo_hit *gbuffer_dev, int64_t n, svo_voxe
     const Hbm &d = *w->hbm;
     hipLaunchKernelGGL(k_hit_voxels, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<const uint4 *>(gbuffer_dev), out_dev, n, d.chunks.p,
                        d.chunk_trees.p, (uint32_t)w->chunks.size(), d.tree.p, d.parent.p, d.parent_level.p, (float)w->chunksize);
-    HIP_TRY(hipGetLastError());
-    return SVO_OK;
-}
-
-// leafUV per pixel (march.hip.h hit_uv) from the G-buffer and the records svo_hit_voxels wrote for it
-int svo_hit_uv(const svo_camera *cam, float eps, int x0, int y0, int rw, int rh, const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev,
-               float *uv_dev, void *stream)
-{
-    if (!cam || !gbuffer_dev || !voxels_dev || !uv_dev || rw < 0 || rh < 0 || x0 < 0 || y0 < 0 || cam->width <= 0 || cam->height <= 0 || !(eps >= 0.0f)) {
-        set_error("svo_hit_uv: bad argument"); return SVO_ERR_INVALID_ARG;
-    }
-    const int64_t n = (int64_t)rw * rh;
-    if (n == 0) return SVO_OK;
-    if ((n + 255) / 256 > 0x7FFFFFFF) { set_error("svo_hit_uv: image too large"); return SVO_ERR_UNSUPPORTED; }
-    hipLaunchKernelGGL(k_hit_uv, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, frame_cam(*cam), cam->width, cam->height, x0, y0, rw, n,
-                       eps == 0.0f ? 1.0f / 8192.0f : eps, reinterpret_cast<const uint4 *>(gbuffer_dev), reinterpret_cast<const uint4 *>(voxels_dev),
-                       reinterpret_cast<float2 *>(uv_dev));
     HIP_TRY(hipGetLastError());
     return SVO_OK;
 }

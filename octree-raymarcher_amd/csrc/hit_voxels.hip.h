@@ -1,8 +1,8 @@
-// hit_voxels.hip.h — svo_hit_voxels and svo_hit_uv: the voxel box of every hit of a G-buffer, and the reference's leafUV on it.
+// hit_voxels.hip.h — svo_hit_voxels: the voxel box of every hit of a G-buffer (svo_hit_uv, the reference's leafUV on it: shade.hip).
 //
 //   traverse (the box it holds on arriving at a node)   src/Traverse.cpp:34-48
 //   the brick cell's leafmin / leafsize                 src/Traverse.cpp:58-66
-//   cubeUV / leafUV                                     shaders/Chunkmarch.glsl:138-149, shaders/World.Fragment.glsl:5-15 (march.hip.h: leaf_uv)
+//   cubeUV / leafUV                                     shaders/Chunkmarch.glsl:138-149, shaders/World.Fragment.glsl:5-15 (march.hip.h leaf_uv, image_stage.hip.h hit_uv)
 //
 // svo_hit has no room for the box and the summed t does not give the point traverse() saw, but (chunk, node, cell) name the voxel:
 // children live in 8-blocks at 1 + 8k, every BRANCH points forward and no reachable block is referenced twice (validate_chunk), so
@@ -13,8 +13,7 @@
 // writes.  Nothing is read back.  Like march.hip.h this is compiled with -ffp-contract=off: every float operation below is
 // separately rounded, the box and the UV are bit for bit what the reference's expressions give.
 #pragma once
-#include "march.hip.h"
-#include "local_shadows.hip.h"
+#include "image_stage.hip.h"
 
 namespace svo {
 
@@ -107,17 +106,6 @@ __global__ __launch_bounds__(256) void k_hit_voxels(const uint4 *gbuffer, void *
         size = voxel;
     }
     store_hit(out, k, lo.x, mk(lo.y, lo.z, size), r1.x & 0xFFFFu, SVO_LOCATE_INSIDE | SVO_LOCATE_SOLID, chunk, node, cell);
-}
-
-// svo_hit_uv: leafUV (march.hip.h hit_uv) per pixel, (0, 0) where there is none
-__global__ __launch_bounds__(256) void k_hit_uv(FrameCam cam, int imgw, int imgh, int x0, int y0, int w, int64_t n, float eps,
-                                                const uint4 *gbuffer, const uint4 *voxels, float2 *uv)
-{
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) return;
-    float u, v;
-    hit_uv(cam, imgw, imgh, x0 + (int)(k % w), y0 + (int)(k / w), eps, gbuffer[2 * k], gbuffer[2 * k + 1], voxels[2 * k], voxels[2 * k + 1], u, v);
-    uv[k] = make_float2(u, v);
 }
 
 } // namespace svo

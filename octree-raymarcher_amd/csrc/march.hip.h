@@ -153,21 +153,6 @@ __device__ __forceinline__ void leaf_uv(V3 p, V3 cmin, float bsize, uint32_t m, 
     v = ((float)((m >> 8) & 0xFFu) + b) / 256.0f;
 }
 
-// leafUV of a pixel from its record (h0, h1) and its voxel record (v0, v1: svo_hit_voxels); false, and (0, 0), where there is none:
-// no hit, SVO_ERR_FLAG, or a voxel record without SVO_LOCATE_INSIDE
-__device__ __forceinline__ bool hit_uv(const FrameCam &cam, int imgw, int imgh, int px, int py, float eps, uint4 h0, uint4 h1, uint4 v0, uint4 v1,
-                                       float &u, float &v)
-{
-    u = v = 0.0f;
-    const uint32_t flags = h1.x >> 16;
-    if (!(flags & SVO_HIT_FLAG) || (flags & SVO_ERR_FLAG) || !((v1.x >> 16) & SVO_LOCATE_INSIDE)) return false;
-    V3 o, d;
-    camera_ray(cam, imgw, imgh, px, py, o, d);
-    const V3 p = o + d * (__uint_as_float(h0.x) - eps);     // the point cubeNormal is taken at, shaders/World.Fragment.glsl:174
-    leaf_uv(p, mk(__uint_as_float(v0.x), __uint_as_float(v0.y), __uint_as_float(v0.z)), __uint_as_float(v0.w), h1.x & 0xFFFFu, eps, u, v);
-    return true;
-}
-
 struct Voxel { V3 lo; float size; uint32_t material, node, cell; };
 
 // 32-byte record as two 16-byte stores.

@@ -13,7 +13,7 @@
 // relative to the pools (DevWide.wide_off / twig_off), so the view reuses it too.  The records of a launch on the view equal,
 // bit for bit, those of the world with LEAF(m) -> 0 and cell m -> 0.
 #pragma once
-#include "march.hip.h"
+#include "image_stage.hip.h"
 #include "wide_tree.hip.h"
 
 namespace svo {
@@ -50,19 +50,17 @@ __global__ __launch_bounds__(256) void k_view_mask(const uint16_t *twig, const u
 }
 
 // svo_trace_translucent: the continuation list in pixel order.  A surface hit of material m (not a runaway) continues from
-// p1 = o + d * t1 along its primary direction d and gets SVO_SEE_THROUGH; every other pixel gets a ray whose line misses the world
-// box (outside it on y and z, parallel to x: both marches' entry tests refuse it), so its record is the all-zero miss.
-__global__ __launch_bounds__(256) void k_continuation(FrameCam cam, int imgw, int imgh, int x0, int y0, int w, int64_t n, uint32_t m,
-                                                      float ox, float oy, float oz, uint4 *surface, float *origins, float *dirs)
+// p1 = o + d * t1 along its primary direction d and gets SVO_SEE_THROUGH; every other pixel gets the ray from `miss` (device.hip
+// miss_ray_origin) along -x, whose line misses the world box (both marches' entry tests refuse it), so its record is the all-zero miss.
+__global__ __launch_bounds__(256) void k_continuation(PixelFrame F, uint32_t m, V3 miss, uint4 *surface, float *origins, float *dirs)
 {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= n) return;
+    if (k >= F.count()) return;
     uint4 r1 = surface[2 * k + 1];
-    const uint32_t flags = r1.x >> 16;
-    V3 o = mk(ox, oy, oz), d = mk(-1.0f, 0.0f, 0.0f);
-    if ((flags & SVO_HIT_FLAG) && !(flags & SVO_ERR_FLAG) && (r1.x & 0xFFFFu) == m) {
+    V3 o = miss, d = mk(-1.0f, 0.0f, 0.0f);
+    if (usable_hit(r1.x >> 16) && (r1.x & 0xFFFFu) == m) {
         V3 eye;
-        camera_ray(cam, imgw, imgh, x0 + (int)(k % w), y0 + (int)(k / w), eye, d);
+        F.ray(k, eye, d);
         const float t1 = __uint_as_float(surface[2 * k].x);
         o = mk(__fadd_rn(eye.x, __fmul_rn(d.x, t1)), __fadd_rn(eye.y, __fmul_rn(d.y, t1)), __fadd_rn(eye.z, __fmul_rn(d.z, t1)));
         r1.x |= (uint32_t)SVO_SEE_THROUGH << 16;

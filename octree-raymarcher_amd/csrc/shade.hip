@@ -1,25 +1,22 @@
 // shade.hip — the shading stage over the G-buffer: Blinn-Phong x 3 lights,
 // shaders/World.Fragment.glsl:63-138,180-197, as one coalesced kernel (32 B read + 16 B written per pixel:
 // HBM-bound).  Albedo from the material table (svo_shade) or from the caller's texture atlas at the hit's leafUV
-// (svo_shade_textured, :5-15,178-182) — see include/svo.h.
+// (svo_shade_textured, :5-15,178-182; svo_hit_uv hands that leafUV to callers with a sampler of their own) — see include/svo.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 #include <string>
 
-#include "march.hip.h"
-#include "hip_own.h"
+#include "image_stage.hip.h"
 
 namespace svo {
 namespace {
 
 struct ShadeArgs {
     svo_shade_params P;
-    float eye[3], fwd[3], right[3], up[3];
-    float tanx, tany;
-    int32_t imgw, imgh, x0, y0, w, h;
-    const uint4 *gbuffer;
+    PixelFrame frame;
+    const uint4 *gbuffer;                       // (svo_shade_packed: svo_gbuffer_pack's uint2 records)
     float4 *rgba;
     // per-launch constants worked out once on the host with the same float expressions the per-pixel code used:
     float gdiffuse[8][3], gspecular[8][3];      // pow(material.diffuse / .specular, gamma), :183-184
@@ -50,38 +47,31 @@ __device__ __forceinline__ float pow_shiny(float x, float y)
     const float l2 = d < 0.015625f ? series : __builtin_amdgcn_logf(x);
     return __builtin_amdgcn_exp2f(y * l2);
 }
-// normalize(ivec3 in {-1,0,1}^3) from the packed record's 2-bit-per-axis code (bit 6: NaN), as k_gbuffer_unpack
-__device__ __forceinline__ V3 normal_from_code(uint32_t code)
-{
-    if (code & (1u << 6)) { const float q = __uint_as_float(0x7FC00000u); return mk(q, q, q); }
-    const float ix = (float)((int)(code & 3u) - 1), iy = (float)((int)((code >> 2) & 3u) - 1), iz = (float)((int)((code >> 4) & 3u) - 1);
-    const float dot = ix * ix + iy * iy + iz * iz;
-    const float inv = dot == 1.0f ? 1.0f : dot == 2.0f ? __uint_as_float(0x3F3504F3u) : dot == 3.0f ? __uint_as_float(0x3F13CD3Au) : __uint_as_float(0x7FC00000u);
-    return mk(ix * inv, iy * inv, iz * inv);
-}
-
 __device__ __forceinline__ int material_index(uint32_t material) { return material < 8 ? (int)material : 0; }
 
 // One pixel's {r, g, b, depth} from its record (a hit: SVO_HIT_FLAG) and its gamma-decoded albedo (:181-182) - the body of every
 // shading kernel
-__device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, uint32_t flags, uint32_t material, float t, V3 n, V3 diffuse, V3 specular)
+__device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, const HitRecord &h, V3 diffuse, V3 specular)
 {
     const svo_shade_params &P = A.P;
+    const FrameCam &cam = A.frame.cam;
     // the ray of this pixel (same generation as the march) and the shaded point alpha + beta * (sigma - EPS), :174
-    const int px = A.x0 + (int)(k % A.w), py = A.y0 + (int)(k / A.w);
+    // (not PixelFrame::ray: the host-made reciprocals and normalize_fast above, within this stage's tolerance and not bit for bit)
+    int px, py;
+    A.frame.pixel(k, px, py);
     const float fx = (float)px + 0.5f, fy = (float)py + 0.5f;
-    const float u = ((fx * A.inv_imgw) * 2.0f - 1.0f) * A.tanx;
-    const float v = (1.0f - (fy * A.inv_imgh) * 2.0f) * A.tany;
-    const V3 eye = ld3(A.eye);
-    const V3 beta = normalize_fast((ld3(A.fwd) + ld3(A.right) * u) + ld3(A.up) * v);
-    const float sdist = t - P.eps;
+    const float u = ((fx * A.inv_imgw) * 2.0f - 1.0f) * cam.tanx;
+    const float v = (1.0f - (fy * A.inv_imgh) * 2.0f) * cam.tany;
+    const V3 eye = ld3(cam.eye);
+    const V3 beta = normalize_fast((ld3(cam.fwd) + ld3(cam.right) * u) + ld3(cam.up) * v);
+    const float sdist = h.t - P.eps;
     const V3 p = eye + beta * sdist;
-    const float shininess = P.materials[material_index(material)].shininess;
+    const float shininess = P.materials[material_index(h.material)].shininess;
     // (1.0 - shadow): the directional light's term for all three (:186-190), unless svo_trace_local_shadows gave each local light its own
-    const float lit = (flags & SVO_SHADOWED) ? 0.0f : 1.0f;
-    const bool local = (flags & SVO_LOCAL_SHADOWS) != 0u;
-    const float lit_point = local ? ((flags & SVO_SHADOWED_POINT) ? 0.0f : 1.0f) : lit;
-    const float lit_spot = local ? ((flags & SVO_SHADOWED_SPOT) ? 0.0f : 1.0f) : lit;
+    const float lit = (h.flags & SVO_SHADOWED) ? 0.0f : 1.0f;
+    const bool local = (h.flags & SVO_LOCAL_SHADOWS) != 0u;
+    const float lit_point = local ? ((h.flags & SVO_SHADOWED_POINT) ? 0.0f : 1.0f) : lit;
+    const float lit_spot = local ? ((h.flags & SVO_SHADOWED_SPOT) ? 0.0f : 1.0f) : lit;
     // normalize(eye - p) = -beta and |p - eye| = sigma - EPS (beta is a unit vector) while the hit lies in front of the eye
     const bool front = sdist > 1.0e-3f;
     const V3 vdir = front ? mk(-beta.x, -beta.y, -beta.z) : normalize_fast(eye - p);
@@ -92,7 +82,7 @@ __device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, uint3
         const float l2 = dot3(lv, lv), il = __builtin_amdgcn_rsqf(l2);
         const V3 l = lv * il;
         const V3 hv = normalize_fast(l + vdir);
-        const float d = maxf0(dot3(n, l));
+        const float d = maxf0(dot3(h.n, l));
         const float s = pow_shiny(maxf0(dot3(vdir, hv)), shininess);
         const float att = attenuation(P.point.constant, P.point.linear, P.point.quadratic, l2 * il);     // |p - position| = l2 / sqrt(l2)
         const V3 amb = ld3(P.point.ambient) * diffuse;
@@ -103,7 +93,7 @@ __device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, uint3
     {   // computeDirectionalLight_BlinnPhong, :99-114
         const V3 l = ld3(A.dir_l);
         const V3 hv = normalize_fast(l + vdir);
-        const float d = maxf0(dot3(n, l));
+        const float d = maxf0(dot3(h.n, l));
         const float s = pow_shiny(maxf0(dot3(vdir, hv)), shininess);
         const V3 amb = ld3(P.directional.ambient) * diffuse;
         const V3 dif = ((ld3(P.directional.diffuse) * d) * diffuse) * lit;
@@ -115,7 +105,7 @@ __device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, uint3
         const float l2 = dot3(lv, lv), il = __builtin_amdgcn_rsqf(l2);
         const V3 l = lv * il;
         const V3 hv = normalize_fast(l + vdir);
-        const float d = maxf0(dot3(n, l));
+        const float d = maxf0(dot3(h.n, l));
         const float s = pow_shiny(maxf0(dot3(vdir, hv)), shininess);
         const float att = attenuation(P.spot.constant, P.spot.linear, P.spot.quadratic, l2 * il);
         const float theta = dot3(l, ld3(A.spot_axis));
@@ -131,10 +121,10 @@ __device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, uint3
 }
 
 // svo_shade's albedo: the material table's (:183-184 with the table in the atlas's place)
-__device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, uint32_t flags, uint32_t material, float t, V3 n)
+__device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, const HitRecord &h)
 {
-    const int mi = material_index(material);
-    return shade_hit(A, k, flags, material, t, n, ld3(A.gdiffuse[mi]), ld3(A.gspecular[mi]));
+    const int mi = material_index(h.material);
+    return shade_hit(A, k, h, ld3(A.gdiffuse[mi]), ld3(A.gspecular[mi]));
 }
 
 // PACKED: the G-buffer is the 8-byte form of svo_gbuffer_pack (8 B read + 16 B written per pixel instead of 32 + 16)
@@ -142,22 +132,10 @@ template <bool PACKED>
 __global__ __launch_bounds__(256) void k_shade(ShadeArgs A)
 {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= (int64_t)A.w * A.h) return;
-    uint32_t flags, material;
-    float t;
-    V3 n;
-    if (PACKED) {
-        const uint2 r = reinterpret_cast<const uint2 *>(A.gbuffer)[k];
-        t = __uint_as_float(r.x); material = r.y & 0xFFFFu; flags = (r.y >> 16) & 0xFFu;
-        n = normal_from_code((r.y >> 24) & 0x7Fu);
-    } else {
-        const uint4 r0 = A.gbuffer[2 * k], r1 = A.gbuffer[2 * k + 1];
-        flags = r1.x >> 16; material = r1.x & 0xFFFFu;
-        t = __uint_as_float(r0.x);
-        n = mk(__uint_as_float(r0.y), __uint_as_float(r0.z), __uint_as_float(r0.w));
-    }
-    if (!(flags & SVO_HIT_FLAG)) { A.rgba[k] = make_float4(0.0f, 0.0f, 0.0f, 1.0f); return; }       // discard
-    A.rgba[k] = shade_hit(A, k, flags, material, t, n);
+    if (k >= A.frame.count()) return;
+    const HitRecord h = PACKED ? load_packed(reinterpret_cast<const uint2 *>(A.gbuffer), k) : load_hit(A.gbuffer, k);
+    if (!(h.flags & SVO_HIT_FLAG)) { A.rgba[k] = make_float4(0.0f, 0.0f, 0.0f, 1.0f); return; }     // discard
+    A.rgba[k] = shade_hit(A, k, h);
 }
 
 // svo_shade_translucent (shaders/ParallaxAlpha.Fragment.glsl:315-323): surface colour C_s, colour C_b of the behind record at the
@@ -166,17 +144,15 @@ __global__ __launch_bounds__(256) void k_shade(ShadeArgs A)
 __global__ __launch_bounds__(256) void k_shade_translucent(ShadeArgs A, const uint4 *behind, float absorption)
 {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= (int64_t)A.w * A.h) return;
-    const uint4 r0 = A.gbuffer[2 * k], r1 = A.gbuffer[2 * k + 1];
-    const uint32_t flags = r1.x >> 16;
-    if (!(flags & SVO_HIT_FLAG)) { A.rgba[k] = make_float4(0.0f, 0.0f, 0.0f, 1.0f); return; }
-    const float t1 = __uint_as_float(r0.x);
-    const float4 cs = shade_hit(A, k, flags, r1.x & 0xFFFFu, t1, mk(__uint_as_float(r0.y), __uint_as_float(r0.z), __uint_as_float(r0.w)));
-    const uint4 b0 = behind[2 * k], b1 = behind[2 * k + 1];
-    const uint32_t bflags = b1.x >> 16;
-    if (!(flags & SVO_SEE_THROUGH) || !(bflags & SVO_HIT_FLAG)) { A.rgba[k] = cs; return; }
-    const float t2 = __uint_as_float(b0.x);
-    const float4 cb = shade_hit(A, k, bflags, b1.x & 0xFFFFu, t1 + t2, mk(__uint_as_float(b0.y), __uint_as_float(b0.z), __uint_as_float(b0.w)));
+    if (k >= A.frame.count()) return;
+    const HitRecord hs = load_hit(A.gbuffer, k);
+    if (!(hs.flags & SVO_HIT_FLAG)) { A.rgba[k] = make_float4(0.0f, 0.0f, 0.0f, 1.0f); return; }
+    const float4 cs = shade_hit(A, k, hs);
+    HitRecord hb = load_hit(behind, k);
+    if (!(hs.flags & SVO_SEE_THROUGH) || !(hb.flags & SVO_HIT_FLAG)) { A.rgba[k] = cs; return; }
+    const float t2 = hb.t;
+    hb.t = hs.t + t2;
+    const float4 cb = shade_hit(A, k, hb);
     float s = t2 * absorption;
     s = (s < 0.0f) ? 0.0f : s;
     s = (1.0f < s) ? 1.0f : s;
@@ -200,27 +176,28 @@ __device__ __forceinline__ V3 atlas_texel(const AtlasArgs &T, const uint8_t *ima
     return mk(T.decode[px[0]], T.decode[px[1]], T.decode[px[2]]);
 }
 
-// k_shade with the albedo of :178-182: the two atlases sampled at the hit's leafUV (march.hip.h hit_uv, separately rounded IEEE
+// k_shade with the albedo of :178-182: the two atlases sampled at the hit's leafUV (image_stage.hip.h hit_uv, separately rounded IEEE
 // operations: the texel is the reference's).  `voxels`: the records svo_hit_voxels wrote for A.gbuffer; a hit without a box gets
 // the material table's albedo.
 __global__ __launch_bounds__(256) void k_shade_textured(ShadeArgs A, const uint4 *voxels, AtlasArgs T)
 {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= (int64_t)A.w * A.h) return;
-    const uint4 r0 = A.gbuffer[2 * k], r1 = A.gbuffer[2 * k + 1];
-    const uint32_t flags = r1.x >> 16, material = r1.x & 0xFFFFu;
-    if (!(flags & SVO_HIT_FLAG)) { A.rgba[k] = make_float4(0.0f, 0.0f, 0.0f, 1.0f); return; }
-    const float t = __uint_as_float(r0.x);
-    const V3 n = mk(__uint_as_float(r0.y), __uint_as_float(r0.z), __uint_as_float(r0.w));
-    FrameCam cam;
-    for (int a = 0; a < 3; ++a) { cam.eye[a] = A.eye[a]; cam.fwd[a] = A.fwd[a]; cam.right[a] = A.right[a]; cam.up[a] = A.up[a]; }
-    cam.tanx = A.tanx; cam.tany = A.tany;
+    if (k >= A.frame.count()) return;
+    const HitRecord h = load_hit(A.gbuffer, k);
+    if (!(h.flags & SVO_HIT_FLAG)) { A.rgba[k] = make_float4(0.0f, 0.0f, 0.0f, 1.0f); return; }
     float u, v;
-    if (!hit_uv(cam, A.imgw, A.imgh, A.x0 + (int)(k % A.w), A.y0 + (int)(k / A.w), A.P.eps, r0, r1, voxels[2 * k], voxels[2 * k + 1], u, v)) {
-        A.rgba[k] = shade_hit(A, k, flags, material, t, n);
-        return;
-    }
-    A.rgba[k] = shade_hit(A, k, flags, material, t, n, atlas_texel(T, T.diffuse, u, v), atlas_texel(T, T.specular, u, v));
+    if (!hit_uv(A.frame, k, A.P.eps, h, voxels[2 * k], voxels[2 * k + 1], u, v)) { A.rgba[k] = shade_hit(A, k, h); return; }
+    A.rgba[k] = shade_hit(A, k, h, atlas_texel(T, T.diffuse, u, v), atlas_texel(T, T.specular, u, v));
+}
+
+// svo_hit_uv: that leafUV per pixel, (0, 0) where there is none
+__global__ __launch_bounds__(256) void k_hit_uv(PixelFrame F, float eps, const uint4 *gbuffer, const uint4 *voxels, float2 *uv)
+{
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= F.count()) return;
+    float u, v;
+    hit_uv(F, k, eps, load_hit(gbuffer, k), voxels[2 * k], voxels[2 * k + 1], u, v);
+    uv[k] = make_float2(u, v);
 }
 
 // ---- packed G-buffer -------------------------------------------------------------------------------------------
@@ -247,19 +224,9 @@ __global__ __launch_bounds__(256) void k_gbuffer_unpack(const uint2 *in, uint4 *
     if (k >= n) return;
     const uint2 p = in[k];
     const uint32_t code = (p.y >> 24) & 0x7Fu, flags = ((p.y >> 16) & 0xFFu) | ((p.y >> 31) ? (uint32_t)SVO_ERR_FLAG : 0u);
-    float nx = 0.0f, ny = 0.0f, nz = 0.0f;
-    if (flags & SVO_HIT_FLAG) {
-        if (code & (1u << 6)) {
-            nx = ny = nz = __uint_as_float(0x7FC00000u);
-        } else {
-            const float ix = (float)((int)(code & 3u) - 1), iy = (float)((int)((code >> 2) & 3u) - 1), iz = (float)((int)((code >> 4) & 3u) - 1);
-            const float dot = ix * ix + iy * iy + iz * iz;       // normalize(ivec3): the same constants as the march kernels
-            const float inv = dot == 1.0f ? 1.0f : dot == 2.0f ? __uint_as_float(0x3F3504F3u) : dot == 3.0f ? __uint_as_float(0x3F13CD3Au) : __uint_as_float(0x7FC00000u);
-            nx = ix * inv; ny = iy * inv; nz = iz * inv;
-        }
-    }
+    const V3 nrm = (flags & SVO_HIT_FLAG) ? normal_from_code(code) : mk(0.0f, 0.0f, 0.0f);
     uint4 a, b;
-    a.x = p.x; a.y = __float_as_uint(nx); a.z = __float_as_uint(ny); a.w = __float_as_uint(nz);
+    a.x = p.x; a.y = __float_as_uint(nrm.x); a.z = __float_as_uint(nrm.y); a.w = __float_as_uint(nrm.z);
     b.x = (p.y & 0xFFFFu) | (flags << 16); b.y = 0u; b.z = 0u; b.w = 0u;
     out[2 * k] = a;
     out[2 * k + 1] = b;
@@ -306,35 +273,25 @@ void svo_shade_defaults(svo_shade_params *p)
 static int pack_common(const void *in, void *out, int64_t n, void *stream, bool pack)
 {
     if (n < 0 || (n > 0 && (!in || !out))) { set_error("svo_gbuffer_pack/unpack: bad argument"); return SVO_ERR_INVALID_ARG; }
-    if (n == 0) return SVO_OK;
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    if (pack) hipLaunchKernelGGL(k_gbuffer_pack, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint4 *)in, (uint2 *)out, n);
-    else hipLaunchKernelGGL(k_gbuffer_unpack, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint2 *)in, (uint4 *)out, n);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("svo_gbuffer_pack/unpack: ") + hipGetErrorString(e)); return hip_status(e); }
-    return SVO_OK;
+    const char *who = "svo_gbuffer_pack/unpack";
+    if (pack) return launch_per_element(who, n, (hipStream_t)stream, k_gbuffer_pack, (const uint4 *)in, (uint2 *)out, n);
+    return launch_per_element(who, n, (hipStream_t)stream, k_gbuffer_unpack, (const uint2 *)in, (uint4 *)out, n);
 }
 
 int svo_gbuffer_pack(const svo_hit *gbuffer_dev, uint64_t *packed_dev, int64_t n, void *stream) { return pack_common(gbuffer_dev, packed_dev, n, stream, true); }
 int svo_gbuffer_unpack(const uint64_t *packed_dev, svo_hit *gbuffer_dev, int64_t n, void *stream) { return pack_common(packed_dev, gbuffer_dev, n, stream, false); }
 
-// kind: 0 = svo_shade, 1 = svo_shade_packed, 2 = svo_shade_translucent (behind_dev, absorption), 3 = svo_shade_textured (behind_dev: the voxel records, atlas)
-static int shade_impl(const svo_camera *cam, const svo_shade_params *p, int x0, int y0, int w, int h,
-                      const void *gbuffer_dev, float *rgba_dev, void *stream, int kind, const void *behind_dev = nullptr, float absorption = 0.0f,
-                      const svo_atlas *atlas = nullptr)
+// What every shade call shares: the argument check and A - the frame, the parameters with their defaults filled in, the per-launch
+// constants, the records and the image.  The caller launches its own kernel over A.frame.count() pixels.
+static int shade_args(const svo_camera *cam, const svo_shade_params *p, int x0, int y0, int w, int h, const void *gbuffer_dev, float *rgba_dev, ShadeArgs &A)
 {
-    if (!cam || !p || !gbuffer_dev || !rgba_dev || w < 0 || h < 0 || x0 < 0 || y0 < 0 || cam->width <= 0 || cam->height <= 0) {
-        set_error("svo_shade: bad argument"); return SVO_ERR_INVALID_ARG;
-    }
-    ShadeArgs A;
+    if (!p || !gbuffer_dev || !rgba_dev || !rect_ok(cam, x0, y0, w, h)) { set_error("svo_shade: bad argument"); return SVO_ERR_INVALID_ARG; }
     A.P = *p;
     if (A.P.eps == 0.0f) A.P.eps = 1.0f / 8192.0f;
     if (A.P.gamma == 0.0f) A.P.gamma = 2.2f;
     if (A.P.near_plane == 0.0f) A.P.near_plane = 0.125f;
     if (A.P.far_plane == 0.0f) A.P.far_plane = 8192.0f;
-    std::memcpy(A.eye, cam->eye, 12); std::memcpy(A.fwd, cam->forward, 12); std::memcpy(A.right, cam->right, 12); std::memcpy(A.up, cam->up, 12);
-    A.tanx = cam->tan_half_x; A.tany = cam->tan_half_y; A.imgw = cam->width; A.imgh = cam->height;
-    A.x0 = x0; A.y0 = y0; A.w = w; A.h = h;
+    A.frame = make_frame(*cam, x0, y0, w, h);
     for (int m = 0; m < 8; ++m)
         for (int c = 0; c < 3; ++c) {
             A.gdiffuse[m][c] = std::pow(A.P.materials[m].diffuse[c], A.P.gamma);
@@ -353,49 +310,56 @@ static int shade_impl(const svo_camera *cam, const svo_shade_params *p, int x0, 
     A.inv_depth_range = 1.0f / (1.0f / A.P.far_plane - 1.0f / A.P.near_plane);
     A.gbuffer = reinterpret_cast<const uint4 *>(gbuffer_dev);
     A.rgba = reinterpret_cast<float4 *>(rgba_dev);
-    const int64_t n = (int64_t)w * h;
-    if (n == 0) return SVO_OK;
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (kind == 3) {
-        AtlasArgs T;
-        T.diffuse = atlas->diffuse_dev; T.specular = atlas->specular_dev ? atlas->specular_dev : atlas->diffuse_dev;      // src/Atlas.cpp:31-32
-        T.width = atlas->width; T.height = atlas->height;
-        for (int v = 0; v < 256; ++v) T.decode[v] = std::pow((float)v / 255.0f, A.P.gamma);
-        hipLaunchKernelGGL(k_shade_textured, grid, dim3(256), 0, (hipStream_t)stream, A, reinterpret_cast<const uint4 *>(behind_dev), T);
-    }
-    else if (kind == 1) hipLaunchKernelGGL(k_shade<true>, grid, dim3(256), 0, (hipStream_t)stream, A);
-    else if (kind == 0) hipLaunchKernelGGL(k_shade<false>, grid, dim3(256), 0, (hipStream_t)stream, A);
-    else hipLaunchKernelGGL(k_shade_translucent, grid, dim3(256), 0, (hipStream_t)stream, A, reinterpret_cast<const uint4 *>(behind_dev),
-                            absorption == 0.0f ? 0.5f : absorption);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("svo_shade: ") + hipGetErrorString(e)); return hip_status(e); }
     return SVO_OK;
 }
 
 int svo_shade(const svo_camera *cam, const svo_shade_params *p, int x0, int y0, int w, int h,
               const svo_hit *gbuffer_dev, float *rgba_dev, void *stream)
 {
-    return shade_impl(cam, p, x0, y0, w, h, gbuffer_dev, rgba_dev, stream, 0);
+    ShadeArgs A;
+    if (const int rc = shade_args(cam, p, x0, y0, w, h, gbuffer_dev, rgba_dev, A)) return rc;
+    return launch_per_element("svo_shade", A.frame.count(), (hipStream_t)stream, k_shade<false>, A);
 }
 
 int svo_shade_packed(const svo_camera *cam, const svo_shade_params *p, int x0, int y0, int w, int h,
                      const uint64_t *packed_dev, float *rgba_dev, void *stream)
 {
-    return shade_impl(cam, p, x0, y0, w, h, packed_dev, rgba_dev, stream, 1);
+    ShadeArgs A;
+    if (const int rc = shade_args(cam, p, x0, y0, w, h, packed_dev, rgba_dev, A)) return rc;
+    return launch_per_element("svo_shade", A.frame.count(), (hipStream_t)stream, k_shade<true>, A);
 }
 
 int svo_shade_translucent(const svo_camera *cam, const svo_shade_params *p, float absorption, int x0, int y0, int w, int h,
                           const svo_hit *surface_dev, const svo_hit *behind_dev, float *rgba_dev, void *stream)
 {
     if (!behind_dev || !(absorption >= 0.0f)) { set_error("svo_shade_translucent: bad argument"); return SVO_ERR_INVALID_ARG; }
-    return shade_impl(cam, p, x0, y0, w, h, surface_dev, rgba_dev, stream, 2, behind_dev, absorption);
+    ShadeArgs A;
+    if (const int rc = shade_args(cam, p, x0, y0, w, h, surface_dev, rgba_dev, A)) return rc;
+    return launch_per_element("svo_shade", A.frame.count(), (hipStream_t)stream, k_shade_translucent, A, reinterpret_cast<const uint4 *>(behind_dev),
+                              absorption == 0.0f ? 0.5f : absorption);
 }
 
 int svo_shade_textured(const svo_camera *cam, const svo_shade_params *p, const svo_atlas *atlas, int x0, int y0, int w, int h,
                        const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, float *rgba_dev, void *stream)
 {
     if (!atlas || !atlas->diffuse_dev || atlas->width <= 0 || atlas->height <= 0 || !voxels_dev) { set_error("svo_shade_textured: bad argument"); return SVO_ERR_INVALID_ARG; }
-    return shade_impl(cam, p, x0, y0, w, h, gbuffer_dev, rgba_dev, stream, 3, voxels_dev, 0.0f, atlas);
+    ShadeArgs A;
+    if (const int rc = shade_args(cam, p, x0, y0, w, h, gbuffer_dev, rgba_dev, A)) return rc;
+    AtlasArgs T;
+    T.diffuse = atlas->diffuse_dev; T.specular = atlas->specular_dev ? atlas->specular_dev : atlas->diffuse_dev;      // src/Atlas.cpp:31-32
+    T.width = atlas->width; T.height = atlas->height;
+    for (int v = 0; v < 256; ++v) T.decode[v] = std::pow((float)v / 255.0f, A.P.gamma);
+    return launch_per_element("svo_shade", A.frame.count(), (hipStream_t)stream, k_shade_textured, A, reinterpret_cast<const uint4 *>(voxels_dev), T);
+}
+
+// leafUV per pixel (image_stage.hip.h hit_uv) from the G-buffer and the records svo_hit_voxels wrote for it
+int svo_hit_uv(const svo_camera *cam, float eps, int x0, int y0, int rw, int rh, const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev,
+               float *uv_dev, void *stream)
+{
+    if (!gbuffer_dev || !voxels_dev || !uv_dev || !rect_ok(cam, x0, y0, rw, rh) || !(eps >= 0.0f)) { set_error("svo_hit_uv: bad argument"); return SVO_ERR_INVALID_ARG; }
+    return launch_per_element("svo_hit_uv", (int64_t)rw * rh, (hipStream_t)stream, k_hit_uv, make_frame(*cam, x0, y0, rw, rh),
+                              eps == 0.0f ? 1.0f / 8192.0f : eps, reinterpret_cast<const uint4 *>(gbuffer_dev), reinterpret_cast<const uint4 *>(voxels_dev),
+                              reinterpret_cast<float2 *>(uv_dev));
 }
 
 } // extern "C"

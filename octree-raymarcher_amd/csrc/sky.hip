@@ -5,21 +5,17 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstring>
-#include <string>
 
-#include "march.hip.h"
-#include "hip_own.h"
+#include "image_stage.hip.h"
 
 namespace svo {
 namespace {
 
 struct SkyArgs {
-    FrameCam cam;
-    int32_t imgw, imgh, x0, y0, w, h;
+    PixelFrame frame;
     const uint8_t *faces[6];
     int32_t size, filter;
-    const uint32_t *records;                    // the 32-byte records (flags in the high half of word 4) or the packed ones (word 1, bits 16-23)
+    const void *records;                        // the 32-byte records or the packed ones (image_stage.hip.h record_flags)
     float *rgba;
 };
 
@@ -42,11 +38,11 @@ template <bool PACKED>
 __global__ __launch_bounds__(256) void k_shade_sky(SkyArgs A)
 {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= (int64_t)A.w * A.h) return;
-    const uint32_t flags = PACKED ? (A.records[2 * k + 1] >> 16) & 0xFFu : A.records[8 * k + 4] >> 16;
+    if (k >= A.frame.count()) return;
+    const uint32_t flags = PACKED ? record_flags(static_cast<const uint2 *>(A.records), k) : record_flags(static_cast<const uint4 *>(A.records), k);
     if (flags & SVO_HIT_FLAG) return;
     V3 o, d;
-    camera_ray(A.cam, A.imgw, A.imgh, A.x0 + (int)(k % A.w), A.y0 + (int)(k / A.w), o, d);
+    A.frame.ray(k, o, d);
     // the OpenGL cube-map table: major axis (X before Y before Z on ties), face, (sc, tc)
     const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
     int face;
@@ -103,39 +99,23 @@ extern "C" {
 int svo_shade_sky(const svo_camera *cam, const svo_sky *sky, int x0, int y0, int w, int h,
                   const svo_hit *gbuffer_dev, const uint64_t *packed_dev, float *rgba_dev, void *stream)
 {
-    bool ok = cam && sky && rgba_dev && (gbuffer_dev != nullptr) != (packed_dev != nullptr) && w >= 0 && h >= 0 && x0 >= 0 && y0 >= 0;
-    ok = ok && cam->width > 0 && cam->height > 0 && sky->size > 0 && (sky->filter == SVO_SKY_LINEAR || sky->filter == SVO_SKY_NEAREST);
+    bool ok = sky && rgba_dev && (gbuffer_dev != nullptr) != (packed_dev != nullptr) && rect_ok(cam, x0, y0, w, h);
+    ok = ok && sky->size > 0 && (sky->filter == SVO_SKY_LINEAR || sky->filter == SVO_SKY_NEAREST);
     for (int f = 0; ok && f < 6; ++f) ok = sky->faces_dev[f] != nullptr;
     if (!ok) { set_error("svo_shade_sky: bad argument"); return SVO_ERR_INVALID_ARG; }
-    const int64_t n = (int64_t)w * h;
-    if (n == 0) return SVO_OK;
-    if ((n + 255) / 256 > 0x7FFFFFFF) { set_error("svo_shade_sky: image too large"); return SVO_ERR_UNSUPPORTED; }
     SkyArgs A;
-    std::memcpy(A.cam.eye, cam->eye, 12); std::memcpy(A.cam.fwd, cam->forward, 12); std::memcpy(A.cam.right, cam->right, 12); std::memcpy(A.cam.up, cam->up, 12);
-    A.cam.tanx = cam->tan_half_x; A.cam.tany = cam->tan_half_y;
-    A.imgw = cam->width; A.imgh = cam->height; A.x0 = x0; A.y0 = y0; A.w = w; A.h = h;
+    A.frame = make_frame(*cam, x0, y0, w, h);
     for (int f = 0; f < 6; ++f) A.faces[f] = sky->faces_dev[f];
     A.size = sky->size; A.filter = sky->filter;
-    A.records = gbuffer_dev ? reinterpret_cast<const uint32_t *>(gbuffer_dev) : reinterpret_cast<const uint32_t *>(packed_dev);
+    A.records = gbuffer_dev ? static_cast<const void *>(gbuffer_dev) : packed_dev;
     A.rgba = rgba_dev;
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (packed_dev) hipLaunchKernelGGL(k_shade_sky<true>, grid, dim3(256), 0, (hipStream_t)stream, A);
-    else hipLaunchKernelGGL(k_shade_sky<false>, grid, dim3(256), 0, (hipStream_t)stream, A);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("svo_shade_sky: ") + hipGetErrorString(e)); return hip_status(e); }
-    return SVO_OK;
+    return launch_per_element("svo_shade_sky", A.frame.count(), (hipStream_t)stream, packed_dev ? k_shade_sky<true> : k_shade_sky<false>, A);
 }
 
 int svo_frame_rgba8(const float *rgba_dev, int64_t n, uint32_t *out_dev, void *stream)
 {
     if (n < 0 || (n > 0 && (!rgba_dev || !out_dev))) { set_error("svo_frame_rgba8: bad argument"); return SVO_ERR_INVALID_ARG; }
-    if (n == 0) return SVO_OK;
-    if ((n + 255) / 256 > 0x7FFFFFFF) { set_error("svo_frame_rgba8: image too large"); return SVO_ERR_UNSUPPORTED; }
-    hipLaunchKernelGGL(k_frame_rgba8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       reinterpret_cast<const float4 *>(rgba_dev), out_dev, n);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("svo_frame_rgba8: ") + hipGetErrorString(e)); return hip_status(e); }
-    return SVO_OK;
+    return launch_per_element("svo_frame_rgba8", n, (hipStream_t)stream, k_frame_rgba8, reinterpret_cast<const float4 *>(rgba_dev), out_dev, n);
 }
 
 } // extern "C"

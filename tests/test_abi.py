@@ -157,6 +157,30 @@ def test_argument_validation_precedes_any_device_work(svo):
     with pytest.raises(svo.SvoError) as e:
         svo.gbuffer_unpack(0, 0, -1)
     assert e.value.code == -1
+    # a rectangle or a count whose grid of 256-thread blocks does not fit one launch: SVO_ERR_UNSUPPORTED, behind the argument check
+    # and before any launch (the dummy pointers are never dereferenced)
+    huge, big_n, ptr = (0, 0, 1 << 20, 1 << 20), 1 << 40, 0x1000
+    atlas = svo.Atlas(ptr, None, 4, 4)
+    shades = {"shade": lambda g, out: svo.shade(cam, P, huge, g, out),
+              "shade_packed": lambda g, out: svo.shade_packed(cam, P, huge, g, out),
+              "shade_translucent": lambda g, out: svo.shade_translucent(cam, P, huge, g, ptr, out),
+              "shade_textured": lambda g, out: svo.shade_textured(cam, P, atlas, huge, g, ptr, out)}
+    for name, call in shades.items():
+        with pytest.raises(svo.SvoError) as e:
+            call(ptr, ptr)
+        assert e.value.code == -6, name
+        for g, out in ((0, ptr), (ptr, 0)):
+            with pytest.raises(svo.SvoError) as e:
+                call(g, out)
+            assert e.value.code == -1, name
+    for call in (svo.gbuffer_pack, svo.gbuffer_unpack):
+        with pytest.raises(svo.SvoError) as e:
+            call(ptr, ptr, big_n)
+        assert e.value.code == -6
+        for a, b in ((0, ptr), (ptr, 0)):
+            with pytest.raises(svo.SvoError) as e:
+                call(a, b, big_n)
+            assert e.value.code == -1
     # defaults mirror src/Main.cpp:101-131 and the ML table
     assert tuple(P.point.position) == (50.0, 8.0, 65.0) and abs(P.spot.cos_phi - np.cos(np.radians(25.0))) < 1e-7
     assert P.materials[4].shininess == 10000.0 and tuple(P.materials[6].specular) == (1.0, 1.0, 1.0)
