@@ -10,6 +10,8 @@
  *                           BoundsPyramid::init                    src/BoundsPyramid.cpp:47-78
  *                           Ocroot::build (water plane)            src/Octree.cpp:319-436
  *   svo_world_create     <- a World whose chunk[] the caller already owns (Ocroot, src/Octree.h:56-76)
+ *   svo_chunk_from_grid / svo_world_chunk_from_grid <- grow() (src/Octree.cpp:74-176) over a grid instead of the height pyramid
+ *   svo_world_chunk_to_grid <- (no counterpart) the chunk's voxels back as a dense grid
  *   svo_world_upload     <- World::load_gpu + RootAllocator::alloc src/World.cpp:57-94, src/Allocator.cpp:28-35
  *   svo_world_update     <- World::modify + RootAllocator::subst   src/World.cpp:268-274, src/Allocator.cpp:37-55
  *   svo_trace            <- World::draw (+ draw_shadowmap)         src/World.cpp:162-266
@@ -64,9 +66,9 @@
  *   - svo_trace* launches of one world may overlap on different streams (frames in flight); each
  *     launch owns a private work-cursor slot from a 64-entry ring, and a launch that comes round
  *     to a slot still in use is ordered on the device behind that earlier launch;
- *   - svo_world_update / svo_world_shift / svo_world_edit_box / svo_world_compact / svo_world_coarsen / svo_world_upload
- *     are ordered behind every launch issued before them on any stream (they drain the device before touching HBM, as World::modify is
- *     ordered on the GL queue) and have completed when they return: launches issued afterwards see
+ *   - svo_world_update / svo_world_shift / svo_world_edit_box / svo_world_compact / svo_world_coarsen /
+ *     svo_world_chunk_from_grid / svo_world_upload are ordered behind every launch issued before them on any stream
+ *     (they drain the device before touching HBM, as World::modify is ordered on the GL queue) and have completed when they return: launches issued afterwards see
  *     the new world, launches issued before saw the old one, none sees a mixture.
  *
  * Semantics are those of the reference's CPU march (src/Traverse.cpp): EPS = 1/8192, step caps
@@ -96,7 +98,8 @@ extern "C" {
                                           svo_world_locate and svo_voxel,
                                           svo_hit_voxels, svo_hit_uv, svo_shade_textured and svo_atlas,
                                           svo_shade_sky, svo_sky and svo_frame_rgba8,
-                                          svo_cursor_place, svo_shade_boxes, svo_box and svo_world_edit_cube */
+                                          svo_cursor_place, svo_shade_boxes, svo_box and svo_world_edit_cube,
+                                          svo_chunk_from_grid, svo_world_chunk_from_grid and svo_world_chunk_to_grid */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -375,6 +378,53 @@ int svo_world_compact(svo_world *, int chunk);
  * (MisraGriesCounter<8>, src/MisraGries.h) of the 8 cells under each; BRANCHes above it are kept, every other node is compacted as
  * by svo_world_compact.  SVO_ERR_UNSUPPORTED on a chunk of depth 2 (nothing changes); host / device as svo_world_compact. */
 int svo_world_coarsen(svo_world *, int chunk);
+
+/* ---- your own voxels: chunks from dense grids, and back ------------------------------------------------------------
+ * A grid is N*N*N uint16_t materials, N = 2^depth, x fastest: cell (x, y, z) at (z*N + y)*N + x - the brick's own order,
+ * z*16 + y*4 + x, at full size.  0 means empty.  depth lies in [SVO_GRID_MIN_DEPTH, SVO_GRID_MAX_DEPTH] (depth 10 is a 2 GiB grid);
+ * anything else is SVO_ERR_INVALID_ARG.  A grid in device memory (grid_dev) is 16-byte aligned, as every device allocation and every
+ * torch tensor is; one that is not is SVO_ERR_INVALID_ARG too.
+ *
+ * The tree of a grid is grow()'s (src/Octree.cpp:74-176) with "all cells equal" in the place of the height bounds, in integers:
+ *   a node at level L with integer corner (x, y, z) covers the cells [x, x+e) x [y, y+e) x [z, z+e), e = N >> L; the root is level 0
+ *   at (0, 0, 0), slot 0;
+ *   all cells 0:                  EMPTY (the word 0);
+ *   all cells equal m != 0:       LEAF | m - at level depth-2 too: a uniform 4^3 block is a LEAF, never a TWIG;
+ *   otherwise, at L == depth-2:   TWIG | k, k = the number of TWIGs before it in visiting order,
+ *                                 twig[k*64 + cz*16 + cy*4 + cx] = grid(x+cx, y+cy, z+cz);
+ *   otherwise:                    BRANCH | first, first = 1 + 8 * (the number of BRANCHes before it in visiting order); child c sits at
+ *                                 first + c with corner (x + (c&1)*e/2, y + ((c>>1)&1)*e/2, z + (c>>2)*e/2);
+ *   visiting order is the FIFO queue's: levels in order, within a level the nodes in the order their parents were visited, children
+ *   in slot order.
+ * So trees = 1 + 8 * BRANCHes, the pools pass svo_world_create's validation, and they are minimal: no BRANCH has eight equal EMPTY /
+ * LEAF children and no brick holds a single value (svo_world_compact leaves them as they are). */
+#define SVO_GRID_MIN_DEPTH 2
+#define SVO_GRID_MAX_DEPTH 10
+
+/* The tree of `grid` (host memory) as malloc'ed pools in *out, with the given frame; the caller frees them with svo_chunk_free.
+ * This is how a world is made from grids without a device (svo_world_create), and the host twin of svo_world_chunk_from_grid.
+ * A NULL argument, a depth out of range, a size that is not greater than 0 or not finite: SVO_ERR_INVALID_ARG; SVO_ERR_OUT_OF_MEMORY. */
+int svo_chunk_from_grid(const uint16_t *grid, uint32_t depth, const float position[3], float size, svo_chunk_desc *out);
+
+/* Chunk `chunk` of an UPLOADED world is replaced by the tree of grid_dev (device memory), built on the device the pools live on:
+ * position and size stay, `depth` becomes the chunk's depth (chunks of one world may differ in depth).  The pools never visit the
+ * host and equal svo_chunk_from_grid's index for index; a host copy is made again on request (svo_world_chunk), and svo_world_info
+ * follows.  Ordered and complete like svo_world_edit_box (it drains the device first); installed like svo_world_coarsen's result (the
+ * chunk's storage capacities do not shrink).  SVO_OK, or SVO_OK_LITERAL_ONLY as for svo_world_edit_box.
+ * A NULL world or grid, a chunk or depth out of range, a misaligned grid: SVO_ERR_INVALID_ARG; then a world that is not resident:
+ * SVO_ERR_NOT_UPLOADED; no device memory for the working arrays: SVO_ERR_OUT_OF_MEMORY; 2^30 nodes or bricks: SVO_ERR_UNSUPPORTED -
+ * all before anything changes. */
+int svo_world_chunk_from_grid(svo_world *, int chunk, const uint16_t *grid_dev, uint32_t depth);
+
+/* The inverse: grid_dev receives the (2^depth)^3 cells of chunk `chunk`, whatever the chunk's own depth D.  Output cell (x, y, z)
+ * reports the finest voxel (X, Y, Z), per axis X = x << (D - depth) if depth <= D (the min-corner voxel of the cell - no filtering:
+ * svo_world_coarsen is the majority filter), else X = x >> (depth - D) (replication).  That voxel's material is found by descending from
+ * the root by integer coordinates: EMPTY gives 0, LEAF offset & 0xFFFF, TWIG the brick cell; blocks no BRANCH reaches are never
+ * visited, and nothing is read out of range whatever the pools hold (a word that points beyond them reads as 0).
+ * Argument and status rules are svo_world_locate's: a NULL world or grid, a chunk or depth out of range, a misaligned grid:
+ * SVO_ERR_INVALID_ARG; then a world that is not resident: SVO_ERR_NOT_UPLOADED - settled before any device work.  Asynchronous on
+ * `stream` and ordered against updates, edits and shifts like svo_world_locate; it takes no launch slot and no scratch. */
+int svo_world_chunk_to_grid(svo_world *, int chunk, uint32_t depth, uint16_t *grid_dev, void *stream);
 
 /* ---- the hot path ------------------------------------------------------------------------ */
 

@@ -171,6 +171,7 @@ MAX_FRAMES = 16                     # SVO_MAX_FRAMES
 ABI_SYMBOLS = [
     "svo_world_generate", "svo_world_create", "svo_world_info_get", "svo_world_chunk", "svo_world_destroy",
     "svo_world_index_float", "svo_world_index", "svo_world_locate", "svo_hit_voxels", "svo_hit_uv", "svo_shade_textured", "svo_world_upload", "svo_world_update",
+    "svo_chunk_from_grid", "svo_world_chunk_from_grid", "svo_world_chunk_to_grid",
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_edit_cube", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_cursor_place", "svo_shade_boxes", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_device_count", "svo_device_alloc", "svo_device_free", "svo_device_cache_trim", "svo_memcpy_h2d", "svo_memcpy_d2h",
@@ -199,6 +200,9 @@ lib.svo_chunk_read.argtypes = [C.c_char_p, C.POINTER(ChunkDesc), C.POINTER(C.c_u
 lib.svo_chunk_free.argtypes = [C.POINTER(ChunkDesc)]
 lib.svo_chunk_free.restype = None
 lib.svo_world_shift.argtypes = [_P, C.POINTER(C.c_int)]
+lib.svo_chunk_from_grid.argtypes = [_P, C.c_uint32, C.POINTER(C.c_float), C.c_float, C.POINTER(ChunkDesc)]
+lib.svo_world_chunk_from_grid.argtypes = [_P, C.c_int, _P, C.c_uint32]
+lib.svo_world_chunk_to_grid.argtypes = [_P, C.c_int, C.c_uint32, _P, _P]
 lib.svo_gbuffer_pack.argtypes = [_P, _P, C.c_int64, _P]
 lib.svo_gbuffer_unpack.argtypes = [_P, _P, C.c_int64, _P]
 lib.svo_shade_defaults.argtypes = [C.POINTER(ShadeParams)]
@@ -367,6 +371,28 @@ def chunk_read(path: str) -> dict:
         twig = np.ctypeslib.as_array(d.twig, shape=(d.twigs * 64,)).copy() if d.twigs else np.zeros(0, np.uint16)
         return {"position": tuple(d.position), "size": d.size, "depth": d.depth, "tree": tree, "twig": twig,
                 "treestoragesize": ts.value, "twigstoragesize": ws.value}
+    finally:
+        lib.svo_chunk_free(C.byref(d))
+
+
+def _grid_depth(grid: np.ndarray) -> int:
+    """depth of a [z, y, x] cube of 2^depth cells per axis (ValueError for any other shape)."""
+    n = grid.shape[0] if grid.ndim == 3 else 0
+    if n < 1 or grid.shape != (n, n, n) or n & (n - 1):
+        raise ValueError("a grid is a [z, y, x] cube of 2^depth cells per axis")
+    return n.bit_length() - 1
+
+
+def chunk_from_grid(grid, position=(0.0, 0.0, 0.0), size: float = 128.0) -> dict:
+    """svo_chunk_from_grid: the tree of a [z, y, x] uint16 grid of materials (0 = empty) as a chunk dict (World.create takes it)."""
+    g = np.ascontiguousarray(grid, dtype=np.uint16)
+    d = ChunkDesc()
+    pos = None if position is None else (C.c_float * 3)(*[float(v) for v in position])
+    _check(lib.svo_chunk_from_grid(g.ctypes.data, _grid_depth(g), pos, float(size), C.byref(d)), "svo_chunk_from_grid")
+    try:
+        tree = np.ctypeslib.as_array(d.tree, shape=(d.trees,)).copy()
+        twig = np.ctypeslib.as_array(d.twig, shape=(d.twigs * 64,)).copy() if d.twigs else np.zeros(0, np.uint16)
+        return {"position": tuple(d.position), "size": d.size, "depth": d.depth, "tree": tree, "twig": twig}
     finally:
         lib.svo_chunk_free(C.byref(d))
 
@@ -577,6 +603,35 @@ class World:
     def coarsen(self, chunk: int):
         """Ocroot::lodmm + World::modify(realloc) (svo_world_coarsen): chunk one level coarser, depth -> depth - 1."""
         return _check(lib.svo_world_coarsen(self._h, int(chunk)), "svo_world_coarsen")
+
+    def chunk_from_grid(self, chunk: int, grid_ptr: int, depth: int):
+        """svo_world_chunk_from_grid: chunk replaced by the tree of the (2^depth)^3 uint16 grid at grid_ptr (device memory, x fastest)."""
+        return _check(lib.svo_world_chunk_from_grid(self._h, int(chunk), grid_ptr, int(depth)), "svo_world_chunk_from_grid")
+
+    def chunk_to_grid(self, chunk: int, depth: int, out_ptr: int, stream: int = 0):
+        """svo_world_chunk_to_grid: the chunk's voxels as a (2^depth)^3 uint16 grid at out_ptr (device memory), asynchronous on stream."""
+        return _check(lib.svo_world_chunk_to_grid(self._h, int(chunk), int(depth), out_ptr, stream), "svo_world_chunk_to_grid")
+
+    def set_chunk_grid(self, chunk: int, grid):
+        """World.chunk_from_grid over a host [z, y, x] uint16 array."""
+        g = np.ascontiguousarray(grid, dtype=np.uint16)
+        depth = _grid_depth(g)
+        gd = DeviceBuffer.from_numpy(g)
+        try:
+            return self.chunk_from_grid(chunk, gd.ptr, depth)
+        finally:
+            gd.free()
+
+    def chunk_grid(self, chunk: int, depth: int) -> np.ndarray:
+        """World.chunk_to_grid into a host [z, y, x] uint16 array."""
+        n = 1 << max(int(depth), 0) if int(depth) <= 10 else 1
+        out = DeviceBuffer(max(n ** 3 * 2, 16))
+        try:
+            self.chunk_to_grid(chunk, depth, out.ptr)
+            _check(lib.svo_stream_synchronize(None), "svo_stream_synchronize")
+            return out.to_numpy(np.uint16, n ** 3).reshape(n, n, n)
+        finally:
+            out.free()
 
     def shift(self, offset):
         """World::shift (src/World.cpp:334-378): slide the grid one chunk along one axis."""

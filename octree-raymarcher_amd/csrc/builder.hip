@@ -29,6 +29,7 @@
 #include <thread>
 #include <vector>
 
+#include "bfs.hip.h"
 #include "hip_own.h"
 #include "terrain.h"
 
@@ -143,7 +144,7 @@ __device__ __forceinline__ uint32_t d_height_material(float y)
     return (uint32_t)(uint16_t)v;
 }
 
-struct Cell { float x, y, z; uint32_t slot; };
+using Cell = BfsCell<float>;        // frontier entry: the node's corner in world units and its slot (bfs.hip.h: k_level_totals, k_emit)
 
 constexpr unsigned FILL_BLOCK = 1024;     // threads per block of the sweeps that number nodes through block_take (hip_own.h)
 
@@ -180,45 +181,6 @@ __global__ __launch_bounds__(256) void k_classify(const Cell *frontier, uint32_t
     }
     word[i] = w;
     flags[i] = (unsigned long long)br | ((unsigned long long)tw << 32);
-}
-
-// the level's totals, from the scan instead of a counter: exclusive rank of the last node + its own flags
-__global__ void k_level_totals(const unsigned long long *flags, const unsigned long long *rank, uint32_t n, uint32_t *totals /* [0] BRANCH, [1] TWIG */)
-{
-    const unsigned long long t = rank[n - 1] + flags[n - 1];
-    totals[0] = (uint32_t)t;
-    totals[1] = (uint32_t)(t >> 32);
-}
-
-// node words; children of every BRANCH appended to the next frontier in parent order (== FIFO queue order);
-// brick jobs listed in TWIG order
-__global__ __launch_bounds__(256) void k_emit(const Cell *frontier, uint32_t n, float half, const uint32_t *word,
-                                              const unsigned long long *rank /* BRANCH rank | TWIG rank << 32 */,
-                                              uint32_t trees, uint32_t twigs, uint32_t *tree, Cell *next, Cell *brick_jobs)
-{
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const Cell e = frontier[i];
-    uint32_t w = word[i];
-    const uint32_t type = node_type(w);
-    if (type == BRANCH) {
-        const uint32_t branch_rank = (uint32_t)rank[i];
-        const uint32_t first = trees + 8 * branch_rank;
-        w = node_make(BRANCH, first);
-#pragma unroll
-        for (uint32_t c = 0; c < 8; ++c) {
-            const float ox = (c & 1) ? 1.0f : 0.0f, oy = (c & 2) ? 1.0f : 0.0f, oz = (c & 4) ? 1.0f : 0.0f;
-            Cell ch; ch.x = e.x + ox * half; ch.y = e.y + oy * half; ch.z = e.z + oz * half; ch.slot = first + c;
-            next[8 * (uint64_t)branch_rank + c] = ch;
-        }
-    } else if (type == TWIG) {
-        const uint32_t twig_rank = (uint32_t)(rank[i] >> 32);
-        const uint32_t brick = twigs + twig_rank;
-        w = node_make(TWIG, brick);
-        Cell job = e; job.slot = brick;
-        brick_jobs[twig_rank] = job;
-    }
-    tree[e.slot] = w;
 }
 
 // Bricks (src/Octree.cpp:122-147), one thread per (brick, z-row): the row's four column heights are looked up with
@@ -580,7 +542,7 @@ struct DeviceGrower {
             if (trees + 8 * nb >= (1ull << 30) || twigs + nt >= (1ull << 30)) { set_error("device builder: chunk exceeds the 30-bit node offset"); return SVO_ERR_UNSUPPORTED; }
             if ((rc = tree.reserve(trees + 8 * nb, true, s)) != SVO_OK || (rc = twig.reserve((twigs + nt) * TWIG_WORDS, true, s)) != SVO_OK ||
                 (rc = next.reserve(std::max<uint64_t>(8 * nb, 1), false, s)) != SVO_OK || (rc = jobs.reserve(std::max<uint64_t>(nt, 1), false, s)) != SVO_OK) return rc;
-            hipLaunchKernelGGL(k_emit, dim3(blocks_for(n, 256)), dim3(256), 0, s, frontier.p, n, half, word.p, rank.p,
+            hipLaunchKernelGGL(k_emit<float>, dim3(blocks_for(n, 256)), dim3(256), 0, s, frontier.p, n, half, word.p, rank.p,
                                (uint32_t)trees, (uint32_t)twigs, tree.p, next.p, jobs.p);
             if (nt) hipLaunchKernelGGL(k_bricks_rows, dim3(blocks_for(nt * 4, 256)), dim3(256), 0, s, jobs.p, (uint32_t)nt, G, P, twig.p);
             HIP_TRY(hipGetLastError());

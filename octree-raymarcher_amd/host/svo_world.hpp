@@ -12,6 +12,8 @@
 //   svo::World::modify(i, ...)       <- World::modify          src/World.cpp:268-274
 //   svo::World::index / index_float  <- src/World.cpp:288-293,323-332
 //   svo::World::locate(points, ...)  <- traverse over a point list (svo_world_locate)   src/Traverse.cpp:34-48
+//   svo::World::chunk_from_grid / chunk_to_grid  <- grow() over a dense voxel grid instead of the height pyramid (svo_world_chunk_from_grid),
+//                                       and the chunk's voxels back as a grid (svo_world_chunk_to_grid)   src/Octree.cpp:74-176
 //   svo::World::hit_voxels(...)      <- hit.bmin / hit.size of fragment main (svo_hit_voxels)   shaders/World.Fragment.glsl:168-172
 //   svo::World::hit_uv / shade_textured  <- leafUV, texture(Diffuse / Specular, uv) (svo_hit_uv, svo_shade_textured)   shaders/World.Fragment.glsl:5-15,178-182
 //   svo::World::shade_sky / frame_rgba8  <- Skybox::draw and the RGBA8 colour attachment (svo_shade_sky, svo_frame_rgba8)   src/Skybox.cpp, src/GBuffer.cpp
@@ -192,6 +194,19 @@ public:
         p.semantics = semantics;
         p.see_through = see_through;
         check(svo_world_locate(world_, points_dev, n, &p, out_dev, stream), "World::locate");
+    }
+
+    // Chunk i replaced by the tree of a dense grid in device memory ((2^depth)^3 uint16 materials, x fastest, 0 = empty; svo.h states the
+    // rule), and the chunk's voxels back as such a grid of any depth in [2, 10] (asynchronous on `stream`).
+    int chunk_from_grid(int i, const uint16_t *grid_dev, uint32_t depth)
+    {
+        const int rc = svo_world_chunk_from_grid(world_, i, grid_dev, depth);
+        check(rc, "World::chunk_from_grid");
+        return rc;                                          // SVO_OK, or SVO_OK_LITERAL_ONLY
+    }
+    void chunk_to_grid(int i, uint32_t depth, uint16_t *grid_dev, void *stream = nullptr)
+    {
+        check(svo_world_chunk_to_grid(world_, i, depth, grid_dev, stream), "World::chunk_to_grid");
     }
 
     // The voxel box of each of n G-buffer records (svo_hit_voxels: hit.bmin / hit.size, shaders/World.Fragment.glsl:168-172) into out_dev;
