@@ -754,22 +754,13 @@ namespace svo {
 constexpr int STACK_REFILL = 8;         // retired lanes per wave that trigger a refill (cheap: rays are staged in LDS)
 constexpr int STACK_WAVES = 6;          // waves per SIMD the stack kernel is register-budgeted for: 80 VGPRs (the asm step holds 63; spills sit in the rare blocks)
 using StackKernel = void (*)(TraceArgs);
-template <int MAXLV, bool BIG, bool GLSL, bool SEG = false> constexpr StackKernel stack_kernel = k_trace_stack<MAXLV, STACK_REFILL, STACK_WAVES, BIG, GLSL, SEG>;
+template <int MAXLV, bool BIG, bool GLSL, bool SEG> constexpr StackKernel stack_kernel = k_trace_stack<MAXLV, STACK_REFILL, STACK_WAVES, BIG, GLSL, SEG>;
 constexpr int STACK_CLASSES = 12;       // depth class x semantics; the bounded set (svo_trace_segments) follows in the same order
-static const StackKernel STACK_KERNELS[] = {
-    stack_kernel<10, true, true>, stack_kernel<10, true, false>,
-    stack_kernel<22, true, true>, stack_kernel<22, true, false>,
-    stack_kernel<6, false, true>, stack_kernel<6, false, false>,
-    stack_kernel<10, false, true>, stack_kernel<10, false, false>,
-    stack_kernel<16, false, true>, stack_kernel<16, false, false>,
-    stack_kernel<22, false, true>, stack_kernel<22, false, false>,
-    stack_kernel<10, true, true, true>, stack_kernel<10, true, false, true>,
-    stack_kernel<22, true, true, true>, stack_kernel<22, true, false, true>,
-    stack_kernel<6, false, true, true>, stack_kernel<6, false, false, true>,
-    stack_kernel<10, false, true, true>, stack_kernel<10, false, false, true>,
-    stack_kernel<16, false, true, true>, stack_kernel<16, false, false, true>,
-    stack_kernel<22, false, true, true>, stack_kernel<22, false, false, true>,
-};
+#define STACK_PAIR(MAXLV, BIG, SEG) stack_kernel<MAXLV, BIG, true, SEG>, stack_kernel<MAXLV, BIG, false, SEG>
+#define STACK_SET(SEG) STACK_PAIR(10, true, SEG), STACK_PAIR(22, true, SEG), STACK_PAIR(6, false, SEG), STACK_PAIR(10, false, SEG), STACK_PAIR(16, false, SEG), STACK_PAIR(22, false, SEG)
+static const StackKernel STACK_KERNELS[] = { STACK_SET(false), STACK_SET(true) };      // launch_stack computes the index
+#undef STACK_SET
+#undef STACK_PAIR
 static_assert(sizeof(STACK_KERNELS) / sizeof(StackKernel) == 2 * STACK_CLASSES, "an unbounded and a bounded instantiation per class");
 static_assert(sizeof(STACK_KERNELS) / sizeof(StackKernel) == sizeof(Hbm::stack_blocks) / sizeof(int), "one grid size per instantiation");
 
@@ -945,10 +936,8 @@ static int launch(svo_world *w, const svo_trace_params *prm, TraceArgs &A, hipSt
     if (kernel == SVO_KERNEL_LITERAL) {
         const int64_t blocks = (A.n + 255) / 256;
         if (blocks > 0x7FFFFFFF) { set_error("svo_trace: too many rays for one launch"); return SVO_ERR_UNSUPPORTED; }
-        if (A.tmax && see) hipLaunchKernelGGL(k_trace_literal_seg<true>, dim3((unsigned)blocks), dim3(256), 0, s, A, see);
-        else if (A.tmax) hipLaunchKernelGGL(k_trace_literal_seg<false>, dim3((unsigned)blocks), dim3(256), 0, s, A, 0u);
-        else if (see) hipLaunchKernelGGL(k_trace_literal_st, dim3((unsigned)blocks), dim3(256), 0, s, A, see);
-        else hipLaunchKernelGGL(k_trace_literal, dim3((unsigned)blocks), dim3(256), 0, s, A);
+        const auto literal = see ? (A.tmax ? k_trace_literal<true, true> : k_trace_literal<true, false>) : (A.tmax ? k_trace_literal<false, true> : k_trace_literal<false, false>);
+        hipLaunchKernelGGL(literal, dim3((unsigned)blocks), dim3(256), 0, s, A, see);      // (see == 0: ST is off and `ignore` is not read)
     } else {
         if (A.ntiles > (1 << 25)) { set_error("svo_trace: more than 2^31 rays in one stack-kernel launch"); return SVO_ERR_UNSUPPORTED; }
         if (A.tile_cost) HIP_TRY(hipMemsetAsync(A.tile_cost, 0, (size_t)A.ntiles * (size_t)(A.from_camera ? A.nframes : 1) * 2 * sizeof(uint32_t), s));

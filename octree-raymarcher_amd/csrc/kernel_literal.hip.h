@@ -7,11 +7,13 @@
 //   traverse   src/Traverse.cpp:34-48      twigmarch  src/Traverse.cpp:50-72
 //   treemarch  src/Traverse.cpp:74-113     chunkmarch src/Traverse.cpp:127-171
 //
-// ST: the see-through instantiation (svo_trace_params.see_through): a LEAF of material `ignore` is stepped over as an EMPTY node
-// and a brick cell holding it as an empty cell, like Chunkmarch.glsl's `ignore` (:190-191,240-241,280).  k_trace_literal is the
-// ST = false one (its device code is unchanged by the template), k_trace_literal_st the other.
+// k_trace_literal<ST, SEG> is the one kernel; device.hip's launch() picks the instantiation.
 //
-// SEG: the bounded instantiations (svo_trace_segments, k_trace_literal_seg<ST>): ray k ends at far = A.tmax[k].  A hit counts only
+// ST: the see-through instantiations (svo_trace_params.see_through): a LEAF of material `ignore` is stepped over as an EMPTY node
+// and a brick cell holding it as an empty cell, like Chunkmarch.glsl's `ignore` (:190-191,240-241,280).  With ST = false `ignore`
+// is not read.
+//
+// SEG: the bounded instantiations (svo_trace_segments): ray k ends at far = A.tmax[k].  A hit counts only
 // if its t < far (strict; the compare sits before store_hit and before the shadow ray), and the march ends as soon as no later hit
 // can pass that compare (DESIGN.md 6g has the argument):
 //   tree loop   every later hit of THIS tree march lies at tw + s with s >= t - leaf_back (t never decreases while p stays inside
@@ -19,7 +21,7 @@
 //               march - as a march that left the chunk, so the chunk loop takes its usual step;
 //   chunk loop  every later hit lies at t + s with s >= -leaf_back and t does not decrease from chunk to chunk (the escape out of a
 //               box that holds p is >= -0): t - leaf_back >= far ends the ray.
-// A NaN on either side fails the compare and the march goes on as the unbounded one.  SEG = false compiles to the kernels as they were.
+// A NaN on either side fails the compare and the march goes on as the unbounded one.  With SEG = false none of this is compiled.
 #pragma once
 #include "march.hip.h"
 
@@ -207,14 +209,17 @@ __device__ inline bool lit_world(const TraceArgs &A, V3 alpha, V3 beta, float &t
     return false;
 }
 
-__global__ __launch_bounds__(256) void k_trace_literal(TraceArgs A)
+// One body for the four kernels.  The bounded ones (SEG) are list mode only: ray k of the list ends at far = A.tmax[k].
+template <bool ST, bool SEG>
+__global__ __launch_bounds__(256) void k_trace_literal(TraceArgs A, uint32_t ignore)
 {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     unsigned rays = 0;
     bool live = k < A.n;
     V3 o = mk(0, 0, 0), d = mk(0, 0, 1);
+    [[maybe_unused]] float far = 0.0f;
     if (live) {
-        if (A.from_camera) {
+        if (!SEG && A.from_camera) {
             int px, py;
             local_to_pixel(A, (int)(k % A.w), (int)(k / A.w), px, py);
             if (py >= A.imgh || px >= A.imgw) { store_miss(A.out, k, 0); live = false; }
@@ -222,6 +227,7 @@ __global__ __launch_bounds__(256) void k_trace_literal(TraceArgs A)
         } else {
             o = ld3(A.origins + 3 * k);
             d = ld3(A.dirs + 3 * k);
+            if constexpr (SEG) far = A.tmax[k];
         }
     }
     if (live) {
@@ -231,105 +237,14 @@ __global__ __launch_bounds__(256) void k_trace_literal(TraceArgs A)
         uint32_t chunk = 0;
         rays = 1;
         bool runaway = false;
-        if (lit_world<false>(A, o, d, t, vox, chunk, cnt, runaway, 0u)) {
+        bool hit = lit_world<ST, SEG>(A, o, d, t, vox, chunk, cnt, runaway, ignore, far);
+        if constexpr (SEG) hit = hit && t < far;                    // the strict compare decides the record
+        if (hit) {
             const V3 point = o + d * (t - A.eps);
             const bool face = A.normal_mode == SVO_NORMAL_FACE;
             const V3 n = face ? face_normal(point, vox.lo, vox.lo + vox.size, d) : cube_normal(point, vox.lo, vox.lo + vox.size, A.eps);
             uint32_t flags = SVO_HIT_FLAG | (face ? (uint32_t)SVO_FACE_NORMAL : 0u);
-            if (A.shadow) {
-                Voxel sv; float st; uint32_t sc;
-                const bool occluded = lit_world<false>(A, point, ld3(A.sdir), st, sv, sc, cnt, runaway, 0u);
-                flags |= SVO_SHADOW_TRACED | (occluded ? SVO_SHADOWED : 0u) | (runaway ? (uint32_t)SVO_ERR_FLAG : 0u);
-                rays = 2;
-            }
-            store_hit(A.out, k, t, n, vox.material, flags, chunk, vox.node, vox.cell);
-        } else {
-            store_miss(A.out, k, runaway ? (uint32_t)SVO_ERR_FLAG : 0u);
-        }
-        if (A.counters) {
-            uint4 c; c.x = cnt.node_words; c.y = cnt.brick_cells; c.z = cnt.chunk_descs; c.w = cnt.tree_steps;
-            reinterpret_cast<uint4 *>(A.counters)[k] = c;
-        }
-    }
-    // rays marched: one atomic per wave (all 64 lanes reach this point)
-    unsigned total = rays;
-    for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off, 64);
-    if ((threadIdx.x & 63) == 0 && total) atomicAdd(&A.work[1], (unsigned long long)total);
-}
-
-// The see-through instantiation: the same body with lit_world<true>.  (It is not shared through a device function: a kernel that
-// calls one is scheduled differently, and k_trace_literal is kept as it was, instruction for instruction.)
-__global__ __launch_bounds__(256) void k_trace_literal_st(TraceArgs A, uint32_t ignore)
-{
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned rays = 0;
-    bool live = k < A.n;
-    V3 o = mk(0, 0, 0), d = mk(0, 0, 1);
-    if (live) {
-        if (A.from_camera) {
-            int px, py;
-            local_to_pixel(A, (int)(k % A.w), (int)(k / A.w), px, py);
-            if (py >= A.imgh || px >= A.imgw) { store_miss(A.out, k, 0); live = false; }
-            else camera_ray(A.cams[0], A.imgw, A.imgh, px, py, o, d);
-        } else {
-            o = ld3(A.origins + 3 * k);
-            d = ld3(A.dirs + 3 * k);
-        }
-    }
-    if (live) {
-        LitCounters cnt = { 0, 0, 0, 0 };
-        Voxel vox; vox.lo = mk(0, 0, 0); vox.size = 0; vox.material = 0; vox.node = 0; vox.cell = 0;
-        float t = 0.0f;
-        uint32_t chunk = 0;
-        rays = 1;
-        bool runaway = false;
-        if (lit_world<true>(A, o, d, t, vox, chunk, cnt, runaway, ignore)) {
-            const V3 point = o + d * (t - A.eps);
-            const bool face = A.normal_mode == SVO_NORMAL_FACE;
-            const V3 n = face ? face_normal(point, vox.lo, vox.lo + vox.size, d) : cube_normal(point, vox.lo, vox.lo + vox.size, A.eps);
-            uint32_t flags = SVO_HIT_FLAG | (face ? (uint32_t)SVO_FACE_NORMAL : 0u);
-            if (A.shadow) {
-                Voxel sv; float st; uint32_t sc;
-                const bool occluded = lit_world<true>(A, point, ld3(A.sdir), st, sv, sc, cnt, runaway, ignore);
-                flags |= SVO_SHADOW_TRACED | (occluded ? SVO_SHADOWED : 0u) | (runaway ? (uint32_t)SVO_ERR_FLAG : 0u);
-                rays = 2;
-            }
-            store_hit(A.out, k, t, n, vox.material, flags, chunk, vox.node, vox.cell);
-        } else {
-            store_miss(A.out, k, runaway ? (uint32_t)SVO_ERR_FLAG : 0u);
-        }
-        if (A.counters) {
-            uint4 c; c.x = cnt.node_words; c.y = cnt.brick_cells; c.z = cnt.chunk_descs; c.w = cnt.tree_steps;
-            reinterpret_cast<uint4 *>(A.counters)[k] = c;
-        }
-    }
-    // rays marched: one atomic per wave (all 64 lanes reach this point)
-    unsigned total = rays;
-    for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off, 64);
-    if ((threadIdx.x & 63) == 0 && total) atomicAdd(&A.work[1], (unsigned long long)total);
-}
-
-// The bounded instantiations (svo_trace_segments): ray k of the list ends at A.tmax[k].  List mode only.
-template <bool ST>
-__global__ __launch_bounds__(256) void k_trace_literal_seg(TraceArgs A, uint32_t ignore)
-{
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned rays = 0;
-    if (k < A.n) {
-        const V3 o = ld3(A.origins + 3 * k), d = ld3(A.dirs + 3 * k);
-        const float far = A.tmax[k];
-        LitCounters cnt = { 0, 0, 0, 0 };
-        Voxel vox; vox.lo = mk(0, 0, 0); vox.size = 0; vox.material = 0; vox.node = 0; vox.cell = 0;
-        float t = 0.0f;
-        uint32_t chunk = 0;
-        rays = 1;
-        bool runaway = false;
-        if (lit_world<ST, true>(A, o, d, t, vox, chunk, cnt, runaway, ignore, far) && t < far) {     // the strict compare decides the record
-            const V3 point = o + d * (t - A.eps);
-            const bool face = A.normal_mode == SVO_NORMAL_FACE;
-            const V3 n = face ? face_normal(point, vox.lo, vox.lo + vox.size, d) : cube_normal(point, vox.lo, vox.lo + vox.size, A.eps);
-            uint32_t flags = SVO_HIT_FLAG | (face ? (uint32_t)SVO_FACE_NORMAL : 0u);
-            if (A.shadow) {                                         // (unbounded: the light is a direction)
+            if (A.shadow) {                                         // (unbounded in every instantiation: the light is a direction)
                 Voxel sv; float st; uint32_t sc;
                 const bool occluded = lit_world<ST>(A, point, ld3(A.sdir), st, sv, sc, cnt, runaway, ignore);
                 flags |= SVO_SHADOW_TRACED | (occluded ? SVO_SHADOWED : 0u) | (runaway ? (uint32_t)SVO_ERR_FLAG : 0u);
@@ -344,6 +259,7 @@ __global__ __launch_bounds__(256) void k_trace_literal_seg(TraceArgs A, uint32_t
             reinterpret_cast<uint4 *>(A.counters)[k] = c;
         }
     }
+    // rays marched: one atomic per wave (all 64 lanes reach this point)
     unsigned total = rays;
     for (int off = 32; off > 0; off >>= 1) total += __shfl_down(total, off, 64);
     if ((threadIdx.x & 63) == 0 && total) atomicAdd(&A.work[1], (unsigned long long)total);
