@@ -50,6 +50,8 @@
  *   svo_shade_boxes      <- ImaginaryCube::draw and the lights' marker cubes over the finished image (src/Main.cpp:223-225)
  *                           src/ImaginaryCube.cpp:64-87, shaders/Imag.Fragment.glsl, src/Light.cpp:141-155, shaders/Light.Fragment.glsl
  *   svo_world_edit_cube  <- modify(): one cube to every chunk that holds one of its corners   src/Main.cpp:321-368
+ *   svo_world_edit_ball  <- (no counterpart; the reference edits cubes only) destroyCube / buildCube with a closed ball as the region
+ *   svo_world_edit_ball_all <- (no counterpart; the reference edits cubes only) one ball to every chunk whose box it touches
  *   svo_trace_local_shadows <- (a departure: the reference gives the directional light's shadow term to all three lights,
  *                           shaders/World.Fragment.glsl:186-190) one occlusion ray per hit towards the point light and the spotlight
  *
@@ -66,7 +68,7 @@
  *   - svo_trace* launches of one world may overlap on different streams (frames in flight); each
  *     launch owns a private work-cursor slot from a 64-entry ring, and a launch that comes round
  *     to a slot still in use is ordered on the device behind that earlier launch;
- *   - svo_world_update / svo_world_shift / svo_world_edit_box / svo_world_compact / svo_world_coarsen /
+ *   - svo_world_update / svo_world_shift / svo_world_edit_box / svo_world_edit_ball(_all) / svo_world_compact / svo_world_coarsen /
  *     svo_world_chunk_from_grid / svo_world_upload are ordered behind every launch issued before them on any stream
  *     (they drain the device before touching HBM, as World::modify is ordered on the GL queue) and have completed when they return: launches issued afterwards see
  *     the new world, launches issued before saw the old one, none sees a mixture.
@@ -99,7 +101,8 @@ extern "C" {
                                           svo_hit_voxels, svo_hit_uv, svo_shade_textured and svo_atlas,
                                           svo_shade_sky, svo_sky and svo_frame_rgba8,
                                           svo_cursor_place, svo_shade_boxes, svo_box and svo_world_edit_cube,
-                                          svo_chunk_from_grid, svo_world_chunk_from_grid and svo_world_chunk_to_grid */
+                                          svo_chunk_from_grid, svo_world_chunk_from_grid and svo_world_chunk_to_grid,
+                                          svo_world_edit_ball and svo_world_edit_ball_all */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -364,6 +367,37 @@ int svo_world_edit_box(svo_world *, int chunk, int op, const float lo[3], const 
  * and AN EDIT APPLIED BEFORE THE FAILING ONE STAYS APPLIED.  A NULL world or bmin, !(size > 0), a NaN or infinite bmin / size or an
  * unknown op: SVO_ERR_INVALID_ARG; then a world that is not resident: SVO_ERR_NOT_UPLOADED - both before anything changes or is written. */
 int svo_world_edit_cube(svo_world *, int op, const float bmin[3], float size, uint16_t material, int chunks_out[8], int *nchunks_out);
+
+/* svo_world_edit_box with the closed ball { p : |p - centre| <= radius } in the place of the closed box: a round hole, a crater, a round
+ * brush.  The reference edits cubes only; the result is defined by its destroyCube / buildCube recursion (src/Octree.cpp:203-430) with
+ * cubesIntersect(box, region) replaced by touch(box) and cube_is_inside(region, box) by inside(box) - visiting order, appends, the brick
+ * level, Octwig(material of the LEAF that is cut) and the doubling of the storage sizes stay as they are, so the pools are specified
+ * index for index.  Both predicates are in float, every operation separately rounded; R2 = radius * radius, lo the box's min corner as
+ * the box edit forms it, hi = lo + edge, c = centre:
+ *   touch:  per axis d = lo - c; if !(d > 0): d = c - hi; if still !(d > 0): d = 0;   touch = dx*dx + dy*dy + dz*dz <= R2
+ *   inside: per axis u = c - lo, v = hi - c, f = (u < v) ? v : u;                      inside = fx*fx + fy*fy + fz*fz <= R2
+ * (sums left to right).  A brick cell is edited iff touch(its box) - the conservative, closed rule the box edit applies to cells: build
+ * writes `material` to touched cells that hold 0, destroy writes 0 to touched cells, replace is destroy then build.  On exact geometry
+ * (power-of-two chunk size, integer position) the edit changes exactly the cells a pass over all cells with that rule would change
+ * (DESIGN.md 6n).  An R2 that overflows to +inf is legal: everything is touched.
+ * Ordered, complete and reported like svo_world_edit_box: an uploaded world only, the device drained first, SVO_OK or
+ * SVO_OK_LITERAL_ONLY, the host copy of the chunk dropped and fetched again on request.
+ * A NULL world or centre, a chunk out of range, an unknown op, a NaN or infinite centre, !(radius > 0) or an infinite radius:
+ * SVO_ERR_INVALID_ARG; then a world that is not resident: SVO_ERR_NOT_UPLOADED - both before anything changes. */
+int svo_world_edit_ball(svo_world *, int chunk, int op, const float centre[3], float radius, uint16_t material);
+
+/* The ball to every chunk whose box [position, position + (float)chunksize] it touches (the same touch, evaluated on the host), in
+ * ascending World::index() order, each chunk once.  Unlike svo_world_edit_cube's corner rule NO CHUNK BETWEEN THE EXTREMES IS SKIPPED: a
+ * ball wider than a chunk reaches every chunk it overlaps.
+ * *nchunks_out (may be NULL) always receives the number of touched chunks; chunks_out (may be NULL) receives them, chunks_cap is its
+ * length.  If chunks_out is given and the count exceeds chunks_cap the call is SVO_ERR_INVALID_ARG and nothing is edited - the count is
+ * still reported, so the caller can retry.  The list is written before the first edit.  A ball that touches no chunk: SVO_OK, count 0.
+ * Returns the largest positive status of the edits (SVO_OK_LITERAL_ONLY) or the first negative one; the edits stop at a failing chunk,
+ * and AN EDIT APPLIED BEFORE THE FAILING ONE STAYS APPLIED.  Argument checks as svo_world_edit_ball (without the chunk): a refused
+ * argument writes nothing.  The count needs no device: it is reported, and a chunks_cap it exceeds refused, before a world that is not
+ * resident is (SVO_ERR_NOT_UPLOADED, the list not written). */
+int svo_world_edit_ball_all(svo_world *, int op, const float centre[3], float radius, uint16_t material,
+                            int *chunks_out, int chunks_cap, int *nchunks_out);
 
 /* Ocroot::defragcopy (src/Octree.cpp:445-614) followed by World::modify with realloc (src/World.cpp:268-274) on chunk `chunk`:
  * the chunk is rebuilt from its root into fresh pools - depth-first, root at 0, blocks at 1 + 8k - so that what no BRANCH reaches

@@ -17,6 +17,7 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     frame_rgba8                               <- the RGBA8 colour attachment               src/GBuffer.cpp, shaders/GBuffer.Fragment.glsl:10
     cursor_place, shade_boxes, Box            <- computeTarget, ImaginaryCube / Light::draw   src/Main.cpp:314-319, src/ImaginaryCube.cpp:59-87
     World.edit_cube                           <- modify()                                  src/Main.cpp:321-368
+    World.edit_ball / edit_ball_all           <- (none: the reference edits cubes only)    destroyCube / buildCube over a closed ball
 
 There is NO CPU fallback: if libsvo_amd.so is missing the import raises, and every device call
 raises SvoError when HIP reports no device.
@@ -172,7 +173,7 @@ ABI_SYMBOLS = [
     "svo_world_generate", "svo_world_create", "svo_world_info_get", "svo_world_chunk", "svo_world_destroy",
     "svo_world_index_float", "svo_world_index", "svo_world_locate", "svo_hit_voxels", "svo_hit_uv", "svo_shade_textured", "svo_world_upload", "svo_world_update",
     "svo_chunk_from_grid", "svo_world_chunk_from_grid", "svo_world_chunk_to_grid",
-    "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_edit_cube", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_cursor_place", "svo_shade_boxes", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
+    "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_edit_cube", "svo_world_edit_ball", "svo_world_edit_ball_all", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_cursor_place", "svo_shade_boxes", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_device_count", "svo_device_alloc", "svo_device_free", "svo_device_cache_trim", "svo_memcpy_h2d", "svo_memcpy_d2h",
     "svo_stream_synchronize", "svo_last_error", "svo_abi_version",
@@ -183,6 +184,8 @@ lib.svo_last_error.restype = C.c_char_p
 lib.svo_abi_version.restype = C.c_int
 lib.svo_world_edit_box.argtypes = [_P, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint16]
 lib.svo_world_edit_cube.argtypes = [_P, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_uint16, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+lib.svo_world_edit_ball.argtypes = [_P, C.c_int, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_uint16]
+lib.svo_world_edit_ball_all.argtypes = [_P, C.c_int, C.POINTER(C.c_float), C.c_float, C.c_uint16, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]
 lib.svo_world_compact.argtypes = [_P, C.c_int]
 lib.svo_world_compact.restype = C.c_int
 lib.svo_world_coarsen.argtypes = [_P, C.c_int]
@@ -594,6 +597,20 @@ class World:
         chunks, n = (C.c_int * 8)(), C.c_int(0)
         rc = _check(lib.svo_world_edit_cube(self._h, int(op), None if bmin is None else (C.c_float * 3)(*[float(v) for v in bmin]), float(size),
                                             C.c_uint16(int(material)), chunks, C.byref(n)), "svo_world_edit_cube")
+        return rc, list(chunks[:n.value])
+
+    def edit_ball(self, chunk: int, op: int, centre, radius: float, material: int = 0):
+        """svo_world_edit_ball: edit_box with the closed ball |p - centre| <= radius as the region; op = EDIT_BUILD / EDIT_DESTROY / EDIT_REPLACE."""
+        return _check(lib.svo_world_edit_ball(self._h, int(chunk), int(op), None if centre is None else (C.c_float * 3)(*[float(v) for v in centre]),
+                                              float(radius), C.c_uint16(int(material))), "svo_world_edit_ball")
+
+    def edit_ball_all(self, op: int, centre, radius: float, material: int = 0):
+        """svo_world_edit_ball_all: the ball to every chunk whose box it touches, in World::index order, each once.  Returns (status,
+        [chunks edited, in order])."""
+        cap = max(int(self.info.width * self.info.height * self.info.depth), 1)
+        chunks, n = (C.c_int * cap)(), C.c_int(0)
+        rc = _check(lib.svo_world_edit_ball_all(self._h, int(op), None if centre is None else (C.c_float * 3)(*[float(v) for v in centre]),
+                                                float(radius), C.c_uint16(int(material)), chunks, cap, C.byref(n)), "svo_world_edit_ball_all")
         return rc, list(chunks[:n.value])
 
     def compact(self, chunk: int):

@@ -260,8 +260,50 @@ static_assert(FILL_DESCEND < (1u << FILL_ACTION_BITS), "every FillAction fits fi
 enum EditOp : uint32_t { EDIT_BUILD = 0, EDIT_DESTROY = 1 };
 constexpr uint32_t FILL_VIRTUAL = 0x80000000u, FILL_VIRTUAL_LEAF = 0x00010000u;
 
+// The region of an edit: two predicates over a node's or a brick cell's closed box [l, h] - touch for cubesIntersect(box, region),
+// inside for cube_is_inside(region, box).  The sweeps see the region nowhere else.
+struct BoxRegion {              // the closed box [lo, hi]
+    float lo[3], hi[3];
+    // cubesIntersect on closed boxes (src/Traverse.cpp:173-178), the host Filler's expressions
+    __device__ bool touch(float lx, float ly, float lz, float hx, float hy, float hz) const
+    {
+        return hx >= lo[0] && hy >= lo[1] && hz >= lo[2] && hi[0] >= lx && hi[1] >= ly && hi[2] >= lz;
+    }
+    // cubeIsInside (src/Traverse.cpp:180-185)
+    __device__ bool inside(float lx, float ly, float lz, float hx, float hy, float hz) const
+    {
+        return lx >= lo[0] && ly >= lo[1] && lz >= lo[2] && hi[0] >= hx && hi[1] >= hy && hi[2] >= hz;
+    }
+};
+struct BallRegion {             // the closed ball |p - c| <= radius, r2 = radius * radius (include/svo.h: svo_world_edit_ball)
+    float c[3], r2;
+    // distance from c to the box [l, h] along one axis: 0 between the faces
+    __device__ static float gap(float l, float h, float p)
+    {
+        float d = l - p;
+        if (!(d > 0.0f)) { d = p - h; if (!(d > 0.0f)) d = 0.0f; }
+        return d;
+    }
+    // distance from c to the box's farther face along one axis
+    __device__ static float reach(float l, float h, float p)
+    {
+        const float u = p - l, v = h - p;
+        return (u < v) ? v : u;
+    }
+    __device__ bool touch(float lx, float ly, float lz, float hx, float hy, float hz) const
+    {
+        const float dx = gap(lx, hx, c[0]), dy = gap(ly, hy, c[1]), dz = gap(lz, hz, c[2]);
+        return dx * dx + dy * dy + dz * dz <= r2;
+    }
+    // the box's farthest corner lies in the ball
+    __device__ bool inside(float lx, float ly, float lz, float hx, float hy, float hz) const
+    {
+        const float fx = reach(lx, hx, c[0]), fy = reach(ly, hy, c[1]), fz = reach(lz, hz, c[2]);
+        return fx * fx + fy * fy + fz * fz <= r2;
+    }
+};
+
 struct FillArgs {
-    float rlo[3], rhi[3];       // the region (closed box)
     float edge;                 // node edge at this level
     uint32_t level, maxlevel;   // maxlevel = depth - TWIG_LEVELS: nodes cut there become bricks
     uint32_t material;          // build: what the region is filled with
@@ -269,7 +311,8 @@ struct FillArgs {
 };
 
 // act[i] = fill_pack(action, kids) (kids = index of the node's child block in the next level's list; svo_format.h)
-__global__ __launch_bounds__(FILL_BLOCK) void k_fill_classify(const Cell *cells, uint32_t n, FillArgs F, const uint32_t *tree,
+template <class Region>
+__global__ __launch_bounds__(FILL_BLOCK) void k_fill_classify(const Cell *cells, uint32_t n, FillArgs F, Region R, const uint32_t *tree,
                                                               uint32_t *act, Cell *next, uint32_t *counters /* [0] child blocks, [1] brick edits */)
 {
     __shared__ uint32_t sh[FILL_BLOCK / 64 + 1];
@@ -278,13 +321,11 @@ __global__ __launch_bounds__(FILL_BLOCK) void k_fill_classify(const Cell *cells,
     const Cell e = live ? cells[i] : Cell{ 0.0f, 0.0f, 0.0f, 0u };
     const float hx = e.x + F.edge, hy = e.y + F.edge, hz = e.z + F.edge;
     uint32_t a = FILL_NONE, word = node_make(EMPTY, 0);
-    // cubesIntersect on closed boxes (src/Traverse.cpp:173-178), the host Filler's expressions
-    const bool touch = live && hx >= F.rlo[0] && hy >= F.rlo[1] && hz >= F.rlo[2] && F.rhi[0] >= e.x && F.rhi[1] >= e.y && F.rhi[2] >= e.z;
+    const bool touch = live && R.touch(e.x, e.y, e.z, hx, hy, hz);
     if (touch) {
         if (!(e.slot & FILL_VIRTUAL)) word = tree[e.slot];
         else if (e.slot & FILL_VIRTUAL_LEAF) word = node_make(LEAF, e.slot & 0xFFFFu);
-        // cubeIsInside (src/Traverse.cpp:180-185)
-        const bool inside = e.x >= F.rlo[0] && e.y >= F.rlo[1] && e.z >= F.rlo[2] && F.rhi[0] >= hx && F.rhi[1] >= hy && F.rhi[2] >= hz;
+        const bool inside = R.inside(e.x, e.y, e.z, hx, hy, hz);
         const uint32_t type = node_type(word);
         if (F.op == EDIT_BUILD) {           // buildCube, src/Octree.cpp:338-430
             if (type == EMPTY) a = inside ? FILL_SET : (F.level == F.maxlevel ? FILL_NEW_BRICK : FILL_SPLIT);
@@ -384,10 +425,9 @@ __global__ __launch_bounds__(FILL_BLOCK) void k_fill_number(Cell *cells, uint32_
 }
 
 // The brick half of both edits (src/Octree.cpp:395-410 / :285-300): build - a cell that is empty and whose voxel box touches the
-// region takes the material; destroy - a cell whose voxel box touches the region is emptied (cubesIntersect on closed boxes,
-// the host Filler's expressions).
-__global__ __launch_bounds__(256) void k_brick_edit(uint16_t *twig, const DevBrickOp *ops, uint32_t n, uint32_t edit,
-                                                    float rlx, float rly, float rlz, float rhx, float rhy, float rhz, uint32_t material)
+// region takes the material; destroy - a cell whose voxel box touches the region is emptied (the region's touch on closed boxes).
+template <class Region>
+__global__ __launch_bounds__(256) void k_brick_edit(uint16_t *twig, const DevBrickOp *ops, uint32_t n, uint32_t edit, Region R, uint32_t material)
 {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n * 64u) return;
@@ -397,7 +437,7 @@ __global__ __launch_bounds__(256) void k_brick_edit(uint16_t *twig, const DevBri
     const uint32_t before = op.fresh ? op.init : (uint32_t)*p;
     const float lx = op.x + (float)cx * op.voxel, ly = op.y + (float)cy * op.voxel, lz = op.z + (float)cz * op.voxel;
     const float hx = lx + op.voxel, hy = ly + op.voxel, hz = lz + op.voxel;
-    const bool touch = hx >= rlx && hy >= rly && hz >= rlz && rhx >= lx && rhy >= ly && rhz >= lz;
+    const bool touch = R.touch(lx, ly, lz, hx, hy, hz);
     uint32_t after = before;
     if (edit == EDIT_BUILD) { if (before == 0u && touch) after = material; }
     else if (touch) after = 0u;
@@ -411,11 +451,18 @@ struct DeviceFiller {
     DevBuf<DevBrickOp> ops;
     Pinned<uint32_t> h_counters;
 
-    // Ocroot::build (edit = EDIT_BUILD: region [lo, hi] filled with `material`) or Ocroot::destroy (EDIT_DESTROY: emptied) applied
+    // Ocroot::build (edit = EDIT_BUILD: region R filled with `material`) or Ocroot::destroy (EDIT_DESTROY: emptied) applied
     // to the chunk in `tree` (trees nodes) and `twig` (twigs bricks); both buffers grow as needed, c's capacities follow the
     // reference's doubling.
     int fill(ChunkPools &c, const float lo[3], const float hi[3], uint32_t material, DevBuf<uint32_t> &tree, uint64_t &trees,
              DevBuf<uint16_t> &twig, uint64_t &twigs, hipStream_t s, uint32_t edit = EDIT_BUILD)
+    {
+        const BoxRegion R = { { lo[0], lo[1], lo[2] }, { hi[0], hi[1], hi[2] } };
+        return fill(c, R, material, tree, trees, twig, twigs, s, edit);
+    }
+    template <class Region>
+    int fill(ChunkPools &c, const Region &R, uint32_t material, DevBuf<uint32_t> &tree, uint64_t &trees,
+             DevBuf<uint16_t> &twig, uint64_t &twigs, hipStream_t s, uint32_t edit)
     {
         int rc;
         const uint32_t maxlevel = c.depth - TWIG_LEVELS;
@@ -424,7 +471,6 @@ struct DeviceFiller {
         if ((rc = h_counters.alloc(80)) != SVO_OK) return rc;
         HIP_TRY(hipMemsetAsync(counters.p, 0, 80 * sizeof(uint32_t), s));
         FillArgs F{};
-        for (int a = 0; a < 3; ++a) { F.rlo[a] = lo[a]; F.rhi[a] = hi[a]; }
         F.maxlevel = maxlevel; F.material = material; F.op = edit;
         // sweep A
         if ((rc = lv[0].cells.reserve(1, false, s)) != SVO_OK) return rc;
@@ -442,7 +488,7 @@ struct DeviceFiller {
             if ((rc = L.act.reserve(n, false, s)) != SVO_OK || (rc = L.cnt.reserve(n, false, s)) != SVO_OK ||
                 (rc = N.cells.reserve((uint64_t)n * 8, false, s)) != SVO_OK) return rc;
             F.level = level; F.edge = edge;
-            hipLaunchKernelGGL(k_fill_classify, dim3(blocks_for(n, FILL_BLOCK)), dim3(FILL_BLOCK), 0, s, L.cells.p, n, F, tree.p, L.act.p, N.cells.p, counters.p + 2 * level);
+            hipLaunchKernelGGL(k_fill_classify<Region>, dim3(blocks_for(n, FILL_BLOCK)), dim3(FILL_BLOCK), 0, s, L.cells.p, n, F, R, tree.p, L.act.p, N.cells.p, counters.p + 2 * level);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(h_counters.p, counters.p + 2 * level, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
@@ -479,8 +525,8 @@ struct DeviceFiller {
                                (uint32_t)trees, (uint32_t)twigs, tree.p, ops.p, counters.p + 64);
         }
         if (brick_edits)
-            hipLaunchKernelGGL(k_brick_edit, dim3(blocks_for((uint64_t)brick_edits * 64, 256)), dim3(256), 0, s, twig.p, ops.p, brick_edits, edit,
-                               F.rlo[0], F.rlo[1], F.rlo[2], F.rhi[0], F.rhi[1], F.rhi[2], material);
+            hipLaunchKernelGGL(k_brick_edit<Region>, dim3(blocks_for((uint64_t)brick_edits * 64, 256)), dim3(256), 0, s, twig.p, ops.p, brick_edits, edit,
+                               R, material);
         HIP_TRY(hipGetLastError());
         // capacity bookkeeping of the reference's appends (src/Octree.cpp:349-351,365-368; terrain.cpp's Filler)
         if (total.x) while (trees1 >= c.tree_capacity) c.tree_capacity *= 2;
@@ -705,7 +751,8 @@ int shift_world_resident(svo_world &w, int axis, int sign)
 // src/Main.cpp:340-367) on an uploaded world, without the host: the chunk's pools are copied out of the packed pools, edited by
 // the three sweeps above and installed again with svo_world_update's slot logic.  A host copy of the chunk, if there was one,
 // is dropped (svo_world_chunk fetches the edited pools on request).
-static int edit_box_resident_impl(svo_world &w, int chunk, int op, const float lo[3], const float hi[3], uint32_t material)
+template <class Region>
+static int edit_resident_impl(svo_world &w, int chunk, int op, const Region &R, uint32_t material)
 {
     HIP_TRY(hipSetDevice(w.device));
     HIP_TRY(hipDeviceSynchronize());              // ordered behind every launch issued before it, like svo_world_update
@@ -726,17 +773,26 @@ static int edit_box_resident_impl(svo_world &w, int chunk, int op, const float l
     meta.tree_capacity = c.tree_capacity; meta.twig_capacity = c.twig_capacity;
     DeviceFiller &filler = ctx.filler;
     if (op == SVO_EDIT_DESTROY || op == SVO_EDIT_REPLACE)
-        if ((rc = filler.fill(meta, lo, hi, material, tree, trees, twig, twigs, s, EDIT_DESTROY)) != SVO_OK) return rc;
+        if ((rc = filler.fill(meta, R, material, tree, trees, twig, twigs, s, EDIT_DESTROY)) != SVO_OK) return rc;
     if (op == SVO_EDIT_BUILD || op == SVO_EDIT_REPLACE)
-        if ((rc = filler.fill(meta, lo, hi, material, tree, trees, twig, twigs, s, EDIT_BUILD)) != SVO_OK) return rc;
+        if ((rc = filler.fill(meta, R, material, tree, trees, twig, twigs, s, EDIT_BUILD)) != SVO_OK) return rc;
     meta.trees_on_device = trees; meta.twigs_on_device = twigs;
     return install_resident_chunk(w, chunk, meta, tree.p, twig.p);
 }
 
 int edit_box_resident(svo_world &w, int chunk, int op, const float lo[3], const float hi[3], uint32_t material)
 {
-    try { return edit_box_resident_impl(w, chunk, op, lo, hi, material); }
+    const BoxRegion R = { { lo[0], lo[1], lo[2] }, { hi[0], hi[1], hi[2] } };
+    try { return edit_resident_impl(w, chunk, op, R, material); }
     catch (const std::bad_alloc &) { set_error("svo_world_edit_box: out of host memory"); return SVO_ERR_OUT_OF_MEMORY; }
+}
+
+// The same edit with the closed ball |p - centre| <= radius as its region (svo_world_edit_ball).
+int edit_ball_resident(svo_world &w, int chunk, int op, const float centre[3], float radius, uint32_t material)
+{
+    const BallRegion R = { { centre[0], centre[1], centre[2] }, radius * radius };
+    try { return edit_resident_impl(w, chunk, op, R, material); }
+    catch (const std::bad_alloc &) { set_error("svo_world_edit_ball: out of host memory"); return SVO_ERR_OUT_OF_MEMORY; }
 }
 
 int generate_world_resident(svo_world &w, int device)

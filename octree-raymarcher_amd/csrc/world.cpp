@@ -262,6 +262,53 @@ int svo_world_edit_cube(svo_world *w, int op, const float bmin[3], float size, u
     return status;
 }
 
+// svo_world_edit_ball's arguments, settled before anything changes (shared with svo_world_edit_ball_all)
+static bool ball_args_ok(const svo_world *w, int op, const float centre[3], float radius)
+{
+    bool ok = w && centre && op >= SVO_EDIT_BUILD && op <= SVO_EDIT_REPLACE && radius > 0.0f && std::isfinite(radius);
+    for (int a = 0; ok && a < 3; ++a) ok = std::isfinite(centre[a]);
+    return ok;
+}
+
+int svo_world_edit_ball(svo_world *w, int chunk, int op, const float centre[3], float radius, uint16_t material)
+{
+    if (!ball_args_ok(w, op, centre, radius) || chunk < 0 || chunk >= (int)w->chunks.size()) { set_error("svo_world_edit_ball: bad argument"); return SVO_ERR_INVALID_ARG; }
+    if (w->device < 0) { set_error("svo_world_edit_ball: the world is not uploaded"); return SVO_ERR_NOT_UPLOADED; }
+    return edit_ball_resident(*w, chunk, op, centre, radius, material);
+}
+
+int svo_world_edit_ball_all(svo_world *w, int op, const float centre[3], float radius, uint16_t material, int *chunks_out, int chunks_cap, int *nchunks_out)
+{
+    if (!ball_args_ok(w, op, centre, radius)) { set_error("svo_world_edit_ball_all: bad argument"); return SVO_ERR_INVALID_ARG; }
+    // the ball's touch (builder.hip: BallRegion) on every chunk's box [position, position + chunksize], in float
+    const float cs = (float)w->chunksize, r2 = radius * radius;
+    std::vector<int> list;
+    try { list.reserve(w->chunks.size()); }
+    catch (const std::bad_alloc &) { set_error("svo_world_edit_ball_all: out of host memory"); return SVO_ERR_OUT_OF_MEMORY; }
+    for (int j = 0; j < (int)w->chunks.size(); ++j) {
+        const float *lo = w->chunks[(size_t)j].position;
+        float d[3];
+        for (int a = 0; a < 3; ++a) {
+            const float hi = lo[a] + cs;
+            d[a] = lo[a] - centre[a];
+            if (!(d[a] > 0.0f)) { d[a] = centre[a] - hi; if (!(d[a] > 0.0f)) d[a] = 0.0f; }
+        }
+        if (d[0] * d[0] + d[1] * d[1] + d[2] * d[2] <= r2) list.push_back(j);
+    }
+    const int n = (int)list.size();
+    if (nchunks_out) *nchunks_out = n;
+    if (chunks_out && n > chunks_cap) { set_error("svo_world_edit_ball_all: the ball touches more chunks than chunks_cap holds"); return SVO_ERR_INVALID_ARG; }
+    if (w->device < 0) { set_error("svo_world_edit_ball_all: the world is not uploaded"); return SVO_ERR_NOT_UPLOADED; }
+    if (chunks_out) for (int k = 0; k < n; ++k) chunks_out[k] = list[(size_t)k];
+    int status = SVO_OK;
+    for (int k = 0; k < n; ++k) {
+        const int rc = edit_ball_resident(*w, list[(size_t)k], op, centre, radius, material);
+        if (rc < 0) return rc;
+        if (rc > status) status = rc;
+    }
+    return status;
+}
+
 int svo_world_info_get(const svo_world *w, svo_world_info *o)
 {
     if (!w || !o) return SVO_ERR_INVALID_ARG;

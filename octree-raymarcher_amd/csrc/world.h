@@ -63,6 +63,8 @@ int  generate_world_resident(svo_world &w, int device);
 void free_builder_context(svo_world &w);
 // builder.hip: Ocroot::build / destroy / replace + World::modify on an uploaded world
 int  edit_box_resident(svo_world &w, int chunk, int op, const float lo[3], const float hi[3], uint32_t material);
+// builder.hip: the same edit with the closed ball |p - centre| <= radius as its region
+int  edit_ball_resident(svo_world &w, int chunk, int op, const float centre[3], float radius, uint32_t material);
 // builder.hip: World::shift's entering plane generated on the device the world is uploaded to
 int  shift_world_resident(svo_world &w, int axis, int sign);
 // builder.hip: the working buffers svo_world_edit_box keeps between calls, lent to compact.hip - the edit's output pools (grown to

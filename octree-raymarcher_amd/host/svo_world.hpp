@@ -19,6 +19,7 @@
 //   svo::World::shade_sky / frame_rgba8  <- Skybox::draw and the RGBA8 colour attachment (svo_shade_sky, svo_frame_rgba8)   src/Skybox.cpp, src/GBuffer.cpp
 //   svo::World::cursor_place / shade_boxes / edit_cube  <- computeTarget, ImaginaryCube::draw, modify() (svo_cursor_place, svo_shade_boxes,
 //                                       svo_world_edit_cube)   src/Main.cpp:314-368, src/ImaginaryCube.cpp:59-87
+//   svo::World::edit_ball / edit_ball_all  <- (none: the reference edits cubes only) svo_world_edit_ball, svo_world_edit_ball_all
 //   svo::World::deinit()             <- World::deinit          src/World.cpp:129-151
 //   svo::chunkmarch(alpha,beta,world,&sigma) <- chunkmarch     src/Traverse.cpp:127-171
 //
@@ -277,6 +278,23 @@ public:
         int chunks[8], n = 0;
         check(svo_world_edit_cube(world_, op, lo, size, material, chunks, &n), "World::edit_cube");
         return std::vector<int>(chunks, chunks + n);
+    }
+
+    // No counterpart in the reference, which edits cubes only: the closed ball |p - centre| <= radius built into / destroyed in / replaced
+    // in chunk i (svo_world_edit_ball), or in every chunk whose box it touches (svo_world_edit_ball_all; returns the chunks edited).
+    void edit_ball(int i, int op, vec3 centre, float radius, uint16_t material)
+    {
+        const float c[3] = { centre.x, centre.y, centre.z };
+        check(svo_world_edit_ball(world_, i, op, c, radius, material), "World::edit_ball");
+    }
+    std::vector<int> edit_ball_all(int op, vec3 centre, float radius, uint16_t material)
+    {
+        const float c[3] = { centre.x, centre.y, centre.z };
+        std::vector<int> chunks((size_t)(volume > 0 ? volume : 1));
+        int n = 0;
+        check(svo_world_edit_ball_all(world_, op, c, radius, material, chunks.data(), (int)chunks.size(), &n), "World::edit_ball_all");
+        chunks.resize((size_t)n);
+        return chunks;
     }
 
     // World::shift(offset): slide the grid by one chunk (src/World.cpp:334-378).
