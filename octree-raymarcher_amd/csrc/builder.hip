@@ -19,13 +19,10 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
-#include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <cstring>
-#include <new>
 #include <thread>
 #include <vector>
 
@@ -452,16 +449,10 @@ struct DeviceFiller {
     Pinned<uint32_t> h_counters;
 
     // Ocroot::build (edit = EDIT_BUILD: region R filled with `material`) or Ocroot::destroy (EDIT_DESTROY: emptied) applied
-    // to the chunk in `tree` (trees nodes) and `twig` (twigs bricks); both buffers grow as needed, c's capacities follow the
-    // reference's doubling.
-    int fill(ChunkPools &c, const float lo[3], const float hi[3], uint32_t material, DevBuf<uint32_t> &tree, uint64_t &trees,
-             DevBuf<uint16_t> &twig, uint64_t &twigs, hipStream_t s, uint32_t edit = EDIT_BUILD)
-    {
-        const BoxRegion R = { { lo[0], lo[1], lo[2] }, { hi[0], hi[1], hi[2] } };
-        return fill(c, R, material, tree, trees, twig, twigs, s, edit);
-    }
+    // to the chunk in `tree` (trees nodes) and `twig` (twigs bricks) whose frame - position, size, depth - is c's; both buffers grow
+    // as needed, the capacities cap = { tree, twig } follow the reference's doubling.
     template <class Region>
-    int fill(ChunkPools &c, const Region &R, uint32_t material, DevBuf<uint32_t> &tree, uint64_t &trees,
+    int fill(const ChunkPools &c, uint64_t cap[2], const Region &R, uint32_t material, DevBuf<uint32_t> &tree, uint64_t &trees,
              DevBuf<uint16_t> &twig, uint64_t &twigs, hipStream_t s, uint32_t edit)
     {
         int rc;
@@ -529,81 +520,56 @@ struct DeviceFiller {
                                R, material);
         HIP_TRY(hipGetLastError());
         // capacity bookkeeping of the reference's appends (src/Octree.cpp:349-351,365-368; terrain.cpp's Filler)
-        if (total.x) while (trees1 >= c.tree_capacity) c.tree_capacity *= 2;
-        while (twigs1 > c.twig_capacity) c.twig_capacity *= 2;
+        if (total.x) while (trees1 >= cap[0]) cap[0] *= 2;
+        while (twigs1 > cap[1]) cap[1] *= 2;
         trees = trees1; twigs = twigs1;
         return SVO_OK;
     }
 };
 
 struct DeviceGrower {
-    DevBuf<Cell> frontier, next, jobs;
-    DevBuf<uint32_t> word, tree, totals;
-    DevBuf<unsigned long long> flags, rank;
+    DevBuf<uint32_t> tree;
     DevBuf<uint16_t> twig;
-    DevBuf<unsigned char> scan_tmp;
-    Pinned<uint32_t> h_totals;
-
     uint64_t hint_tree = 1024, hint_twig = 0;   // what the previous chunk needed: the next one starts there instead of doubling its way up
 
-    // grow() and - if the terrain has water - Ocroot::build behind it, both on the device.  Node words and bricks stay in HBM:
-    // tree_dev / bricks_dev receive the device arrays, c.trees_on_device / c.twigs_on_device their lengths; the host copies are
-    // fetched on request (device.hip: fetch_pools).
+    // grow() (bfs_grow over the arrays B) and - if the terrain has water - Ocroot::build behind it, both on the device.  Node words and
+    // bricks stay in HBM: tree_dev / bricks_dev receive the device arrays, c.trees_on_device / c.twigs_on_device their lengths; the
+    // host copies are fetched on request (device.hip: fetch_pools).
     int grow(ChunkPools &c, const float position[3], float size, uint32_t depth, const DevPyramid &P, const TerrainParams &tp, hipStream_t s,
-             DeviceFiller &filler, DevBuf<uint32_t> &tree_dev, DevBuf<uint16_t> &bricks_dev)
+             BfsArrays &B, DeviceFiller &filler, DevBuf<uint32_t> &tree_dev, DevBuf<uint16_t> &bricks_dev)
     {
         c.position[0] = position[0]; c.position[1] = position[1]; c.position[2] = position[2];
         c.size = size; c.depth = depth;
-        c.tree_capacity = 16; c.twig_capacity = 16;
-        uint64_t trees = 1, twigs = 0;
+        uint64_t trees = 1, twigs = 0, cap[2] = { 16, 16 };
         int rc;
-        if ((rc = frontier.reserve(1, false, s)) != SVO_OK || (rc = tree.reserve(hint_tree, false, s)) != SVO_OK ||
-            (hint_twig && (rc = twig.reserve(hint_twig, false, s)) != SVO_OK) || (rc = totals.reserve(64, false, s)) != SVO_OK) return rc;
-        if ((rc = h_totals.alloc(2)) != SVO_OK) return rc;
-        HIP_TRY(hipMemsetAsync(totals.p, 0, 64 * sizeof(uint32_t), s));
-        const Cell root = { position[0], position[1], position[2], 0u };
-        HIP_TRY(hipMemcpyAsync(frontier.p, &root, sizeof root, hipMemcpyHostToDevice, s));
-        uint32_t n = 1;
-        float edge = size;
+        if ((rc = tree.reserve(hint_tree, false, s)) != SVO_OK || (hint_twig && (rc = twig.reserve(hint_twig, false, s)) != SVO_OK)) return rc;
         GrowArgs G{};
         G.px = position[0]; G.py = position[1]; G.pz = position[2]; G.size = size; G.depth = depth;
         const bool coarse = tp.coarse_depth >= TWIG_LEVELS && tp.coarse_depth < depth;
         G.coarse_depth = coarse ? tp.coarse_depth : 0;
         for (int a = 0; a < 3; ++a) { G.rmin[a] = tp.refine_min[a]; G.rmax[a] = tp.refine_max[a]; }
-
-        for (uint32_t level = 0; n > 0; ++level) {
-            const float half = edge / 2;
-            G.level = level; G.edge = edge;
-            if (level >= 32) { set_error("device builder: more than 32 levels"); return SVO_ERR_UNSUPPORTED; }
-            if ((rc = word.reserve(n, false, s)) != SVO_OK || (rc = flags.reserve(n, false, s)) != SVO_OK || (rc = rank.reserve(n, false, s)) != SVO_OK) return rc;
-            hipLaunchKernelGGL(k_classify, dim3(blocks_for(n, 256)), dim3(256), 0, s, frontier.p, n, G, P, word.p, flags.p);
-            size_t need = 0;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, flags.p, rank.p, (int)n, s));
-            if ((rc = scan_tmp.reserve(need + 16, false, s)) != SVO_OK) return rc;
-            HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp.p, need, flags.p, rank.p, (int)n, s));
-            hipLaunchKernelGGL(k_level_totals, dim3(1), dim3(1), 0, s, flags.p, rank.p, n, totals.p + 2 * level);
-            HIP_TRY(hipMemcpyAsync(h_totals.p, totals.p + 2 * level, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            const uint64_t nb = h_totals.p[0], nt = h_totals.p[1];
-            if (trees + 8 * nb >= (1ull << 30) || twigs + nt >= (1ull << 30)) { set_error("device builder: chunk exceeds the 30-bit node offset"); return SVO_ERR_UNSUPPORTED; }
-            if ((rc = tree.reserve(trees + 8 * nb, true, s)) != SVO_OK || (rc = twig.reserve((twigs + nt) * TWIG_WORDS, true, s)) != SVO_OK ||
-                (rc = next.reserve(std::max<uint64_t>(8 * nb, 1), false, s)) != SVO_OK || (rc = jobs.reserve(std::max<uint64_t>(nt, 1), false, s)) != SVO_OK) return rc;
-            hipLaunchKernelGGL(k_emit<float>, dim3(blocks_for(n, 256)), dim3(256), 0, s, frontier.p, n, half, word.p, rank.p,
-                               (uint32_t)trees, (uint32_t)twigs, tree.p, next.p, jobs.p);
-            if (nt) hipLaunchKernelGGL(k_bricks_rows, dim3(blocks_for(nt * 4, 256)), dim3(256), 0, s, jobs.p, (uint32_t)nt, G, P, twig.p);
-            HIP_TRY(hipGetLastError());
-            // capacity bookkeeping exactly as the host builder (src/Octree.cpp:149-150,160-161)
-            if (nb) while (trees + 8 * nb >= c.tree_capacity) c.tree_capacity *= 2;
-            while (twigs + nt > c.twig_capacity) c.twig_capacity *= 2;
-            trees += 8 * nb; twigs += nt;
-            std::swap(frontier, next);
-            n = (uint32_t)(8 * nb);
-            edge = half;
-        }
+        rc = bfs_grow<float>(B, Cell{ position[0], position[1], position[2], 0u }, size, trees, twigs, tree.p, s,
+            [&](uint32_t level, float edge, const Cell *frontier, uint32_t n, uint32_t *word, unsigned long long *flags) -> int {
+                if (level >= 32) { set_error("device builder: more than 32 levels"); return SVO_ERR_UNSUPPORTED; }
+                G.level = level; G.edge = edge;
+                hipLaunchKernelGGL(k_classify, dim3(blocks_for(n, 256)), dim3(256), 0, s, frontier, n, G, P, word, flags);
+                return SVO_OK;
+            },
+            [&](uint64_t nb, uint64_t nt) -> int {
+                if (trees + 8 * nb >= (1ull << 30) || twigs + nt >= (1ull << 30)) { set_error("device builder: chunk exceeds the 30-bit node offset"); return SVO_ERR_UNSUPPORTED; }
+                // capacity bookkeeping exactly as the host builder (src/Octree.cpp:149-150,160-161)
+                if (nb) while (trees + 8 * nb >= cap[0]) cap[0] *= 2;
+                while (twigs + nt > cap[1]) cap[1] *= 2;
+                const int r = tree.reserve(trees + 8 * nb, true, s);
+                return r != SVO_OK ? r : twig.reserve((twigs + nt) * TWIG_WORDS, true, s);
+            },
+            [&](const Cell *jobs, uint32_t nt) { hipLaunchKernelGGL(k_bricks_rows, dim3(blocks_for((uint64_t)nt * 4, 256)), dim3(256), 0, s, jobs, nt, G, P, twig.p); });
+        if (rc != SVO_OK) return rc;
         if (tp.water) {     // World::g_chunk, src/World.cpp:316-320: everything of the chunk below the water level
-            const float hi[3] = { position[0] + size, tp.water_level, position[2] + size };
-            if ((rc = filler.fill(c, position, hi, tp.water_material, tree, trees, twig, twigs, s)) != SVO_OK) return rc;
+            const BoxRegion R = { { position[0], position[1], position[2] }, { position[0] + size, tp.water_level, position[2] + size } };
+            if ((rc = filler.fill(c, cap, R, tp.water_material, tree, trees, twig, twigs, s, EDIT_BUILD)) != SVO_OK) return rc;
         }
+        c.tree_capacity = cap[0]; c.twig_capacity = cap[1];
         c.tree.clear(); c.twig.clear();
         c.trees_on_device = trees;
         c.twigs_on_device = twigs;
@@ -613,22 +579,52 @@ struct DeviceGrower {
     }
 };
 
+// The builders and their working buffers.  svo_world_shift, the edits, compact / coarsen and the grid calls keep one between calls on
+// an uploaded world (created by the first of them, freed with the device copy) - a few hundred MB for depth-12 chunks, DESIGN.md §6o
+// has the figures - so that an interactive caller's edits and slides do not pay some forty hipMalloc / hipFree each.
+struct BuilderContext {
+    DevicePyramidBuilder pyr;
+    DeviceGrower grower;
+    DeviceFiller filler;
+    BfsArrays bfs;                          // the grower's and grid.hip's level arrays
+    DevBuf<uint32_t> edit_tree;             // the pools an edit, compact / coarsen or the grid writes before they are installed
+    DevBuf<uint16_t> edit_twig;
+    LodScratch lod;
+    GridScratch grid;
+};
+static BuilderContext &builder_context(svo_world &w)
+{
+    if (!w.builder_ctx) w.builder_ctx = new BuilderContext();
+    return *static_cast<BuilderContext *>(w.builder_ctx);
+}
+BfsArrays &bfs_arrays(svo_world &w) { return builder_context(w).bfs; }
+LodScratch &lod_scratch(svo_world &w) { return builder_context(w).lod; }
+GridScratch &grid_scratch(svo_world &w) { return builder_context(w).grid; }
+int edit_scratch(svo_world &w, uint64_t trees, uint64_t twigs, uint32_t **tree, uint16_t **twig)
+{
+    BuilderContext &ctx = builder_context(w);
+    int rc;
+    if ((rc = ctx.edit_tree.reserve(std::max<uint64_t>(trees, 1), false, nullptr)) != SVO_OK ||
+        (rc = ctx.edit_twig.reserve(std::max<uint64_t>(twigs, 1) * TWIG_WORDS, false, nullptr)) != SVO_OK) return rc;
+    *tree = ctx.edit_tree.p; *twig = ctx.edit_twig.p;
+    return SVO_OK;
+}
+
 // A chunk of a terrain window grown on the device with its device arrays (node words, bricks); a GrownWindow lists them in walk
 // order, and a failure on the way frees whatever was grown.
 struct GrownChunk { ChunkPools meta; int index = 0; DevBuf<uint32_t> tree_dev; DevBuf<uint16_t> twig_dev; };
 using GrownWindow = std::vector<GrownChunk>;
 
 // World::g_pyramid + g_chunk (src/World.cpp:296-321) on the device for every chunk of `win`, a column's pyramid built once.
-static int grow_window(const TerrainWindow &win, const TerrainParams &tp, DevicePyramidBuilder &pyr, DeviceGrower &grower,
-                       DeviceFiller &filler, hipStream_t s, GrownWindow &out)
+static int grow_window(const TerrainWindow &win, const TerrainParams &tp, BuilderContext &ctx, hipStream_t s, GrownWindow &out)
 {
     for (int k = 0; k < win.size(); ++k) {
         const TerrainWindow::Chunk at = win.chunk(k);
         int rc;
-        if (k % win.column_height() == 0 && (rc = pyr.build(column_pyramid(tp, at.x, at.z), s)) != SVO_OK) return rc;
+        if (k % win.column_height() == 0 && (rc = ctx.pyr.build(column_pyramid(tp, at.x, at.z), s)) != SVO_OK) return rc;
         GrownChunk &e = out.emplace_back();
         e.index = at.index;
-        if ((rc = grower.grow(e.meta, at.position, (float)win.chunksize, tp.depth, pyr.view, tp, s, filler, e.tree_dev, e.twig_dev)) != SVO_OK) return rc;
+        if ((rc = ctx.grower.grow(e.meta, at.position, (float)win.chunksize, tp.depth, ctx.pyr.view, tp, s, ctx.bfs, ctx.filler, e.tree_dev, e.twig_dev)) != SVO_OK) return rc;
     }
     return SVO_OK;
 }
@@ -650,11 +646,8 @@ static int generate_world_resident_impl(svo_world &w, int device)
     GrownWindow grown;
     hipStream_t s = nullptr;
     {
-        DevicePyramidBuilder pyr;
-        DeviceGrower grower;
-        DeviceFiller filler;
-        const int rc = grow_window(TerrainWindow::whole(w.width, w.height, w.depth, w.chunksize, w.chunkcoordmin), w.terrain,
-                                   pyr, grower, filler, s, grown);
+        BuilderContext ctx;                 // (its buffers are gone before the pools are allocated)
+        const int rc = grow_window(TerrainWindow::whole(w.width, w.height, w.depth, w.chunksize, w.chunkcoordmin), w.terrain, ctx, s, grown);
         if (rc != SVO_OK) return rc;
         lapt("noise + mips + grow + fill");
     }
@@ -676,40 +669,6 @@ static int generate_world_resident_impl(svo_world &w, int device)
     return literal_only ? SVO_OK_LITERAL_ONLY : SVO_OK;
 }
 
-// What svo_world_shift and svo_world_edit_box keep between calls on an uploaded world (created by the first one, freed with the
-// device copy): the builders' working buffers - a few hundred MB for depth-12 chunks - so that an interactive caller's edits and
-// slides do not pay some forty hipMalloc / hipFree each.
-struct BuilderContext {
-    DevicePyramidBuilder pyr;
-    DeviceGrower grower;
-    DeviceFiller filler;
-    DevBuf<uint32_t> edit_tree;
-    DevBuf<uint16_t> edit_twig;
-    std::vector<DevBuf<uint8_t>> sweep;     // compact.hip's level arrays
-};
-static BuilderContext &builder_context(svo_world &w)
-{
-    if (!w.builder_ctx) w.builder_ctx = new BuilderContext();
-    return *static_cast<BuilderContext *>(w.builder_ctx);
-}
-int edit_scratch(svo_world &w, uint64_t trees, uint64_t twigs, uint32_t **tree, uint16_t **twig)
-{
-    BuilderContext &ctx = builder_context(w);
-    int rc;
-    if ((rc = ctx.edit_tree.reserve(std::max<uint64_t>(trees, 1), false, nullptr)) != SVO_OK ||
-        (rc = ctx.edit_twig.reserve(std::max<uint64_t>(twigs, 1) * TWIG_WORDS, false, nullptr)) != SVO_OK) return rc;
-    *tree = ctx.edit_tree.p; *twig = ctx.edit_twig.p;
-    return SVO_OK;
-}
-int sweep_scratch(svo_world &w, uint32_t k, size_t bytes, void **out)
-{
-    BuilderContext &ctx = builder_context(w);
-    if (ctx.sweep.size() <= k) ctx.sweep.resize(k + 1);
-    const int rc = ctx.sweep[k].reserve(std::max<size_t>(bytes, 16), false, nullptr);
-    if (rc != SVO_OK) return rc;
-    *out = ctx.sweep[k].p;
-    return SVO_OK;
-}
 void free_builder_context(svo_world &w)
 {
     delete static_cast<BuilderContext *>(w.builder_ctx);
@@ -728,8 +687,7 @@ static int shift_world_resident_impl(svo_world &w, int axis, int sign)
     // slots hold chunks of two positions of the window ("none sees a mixture", svo.h); a wide tree that could not be rebuilt on
     // the way only takes the stack kernel away (SVO_OK_LITERAL_ONLY).
     GrownWindow plane;
-    int rc = grow_window(TerrainWindow::whole(w.width, w.height, w.depth, w.chunksize, w.chunkcoordmin).entering(axis, sign), w.terrain,
-                         ctx.pyr, ctx.grower, ctx.filler, nullptr, plane);
+    int rc = grow_window(TerrainWindow::whole(w.width, w.height, w.depth, w.chunksize, w.chunkcoordmin).entering(axis, sign), w.terrain, ctx, nullptr, plane);
     if (rc != SVO_OK) return rc;
     int status = SVO_OK;
     for (const GrownChunk &e : plane) {
@@ -741,11 +699,7 @@ static int shift_world_resident_impl(svo_world &w, int axis, int sign)
     return status;
 }
 
-int shift_world_resident(svo_world &w, int axis, int sign)
-{
-    try { return shift_world_resident_impl(w, axis, sign); }
-    catch (const std::bad_alloc &) { set_error("svo_world_shift: out of host memory"); return SVO_ERR_OUT_OF_MEMORY; }
-}
+int shift_world_resident(svo_world &w, int axis, int sign) { return fenced("svo_world_shift", [&] { return shift_world_resident_impl(w, axis, sign); }); }
 
 // Ocroot::build / destroy / replace + World::modify (src/Octree.cpp:203-443, src/World.cpp:268-274; the caller's pattern is
 // src/Main.cpp:340-367) on an uploaded world, without the host: the chunk's pools are copied out of the packed pools, edited by
@@ -767,42 +721,32 @@ static int edit_resident_impl(svo_world &w, int chunk, int op, const Region &R, 
     if ((rc = tree.reserve(trees + 1024, false, s)) != SVO_OK || (rc = twig.reserve((twigs + 16) * TWIG_WORDS, false, s)) != SVO_OK) return rc;
     HIP_TRY(hipMemcpyAsync(tree.p, w.hbm->tree.p + e.tree_off, trees * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
     if (twigs) HIP_TRY(hipMemcpyAsync(twig.p, w.hbm->twig.p + e.twig_off * TWIG_WORDS, twigs * TWIG_WORDS * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
-    ChunkPools meta;
-    std::memcpy(meta.position, c.position, sizeof meta.position);
-    meta.size = c.size; meta.depth = c.depth;
-    meta.tree_capacity = c.tree_capacity; meta.twig_capacity = c.twig_capacity;
-    DeviceFiller &filler = ctx.filler;
+    uint64_t cap[2] = { c.tree_capacity, c.twig_capacity };
     if (op == SVO_EDIT_DESTROY || op == SVO_EDIT_REPLACE)
-        if ((rc = filler.fill(meta, R, material, tree, trees, twig, twigs, s, EDIT_DESTROY)) != SVO_OK) return rc;
+        if ((rc = ctx.filler.fill(c, cap, R, material, tree, trees, twig, twigs, s, EDIT_DESTROY)) != SVO_OK) return rc;
     if (op == SVO_EDIT_BUILD || op == SVO_EDIT_REPLACE)
-        if ((rc = filler.fill(meta, R, material, tree, trees, twig, twigs, s, EDIT_BUILD)) != SVO_OK) return rc;
-    meta.trees_on_device = trees; meta.twigs_on_device = twigs;
-    return install_resident_chunk(w, chunk, meta, tree.p, twig.p);
+        if ((rc = ctx.filler.fill(c, cap, R, material, tree, trees, twig, twigs, s, EDIT_BUILD)) != SVO_OK) return rc;
+    return install_rebuilt(w, chunk, c.depth, cap, trees, twigs, tree.p, twig.p);
 }
 
 int edit_box_resident(svo_world &w, int chunk, int op, const float lo[3], const float hi[3], uint32_t material)
 {
     const BoxRegion R = { { lo[0], lo[1], lo[2] }, { hi[0], hi[1], hi[2] } };
-    try { return edit_resident_impl(w, chunk, op, R, material); }
-    catch (const std::bad_alloc &) { set_error("svo_world_edit_box: out of host memory"); return SVO_ERR_OUT_OF_MEMORY; }
+    return fenced("svo_world_edit_box", [&] { return edit_resident_impl(w, chunk, op, R, material); });
 }
 
 // The same edit with the closed ball |p - centre| <= radius as its region (svo_world_edit_ball).
 int edit_ball_resident(svo_world &w, int chunk, int op, const float centre[3], float radius, uint32_t material)
 {
     const BallRegion R = { { centre[0], centre[1], centre[2] }, radius * radius };
-    try { return edit_resident_impl(w, chunk, op, R, material); }
-    catch (const std::bad_alloc &) { set_error("svo_world_edit_ball: out of host memory"); return SVO_ERR_OUT_OF_MEMORY; }
+    return fenced("svo_world_edit_ball", [&] { return edit_resident_impl(w, chunk, op, R, material); });
 }
 
 int generate_world_resident(svo_world &w, int device)
 {
-    try {
-        const int rc = generate_world_resident_impl(w, device);
-        if (rc < 0) release_device(w);
-        return rc;
-    }
-    catch (const std::bad_alloc &) { release_device(w); set_error("svo_world_generate (device builder): out of host memory"); return SVO_ERR_OUT_OF_MEMORY; }
+    const int rc = fenced("svo_world_generate (device builder)", [&] { return generate_world_resident_impl(w, device); });
+    if (rc < 0) release_device(w);
+    return rc;
 }
 
 } // namespace svo

@@ -17,7 +17,6 @@
 
 #include <algorithm>
 #include <cstring>
-#include <new>
 
 namespace svo {
 
@@ -163,13 +162,7 @@ int rebuild_chunk(svo_world *w, int chunk, bool lod, const char *who)
         set_error(std::string(who) + ": a chunk of depth 2 has no coarser level (depth 1 cannot hold a brick)");
         return SVO_ERR_UNSUPPORTED;
     }
-    try {
-        if (w->device >= 0) return rebuild_resident(*w, chunk, lod);
-        return rebuild_host(*w, chunk, lod, who);
-    } catch (const std::bad_alloc &) {
-        set_error(std::string(who) + ": out of host memory");
-        return SVO_ERR_OUT_OF_MEMORY;
-    }
+    return fenced(who, [&] { return w->device >= 0 ? rebuild_resident(*w, chunk, lod) : rebuild_host(*w, chunk, lod, who); });
 }
 
 } // namespace

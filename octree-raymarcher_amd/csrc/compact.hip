@@ -45,7 +45,7 @@ __device__ __forceinline__ uint32_t res_kind(uint2 r) { return r.y >> 8; }
 __device__ __forceinline__ uint32_t leaf_value(uint32_t word) { return node_type(word) == LEAF ? node_offset(word) & 0xFFFFu : 0u; }
 __device__ __forceinline__ uint32_t octant(uint32_t x, uint32_t y, uint32_t z) { return (x & 1u) | (y & 1u) << 1 | (z & 1u) << 2; }
 
-// One level's arrays (sweep_scratch).  old: the node's index in the old pool; kids: index of its child block in the next level's
+// One level's arrays (hip_own.h: LodScratch::Level owns them).  old: the node's index in the old pool; kids: index of its child block in the next level's
 // list (NO_KIDS unless the recursion descends into it); res / cnt: sweep B's result and {blocks, bricks} of the subtree - in sweep
 // C cnt becomes the {blocks, bricks} that precede the node in preorder; slot: the node's index in the new pool (or DEAD); cand:
 // the BRANCH / TWIG nodes of the level (indices into this level's list).
@@ -225,18 +225,18 @@ int rebuild_resident_impl(svo_world &w, int chunk, bool lod)
     A.coarse_level = lod ? c.depth - 1 - TWIG_LEVELS : UINT32_MAX;
     const uint32_t last_level = lod ? A.coarse_level : maxlevel;        // no BRANCH below it is descended into
     int rc;
-    // sweep scratch: arrays 0 .. 5 of level l at 8 * l + k, the counters at 8 * 32
+    LodScratch &S = lod_scratch(w);
+    if (S.lv.size() < last_level + 2) S.lv.resize(last_level + 2);
     auto level_arrays = [&](uint32_t l, uint32_t n, LodLevel &L) -> int {
-        void *p[6];
-        const size_t b4 = std::max<size_t>(n, 1) * 4, b8 = std::max<size_t>(n, 1) * 8;
-        const size_t bytes[6] = { b4, b4, b4, b4, b8, b8 };
-        for (uint32_t k = 0; k < 6; ++k) if ((rc = sweep_scratch(w, 8 * l + k, bytes[k], &p[k])) != SVO_OK) return rc;
-        L.old = (uint32_t *)p[0]; L.kids = (uint32_t *)p[1]; L.slot = (uint32_t *)p[2]; L.cand = (uint32_t *)p[3];
-        L.res = (uint2 *)p[4]; L.cnt = (uint2 *)p[5]; L.n = n; L.ncand = 0;
+        LodScratch::Level &B = S.lv[l];
+        const size_t m = std::max<size_t>(n, 1);
+        if ((rc = B.old.reserve(m, false, s)) != SVO_OK || (rc = B.kids.reserve(m, false, s)) != SVO_OK || (rc = B.slot.reserve(m, false, s)) != SVO_OK ||
+            (rc = B.cand.reserve(m, false, s)) != SVO_OK || (rc = B.res.reserve(m, false, s)) != SVO_OK || (rc = B.cnt.reserve(m, false, s)) != SVO_OK) return rc;
+        L.old = B.old.p; L.kids = B.kids.p; L.slot = B.slot.p; L.cand = B.cand.p; L.res = B.res.p; L.cnt = B.cnt.p; L.n = n; L.ncand = 0;
         return SVO_OK;
     };
-    uint32_t *ctr = nullptr;
-    if ((rc = sweep_scratch(w, 8 * 32, 2 * 32 * sizeof(uint32_t), (void **)&ctr)) != SVO_OK) return rc;
+    if ((rc = S.ctr.reserve(2 * 32, false, s)) != SVO_OK) return rc;
+    uint32_t *const ctr = S.ctr.p;
     HIP_TRY(hipMemsetAsync(ctr, 0, 2 * 32 * sizeof(uint32_t), s));
     std::vector<LodLevel> lv(last_level + 2);
     if ((rc = level_arrays(0, 1, lv[0])) != SVO_OK) return rc;
@@ -247,10 +247,11 @@ int rebuild_resident_impl(svo_world &w, int chunk, bool lod)
     for (uint32_t level = 0;; ++level) {
         LodLevel &L = lv[level];
         last = level;
-        uint32_t *next_old = nullptr;
-        // (level last_level descends into nothing: its children's list is never written; a one-entry dummy stands in)
-        if ((rc = sweep_scratch(w, 8 * (level + 1), (level < last_level ? (size_t)L.n * 8 : 1) * 4, (void **)&next_old)) != SVO_OK) return rc;
-        hipLaunchKernelGGL(k_lod_gather, dim3(blocks_for(L.n, LOD_BLOCK)), dim3(LOD_BLOCK), 0, s, A, level, L, next_old, ctr + 2 * level);
+        // the children's list, written before the next level's arrays are sized (level_arrays then finds `old` large enough and leaves it
+        // alone); level last_level descends into nothing: its list is never written, a one-entry dummy stands in
+        DevBuf<uint32_t> &next_old = S.lv[level + 1].old;
+        if ((rc = next_old.reserve(level < last_level ? (size_t)L.n * 8 : 1, false, s)) != SVO_OK) return rc;
+        hipLaunchKernelGGL(k_lod_gather, dim3(blocks_for(L.n, LOD_BLOCK)), dim3(LOD_BLOCK), 0, s, A, level, L, next_old.p, ctr + 2 * level);
         HIP_TRY(hipGetLastError());
         uint32_t h[2];
         HIP_TRY(hipMemcpyAsync(h, ctr + 2 * level, sizeof h, hipMemcpyDeviceToHost, s));
@@ -291,12 +292,7 @@ int rebuild_resident_impl(svo_world &w, int chunk, bool lod)
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
-    ChunkPools meta;
-    std::memcpy(meta.position, c.position, sizeof meta.position);
-    meta.size = c.size; meta.depth = lod ? c.depth - 1 : c.depth;
-    meta.fit_capacity(trees, twigs);                                    // (install_resident_chunk keeps the slot's capacity as the floor)
-    meta.trees_on_device = trees; meta.twigs_on_device = twigs;
-    return install_resident_chunk(w, chunk, meta, tree, twig);
+    return install_rebuilt(w, chunk, lod ? c.depth - 1 : c.depth, nullptr, trees, twigs, tree, twig);
 }
 
 } // namespace

@@ -7,23 +7,20 @@
 //                    16 rows of a block (4 y x 4 z) sit in one workgroup and are folded through LDS.  Every cell is read once
 //   k_grid_mip       one level up: eight equal, non-MIXED entries give that value
 //   hipcub reduce    MIXED entries above the base = BRANCHes, in the base = TWIGs: the pools' sizes before anything is written
-//   per level        k_grid_classify (the frontier node's entry of the pyramid -> EMPTY / LEAF / BRANCH / TWIG), the scan that ranks
-//                    the flags, k_level_totals, k_emit (bfs.hip.h: node words, children in FIFO order, brick jobs),
-//                    k_grid_bricks (one thread per brick z-row: four 8-byte loads, one 32-byte store - MIXED blocks are the only
+//   per level        k_grid_classify (the frontier node's entry of the pyramid -> EMPTY / LEAF / BRANCH / TWIG), bfs_grow's steps
+//                    (bfs.hip.h: the scan that ranks the flags, k_level_totals, k_emit - node words, children in FIFO order, brick
+//                    jobs), k_grid_bricks (one thread per brick z-row: four 8-byte loads, one 32-byte store - MIXED blocks are the only
 //                    cells read a second time)
-// The pools are written to the edits' resident scratch (edit_scratch), the working arrays to sweep_scratch, and installed through
-// install_resident_chunk like svo_world_coarsen's.  No float arithmetic anywhere.
+// The pools are written to the edits' resident scratch (edit_scratch), the pyramid to the world's GridScratch, the level arrays are the
+// BfsArrays the terrain grower uses too, and the install is svo_world_coarsen's (install_rebuilt).  No float arithmetic anywhere.
 //   k_to_grid        the inverse: one thread per run of 8 output cells along x, one descent from the root per EMPTY / LEAF node or
 //                    brick cell the run crosses (a run inside one node: one descent), one 16-byte store.  Every index read from the
 //                    pools is checked against the chunk's counts.
 #include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <new>
 
 #include "bfs.hip.h"
 #include "hip_own.h"
@@ -203,9 +200,6 @@ int build_summary(const uint16_t *grid, uint32_t depth, uint32_t *pyr, hipStream
     return SVO_OK;
 }
 
-// sweep_scratch arrays of the build
-enum : uint32_t { S_PYRAMID = 0, S_COUNTS, S_REDUCE, S_FRONT_A, S_FRONT_B, S_WORD, S_FLAGS, S_RANK, S_SCAN, S_JOBS };
-
 int chunk_from_grid_resident(svo_world &w, int chunk, const uint16_t *grid, uint32_t depth)
 {
     HIP_TRY(hipSetDevice(w.device));
@@ -213,75 +207,48 @@ int chunk_from_grid_resident(svo_world &w, int chunk, const uint16_t *grid, uint
     hipStream_t s = nullptr;
     const uint32_t maxlevel = depth - TWIG_LEVELS;
     int rc;
-    auto scratch = [&](uint32_t k, size_t bytes, auto **out) { return sweep_scratch(w, k, bytes, (void **)out); };
+    GridScratch &S = grid_scratch(w);
+    BfsArrays &B = bfs_arrays(w);
     // the pyramid, and from it the pools' sizes
-    uint32_t *pyr = nullptr, *counts = nullptr;
     const uint64_t above = pyramid_offset(maxlevel), base = 1ull << (3 * maxlevel);
-    if ((rc = scratch(S_PYRAMID, (above + base) * sizeof(uint32_t), &pyr)) != SVO_OK || (rc = scratch(S_COUNTS, 80 * sizeof(uint32_t), &counts)) != SVO_OK) return rc;
+    if ((rc = S.pyramid.reserve(above + base, false, s)) != SVO_OK || (rc = S.counts.reserve(2, false, s)) != SVO_OK || (rc = B.h_totals.alloc(2)) != SVO_OK) return rc;
+    uint32_t *const pyr = S.pyramid.p, *const counts = S.counts.p, *const h = B.h_totals.p;
     if ((rc = build_summary(grid, depth, pyr, s)) != SVO_OK) return rc;
-    HIP_TRY(hipMemsetAsync(counts, 0, 80 * sizeof(uint32_t), s));
+    HIP_TRY(hipMemsetAsync(counts, 0, 2 * sizeof(uint32_t), s));
     {
         size_t need_above = 0, need_base = 0;
-        unsigned char *tmp = nullptr;
         if (above) HIP_TRY(hipcub::DeviceReduce::Sum(nullptr, need_above, MixedIterator(pyr, IsMixed()), counts, (int)above, s));
         HIP_TRY(hipcub::DeviceReduce::Sum(nullptr, need_base, MixedIterator(pyr + above, IsMixed()), counts + 1, (int)base, s));
-        if ((rc = scratch(S_REDUCE, std::max(need_above, need_base) + 16, &tmp)) != SVO_OK) return rc;
+        if ((rc = S.reduce_tmp.reserve(std::max(need_above, need_base) + 16, false, s)) != SVO_OK) return rc;
+        unsigned char *const tmp = S.reduce_tmp.p;
         if (above) HIP_TRY(hipcub::DeviceReduce::Sum(tmp, need_above, MixedIterator(pyr, IsMixed()), counts, (int)above, s));
         HIP_TRY(hipcub::DeviceReduce::Sum(tmp, need_base, MixedIterator(pyr + above, IsMixed()), counts + 1, (int)base, s));
     }
-    uint32_t h[2];
-    HIP_TRY(hipMemcpyAsync(h, counts, sizeof h, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h, counts, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const uint64_t trees = 1 + 8ull * h[0], twigs = h[1];
     if (trees >= (1ull << 30) || twigs >= (1ull << 30)) { set_error("svo_world_chunk_from_grid: chunk exceeds the 30-bit node offset"); return SVO_ERR_UNSUPPORTED; }
     uint32_t *tree = nullptr;
     uint16_t *twig = nullptr;
     if ((rc = edit_scratch(w, trees, twigs, &tree, &twig)) != SVO_OK) return rc;
-    // grow(): the frontier of each level, root first
-    GridCell *frontier = nullptr, *next = nullptr, *jobs = nullptr;
-    uint32_t front_k = S_FRONT_A, next_k = S_FRONT_B;
-    if ((rc = scratch(front_k, sizeof(GridCell), &frontier)) != SVO_OK) return rc;
-    const GridCell root = { 0u, 0u, 0u, 0u };
-    HIP_TRY(hipMemcpyAsync(frontier, &root, sizeof root, hipMemcpyHostToDevice, s));
+    // grow(): the corners are in cells, a node's coordinate in level L of the pyramid is its corner >> (depth - L)
+    const char *const disagree = "svo_world_chunk_from_grid: the walk disagrees with the summary's counts";
     uint64_t trees_done = 1, twigs_done = 0;
-    uint32_t n = 1;
-    for (uint32_t level = 0; n > 0; ++level) {
-        uint32_t *word = nullptr;
-        unsigned long long *flags = nullptr, *rank = nullptr;
-        unsigned char *scan_tmp = nullptr;
-        if ((rc = scratch(S_WORD, (size_t)n * 4, &word)) != SVO_OK || (rc = scratch(S_FLAGS, (size_t)n * 8, &flags)) != SVO_OK ||
-            (rc = scratch(S_RANK, (size_t)n * 8, &rank)) != SVO_OK) return rc;
-        hipLaunchKernelGGL(k_grid_classify, dim3(blocks_for(n, 256)), dim3(256), 0, s, frontier, n, pyr + pyramid_offset(level), level, depth - level,
-                           level == maxlevel ? 1u : 0u, word, flags);
-        size_t need = 0;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, flags, rank, (int)n, s));
-        if ((rc = scratch(S_SCAN, need + 16, &scan_tmp)) != SVO_OK) return rc;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, need, flags, rank, (int)n, s));
-        hipLaunchKernelGGL(k_level_totals, dim3(1), dim3(1), 0, s, flags, rank, n, counts + 2 + 2 * level);
-        HIP_TRY(hipMemcpyAsync(h, counts + 2 + 2 * level, sizeof h, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        const uint64_t nb = h[0], nt = h[1];
-        // (the walk numbers exactly what the reduce counted: anything else would write beyond the pools)
-        if (trees_done + 8 * nb > trees || twigs_done + nt > twigs) { set_error("svo_world_chunk_from_grid: the walk disagrees with the summary's counts"); return SVO_ERR_HIP; }
-        if ((rc = scratch(next_k, std::max<uint64_t>(8 * nb, 1) * sizeof(GridCell), &next)) != SVO_OK ||
-            (rc = scratch(S_JOBS, std::max<uint64_t>(nt, 1) * sizeof(GridCell), &jobs)) != SVO_OK) return rc;
-        hipLaunchKernelGGL(k_emit<uint32_t>, dim3(blocks_for(n, 256)), dim3(256), 0, s, frontier, n, (1u << (depth - level)) >> 1, word, rank,
-                           (uint32_t)trees_done, (uint32_t)twigs_done, tree, next, jobs);
-        if (nt) hipLaunchKernelGGL(k_grid_bricks, dim3(blocks_for(nt * 4, 256)), dim3(256), 0, s, jobs, (uint32_t)nt, grid, depth, twig);
-        HIP_TRY(hipGetLastError());
-        trees_done += 8 * nb; twigs_done += nt;
-        std::swap(frontier, next); std::swap(front_k, next_k);
-        n = (uint32_t)(8 * nb);
-    }
+    rc = bfs_grow<uint32_t>(B, GridCell{ 0u, 0u, 0u, 0u }, 1u << depth, trees_done, twigs_done, tree, s,
+        [&](uint32_t level, uint32_t, const GridCell *frontier, uint32_t n, uint32_t *word, unsigned long long *flags) -> int {
+            hipLaunchKernelGGL(k_grid_classify, dim3(blocks_for(n, 256)), dim3(256), 0, s, frontier, n, pyr + pyramid_offset(level), level, depth - level,
+                               level == maxlevel ? 1u : 0u, word, flags);
+            return SVO_OK;
+        },
+        [&](uint64_t nb, uint64_t nt) -> int {      // (the walk numbers exactly what the reduce counted: anything else would write beyond the pools)
+            if (trees_done + 8 * nb > trees || twigs_done + nt > twigs) { set_error(disagree); return SVO_ERR_HIP; }
+            return SVO_OK;
+        },
+        [&](const GridCell *jobs, uint32_t nt) { hipLaunchKernelGGL(k_grid_bricks, dim3(blocks_for((uint64_t)nt * 4, 256)), dim3(256), 0, s, jobs, nt, grid, depth, twig); });
+    if (rc != SVO_OK) return rc;
     HIP_TRY(hipStreamSynchronize(s));
-    if (trees_done != trees || twigs_done != twigs) { set_error("svo_world_chunk_from_grid: the walk disagrees with the summary's counts"); return SVO_ERR_HIP; }
-    const ChunkPools &c = w.chunks[(size_t)chunk];
-    ChunkPools meta;
-    std::memcpy(meta.position, c.position, sizeof meta.position);
-    meta.size = c.size; meta.depth = depth;
-    meta.fit_capacity(trees, twigs);                                    // (install_resident_chunk keeps the slot's capacity as the floor)
-    meta.trees_on_device = trees; meta.twigs_on_device = twigs;
-    return install_resident_chunk(w, chunk, meta, tree, twig);
+    if (trees_done != trees || twigs_done != twigs) { set_error(disagree); return SVO_ERR_HIP; }
+    return install_rebuilt(w, chunk, depth, nullptr, trees, twigs, tree, twig);
 }
 
 bool grid_args_ok(const svo_world *w, int chunk, const void *grid_dev, uint32_t depth)
@@ -302,8 +269,7 @@ int svo_world_chunk_from_grid(svo_world *w, int chunk, const uint16_t *grid_dev,
 {
     if (!grid_args_ok(w, chunk, grid_dev, depth)) { set_error("svo_world_chunk_from_grid: bad argument (chunk in range, depth in [2, 10], a 16-byte aligned grid)"); return SVO_ERR_INVALID_ARG; }
     if (w->device < 0) { set_error("svo_world_chunk_from_grid: the world is not uploaded (svo_chunk_from_grid builds host pools)"); return SVO_ERR_NOT_UPLOADED; }
-    try { return chunk_from_grid_resident(*w, chunk, grid_dev, depth); }
-    catch (const std::bad_alloc &) { set_error("svo_world_chunk_from_grid: out of host memory"); return SVO_ERR_OUT_OF_MEMORY; }
+    return fenced("svo_world_chunk_from_grid", [&] { return chunk_from_grid_resident(*w, chunk, grid_dev, depth); });
 }
 
 int svo_world_chunk_to_grid(svo_world *w, int chunk, uint32_t depth, uint16_t *grid_dev, void *stream)

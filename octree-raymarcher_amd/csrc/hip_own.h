@@ -4,8 +4,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstring>
 #include <string>
 #include <utility>
+#include <vector>
 
 #include "world.h"
 
@@ -80,6 +82,35 @@ template <typename T> struct Pinned : NoCopy {              // n elements of pin
     ~Pinned() { if (p) (void)hipHostFree(p); }
     int alloc(size_t n) { if (!p) HIP_TRY(hipHostMalloc((void **)&p, n * sizeof(T))); return SVO_OK; }
 };
+
+// What compact.hip and grid.hip keep between calls on a world.  Its builder context (builder.hip) owns them beside the builders' own
+// arrays and the loop's (bfs.hip.h: BfsArrays); nothing aliases anything else, a world that uses all of them keeps all of them.
+struct LodScratch {
+    struct Level { DevBuf<uint32_t> old, kids, slot, cand; DevBuf<uint2> res, cnt; };    // compact.hip: LodLevel says what each holds
+    std::vector<Level> lv;
+    DevBuf<uint32_t> ctr;                                   // [2 * level + {0, 1}] of sweep A
+};
+struct GridScratch {
+    DevBuf<uint32_t> pyramid, counts;                       // the summary pyramid; [0] MIXED entries above its base, [1] in it
+    DevBuf<unsigned char> reduce_tmp;
+};
+LodScratch &lod_scratch(svo_world &w);
+GridScratch &grid_scratch(svo_world &w);
+
+// A chunk rebuilt on the device (trees node words at tree_dev, twigs bricks at twig_dev) takes the place of `chunk`: the old position
+// and size, the new depth, the capacities { tree, twig } the caller arrived at (the edits: the old ones, doubled as the reference doubles
+// them) or, null, fresh ones fitted to the counts (compact, coarsen, the grid; install_resident_chunk keeps the slot's as the floor).
+inline int install_rebuilt(svo_world &w, int chunk, uint32_t depth, const uint64_t *capacity, uint64_t trees, uint64_t twigs, const uint32_t *tree_dev, const uint16_t *twig_dev)
+{
+    const ChunkPools &old = w.chunks[(size_t)chunk];
+    ChunkPools meta;
+    std::memcpy(meta.position, old.position, sizeof meta.position);
+    meta.size = old.size; meta.depth = depth;
+    if (capacity) { meta.tree_capacity = capacity[0]; meta.twig_capacity = capacity[1]; }
+    else meta.fit_capacity(trees, twigs);
+    meta.trees_on_device = trees; meta.twigs_on_device = twigs;
+    return install_resident_chunk(w, chunk, meta, tree_dev, twig_dev);
+}
 
 // An event that orders the streams of a world's callers behind one another: created by its first use, destroyed with its owner.
 struct Event : NoCopy {

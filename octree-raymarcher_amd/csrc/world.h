@@ -1,5 +1,6 @@
 // world.h — the svo_world handle behind include/svo.h.
 #pragma once
+#include <new>
 #include <string>
 #include <vector>
 #ifdef __HIP__
@@ -38,6 +39,12 @@ struct svo_world {
 namespace svo {
 constexpr unsigned WORK_SLOTS = 64;               // launches of one world that overlap freely; the 65th waits (on the device) for the 1st
 void set_error(const std::string &msg);
+// the C ABI's fence against std::bad_alloc: f's status, or "<who>: out of host memory"
+template <class F> int fenced(const char *who, F &&f)
+{
+    try { return f(); }
+    catch (const std::bad_alloc &) { set_error(std::string(who) + ": out of host memory"); return SVO_ERR_OUT_OF_MEMORY; }
+}
 int  validate_chunk(const ChunkPools &c, std::string &why);
 bool chunk_is_exact(const ChunkPools &c, int chunksize);
 void classify_world(svo_world &w);
@@ -67,10 +74,9 @@ int  edit_box_resident(svo_world &w, int chunk, int op, const float lo[3], const
 int  edit_ball_resident(svo_world &w, int chunk, int op, const float centre[3], float radius, uint32_t material);
 // builder.hip: World::shift's entering plane generated on the device the world is uploaded to
 int  shift_world_resident(svo_world &w, int axis, int sign);
-// builder.hip: the working buffers svo_world_edit_box keeps between calls, lent to compact.hip - the edit's output pools (grown to
-// `trees` node words and `twigs` bricks) and numbered sweep arrays (array k grown to `bytes`)
+// builder.hip: the edit's output pools, which svo_world_edit_box keeps between calls, lent to compact.hip and grid.hip (grown to
+// `trees` node words and `twigs` bricks)
 int  edit_scratch(svo_world &w, uint64_t trees, uint64_t twigs, uint32_t **tree, uint16_t **twig);
-int  sweep_scratch(svo_world &w, uint32_t k, size_t bytes, void **out);
 // compact.hip: Ocroot::defragcopy (lod = false) or Ocroot::lodmm (lod = true) + World::modify on an uploaded world
 int  rebuild_resident(svo_world &w, int chunk, bool lod);
 } // namespace svo

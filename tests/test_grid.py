@@ -159,6 +159,56 @@ def test_a_replaced_chunk_is_edited_compacted_and_coarsened(svo):
     W.destroy(); R.destroy()
 
 
+def test_one_world_through_every_builder_in_turn(svo):
+    """The builders share a world's scratch: the terrain grower and the grid walk the same level arrays, compact / coarsen and the grid
+    keep arrays of their own beside them, every one of them writes the edits' pools.  One 2x1x1 world of depth 5, generated on the
+    device with water (the grower and the filler have run), takes eight steps that hand those arrays from one builder to the next - to a
+    deeper grid after compact, back to the terrain, then to a shallower grid; after each the chunks equal, index for index, what the
+    models give for that step alone, and at the end both kernels march the same frame."""
+    import ball_model as B
+    W = svo.World.generate(2, 1, 1, 128, 5, build_device=0)
+    fresh = {x: svo.World.generate(2, 1, 1, 128, 5, chunkcoordmin=(x, 0, 0)) for x in (0, 1)}      # host-generated: what a shift must leave
+
+    def terrain(x, what):
+        assert tuple(W.info.chunkcoordmin) == (x, 0, 0), what
+        for i in range(2):
+            assert W.chunk(i)["position"] == fresh[x].chunk(i)["position"], f"{what}: chunk {i}"
+            same_pools(W.chunk(i), fresh[x].chunk(i), f"{what}: chunk {i}")
+
+    def at(i, chunk):
+        return dict(chunk, position=W.chunk(i)["position"])
+
+    assert W.shift((1, 0, 0)) == svo.SVO_OK
+    terrain(1, "1 shift +x")
+    assert W.chunk(0)["position"] == (256.0, 0.0, 0.0)
+    assert W.set_chunk_grid(0, G.grids()["g5"]) == svo.SVO_OK
+    same_pools(W.chunk(0), G.model_chunk("g5"), "2 grid g5")
+    centre, radius = (256.0 + 70.5, 40.0, 61.0), 37.3
+    assert W.edit_ball(0, svo.EDIT_DESTROY, centre, radius) == svo.SVO_OK
+    carved = B.pools_of(B.edit(B.chunk_of(at(0, G.model_chunk("g5"))), svo.EDIT_DESTROY, B.Ball(centre, radius)))
+    assert carved["tree"].size > G.model_chunk("g5")["tree"].size          # the ball split nodes
+    same_pools(W.chunk(0), carved, "3 ball")
+    assert W.compact(0) == svo.SVO_OK
+    same_pools(W.chunk(0), M.compact(carved), "4 compact")
+    assert W.set_chunk_grid(0, G.grids()["g6"]) == svo.SVO_OK
+    same_pools(W.chunk(0), G.model_chunk("g6"), "5 grid g6 after compact")
+    assert W.coarsen(0) == svo.SVO_OK
+    same_pools(W.chunk(0), M.coarsen(G.model_chunk("g6"), full=False), "6 coarsen")
+    same_pools(W.chunk(1), fresh[1].chunk(1), "6 coarsen: the chunk beside it")
+    assert W.shift((-1, 0, 0)) == svo.SVO_OK
+    terrain(0, "7 shift -x after the grid")
+    assert W.set_chunk_grid(1, G.grids()["g3"]) == svo.SVO_OK
+    same_pools(W.chunk(1), G.model_chunk("g3"), "8 grid g3")
+    same_pools(W.chunk(0), fresh[0].chunk(0), "8 grid g3: the chunk beside it")
+    cam = svo.default_camera(2, 1, 128, 64, 48)
+    frame = W.draw(cam, shadow=True, kernel=svo.KERNEL_STACK)
+    assert int((frame["flags"] & 1).sum()) > 200
+    assert_gbuffer_equal(W.draw(cam, shadow=True, kernel=svo.KERNEL_LITERAL), frame, "the frame at the end, literal against stack")
+    W.destroy()
+    for F in fresh.values():
+        F.destroy()
+
+
 def test_refused_calls_change_nothing(svo):
     H = svo.World.create([G.model_chunk("g3")], 1, 1, 1, 128)
     buf = svo.DeviceBuffer(8 ** 3 * 2)
