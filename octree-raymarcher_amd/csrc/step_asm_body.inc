@@ -62,11 +62,9 @@ __device__ __forceinline__ void march_steps_asm<SVO_STEP_BIG, SVO_STEP_GLSL>(
         "1:\n\t"
         "v_xor_b32 %[q6], %[uz], %[puz]\n\t"
         "v_or3_b32 %[q4], %[q4], %[q5], %[q6]\n\t"
-        "v_or_b32 %[q4], 1, %[q4]\n\t"
-        "v_ffbh_u32 %[q4], %[q4]\n\t"
-        "v_sub_u32 %[q4], 33, %[q4]\n\t"
-        "v_lshrrev_b32 %[q4], 1, %[q4]\n\t"
-        "v_sub_u32 %[q4], %[nw], %[q4]\n\t"
+        "v_ffbh_u32 %[q4], %[q4]\n\t"                        // z leading zeros: the highest differing bit is bit 31 - z, its wide level nw - ceil((32 - z) / 2)
+        "v_lshrrev_b32 %[q4], 1, %[q4]\n\t"                  //   = nw - 16 + (z >> 1); no bit differs: -1 >> 1, the largest int - every cached level survives
+        "v_add3_u32 %[q4], %[q4], %[nw], -16\n\t"
         "v_med3_i32 %[val], %[q4], 0, %[val]\n\t"              // deepest cached wide level whose node is unchanged
         "v_lshl_add_u32 %[q2], %[val], 8, %[lds]\n\t"
         "ds_read_b32 %[q3], %[q2]\n\t"
@@ -203,15 +201,14 @@ __device__ __forceinline__ void march_steps_asm<SVO_STEP_BIG, SVO_STEP_GLSL>(
         "s_or_b64 exec, %[sadv], %[sent]\n\t"
         "s_cbranch_execz 90f\n\t"
         "v_not_b32 %[q7], %[low]\n\t"
-        "v_add_u32 %[q4], 1, %[low]\n\t"
+        "v_bcnt_u32_b32 %[q4], %[low], 0\n\t"                // low = 2^k - 1: k
         "v_and_b32 %[q1], %[ux], %[q7]\n\t"
         "v_and_b32 %[q2], %[uy], %[q7]\n\t"
         "v_and_b32 %[q3], %[uz], %[q7]\n\t"
-        "v_cvt_f32_u32 %[q4], %[q4]\n\t"
         "v_cvt_f32_i32 %[q1], %[q1]\n\t"
         "v_cvt_f32_i32 %[q2], %[q2]\n\t"
         "v_cvt_f32_i32 %[q3], %[q3]\n\t"
-        "v_mul_f32 %[q4], %[rs], %[q4]\n\t"                    // cell edge
+        "v_ldexp_f32 %[q4], %[rs], %[q4]\n\t"                  // cell edge res * 2^k: the product res * float(low + 1) of the C++ step, which is exact too
         "v_fma_f32 %[q1], %[q1], %[rs], %[lx]\n\t"             // cell lo = l + k*res: product and sum are exact on exact geometry
         "v_fma_f32 %[q2], %[q2], %[rs], %[ly]\n\t"             // (lattice values below 2^24 steps), so the fused form rounds
         "v_fma_f32 %[q3], %[q3], %[rs], %[lz]\n\t"             // nowhere the reference's mul + add would
@@ -236,13 +233,12 @@ __device__ __forceinline__ void march_steps_asm<SVO_STEP_BIG, SVO_STEP_GLSL>(
         "v_cndmask_b32 %[r1], %[r1], %[q5], vcc\n\t"
         "v_cndmask_b32_e64 %[r2], %[r2], %[q6], %[smar]\n\t"
         "v_cndmask_b32_e64 %[r3], %[r3], %[q7], %[sstay]\n\t"
-        "v_sub_u32 %[q5], 1, %[crp]\n\t"                       // |creepn| + 1
         "v_cmp_lt_f32 vcc, %[r3], %[r2]\n\t"                   // glm::min(t.y, t.z) = (t.z < t.y) ? t.z : t.y
+        "v_sub_u32 %[q5], 1, %[crp]\n\t"                       // |creepn| + 1
         "v_and_b32 %[q6], 0x1ffffff, %[w]\n\t"                 // (entering lanes) brick index ...
-        "v_add_u32 %[q6], %[tof], %[q6]\n\t"
         "v_cndmask_b32 %[r2], %[r2], %[r3], vcc\n\t"
         "v_cmp_lt_f32 vcc, %[r2], %[r1]\n\t"                   // glm::min(t.x, .)
-        SVO_STEP_MASK_OFFSET                                   // ... as a byte offset into the mask pool (two wait states between v_cmp and v_cndmask either way)
+        SVO_STEP_MASK_OFFSET                                   // ... + the chunk's first brick, as a byte offset into the mask pool (two wait states between v_cmp and v_cndmask either way)
         "v_cndmask_b32 %[r1], %[r1], %[r2], vcc\n\t"
         SVO_STEP_ESCAPE_GUARD                                  // (GLSL twin only: d < EPS ? BIGEPS : d, shaders/Chunkmarch.glsl:113)
         "v_add_f32 %[r1], %[eps], %[r1]\n\t"                   // escape + EPS
