@@ -54,6 +54,10 @@
  *   svo_world_edit_ball_all <- (no counterpart; the reference edits cubes only) one ball to every chunk whose box it touches
  *   svo_trace_local_shadows <- (a departure: the reference gives the directional light's shadow term to all three lights,
  *                           shaders/World.Fragment.glsl:186-190) one occlusion ray per hit towards the point light and the spotlight
+ *   svo_shadowmap_render <- World::draw_shadowmap under the OrthoCamera (src/World.cpp:162-203, shaders/ShadowmapWorld.Fragment.glsl,
+ *                           src/Main.cpp:149,190-198): the world marched once from the directional light into a depth image
+ *   svo_shadowmap_apply  <- computeShadow                          shaders/World.Fragment.glsl:140-155,186
+ *   svo_shadowmap_fit    <- the OrthoCamera's placement and glm::ortho(-w, w, -h, h)   src/Main.cpp:149, src/Camera.cpp:50-53
  *
  * Conventions
  *   - plain C, opaque handle, caller owns every buffer it passes in;
@@ -102,7 +106,8 @@ extern "C" {
                                           svo_shade_sky, svo_sky and svo_frame_rgba8,
                                           svo_cursor_place, svo_shade_boxes, svo_box and svo_world_edit_cube,
                                           svo_chunk_from_grid, svo_world_chunk_from_grid and svo_world_chunk_to_grid,
-                                          svo_world_edit_ball and svo_world_edit_ball_all */
+                                          svo_world_edit_ball and svo_world_edit_ball_all,
+                                          svo_shadowmap, svo_shadowmap_fit, svo_shadowmap_render and svo_shadowmap_apply */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -628,6 +633,76 @@ int svo_trace_translucent(svo_world *, const svo_camera *cam, const svo_trace_pa
 int svo_trace_local_shadows(svo_world *, const svo_camera *cam, const svo_trace_params *params,
                             const float point_position[3], const float spot_position[3],
                             int x0, int y0, int w, int h, svo_hit *gbuffer_dev, void *stream);
+
+/* ---- shadow map: the directional light rendered once, looked up per frame ---------------------------------
+ * The reference shadows its scene with a shadow map: each frame it marches the world from the directional light into a depth image
+ * (World::draw_shadowmap, src/World.cpp:162-203) and computeShadow looks every hit point up in it (shaders/World.Fragment.glsl:140-155).
+ * svo_trace_params.shadow replaces that with one exact shadow ray per primary hit, paid for on every frame.  The directional light
+ * does not move with the camera: with a fixed sun and a world that changes only at edits, render the map once, then trace every
+ * frame with shadow = 0 and apply the map - one gather per hit pixel.
+ * A departure, as svo_trace_local_shadows is: the reference's pass marches one uniform ray per fragment from the light's position
+ * (its per-fragment direction is commented out, shaders/ShadowmapWorld.Fragment.glsl:8), compares an inverse-distance depth, and its
+ * sampler wraps (GL_REPEAT, src/Light.cpp:176-179).  Here the light's view is a true orthographic raster of parallel rays, the depth
+ * is the march's own t, and a point outside the map is lit.  One bit per light in the record: no PCF (out of scope). */
+typedef struct svo_shadowmap {
+    float   origin[3];              /* centre of the light's image plane; rays start ON this plane */
+    float   direction[3];           /* unit; every ray's direction (directionalLight.direction) */
+    float   right[3], up[3];        /* orthonormal with direction (the caller's, as svo_camera's basis is) */
+    float   half_width, half_height;    /* world units: glm::ortho(-w, w, -h, h), src/Camera.cpp:50-53 */
+    int32_t width, height;          /* texels; multiples of 8, 8..16384 */
+    float  *depth_dev;              /* width*height float, row-major, row 0 at +up */
+} svo_shadowmap;
+
+/* A map that holds the whole world.  Host only, needs no device.  Fills everything in *out except depth_dev, which is left as it is:
+ * direction normalised; right and up completing an orthonormal basis from the hint (0,1,0), or (0,0,1) when the direction is within
+ * about 8 degrees of vertical (right = normalize(direction x hint), up = right x direction, as svo_camera's basis is made); the plane
+ * placed so that every corner c of the world box (chunkcoordmin * chunksize to + dims * chunksize) has dot(c - origin, direction) >= 1;
+ * half extents so that every corner projects strictly inside (-half_width, half_width) x (-half_height, half_height).  Computed in
+ * double, rounded to float once; the properties are the contract, not the bits.
+ * A NULL argument, a zero, NaN or infinite direction, a width or height that is not a multiple of 8 in 8..16384: SVO_ERR_INVALID_ARG. */
+int svo_shadowmap_fit(const svo_world *, const float direction[3], int width, int height, svo_shadowmap *out);
+
+/* Render the map.  Texel (i, j) marches the ray - every operation in float, separately rounded, the shape of svo_camera's u and v -
+ *   u = (((i + 0.5f) / width ) * 2 - 1) * half_width
+ *   v = (1 - ((j + 0.5f) / height) * 2) * half_height
+ *   o = origin + right * u + up * v      (per component, left to right)
+ *   d = direction                        (as given, not re-normalised)
+ * exactly as svo_trace_rays marches (o, d) under `params` with shadow = 0 and counters_dev / tile_cost_dev / tile_order_dev dropped:
+ * eps, the caps, semantics, kernel and see_through are honoured (see_through: a shadow map that water does not darken).
+ *   depth_dev[j*width + i] = that record's t if it has SVO_HIT_FLAG and no SVO_ERR_FLAG, +inf otherwise.
+ * All texels go through ONE ray-list launch (svo_trace_last_ray_count then reports width*height).  The list is written in tile order -
+ * slot tile*64 + jj*8 + ii holds texel (8*(tile % (width/8)) + ii, 8*(tile / (width/8)) + jj) - so that a wave marches an 8x8 block of
+ * neighbouring parallel rays; nothing observable depends on it.  The list and its records live in the world's scratch, 56 bytes per
+ * texel; calls of one world on different streams are ordered behind one another on the device.
+ * SVO_ERR_INVALID_ARG: a NULL world, map, params or depth_dev; a width or height that is not a multiple of 8 in 8..16384; a half_* that
+ * is not greater than 0 or not finite; a non-finite origin or basis; | |direction|^2 - 1 | > 1e-3.  Then whatever svo_trace_rays would
+ * refuse (SVO_ERR_NOT_UPLOADED and the rest).  All settled before any device work.  Asynchronous on `stream`, ordered against updates,
+ * edits and shifts as svo_trace_rays is.  A map rendered before an edit is STALE: nothing invalidates it, re-rendering it is the
+ * caller's job. */
+int svo_shadowmap_render(svo_world *, const svo_shadowmap *map, const svo_trace_params *params, void *stream);
+
+/* Look the hits of a frame up in the map.  Takes no world.  gbuffer_dev holds the w*h records that svo_trace(cam, ..., x0, y0, w, h)
+ * wrote; eps is that launch's (0 = 1/8192; pass 1/4096 under SVO_SEMANTICS_GLSL), as with svo_hit_uv.  For every record with
+ * SVO_HIT_FLAG and without SVO_ERR_FLAG, in float, every operation separately rounded:
+ *   P  = o + d * (t - eps)                       (o, d) the pixel's camera ray: where the shadow ray would start
+ *   q  = P - origin
+ *   s  = q.x*D.x + q.y*D.y + q.z*D.z             (left to right; D = direction; likewise a with right, b with up)
+ *   fu = (a / half_width  + 1) * 0.5f * (float)width
+ *   fv = (1 - b / half_height) * 0.5f * (float)height
+ *   inside   = fu >= 0 && fu < width && fv >= 0 && fv < height     (NaN fails)
+ *   i = (int)floorf(fu), j = (int)floorf(fv)     nearest sampling, as the reference's; a texel-centre point maps back to i + 0.5
+ *   occluded = inside && depth_dev[j*width + i] < s - bias
+ * The record gets SVO_SHADOW_TRACED; SVO_SHADOWED is set if occluded and cleared if not; no other byte of it changes.  Records without
+ * a usable hit stay byte for byte as they were.  A frame traced with shadow = 0 and then applied has the flag layout of a shadow = 1
+ * frame: svo_shade* and svo_gbuffer_pack work on it unchanged.  Outside the map a point is lit (the reference's sampler wraps).
+ * Bits 5-7 are not touched; svo_trace_local_shadows copies SVO_SHADOWED for a light not asked for, so svo_shadowmap_apply goes BEFORE it.
+ * bias is the caller's, in world units along the light.  A texel is 2*half_width/width world units wide, and under a slanted light
+ * the depth varies by about that much across it: one to two texel widths is a good start; too little gives acne, too much detaches
+ * shadows from their casters.
+ * SVO_ERR_INVALID_ARG: a NULL pointer, a negative rectangle or a camera without an image size, eps < 0, a negative or NaN bias, or the
+ * map checks of svo_shadowmap_render.  w*h == 0: SVO_OK.  Asynchronous on `stream`. */
+int svo_shadowmap_apply(const svo_camera *cam, const svo_shadowmap *map, float eps, float bias, int x0, int y0, int w, int h,
+                        svo_hit *gbuffer_dev, void *stream);
 
 /* ---- packed G-buffer (8 bytes / pixel) for the multi-GPU gather ------------------------------------------
  * { float t; uint32 w } with w = material (bits 0-15) | flags & 0xFF (bits 16-23) | normal code (bits 24-30) |

@@ -9,6 +9,7 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     World.chunkmarch(origins, dirs)           <- chunkmarch             src/Traverse.cpp:127-171
     World.draw_translucent(camera, m)         <- ParallaxAlpha's march past water   shaders/ParallaxAlpha.Fragment.glsl:141-199,276-335
     World.trace_local_shadows(camera, ...)    <- (none: the reference's three lights share the directional light's shadow term)
+    World.shadowmap_fit / shadowmap_render, shadowmap_apply   <- OrthoCamera, World::draw_shadowmap, computeShadow   src/World.cpp:162-203, shaders/World.Fragment.glsl:140-155
     World.index / index_float                 <- World::index(_float)   src/World.cpp:288-293,323-332
     World.locate / locate_points              <- traverse               src/Traverse.cpp:34-48 (the voxel under each point)
     World.hit_voxels / hit_boxes              <- hit.bmin / hit.size of fragment main   shaders/World.Fragment.glsl:168-172
@@ -139,6 +140,12 @@ class Atlas(C.Structure):
     _fields_ = [("diffuse_dev", C.c_void_p), ("specular_dev", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
 
 
+class ShadowMap(C.Structure):
+    """svo_shadowmap: the directional light's orthographic view and its depth image (width*height float on the device, row 0 at +up)."""
+    _fields_ = [("origin", C.c_float * 3), ("direction", C.c_float * 3), ("right", C.c_float * 3), ("up", C.c_float * 3),
+                ("half_width", C.c_float), ("half_height", C.c_float), ("width", C.c_int32), ("height", C.c_int32), ("depth_dev", C.c_void_p)]
+
+
 class Sky(C.Structure):
     """svo_sky: six size x size RGB8 cube-map faces on the device (+X, -X, +Y, -Y, +Z, -Z; rows tightly packed, row 0 at t = 0).
     Sky(face_ptrs, size, filter): face_ptrs are six device pointers (None = NULL)."""
@@ -175,6 +182,7 @@ ABI_SYMBOLS = [
     "svo_chunk_from_grid", "svo_world_chunk_from_grid", "svo_world_chunk_to_grid",
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_edit_cube", "svo_world_edit_ball", "svo_world_edit_ball_all", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_cursor_place", "svo_shade_boxes", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
+    "svo_shadowmap_fit", "svo_shadowmap_render", "svo_shadowmap_apply",
     "svo_device_count", "svo_device_alloc", "svo_device_free", "svo_device_cache_trim", "svo_memcpy_h2d", "svo_memcpy_d2h",
     "svo_stream_synchronize", "svo_last_error", "svo_abi_version",
 ]
@@ -216,6 +224,9 @@ lib.svo_shade_translucent.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams),
 lib.svo_trace_translucent.argtypes = [_P, C.POINTER(Camera), C.POINTER(TraceParams), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]
 lib.svo_trace_local_shadows.argtypes = [_P, C.POINTER(Camera), C.POINTER(TraceParams), C.POINTER(C.c_float), C.POINTER(C.c_float),
                                         C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]
+lib.svo_shadowmap_fit.argtypes = [_P, C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(ShadowMap)]
+lib.svo_shadowmap_render.argtypes = [_P, C.POINTER(ShadowMap), C.POINTER(TraceParams), _P]
+lib.svo_shadowmap_apply.argtypes = [C.POINTER(Camera), C.POINTER(ShadowMap), C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]
 lib.svo_world_upload.argtypes = [_P, C.c_int]
 lib.svo_world_update.argtypes = [_P, C.c_int, C.POINTER(ChunkDesc), C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int]
 lib.svo_trace.argtypes = [_P, C.POINTER(Camera), C.POINTER(TraceParams), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]
@@ -476,6 +487,14 @@ def shade_boxes(cam: Camera, boxes_ptr: int, nboxes: int, rect, rgba_ptr: int, n
            "svo_shade_boxes")
 
 
+def shadowmap_apply(cam: Camera, smap: ShadowMap, eps: float, bias: float, rect, gbuffer_ptr: int, stream: int = 0):
+    """svo_shadowmap_apply: SHADOW_TRACED and SHADOWED of every usable hit of the G-buffer svo_trace(cam, rect) filled, from a lookup of
+    its sample point in the rendered map; eps is the launch's (0 = 1/8192), bias in world units along the light."""
+    x0, y0, w, h = rect
+    _check(lib.svo_shadowmap_apply(C.byref(cam) if cam is not None else None, C.byref(smap) if smap is not None else None, eps, bias,
+                                   x0, y0, w, h, gbuffer_ptr, stream), "svo_shadowmap_apply")
+
+
 def see_through_chunk(chunk: dict, material: int) -> dict:
     """The chunk as a see-through march of `material` sees it: LEAF nodes of that material (offset & 0xFFFF) and brick cells
     holding it set to 0, the tree's shape unchanged.  Host numpy; what svo_trace_params.see_through is defined against."""
@@ -708,6 +727,19 @@ class World:
         _check(lib.svo_trace_local_shadows(self._h, C.byref(cam) if cam is not None else None, C.byref(params) if params is not None else None,
                                            vec[0], vec[1], x0, y0, w, h, gbuffer_ptr, stream), "svo_trace_local_shadows")
 
+    def shadowmap_fit(self, direction, width: int, height: int, smap: Optional[ShadowMap] = None) -> ShadowMap:
+        """svo_shadowmap_fit: a map of width x height texels that holds the whole world box, seen along `direction`; depth_dev of
+        `smap` (a new ShadowMap if None) is left as it is."""
+        smap = ShadowMap() if smap is None else smap
+        vec = None if direction is None else (C.c_float * 3)(*[float(c) for c in direction])
+        _check(lib.svo_shadowmap_fit(self._h, vec, int(width), int(height), C.byref(smap)), "svo_shadowmap_fit")
+        return smap
+
+    def shadowmap_render(self, smap: ShadowMap, params: TraceParams, stream: int = 0):
+        """svo_shadowmap_render: the world marched once from the light into smap.depth_dev (the march's t, +inf where nothing is hit)."""
+        _check(lib.svo_shadowmap_render(self._h, C.byref(smap) if smap is not None else None, C.byref(params) if params is not None else None,
+                                        stream), "svo_shadowmap_render")
+
     def tile_order(self, cost_ptr: int, order_ptr: int, ntiles: int, stream: int = 0):
         """svo_tile_order: tile indices by descending cost (of one frame) into order_ptr."""
         _check(lib.svo_tile_order(self._h, cost_ptr, order_ptr, ntiles, stream), "svo_tile_order")
@@ -719,15 +751,20 @@ class World:
 
     # -- convenience: World::draw / chunkmarch returning numpy -------------------------------
     def draw(self, cam: Camera, rect=None, shadow: bool = False, kernel: int = KERNEL_AUTO, counters: bool = False,
-             light_dir=(1.0, -1.0, 0.0), normal_mode: int = 0, semantics: int = 0, see_through: int = 0, local_shadows=None):
+             light_dir=(1.0, -1.0, 0.0), normal_mode: int = 0, semantics: int = 0, see_through: int = 0, local_shadows=None, shadowmap=None):
         """Trace a rectangle of the camera image; returns the G-buffer (HIT_DTYPE[h, w]) [+ counters].
-        local_shadows=(point, spot): positions (or None) handed to trace_local_shadows behind the trace."""
+        local_shadows=(point, spot): positions (or None) handed to trace_local_shadows behind the trace.
+        shadowmap=(map, bias): a rendered ShadowMap applied behind the trace (shadowmap_apply) in place of shadow=True."""
         x0, y0, w, h = rect if rect is not None else (0, 0, cam.width, cam.height)
         out = DeviceBuffer(max(w * h, 1) * 32)
         cnt = DeviceBuffer(max(w * h, 1) * 16) if counters else None
         prm = trace_params(shadow=shadow, kernel=kernel, light_dir=light_dir, counters_dev=cnt.ptr if cnt else None, normal_mode=normal_mode,
                            semantics=semantics, see_through=see_through)
+        if shadowmap is not None:
+            prm.shadow = 0
         self.trace(cam, prm, (x0, y0, w, h), out.ptr)
+        if shadowmap is not None:
+            shadowmap_apply(cam, shadowmap[0], 1.0 / 4096.0 if semantics == SEMANTICS_GLSL else 0.0, shadowmap[1], (x0, y0, w, h), out.ptr)
         if local_shadows is not None:
             self.trace_local_shadows(cam, prm, (x0, y0, w, h), out.ptr, point=local_shadows[0], spot=local_shadows[1])
         _check(lib.svo_stream_synchronize(None), "svo_stream_synchronize")

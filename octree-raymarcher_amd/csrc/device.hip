@@ -27,6 +27,7 @@
 #include "kernel_stack.hip.h"
 #include "see_through.hip.h"
 #include "local_shadows.hip.h"
+#include "shadowmap.hip.h"
 #include "locate.hip.h"
 #include "hit_voxels.hip.h"
 #include "hip_own.h"
@@ -1133,6 +1134,111 @@ int svo_trace_local_shadows(svo_world *w, const svo_camera *cam, const svo_trace
                             reinterpret_cast<uint4 *>(gbuffer_dev));
     if (rc != SVO_OK) return rc;
     return list.done.record(s);
+}
+
+// ---- the directional light's shadow map (shadowmap.hip.h) -------------------------------------------------------------------------
+// what svo_shadowmap_render and svo_shadowmap_apply ask of a map before anything else
+static bool map_ok(const svo_shadowmap *m)
+{
+    if (!m || !m->depth_dev) return false;
+    if (m->width < 8 || m->width > 16384 || m->width % 8 || m->height < 8 || m->height > 16384 || m->height % 8) return false;
+    if (!(m->half_width > 0.0f && m->half_width < INFINITY && m->half_height > 0.0f && m->half_height < INFINITY)) return false;
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(m->origin[a]) || !std::isfinite(m->direction[a]) || !std::isfinite(m->right[a]) || !std::isfinite(m->up[a])) return false;
+    const float q = m->direction[0] * m->direction[0] + m->direction[1] * m->direction[1] + m->direction[2] * m->direction[2];
+    return std::fabs(q - 1.0f) <= 1e-3f;
+}
+
+static MapFrame map_frame(const svo_shadowmap &m)
+{
+    MapFrame M;
+    std::memcpy(M.origin, m.origin, sizeof M.origin); std::memcpy(M.dir, m.direction, sizeof M.dir);
+    std::memcpy(M.right, m.right, sizeof M.right); std::memcpy(M.up, m.up, sizeof M.up);
+    M.half_w = m.half_width; M.half_h = m.half_height; M.width = m.width; M.height = m.height;
+    return M;
+}
+
+// A map that holds the whole world box, host only: the basis in double from the hint (0,1,0) - (0,0,1) within 8 degrees of vertical -,
+// the plane `back` in front of the nearest corner, the half extents a margin over the farthest one, everything rounded to float once.
+int svo_shadowmap_fit(const svo_world *w, const float direction[3], int width, int height, svo_shadowmap *out)
+{
+    if (!w || !direction || !out || width < 8 || width > 16384 || width % 8 || height < 8 || height > 16384 || height % 8) {
+        set_error("svo_shadowmap_fit: bad argument"); return SVO_ERR_INVALID_ARG;
+    }
+    double d[3] = { direction[0], direction[1], direction[2] };
+    const double len = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    if (!(len > 0.0 && len < INFINITY)) { set_error("svo_shadowmap_fit: the direction is zero or not finite"); return SVO_ERR_INVALID_ARG; }
+    for (double &c : d) c /= len;
+    const double hint[3] = { 0.0, std::fabs(d[1]) > 0.99 ? 0.0 : 1.0, std::fabs(d[1]) > 0.99 ? 1.0 : 0.0 };     // cos 8 deg = 0.990
+    double r[3] = { d[1] * hint[2] - d[2] * hint[1], d[2] * hint[0] - d[0] * hint[2], d[0] * hint[1] - d[1] * hint[0] };
+    const double rl = std::sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+    for (double &c : r) c /= rl;
+    const double u[3] = { r[1] * d[2] - r[2] * d[1], r[2] * d[0] - r[0] * d[2], r[0] * d[1] - r[1] * d[0] };
+    const double cs = (double)w->chunksize;
+    const int dims[3] = { w->width, w->height, w->depth };
+    double lo[3], hi[3], mid[3], diag = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = (double)w->chunkcoordmin[a] * cs; hi[a] = lo[a] + (double)dims[a] * cs; mid[a] = 0.5 * (lo[a] + hi[a]);
+        diag += (hi[a] - lo[a]) * (hi[a] - lo[a]);
+    }
+    diag = std::sqrt(diag);
+    double near_s = INFINITY, far_a = 0.0, far_b = 0.0;
+    for (int k = 0; k < 8; ++k) {
+        double q[3];
+        for (int a = 0; a < 3; ++a) q[a] = ((k >> a & 1) ? hi[a] : lo[a]) - mid[a];
+        near_s = std::min(near_s, q[0] * d[0] + q[1] * d[1] + q[2] * d[2]);
+        far_a = std::max(far_a, std::fabs(q[0] * r[0] + q[1] * r[1] + q[2] * r[2]));
+        far_b = std::max(far_b, std::fabs(q[0] * u[0] + q[1] * u[1] + q[2] * u[2]));
+    }
+    // the margins cover the rounding to float of the origin, of the basis (2^-24 of a lever of at most the diagonal plus the offset) and of the extents
+    const double back = near_s - 2.0 - diag / 1024.0;
+    for (int a = 0; a < 3; ++a) {
+        out->origin[a] = (float)(mid[a] + d[a] * back);
+        out->direction[a] = (float)d[a]; out->right[a] = (float)r[a]; out->up[a] = (float)u[a];
+    }
+    out->half_width = (float)(far_a * (1.0 + 1.0 / 1024.0) + 1.0);
+    out->half_height = (float)(far_b * (1.0 + 1.0 / 1024.0) + 1.0);
+    out->width = width; out->height = height;
+    return SVO_OK;
+}
+
+// The depth image of the world seen from the light: the texel rays in tile order (shadowmap.hip.h), ONE ray-list launch into scratch
+// records, the fold into depth_dev.
+int svo_shadowmap_render(svo_world *w, const svo_shadowmap *map, const svo_trace_params *prm, void *stream)
+{
+    if (!w || !prm || !map_ok(map)) { set_error("svo_shadowmap_render: bad argument"); return SVO_ERR_INVALID_ARG; }
+    svo_trace_params march = *prm;                                      // (the caller's per-ray and per-tile buffers are sized for its frames)
+    march.shadow = 0;
+    march.counters_dev = nullptr; march.tile_cost_dev = nullptr; march.tile_order_dev = nullptr;
+    TraceArgs A;                                                        // (checks see_through, semantics, residency and the kernel id before any device work)
+    int rc = fill_common(w, &march, A);
+    if (rc != SVO_OK) return rc;
+    if ((rc = pick_kernel(w, &march, A)) < 0) return rc;
+    const MapFrame M = map_frame(*map);
+    const int64_t n = M.count();                                        // (<= 2^28)
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(w->device));
+    // the records and the list live in the world's scratch: calls on different streams are ordered behind one another (as svo_trace_local_shadows')
+    OrderedScratch<float> &list = w->hbm->shadowmap;
+    if ((rc = list.reserve((size_t)n * 14, "svo_shadowmap_render")) != SVO_OK) return rc;
+    if ((rc = list.done.wait(s)) != SVO_OK) return rc;
+    float *records = list.buf.p, *origins = records + 8 * n, *dirs = origins + 3 * n;
+    if ((rc = launch_per_element("svo_shadowmap_render", n, s, k_shadowmap_rays, M, origins, dirs)) != SVO_OK) return rc;
+    if ((rc = svo_trace_rays(w, origins, dirs, n, &march, reinterpret_cast<svo_hit *>(records), stream)) != SVO_OK) return rc;
+    rc = launch_per_element("svo_shadowmap_render", n, s, k_shadowmap_depth, M, reinterpret_cast<const uint4 *>(records), map->depth_dev);
+    if (rc != SVO_OK) return rc;
+    return list.done.record(s);
+}
+
+int svo_shadowmap_apply(const svo_camera *cam, const svo_shadowmap *map, float eps, float bias, int x0, int y0, int rw, int rh,
+                        svo_hit *gbuffer_dev, void *stream)
+{
+    if (!gbuffer_dev || !rect_ok(cam, x0, y0, rw, rh) || !(eps >= 0.0f) || !(bias >= 0.0f) || !map_ok(map)) {
+        set_error("svo_shadowmap_apply: bad argument"); return SVO_ERR_INVALID_ARG;
+    }
+    return launch_per_element("svo_shadowmap_apply", (int64_t)rw * rh, (hipStream_t)stream, k_shadowmap_apply, make_frame(*cam, x0, y0, rw, rh),
+                              eps == 0.0f ? 1.0f / 8192.0f : eps, map_frame(*map), static_cast<const float *>(map->depth_dev), bias,
+                              reinterpret_cast<uint4 *>(gbuffer_dev));
 }
 
 // Point queries (locate.hip.h): one thread per point, the tree pool (SVO_KERNEL_LITERAL) or the wide pool (SVO_KERNEL_STACK; AUTO where

@@ -152,6 +152,7 @@ struct Hbm {
     OrderedScratch<unsigned char> sort;                     // svo_tile_order
     OrderedScratch<float> cont;                             // svo_trace_translucent: continuation origins and directions, [2][rays][3]
     OrderedScratch<float> local;                            // svo_trace_local_shadows: per light asked for, [rays] records of 8 words, then origins and directions [2][rays][3]
+    OrderedScratch<float> shadowmap;                        // svo_shadowmap_render: [texels] records of 8 words, then origins and directions [2][texels][3], in tile order
     // see-through view (svo_trace_params.see_through, see_through.hip.h): the wide and mask pools with one material taken out, built
     // on the device at the first launch that asks for it, dropped by every change to the pools
     Pooled<uint32_t> view_wide; Pooled<uint64_t> view_mask;

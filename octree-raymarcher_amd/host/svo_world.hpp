@@ -9,6 +9,8 @@
 //   svo::World::load_gpu()           <- World::load_gpu        src/World.cpp:57-94
 //   svo::World::draw(camera, ...)    <- World::draw (+ draw_shadowmap as the fused shadow ray)  src/World.cpp:162-266
 //   svo::World::local_shadows(...)   <- (none: per-light shadows of the point light and the spotlight, svo_trace_local_shadows)
+//   svo::World::shadowmap_fit / shadowmap_render / shadowmap_apply  <- the OrthoCamera, World::draw_shadowmap and computeShadow (svo_shadowmap_*):
+//                                       the directional light rendered once, looked up per frame   src/World.cpp:162-203, shaders/World.Fragment.glsl:140-155
 //   svo::World::modify(i, ...)       <- World::modify          src/World.cpp:268-274
 //   svo::World::index / index_float  <- src/World.cpp:288-293,323-332
 //   svo::World::locate(points, ...)  <- traverse over a point list (svo_world_locate)   src/Traverse.cpp:34-48
@@ -70,6 +72,29 @@ public:
     int width = 0, height = 0;
 private:
     svo_hit *dev_ = nullptr;
+};
+
+// The directional light's view and its depth image in HBM (svo_shadowmap): World::shadowmap_fit places it, resize() sizes the image.
+class ShadowMap : public svo_shadowmap {
+public:
+    ShadowMap() { std::memset(static_cast<svo_shadowmap *>(this), 0, sizeof(svo_shadowmap)); }
+    ~ShadowMap() { svo_device_free(depth_dev); }
+    ShadowMap(const ShadowMap &) = delete;
+    ShadowMap &operator=(const ShadowMap &) = delete;
+    void resize(int w, int h)
+    {
+        svo_device_free(depth_dev);
+        width = w; height = h;
+        depth_dev = static_cast<float *>(svo_device_alloc(sizeof(float) * (size_t)w * h));
+        if (!depth_dev) throw Error(SVO_ERR_OUT_OF_MEMORY, "ShadowMap::resize");
+    }
+    std::vector<float> download() const
+    {
+        std::vector<float> host((size_t)width * height);
+        check(svo_memcpy_d2h(host.data(), depth_dev, host.size() * sizeof(float)), "ShadowMap::download");
+        return host;
+    }
+    float texel() const { return 2.0f * std::fmax(half_width / (float)width, half_height / (float)height); }    // world units: the scale of a good bias
 };
 
 struct Camera : svo_camera {
@@ -171,6 +196,29 @@ public:
         if (light_dir) std::memcpy(p.light_dir, light_dir, sizeof p.light_dir);
         check(svo_trace_local_shadows(world_, &cam, &p, point_position, spot_position, 0, 0, cam.width, cam.height, gbuffer.device(), stream),
               "World::local_shadows");
+    }
+
+    // The shadow map of a fixed sun (svo_shadowmap_fit / _render / _apply; the reference's World::draw_shadowmap and computeShadow,
+    // src/World.cpp:162-203, shaders/World.Fragment.glsl:140-155): fit a width x height map around the world along `direction`, render it
+    // once - and again after every edit, a rendered map is stale behind one -, then per frame draw(cam, out, false) and shadowmap_apply:
+    // one lookup per hit in the place of one shadow ray.  bias in world units along the light, one to two ShadowMap::texel() is a good start.
+    void shadowmap_fit(const float direction[3], int width, int height, ShadowMap &map) const
+    {
+        if (map.width != width || map.height != height || !map.depth_dev) map.resize(width, height);
+        check(svo_shadowmap_fit(world_, direction, width, height, &map), "World::shadowmap_fit");
+    }
+    void shadowmap_render(const ShadowMap &map, uint32_t see_through = 0, void *stream = nullptr)
+    {
+        svo_trace_params p;
+        std::memset(&p, 0, sizeof p);
+        p.semantics = semantics;
+        p.see_through = see_through;
+        check(svo_shadowmap_render(world_, &map, &p, stream), "World::shadowmap_render");
+    }
+    void shadowmap_apply(const Camera &cam, GBuffer &gbuffer, const ShadowMap &map, float bias, void *stream = nullptr) const
+    {
+        check(svo_shadowmap_apply(&cam, &map, semantics == SVO_SEMANTICS_GLSL ? 1.0f / 4096.0f : 0.0f, bias, 0, 0, cam.width, cam.height, gbuffer.device(), stream),
+              "World::shadowmap_apply");
     }
 
     // Rays with a far end (svo_trace_segments): n rays (origins / dirs [n][3], tmax [n], all on the device) into out_dev; a hit counts only
