@@ -58,6 +58,9 @@
  *                           src/Main.cpp:149,190-198): the world marched once from the directional light into a depth image
  *   svo_shadowmap_apply  <- computeShadow                          shaders/World.Fragment.glsl:140-155,186
  *   svo_shadowmap_fit    <- the OrthoCamera's placement and glm::ortho(-w, w, -h, h)   src/Main.cpp:149, src/Camera.cpp:50-53
+ *   svo_hit_ao           <- (a departure: the reference has no ambient occlusion; its ambient term is one constant per material,
+ *                           shaders/World.Fragment.glsl:63-73) contact darkening from the eight lattice cells around each hit's face
+ *   svo_shade_ao         <- (a departure, with it) that factor on the shaded image
  *
  * Conventions
  *   - plain C, opaque handle, caller owns every buffer it passes in;
@@ -107,7 +110,8 @@ extern "C" {
                                           svo_cursor_place, svo_shade_boxes, svo_box and svo_world_edit_cube,
                                           svo_chunk_from_grid, svo_world_chunk_from_grid and svo_world_chunk_to_grid,
                                           svo_world_edit_ball and svo_world_edit_ball_all,
-                                          svo_shadowmap, svo_shadowmap_fit, svo_shadowmap_render and svo_shadowmap_apply */
+                                          svo_shadowmap, svo_shadowmap_fit, svo_shadowmap_render and svo_shadowmap_apply,
+                                          svo_hit_ao and svo_shade_ao */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -591,6 +595,52 @@ int svo_hit_voxels(svo_world *, const svo_hit *gbuffer_dev, int64_t n, svo_voxel
  * size or eps < 0: SVO_ERR_INVALID_ARG.  Asynchronous on `stream`. */
 int svo_hit_uv(const svo_camera *cam, float eps, int x0, int y0, int w, int h,
                const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, float *uv_dev, void *stream);
+
+/* Voxel ambient occlusion (not in the reference: an opt-in departure, as svo_trace_local_shadows is): ao_dev[k] in [0, 1], 1 = open,
+ * for pixel k of the rectangle svo_trace(cam, x0, y0, w, h) filled - gbuffer_dev its w*h records (or the surface records of a
+ * translucent frame), voxels_dev what svo_hit_voxels wrote for them.  The occluders of a surface point are the eight lattice cells
+ * around the open cell in front of the face that was hit; "is this cell solid" is what svo_world_locate answers.  No rays, no sampling.
+ * Of params only eps, semantics, kernel and see_through are read (NULL = defaults); eps == 0 means 1/8192, or 1/4096 under
+ * SVO_SEMANTICS_GLSL, as in svo_trace_local_shadows.
+ * A pixel gets the rule below if its record has SVO_HIT_FLAG and no SVO_ERR_FLAG, its voxel record has SVO_LOCATE_INSIDE and the voxel
+ * record's chunk is below the world's chunk count (checked before anything is loaded through it).  Every other pixel gets 1.0f.
+ * In float throughout, every operation separately rounded:
+ *   1. sample point   (o, d) the pixel's camera ray as the march forms it; P = o + d * (t - eps) - the point the normals and leafUV
+ *                     are taken at;
+ *   2. face           lo = bmin, hi = bmin + size of the voxel record; the SVO_NORMAL_FACE rule: c = (lo + hi) * 0.5f, q = P - c,
+ *                     the axis k is the one of the largest |q| (the first axis on ties), sgn is +1 or -1 like q[k], and against d[k]
+ *                     when q[k] is exactly 0;
+ *   3. lattice        e = cell if cell > 0; otherwise the finest voxel of the hit's chunk, ldexpf(chunksize, -(int)depth) with depth
+ *                     of the voxel record's chunk - a LEAF hit, however large its node, is shaded on the chunk's finest lattice.
+ *                     The lattice is anchored at the world origin;
+ *   4. the open cell  in front of the face: u < v the two axes other than k; for j in {u, v}: r_j = P[j] / e, g_j = floorf(r_j),
+ *                     f_j = r_j - g_j, Q[j] = (g_j + 0.5f) * e; Q[k] = (sgn > 0 ? hi[k] : lo[k]) + sgn * (e * 0.5f).  If r_u or r_v is
+ *                     not finite the pixel gets 1.0f;
+ *   5. neighbours     (a, b) = (-1,-1), (0,-1), (1,-1), (-1,0), (1,0), (-1,1), (0,1), (1,1): N = Q with N[u] = Q[u] + (float)a * e,
+ *                     N[v] = Q[v] + (float)b * e; occ(a, b) = 1 iff the record svo_world_locate writes for N under params has
+ *                     SVO_LOCATE_SOLID - a point outside the world or off its chunk is open, a LEAF is solid whatever its material,
+ *                     see_through = m opens material m;
+ *   6. corners        for (sa, sb) in {-1, +1}^2: s1 = occ(sa, 0), s2 = occ(0, sb), cn = occ(sa, sb);
+ *                     level = (s1 && s2) ? 0 : 3 - (s1 + s2 + cn); A(sa, sb) = (float)level / 3.0f;
+ *   7. bilinear       l0 = A(-1,-1) + (A(1,-1) - A(-1,-1)) * f_u; l1 = A(-1,1) + (A(1,1) - A(-1,1)) * f_u; ao = l0 + (l1 - l0) * f_v.
+ *                     Four open corners give exactly 1, four closed ones exactly 0.
+ * Kernel selection is svo_world_locate's: SVO_KERNEL_LITERAL walks the tree pool, SVO_KERNEL_STACK the wide trees (refused with
+ * SVO_ERR_UNSUPPORTED where svo_world_locate refuses it), SVO_KERNEL_AUTO the wide trees where they are allowed; all write the same floats.
+ * A NULL world or cam, a NULL buffer with w*h > 0, a rectangle that starts or extends backwards, cell negative, NaN or infinite,
+ * see_through > 0xFFFF, an unknown semantics or kernel: SVO_ERR_INVALID_ARG; then a world that is not resident: SVO_ERR_NOT_UPLOADED;
+ * then w*h == 0: SVO_OK; w*h >= 2^31: SVO_ERR_UNSUPPORTED.  All settled before any device work; a refused call writes nothing.
+ * Asynchronous on `stream`, ordered against updates, edits and shifts like svo_world_locate.  No launch slot and no scratch: calls on
+ * different streams are independent.  Nothing is cached: the pools are read as they are, the call after an edit sees the edit. */
+int svo_hit_ao(svo_world *, const svo_camera *cam, const svo_trace_params *params, float cell,
+               int x0, int y0, int w, int h,
+               const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, float *ao_dev, void *stream);
+
+/* svo_hit_ao's factor on an image a shade call has written (n float4 pixels): f = 1.0f - strength * (1.0f - ao); r, g and b are each
+ * multiplied by f, the depth float is not written.  ao == 1 gives f == 1 exactly and the pixel keeps its bits; a NaN ao leaves its
+ * pixel alone.  It goes after svo_shade* and before svo_shade_sky, svo_shade_boxes and svo_frame_rgba8 (miss pixels have ao == 1).
+ * Scaling the whole colour, not only the ambient addend, is a stated departure: svo_shade stays as it is.
+ * strength outside [0, 1] or NaN, n < 0, a NULL pointer with n > 0: SVO_ERR_INVALID_ARG; n == 0: SVO_OK.  Asynchronous on `stream`. */
+int svo_shade_ao(const float *ao_dev, float strength, int64_t n, float *rgba_dev, void *stream);
 
 /* order_dev[0..ntiles) = the tile indices sorted by descending cost[i][0] + cost[i][1] (a stable device sort; cost_dev as
  * svo_trace_params.tile_cost_dev of ONE frame wrote it).  Asynchronous on `stream`; calls of one world on different streams are

@@ -19,6 +19,7 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     cursor_place, shade_boxes, Box            <- computeTarget, ImaginaryCube / Light::draw   src/Main.cpp:314-319, src/ImaginaryCube.cpp:59-87
     World.edit_cube                           <- modify()                                  src/Main.cpp:321-368
     World.edit_ball / edit_ball_all           <- (none: the reference edits cubes only)    destroyCube / buildCube over a closed ball
+    World.hit_ao / ao_image, shade_ao         <- (none: the reference has no ambient occlusion)   the eight lattice cells around each hit's face
 
 There is NO CPU fallback: if libsvo_amd.so is missing the import raises, and every device call
 raises SvoError when HIP reports no device.
@@ -182,7 +183,7 @@ ABI_SYMBOLS = [
     "svo_chunk_from_grid", "svo_world_chunk_from_grid", "svo_world_chunk_to_grid",
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_edit_cube", "svo_world_edit_ball", "svo_world_edit_ball_all", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_cursor_place", "svo_shade_boxes", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
-    "svo_shadowmap_fit", "svo_shadowmap_render", "svo_shadowmap_apply",
+    "svo_shadowmap_fit", "svo_shadowmap_render", "svo_shadowmap_apply", "svo_hit_ao", "svo_shade_ao",
     "svo_device_count", "svo_device_alloc", "svo_device_free", "svo_device_cache_trim", "svo_memcpy_h2d", "svo_memcpy_d2h",
     "svo_stream_synchronize", "svo_last_error", "svo_abi_version",
 ]
@@ -240,6 +241,8 @@ lib.svo_world_locate.argtypes = [_P, _P, C.c_int64, C.POINTER(TraceParams), _P, 
 lib.svo_hit_voxels.argtypes = [_P, _P, C.c_int64, _P, _P]
 lib.svo_hit_uv.argtypes = [C.POINTER(Camera), C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
 lib.svo_shade_textured.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams), C.POINTER(Atlas), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
+lib.svo_hit_ao.argtypes = [_P, C.POINTER(Camera), C.POINTER(TraceParams), C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
+lib.svo_shade_ao.argtypes = [_P, C.c_float, C.c_int64, _P, _P]
 lib.svo_shade_sky.argtypes = [C.POINTER(Camera), C.POINTER(Sky), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
 lib.svo_frame_rgba8.argtypes = [_P, C.c_int64, _P, _P]
 lib.svo_cursor_place.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), _P, C.c_float, _P, _P]
@@ -457,6 +460,12 @@ def shade_textured(cam: Camera, params: ShadeParams, atlas: Atlas, rect, gbuffer
     _check(lib.svo_shade_textured(C.byref(cam) if cam is not None else None, C.byref(params) if params is not None else None,
                                   C.byref(atlas) if atlas is not None else None, x0, y0, w, h, gbuffer_ptr, voxels_ptr, rgba_ptr, stream),
            "svo_shade_textured")
+
+
+def shade_ao(ao_ptr: int, strength: float, n: int, rgba_ptr: int, stream: int = 0):
+    """svo_shade_ao: r, g, b of n float4 pixels scaled by 1 - strength * (1 - ao), ao the floats World.hit_ao wrote; behind a shade call,
+    before shade_sky, shade_boxes and frame_rgba8."""
+    _check(lib.svo_shade_ao(ao_ptr, strength, n, rgba_ptr, stream), "svo_shade_ao")
 
 
 def shade_sky(cam: Camera, sky: Sky, rect, rgba_ptr: int, gbuffer_ptr: Optional[int] = None, packed_ptr: Optional[int] = None, stream: int = 0):
@@ -713,6 +722,14 @@ class World:
         all zero for a record without a usable hit or whose (chunk, node, cell) name nothing reachable."""
         _check(lib.svo_hit_voxels(self._h, gbuffer_ptr, n, out_ptr, stream), "svo_hit_voxels")
 
+    def hit_ao(self, cam: Camera, params: Optional[TraceParams], rect, gbuffer_ptr: int, voxels_ptr: int, ao_ptr: int, cell: float = 0.0, stream: int = 0):
+        """svo_hit_ao: voxel ambient occlusion (w*h floats in [0, 1], 1 = open) of the G-buffer svo_trace(cam, rect) filled and the
+        records hit_voxels wrote for it; cell 0 = the finest voxel of each hit's chunk.  Only eps, semantics, kernel and see_through of
+        params are read; None = defaults."""
+        x0, y0, w, h = rect
+        _check(lib.svo_hit_ao(self._h, C.byref(cam) if cam is not None else None, C.byref(params) if params is not None else None, cell,
+                              x0, y0, w, h, gbuffer_ptr, voxels_ptr, ao_ptr, stream), "svo_hit_ao")
+
     def trace_translucent(self, cam: Camera, params: TraceParams, rect, surface_ptr: int, behind_ptr: int, stream: int = 0):
         """svo_trace_translucent: the surface G-buffer and, behind every hit of material params.see_through, the continuation's."""
         x0, y0, w, h = rect
@@ -841,3 +858,27 @@ class World:
         gd.free()
         out.free()
         return v
+
+    def ao_image(self, cam: Camera, records, rect=None, voxels=None, cell: float = 0.0, kernel: int = KERNEL_AUTO, semantics: int = 0,
+                 see_through: int = 0, eps: float = 0.0):
+        """World.hit_ao over host records (HIT_DTYPE[h, w], as World.draw(cam, rect) returns them); voxels: their VOXEL_DTYPE records
+        (None = hit_voxels').  Returns float32[h, w]."""
+        x0, y0, w, h = rect if rect is not None else (0, 0, cam.width, cam.height)
+        g = np.ascontiguousarray(records, dtype=HIT_DTYPE).reshape(-1)
+        n = w * h
+        assert g.shape[0] == n
+        gd, vd, out = DeviceBuffer.from_numpy(g), DeviceBuffer(max(n, 1) * 32), DeviceBuffer(max(n, 1) * 4)
+        try:
+            if voxels is None:
+                self.hit_voxels(gd.ptr, n, vd.ptr)
+            elif n:
+                v = np.ascontiguousarray(voxels, dtype=VOXEL_DTYPE).reshape(-1)
+                assert v.shape[0] == n
+                _check(lib.svo_memcpy_h2d(vd.ptr, v.ctypes.data, v.nbytes), "svo_memcpy_h2d")
+            self.hit_ao(cam, trace_params(kernel=kernel, semantics=semantics, see_through=see_through, eps=eps), (x0, y0, w, h),
+                        gd.ptr, vd.ptr, out.ptr, cell=cell)
+            _check(lib.svo_stream_synchronize(None), "svo_stream_synchronize")
+            return out.to_numpy(np.float32, n).reshape(h, w)
+        finally:
+            for b in (gd, vd, out):
+                b.free()

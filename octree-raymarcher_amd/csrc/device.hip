@@ -4,6 +4,7 @@
 //   svo_world_update  <- World::modify + RootAllocator::subst     src/World.cpp:268-274, src/Allocator.cpp:37-55
 //   svo_trace*        <- World::draw / draw_shadowmap             src/World.cpp:162-266
 //   svo_world_locate  <- traverse over a point list               src/Traverse.cpp:34-48 (locate.hip.h)
+//   svo_hit_ao        <- (none: the reference has no ambient occlusion)                    (ao.hip.h)
 //
 // The reference's first-fit free-list allocator over GL buffers is not reproduced: a world is
 // packed into one flat pool per kind with per-chunk slots sized by the chunk's host capacity
@@ -29,6 +30,7 @@
 #include "local_shadows.hip.h"
 #include "shadowmap.hip.h"
 #include "locate.hip.h"
+#include "ao.hip.h"
 #include "hit_voxels.hip.h"
 #include "hip_own.h"
 #include "wide_tree.hip.h"
@@ -1266,6 +1268,37 @@ int svo_world_locate(svo_world *w, const float *points_dev, int64_t n, const svo
     else hipLaunchKernelGGL(k_locate_literal, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A, see);
     HIP_TRY(hipGetLastError());
     return SVO_OK;
+}
+
+// Voxel ambient occlusion (ao.hip.h): svo_world_locate's walks on the eight lattice cells around the open cell in front of every hit's
+// face, folded in registers.  Kernel selection, and no launch slot, no scratch and no cache, as svo_world_locate.
+int svo_hit_ao(svo_world *w, const svo_camera *cam, const svo_trace_params *prm, float cell, int x0, int y0, int rw, int rh,
+               const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, float *ao_dev, void *stream)
+{
+    if (!w || !rect_ok(cam, x0, y0, rw, rh) || !(cell >= 0.0f && cell < INFINITY)) { set_error("svo_hit_ao: bad world, camera, rectangle or cell"); return SVO_ERR_INVALID_ARG; }
+    const int64_t n = (int64_t)rw * rh;
+    if (n > 0 && (!gbuffer_dev || !voxels_dev || !ao_dev)) { set_error("svo_hit_ao: NULL buffer"); return SVO_ERR_INVALID_ARG; }
+    if (prm && prm->see_through > 0xFFFFu) { set_error("svo_hit_ao: see_through is a 16-bit material"); return SVO_ERR_INVALID_ARG; }
+    if (prm && prm->semantics != SVO_SEMANTICS_CPU && prm->semantics != SVO_SEMANTICS_GLSL) { set_error("svo_hit_ao: unknown semantics"); return SVO_ERR_INVALID_ARG; }
+    if (prm && prm->kernel != SVO_KERNEL_AUTO && prm->kernel != SVO_KERNEL_LITERAL && prm->kernel != SVO_KERNEL_STACK) { set_error("svo_hit_ao: unknown kernel id"); return SVO_ERR_INVALID_ARG; }
+    TraceArgs A;
+    const int rc = fill_common(w, prm, A);                              // (residency; the world box, the tables, the pools and the resolved eps)
+    if (rc != SVO_OK) return rc;
+    A.counters = nullptr; A.tile_cost = nullptr; A.tile_order = nullptr;   // only eps, kernel, semantics and see_through are read
+    const int kernel = pick_kernel(w, prm, A);
+    if (kernel < 0) return kernel;
+    if (n == 0) return SVO_OK;
+    if (n > 0x7FFFFFFF) { set_error("svo_hit_ao: image too large"); return SVO_ERR_UNSUPPORTED; }
+    HIP_TRY(hipSetDevice(w->device));
+    A.n = n;
+    const PixelFrame F = make_frame(*cam, x0, y0, rw, rh);
+    const uint32_t see = prm ? prm->see_through : 0u;
+    const uint4 *g = reinterpret_cast<const uint4 *>(gbuffer_dev), *v = reinterpret_cast<const uint4 *>(voxels_dev);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)((n + 31) / 32));                         // eight lanes per pixel
+    if (kernel == SVO_KERNEL_STACK) hipLaunchKernelGGL(k_hit_ao<true>, grid, dim3(256), 0, s, A, F, cell, see, g, v, ao_dev);
+    else hipLaunchKernelGGL(k_hit_ao<false>, grid, dim3(256), 0, s, A, F, cell, see, g, v, ao_dev);
+    return launch_status("svo_hit_ao");
 }
 
 // The parent index for a svo_hit_voxels call on `s`: built on the device at the first call after a change to the pools - level 0

@@ -232,6 +232,18 @@ __global__ __launch_bounds__(256) void k_gbuffer_unpack(const uint2 *in, uint4 *
     out[2 * k + 1] = b;
 }
 
+// svo_shade_ao: r, g and b scaled by f = 1 - strength * (1 - ao); the depth float is not written, and neither is a pixel whose f is
+// exactly 1 (ao == 1, strength == 0) or NaN (a NaN ao)
+__global__ __launch_bounds__(256) void k_shade_ao(const float *ao, float strength, int64_t n, float4 *rgba)
+{
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const float f = 1.0f - strength * (1.0f - ao[k]);
+    if (f == 1.0f || f != f) return;
+    float *px = reinterpret_cast<float *>(rgba + k);
+    px[0] = px[0] * f; px[1] = px[1] * f; px[2] = px[2] * f;
+}
+
 } // namespace
 } // namespace svo
 
@@ -360,6 +372,13 @@ int svo_hit_uv(const svo_camera *cam, float eps, int x0, int y0, int rw, int rh,
     return launch_per_element("svo_hit_uv", (int64_t)rw * rh, (hipStream_t)stream, k_hit_uv, make_frame(*cam, x0, y0, rw, rh),
                               eps == 0.0f ? 1.0f / 8192.0f : eps, reinterpret_cast<const uint4 *>(gbuffer_dev), reinterpret_cast<const uint4 *>(voxels_dev),
                               reinterpret_cast<float2 *>(uv_dev));
+}
+
+// The ambient-occlusion factor of svo_hit_ao over an image a shade call has written
+int svo_shade_ao(const float *ao_dev, float strength, int64_t n, float *rgba_dev, void *stream)
+{
+    if (!(strength >= 0.0f && strength <= 1.0f) || n < 0 || (n > 0 && (!ao_dev || !rgba_dev))) { set_error("svo_shade_ao: bad argument"); return SVO_ERR_INVALID_ARG; }
+    return launch_per_element("svo_shade_ao", n, (hipStream_t)stream, k_shade_ao, ao_dev, strength, n, reinterpret_cast<float4 *>(rgba_dev));
 }
 
 } // extern "C"

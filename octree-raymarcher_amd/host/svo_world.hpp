@@ -18,6 +18,7 @@
 //                                       and the chunk's voxels back as a grid (svo_world_chunk_to_grid)   src/Octree.cpp:74-176
 //   svo::World::hit_voxels(...)      <- hit.bmin / hit.size of fragment main (svo_hit_voxels)   shaders/World.Fragment.glsl:168-172
 //   svo::World::hit_uv / shade_textured  <- leafUV, texture(Diffuse / Specular, uv) (svo_hit_uv, svo_shade_textured)   shaders/World.Fragment.glsl:5-15,178-182
+//   svo::World::hit_ao / shade_ao    <- (none: the reference has no ambient occlusion) svo_hit_ao, svo_shade_ao
 //   svo::World::shade_sky / frame_rgba8  <- Skybox::draw and the RGBA8 colour attachment (svo_shade_sky, svo_frame_rgba8)   src/Skybox.cpp, src/GBuffer.cpp
 //   svo::World::cursor_place / shade_boxes / edit_cube  <- computeTarget, ImaginaryCube::draw, modify() (svo_cursor_place, svo_shade_boxes,
 //                                       svo_world_edit_cube)   src/Main.cpp:314-368, src/ImaginaryCube.cpp:59-87
@@ -277,6 +278,23 @@ public:
                         const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, float *rgba_dev, void *stream = nullptr) const
     {
         check(svo_shade_textured(&cam, &p, &atlas, x0, y0, w, h, gbuffer_dev, voxels_dev, rgba_dev, stream), "World::shade_textured");
+    }
+
+    // Voxel ambient occlusion of the rectangle draw() filled (svo_hit_ao: w*h floats in [0, 1], 1 = open, from the eight lattice cells around
+    // the open cell in front of each hit's face; cell 0 = the finest voxel of the hit's chunk), and its factor on the shaded image
+    // (svo_shade_ao: behind a shade call, before shade_sky, shade_boxes and frame_rgba8).
+    void hit_ao(const svo_camera &cam, int x0, int y0, int w, int h, const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, float *ao_dev,
+                float cell = 0.0f, uint32_t see_through = 0, void *stream = nullptr)
+    {
+        svo_trace_params p;
+        std::memset(&p, 0, sizeof p);
+        p.semantics = semantics;
+        p.see_through = see_through;
+        check(svo_hit_ao(world_, &cam, &p, cell, x0, y0, w, h, gbuffer_dev, voxels_dev, ao_dev, stream), "World::hit_ao");
+    }
+    void shade_ao(const float *ao_dev, float strength, int64_t n, float *rgba_dev, void *stream = nullptr) const
+    {
+        check(svo_shade_ao(ao_dev, strength, n, rgba_dev, stream), "World::shade_ao");
     }
 
     // The skybox behind the misses (svo_shade_sky; src/Skybox.cpp, src/Main.cpp:227) over an image a shade call has written for the same

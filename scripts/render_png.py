@@ -1,5 +1,7 @@
 """Render one shaded frame (svo_trace + svo_shade) to a PNG — a human-readable sanity check of the whole path.
-    python scripts/render_png.py out.png [depth] [width] [height]
+    python scripts/render_png.py out.png [depth] [width] [height] [--ao STRENGTH]
+--ao STRENGTH (0..1): a ball of radius 12 is carved out of the terrain under the image's centre and the frame gets voxel ambient occlusion
+(svo_hit_ao + svo_shade_ao) at that strength: the ball reads as a hole, creases and the foot of walls darken.
 """
 import importlib, os, struct, sys, zlib
 import numpy as np
@@ -17,6 +19,11 @@ def write_png(path, rgb):
                            chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
 
 
+ao = None
+if "--ao" in sys.argv:
+    i = sys.argv.index("--ao")
+    ao = float(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 out = sys.argv[1] if len(sys.argv) > 1 else "frame.png"
 depth = int(sys.argv[2]) if len(sys.argv) > 2 else 9
 w = int(sys.argv[3]) if len(sys.argv) > 3 else 960
@@ -24,11 +31,23 @@ h = int(sys.argv[4]) if len(sys.argv) > 4 else 540
 W = svo.World.generate(4, 1, 4, 128, depth, build_device=0); W.upload(0)
 cam = svo.make_camera((256.3, 150.0, -40.0), (0.0, -0.5, 0.866), (0.0, 1.0, 0.0), 60.0, w, h)
 g = W.draw(cam, shadow=True)
+if ao is not None:
+    c = g[h // 2, w // 2]
+    assert c["flags"] & 1, "the image's centre sees no terrain"
+    fwd = np.array(cam.forward, np.float64)
+    W.edit_ball_all(svo.EDIT_DESTROY, np.array(cam.eye, np.float64) + fwd * float(c["t"]), 12.0)
+    g = W.draw(cam, shadow=True)
 P = svo.shade_defaults()
 # the reference's lights sit near the origin of a 4x4x4 world; for a picture, put a stronger sun-like term in
 P.directional.diffuse[:] = [0.9, 0.85, 0.7]; P.directional.ambient[:] = [0.25, 0.3, 0.4]
 gb = svo.DeviceBuffer.from_numpy(g); rgba = svo.DeviceBuffer(w * h * 16)
-svo.shade(cam, P, (0, 0, w, h), gb.ptr, rgba.ptr); svo.lib.svo_stream_synchronize(None)
+svo.shade(cam, P, (0, 0, w, h), gb.ptr, rgba.ptr)
+if ao is not None:
+    vox, aod = svo.DeviceBuffer(w * h * 32), svo.DeviceBuffer(w * h * 4)
+    W.hit_voxels(gb.ptr, w * h, vox.ptr)
+    W.hit_ao(cam, None, (0, 0, w, h), gb.ptr, vox.ptr, aod.ptr)
+    svo.shade_ao(aod.ptr, ao, w * h, rgba.ptr)
+svo.lib.svo_stream_synchronize(None)
 img = rgba.to_numpy(np.float32, w * h * 4).reshape(h, w, 4)
 rgb = np.nan_to_num(img[..., :3], nan=0.0)
 hit = (g["flags"] & 1) != 0
