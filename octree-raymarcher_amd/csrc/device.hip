@@ -845,10 +845,12 @@ static int pick_kernel(const svo_world *w, const svo_trace_params *prm, const Tr
 {
     const int want = prm ? prm->kernel : SVO_KERNEL_AUTO;
     // (brick indices and wide node indices are 32-bit in the kernel at any size: fewer than 2^32 bricks / wide nodes per world)
-    const bool stack_ok = w->exact_geometry && w->max_levels <= (int)WIDE_MAX_LEVELS && w->wide_ok && w->twig_pool_cap < (1ull << 32);
+    // (... and chunk indices are formed with 24-bit multiplies, kernel_stack.hip.h chunk_index_u24: fewer than 2^24 chunks)
+    const bool stack_ok = w->exact_geometry && w->max_levels <= (int)WIDE_MAX_LEVELS && w->wide_ok && w->twig_pool_cap < (1ull << 32) &&
+                          (long long)w->width * w->height * w->depth < (1ll << 24);
     if (want == SVO_KERNEL_LITERAL) return SVO_KERNEL_LITERAL;
     if (want == SVO_KERNEL_STACK) {
-        if (!stack_ok) { set_error("svo_trace: SVO_KERNEL_STACK needs exact geometry, chunk depth <= 24 and the world's wide trees (svo_world_info.wide_nodes)"); return SVO_ERR_UNSUPPORTED; }
+        if (!stack_ok) { set_error("svo_trace: SVO_KERNEL_STACK needs exact geometry, chunk depth <= 24, fewer than 2^24 chunks and the world's wide trees (svo_world_info.wide_nodes)"); return SVO_ERR_UNSUPPORTED; }
         return SVO_KERNEL_STACK;
     }
     if (want != SVO_KERNEL_AUTO) { set_error("svo_trace: unknown kernel id"); return SVO_ERR_INVALID_ARG; }

@@ -44,7 +44,7 @@
 //    reference's own expressions instead of being held): 80 VGPRs, 6 waves per SIMD, no spill inside the pass loop.
 //  * The chunk table of worlds of up to 64 chunks sits in LDS: the chunk step waits for no global load.
 //  * Instantiations (round 4): BIG - 64-bit wide-tree and mask addresses for worlds beyond 4 GiB of wide nodes / 2^29 bricks, a
-//    128-chunk LDS table; GLSL - the march of shaders/Chunkmarch.glsl (svo_trace_params.semantics): guarded escape distance, LEAF
+//    126-chunk LDS table; GLSL - the march of shaders/Chunkmarch.glsl (svo_trace_params.semantics): guarded escape distance, LEAF
 //    hits at t, tnear > 0 at the world entry, no containment re-check.  The asm statement (step_asm_body.inc) and the creep block
 //    (creep_block.inc) are shared text.
 //
@@ -88,12 +88,45 @@ constexpr int DRAIN_STEPS = 8;          // (round 4: 8 instead of 4 - one frame 
 // 1/x for x an exact power of two (normal range): exponent negation, no division sequence.
 __device__ __forceinline__ float recip_pow2(float x) { return __uint_as_float(0x7F000000u - __float_as_uint(x)); }
 
-// World::index(World::index_float(p)) for a power-of-two chunk edge (src/World.cpp:288-293,323-332):
+// A wave vote.  HIP's __ballot(int) takes a lane value: a bool goes through v_cndmask 0/1 and a second compare wherever the
+// optimiser does not see through it; the builtin takes the compare's own mask.
+__device__ __forceinline__ unsigned long long vote(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+// ... and the number of its lanes as a 32-bit scalar.  __popcll is 64 bits wide and the optimiser, knowing that, widens every
+// comparison of the count back to 64 bits - a v_cmp_*_u64 on an SGPR pair with moves around it, the SALU has no ordered 64-bit
+// compare.  Behind the (empty) statement the count is an int in an SGPR and a comparison of it one s_cmp.
+__device__ __forceinline__ int vote_count(unsigned long long m)
+{
+    int n = (int)__popcll(m);
+    asm("" : "+s"(n));
+    return n;
+}
+
+// What the chunk step needs of the chunk grid, eight words that k_trace_stack stages in LDS once per wave beside the chunk
+// table: read there, the block waits for an LDS read where it waited for scalar loads of ten kernel arguments (a trip to the
+// scalar cache in six of ten passes; holding them in SGPRs across the march loop is what the kernel has no room for).
+struct ChunkGrid {
+    float inv;                  // 1 / chunksize, exact: the edge is a power of two
+    int32_t off[3];             // cbase - ccm: grid cell of a chunk coordinate = coordinate + off, within one period of the grid
+    int32_t dimw, dimh, dimd;
+    uint32_t table_in_lds;      // the chunk table lies in LDS as well (at most CHUNK_TAB chunks)
+};
+static_assert(sizeof(ChunkGrid) == 32, "two 16-byte LDS reads");
+
+// m mod dim for -dim <= m < 2 dim (cbase - 1 <= m <= cbase + dim with 0 <= cbase < dim, below): of m, m + dim and m - dim the one
+// in [0, dim) is the smallest as an unsigned number, the others are negative (huge) or larger by dim - add, subtract, v_min3_u32
+// where "subtract dim if >= dim, then add dim if negative" took six instructions per axis.
+__device__ __forceinline__ int wrap_once(int m, int dim)
+{
+    const uint32_t a = (uint32_t)m, b = (uint32_t)(m + dim), c = (uint32_t)(m - dim);
+    return (int)min(min(a, b), c);
+}
+
+// World::index_float(p) for a power-of-two chunk edge (src/World.cpp:288-293,323-332), as the grid cell (mx, my, mz):
 // p / chunksize == p * inv (exact), and positive_mod() of a coordinate that lies within one grid
 // period of the grid's first chunk is a conditional add/subtract.  Only for p inside the world box.
-__device__ __forceinline__ int chunk_index_pow2(const TraceArgs &A, V3 p)
+__device__ __forceinline__ void chunk_cell_pow2(const ChunkGrid &G, V3 p, int &mx, int &my, int &mz)
 {
-    float qx = p.x * A.inv_chunksize, qy = p.y * A.inv_chunksize, qz = p.z * A.inv_chunksize;
+    float qx = p.x * G.inv, qy = p.y * G.inv, qz = p.z * G.inv;
     if (qx < 0.0f) qx -= 1.0f;
     if (qy < 0.0f) qy -= 1.0f;
     if (qz < 0.0f) qz -= 1.0f;
@@ -101,12 +134,23 @@ __device__ __forceinline__ int chunk_index_pow2(const TraceArgs &A, V3 p)
     // p lies inside the world box (the caller's isInsideCube test, src/Traverse.cpp:145): wlo <= p <= whi with
     // wlo = ccm * chunksize and whi = (ccm + dims) * chunksize exactly, so ccm - 1 <= i <= ccm + dims per axis (the - 1:
     // index_float sends an exact negative multiple one chunk down) - within one grid period, no general modulo needed
-    const int rx = ix - A.ccm[0], ry = iy - A.ccm[1], rz = iz - A.ccm[2];
-    int mx = A.cbase[0] + rx, my = A.cbase[1] + ry, mz = A.cbase[2] + rz;
-    mx -= (mx >= A.dimw) ? A.dimw : 0; mx += (mx < 0) ? A.dimw : 0;
-    my -= (my >= A.dimh) ? A.dimh : 0; my += (my < 0) ? A.dimh : 0;
-    mz -= (mz >= A.dimd) ? A.dimd : 0; mz += (mz < 0) ? A.dimd : 0;
-    return my * A.dimw * A.dimd + mz * A.dimw + mx;
+    // (cbase + (i - ccm) == i + (cbase - ccm) in 32-bit arithmetic)
+    mx = wrap_once(ix + G.off[0], G.dimw); my = wrap_once(iy + G.off[1], G.dimh); mz = wrap_once(iz + G.off[2], G.dimd);
+}
+// World::index (src/World.cpp:288-293) of the grid cell, (my * dimd + mz) * dimw + mx.  The stack kernel marches worlds of fewer
+// than 2^24 chunks (device.hip, pick_kernel: larger ones go to the literal kernel): 0 <= mx < dimw, my < dimh, mz < dimd, every
+// dimension and the partial sum my * dimd + mz < dimh * dimd are then below 2^24 and both products exact as 24-bit ones
+// (v_mul_u32_u24 / v_mad_u32_u24, full rate, where v_mul_lo_u32 runs at a quarter).
+// (as a statement: the optimiser turns the inner __umul24, of which the outer one needs 24 bits only, back into a 32-bit multiply)
+__device__ __forceinline__ uint32_t mad_u24(uint32_t a, uint32_t b, uint32_t c)
+{
+    uint32_t r;
+    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+__device__ __forceinline__ int chunk_index_u24(const ChunkGrid &G, int mx, int my, int mz)
+{
+    return (int)mad_u24(mad_u24((uint32_t)my, (uint32_t)G.dimd, (uint32_t)mz), (uint32_t)G.dimw, (uint32_t)mx);
 }
 
 // cubeNormal (shaders/Chunkmarch.glsl:128-136) for a cube whose half edge is a power of two:
@@ -157,17 +201,23 @@ __device__ __forceinline__ uint32_t wide_slot(int ux, int uy, int uz, int sh)
 __device__ __forceinline__ bool is_branch(uint32_t word) { return (int32_t)word < (int32_t)0xC0000000; }
 
 // The launch arguments as they lie in the kernarg segment, behind a barrier the optimiser cannot see through: a rare
-// block that reads its arguments through this re-loads them with scalar loads where it runs, instead of pinning
-// ~60 SGPRs (camera, world grid) across the march loop, which spilled into VGPR lanes (v_readlane in the hot path).
+// block that reads its arguments through this re-loads them where it runs, instead of pinning ~60 SGPRs (camera, world
+// grid) across the march loop, which spilled into VGPR lanes (v_readlane in the hot path).  What the loads compile to, at every
+// call site of this kernel (the refill's tile order pointer, tile generation, note_tile_cost): VECTOR loads of the uniform address,
+// scalar base plus a zero lane offset (global_load_dword(x2/x4) v, vzero, s[..] offset:field), not s_load - the copy through memcpy
+// loses the constant address space - each group waited for (s_waitcnt vmcnt) before the next is issued, and whatever is derived
+// from the values is computed per lane.  A few hundred cycles per tile of 64 rays; tile generation is 2.8 % of the kernel's
+// instructions.  Reading the fields through an address_space(4) pointer gives s_load and costs the march loop ten more spilled
+// VGPRs, some inside the chunk step (profiles/blocks_diet_ab.txt): left as it is.
 __device__ __forceinline__ TraceArgs args_reloaded()
 {
     auto p = __builtin_amdgcn_kernarg_segment_ptr();
     asm volatile("" : "+s"(p));
     TraceArgs T;
-    __builtin_memcpy(&T, p, sizeof T);              // only the fields the caller uses survive (scalar loads)
+    __builtin_memcpy(&T, p, sizeof T);              // only the fields the caller uses survive
     return T;
 }
-// camera f of the launch, read where it is needed with scalar loads at a uniform offset
+// camera f of the launch, read where it is needed at a uniform offset (vector loads in tile generation, see above)
 __device__ __forceinline__ FrameCam camera_reloaded(int f)
 {
     auto p = __builtin_amdgcn_kernarg_segment_ptr();
@@ -265,15 +315,24 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
     // the chunk table (bmin, levels, wide offset, brick offset) of worlds of up to 64 chunks - the reference's default is 4x4x4 -
     // staged in LDS: the chunk step then reads it there instead of waiting for a 32-byte global load per lane (the block runs
     // in six of ten passes and a wave waits out the slowest lane's load each time)
-    // (the large-world instantiation holds 128 chunks - a 10x1x10 grid of depth-12 chunks is 68 GB of pools - for 1.5 KB more LDS
-    // per wave: 22 instead of 24 waves fit a CU's 160 KB)
-    constexpr int CHUNK_TAB = (BIG && MAXLV <= 10) ? 128 : 64;      // (the deep instantiation's descent column already takes the room)
+    // (the large-world instantiation holds 126 chunks - a 10x1x10 grid of depth-12 chunks is 68 GB of pools - for 1.5 KB more LDS
+    // per wave: 22 instead of 24 waves fit a CU's 160 KB; 126, not 128 - and 62, not 64, under the deepest instantiation's descent
+    // column, which takes as much: the table and the 32 bytes of chunk_grid below together take what the table alone took, so
+    // that none of the 7,424- and 7,680-byte instantiations crosses an LDS allocation step)
+    constexpr int CHUNK_TAB = (BIG && MAXLV <= 10) ? 126 : MAXLV > 16 ? 62 : 64;      // (the deep instantiations' descent column already takes the room)
     __shared__ uint32_t chunk_tab[6][CHUNK_TAB];
+    __shared__ __attribute__((aligned(16))) ChunkGrid chunk_grid;       // (32 B: 5,920 B of LDS per wave where the table holds 64 chunks; 24 waves per CU could take 6,826)
     stk[0][threadIdx.x] = 0u;              // o, d, 1/d, world-entry t, output index (as int; -1 = no ray)
     const int lane = threadIdx.x;
     const bool want_cost = A.tile_cost != nullptr;      // (one SGPR held; the blocks below must not re-read the kernel arguments for a feature that is off)
     const int n_chunks = A.dimw * A.dimh * A.dimd;
     const bool chunks_in_lds = n_chunks <= CHUNK_TAB;
+    if (lane == 0) {
+        chunk_grid.inv = A.inv_chunksize;
+        for (int a = 0; a < 3; ++a) chunk_grid.off[a] = A.cbase[a] - A.ccm[a];
+        chunk_grid.dimw = A.dimw; chunk_grid.dimh = A.dimh; chunk_grid.dimd = A.dimd;
+        chunk_grid.table_in_lds = chunks_in_lds ? 1u : 0u;
+    }
     if (chunks_in_lds)
         for (int i = lane; i < n_chunks; i += 64) {
             const DevWide ch = A.wchunks[i];
@@ -360,8 +419,8 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
     int creepn = 0;
     for (;;) {
         // ==== refill retired lanes =============================================================
-        unsigned long long dead = __ballot(mode == M_DONE);
-        while (more && __popcll(dead) >= REFILL) {
+        unsigned long long dead = vote(mode == M_DONE);
+        while (more && vote_count(dead) >= REFILL) {
             if (tile_next >= 64) {
                 int t32 = -1, tcol = 0, trow = 0, tframe = 0;   // raster index of the tile, its column and row, its frame
                 const uint32_t *order = args_reloaded().tile_order;
@@ -459,10 +518,10 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
                     mode = M_WORLD;
                 }
             }
-            const int ndead = __popcll(dead);
+            const int ndead = vote_count(dead);
             tile_next += (ndead < avail) ? ndead : avail;
             __syncthreads();                                // reads done before a later tile overwrites the buffer
-            dead = __ballot(mode == M_DONE);
+            dead = vote(mode == M_DONE);
         }
         if (dead == ~0ull) break;                       // nothing alive and nothing left to fetch
 #ifdef SVO_STACK_TIMING
@@ -472,12 +531,14 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
 #endif
 
         // ==== votes: which of the rare blocks run this iteration ================================
-        const int n_busy = __popcll(__ballot(mode == M_TREE || mode == M_TWIG));
-        const int n_world = __popcll(__ballot(mode == M_WORLD));
-        const int n_hit = __popcll(__ballot(mode == M_HIT));
-        const bool run_world = n_world > 0 && (n_world >= VOTE_WORLD || n_busy < VOTE_BUSY ||
-                                               __ballot(mode == M_WORLD && creepn <= -CREEP_SERIOUS) != 0ull);
-        const bool run_hit = n_hit > 0 && (n_hit >= VOTE_HIT || n_busy < VOTE_BUSY);
+        const int n_busy = vote_count(vote(mode == M_TREE || mode == M_TWIG));
+        const int n_world = vote_count(vote(mode == M_WORLD));
+        const int n_hit = vote_count(vote(mode == M_HIT));
+        // (n > 0 && (n >= VOTE || n_busy < VOTE_BUSY) as one scalar compare against a selected threshold)
+        const bool few_busy = n_busy < VOTE_BUSY;
+        bool run_world = n_world >= (few_busy ? 1 : VOTE_WORLD);
+        if (!run_world && n_world > 0) run_world = vote(mode == M_WORLD && creepn <= -CREEP_SERIOUS) != 0ull;
+        const bool run_hit = n_hit >= (few_busy ? 1 : VOTE_HIT);
 
         if (SVO_UNLIKELY(mode != M_DONE && mode != M_HIT && ++guard > STEP_GUARD)) {     // runaway ray: give up, flag it
             if (outk < 0) store_flags(A.out, outk & 0x7FFFFFFF, SVO_HIT_FLAG | SVO_SHADOW_TRACED | SVO_ERR_FLAG | (A.normal_mode == SVO_NORMAL_FACE ? (uint32_t)SVO_FACE_NORMAL : 0u));
@@ -489,7 +550,10 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
 #ifdef SVO_STACK_TIMING
         n_world_runs += run_world; n_hit_runs += run_hit;
 #endif
-        if (run_world && mode == M_WORLD) {
+        // (the votes are wave-uniform: a scalar branch over a block that does not run - folded into the lane mask, a pass without the
+        // block paid the mask's scalar arithmetic and an EXEC round trip; the empty statement keeps the two tests apart)
+        if (SVO_LIKELY(run_world)) { asm volatile("");
+        if (mode == M_WORLD) {
             if (cw < 0) {                               // left its chunk in the step: t += escape(chunk box) + EPS, src/Traverse.cpp:164-168
                 cw &= ~CW_ESCAPE_PENDING;
                 if constexpr (GLSL) tw += guarded(escape(O, g, clo, clo + csize), eps) + eps;       // (the guard's threshold IS the march's EPS, Chunkmarch.glsl:113)
@@ -502,7 +566,11 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
                 const V3 p = alpha + beta * tw;
                 miss = !inside(p, wlo, whi);
                 if (!miss) {
-                    const int ci_new = chunk_index_pow2(A, p);
+                    const ChunkGrid G = chunk_grid;                 // (two LDS reads at a uniform address)
+                    const bool table_in_lds = __builtin_amdgcn_readfirstlane((int)G.table_in_lds) != 0;
+                    int mx, my, mz;
+                    chunk_cell_pow2(G, p, mx, my, mz);
+                    const int ci_new = chunk_index_u24(G, mx, my, mz);
                     // The descent cache (stk column, pux/puy/puz, valid) is keyed by chunk and cell, not by ray: a ray that
                     // enters the chunk this lane marched last - a shadow ray leaving its primary hit, the next pixel of the
                     // tile, a ray pinned on a chunk face - restarts below the deepest common level instead of at the root.
@@ -512,7 +580,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
                     if (ci_new != ci) { valid = 0; pux = 0; puy = 0; puz = 0; }
                     ci = ci_new;
                     uint32_t ch_levels, ch_wide, ch_twig;
-                    if (chunks_in_lds) {
+                    if (table_in_lds) {
                         clo = mk(__uint_as_float(chunk_tab[0][ci]), __uint_as_float(chunk_tab[1][ci]), __uint_as_float(chunk_tab[2][ci]));
                         ch_levels = chunk_tab[3][ci]; ch_wide = chunk_tab[4][ci]; ch_twig = chunk_tab[5][ci];
                     } else {
@@ -545,7 +613,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
                 if (want_cost) note_tile_cost(outk, guard);
                 mode = M_DONE;                          // shadow miss: record already says "traced, lit"
             }
-        }
+        } }
 
         // ---- one step of the current level: tree (src/Traverse.cpp:79-111) or brick (:54-70) -----
         //      First decide what the step does (locate the cell, read its node / mask bit), then apply exactly one of
@@ -555,7 +623,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
         //      rays after the tile cursors ran dry, alone on their SIMD and bound by their own instruction stream.
         int pass = 0;
         // in the bulk: STEP_EXTRA more steps, decided once per pass of the outer loop (n_busy: before the chunk step)
-        const int fixed_steps = (n_busy >= STEP_LANES && __ballot(creepn > 0 || creepn <= -4 * CREEP_SERIOUS) == 0ull) ? STEP_EXTRA : 0;
+        const int fixed_steps = (n_busy >= STEP_LANES && vote(creepn > 0 || creepn <= -4 * CREEP_SERIOUS) == 0ull) ? STEP_EXTRA : 0;
         for (;;) {
 #ifdef SVO_STACK_TIMING
         n_lane_twig += mode == M_TWIG ? (pass == 0 ? 1u + (unsigned)fixed_steps : (unsigned)DRAIN_STEPS) : 0u;        // ... of them started inside a brick
@@ -692,9 +760,9 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
         ++pass;
         if (pass <= fixed_steps) continue;
         if (more || pass >= 256) break;
-        const unsigned long long marching = __ballot(mode == M_TREE || mode == M_TWIG);
-        if (marching == 0ull || marching != __ballot(mode != M_DONE) || __ballot(creepn > 0 || creepn <= -4 * CREEP_SERIOUS) != 0ull) break;
-        if constexpr (SEG) if (__ballot(past_far_end<GLSL>(mode, t, tt_saved, tw, eps, far)) != 0ull) break;       // a lane of the draining wave has reached its far end
+        const unsigned long long marching = vote(mode == M_TREE || mode == M_TWIG);
+        if (marching == 0ull || marching != vote(mode != M_DONE) || vote(creepn > 0 || creepn <= -4 * CREEP_SERIOUS) != 0ull) break;
+        if constexpr (SEG) if (vote(past_far_end<GLSL>(mode, t, tt_saved, tw, eps, far)) != 0ull) break;       // a lane of the draining wave has reached its far end
         }
         guard += pass - 1;
         if constexpr (SEG) {
@@ -722,7 +790,8 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
                 mode = M_DONE;
             }
         }
-        if (run_hit && mode == M_HIT) {
+        if (run_hit) { asm volatile("");
+        if (mode == M_HIT) {
             // which voxel: the node comes from the descent cache; the frame still describes the level that hit
             const int nw = levels ? (levels + 1) >> 1 : 1;
             const uint32_t wn = valid > 0 ? stk[valid][lane] : 0u, slot = wide_slot(pux, puy, puz, 2 * (nw - 1 - valid));
@@ -738,7 +807,10 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
                 else wnode_in_pool = (wide_b >> 8) + wn;
                 const uint32_t *wb = A.wbase + wnode_in_pool * WIDE_BASE_WORDS;
                 const int level_child = 2 * valid + 1 - (2 * nw - levels);
-                node = plev == level_child ? wb[0] + ci : wb[1 + ci] + gi;
+                // one load at a selected index, issued while the entry is on its way and waited for together with it (it was two
+                // loads behind a lane-divergent branch, each with a wait of its own)
+                const bool child = plev == level_child;
+                node = wb[child ? 0u : 1u + ci] + (child ? ci : gi);
             }
             const uint32_t hitc = (uint32_t)cnt;                    // which brick cell (or SVO_CELL_NONE: a LEAF)
             V3 vlo;
@@ -775,7 +847,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
                 mode = hit ? M_WORLD : M_DONE;          // a shadow ray that misses the world box stays "lit"
                 rays_marched++;
             }
-        }
+        } }
     }
 
     unsigned total = rays_marched;
