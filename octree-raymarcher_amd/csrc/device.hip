@@ -79,15 +79,6 @@ __global__ __launch_bounds__(256) void k_tile_keys(const uint32_t *cost, uint32_
     idx[i] = (uint32_t)i;
 }
 
-static int launch_brick_masks(svo_world &w, uint64_t first, uint64_t count, hipStream_t s)
-{
-    const uint64_t blocks = (count * 8 + 255) / 256;
-    if (blocks > 0x7FFFFFFFull) { set_error("brick pool too large for one mask launch"); return SVO_ERR_UNSUPPORTED; }
-    hipLaunchKernelGGL(k_brick_masks, dim3((unsigned)blocks), dim3(256), 0, s, w.hbm->twig.p, w.hbm->mask.p, w.hbm->bmat.p, first, count);
-    HIP_TRY(hipGetLastError());
-    return SVO_OK;
-}
-
 // ---- the large device buffers of a world (tree, brick, mask, material, wide pools, the wide builder's scratch) -------------
 // A caller that replaces its world - destroy + generate, a re-pack after an edit outgrew the pools - asks for the sizes it has
 // just given back.  hipFree + hipMalloc of multi-GB buffers is not free on every runtime (on the development pool a hipMalloc
@@ -279,7 +270,7 @@ int copy_chunk(svo_world &w, int i, const uint32_t *tree, const uint16_t *twig, 
     if (tl < tr) HIP_TRY(copy(w.hbm->tree.p + e.tree_off + tl, tree + tl, (tr - tl) * sizeof(uint32_t)));
     if (bl >= br) return SVO_OK;
     HIP_TRY(copy(w.hbm->twig.p + (e.twig_off + bl) * TWIG_WORDS, twig + bl * TWIG_WORDS, (br - bl) * TWIG_WORDS * sizeof(uint16_t)));
-    return launch_brick_masks(w, e.twig_off + bl, br - bl, s);
+    return launch_per_element("brick masks", (int64_t)(br - bl) * 8, s, k_brick_masks, w.hbm->twig.p, w.hbm->mask.p, w.hbm->bmat.p, e.twig_off + bl, br - bl);
 }
 
 // A chunk built on the device keeps its node words and bricks there until somebody asks for the host copy.
@@ -782,11 +773,36 @@ static V3 miss_ray_origin(const svo_world *w)
     return V3{ world_min(w, 0), world_min(w, 1) - (float)w->height * cs - cs, world_min(w, 2) - (float)w->depth * cs - cs };
 }
 
+// What every entry point refuses in a svo_trace_params (null: the defaults), with the message of `who`.  The entry points differ in
+// what they look at before which of these (svo_trace asks for residency between the first and the second, and reads the kernel id
+// last of all), so `which` picks the checks of one call; what a call returns when several faults meet is part of the ABI by now.
+enum { PRM_SEE_THROUGH = 1, PRM_SEMANTICS = 2, PRM_KERNEL = 4, PRM_ALL = 7 };
+static int refuse_params(const char *who, const svo_trace_params *prm, int which = PRM_ALL)
+{
+    const auto refuse = [who](const char *what) { set_error(std::string(who) + what); return SVO_ERR_INVALID_ARG; };
+    if (!prm) return SVO_OK;
+    if ((which & PRM_SEE_THROUGH) && prm->see_through > 0xFFFFu) return refuse(": see_through is a 16-bit material");
+    if ((which & PRM_SEMANTICS) && prm->semantics != SVO_SEMANTICS_CPU && prm->semantics != SVO_SEMANTICS_GLSL) return refuse(": unknown semantics");
+    if ((which & PRM_KERNEL) && prm->kernel != SVO_KERNEL_AUTO && prm->kernel != SVO_KERNEL_LITERAL && prm->kernel != SVO_KERNEL_STACK) return refuse(": unknown kernel id");
+    return SVO_OK;
+}
+
+// The params of the march a stage issues on a ray list of its own: the caller's, without the per-ray and per-tile buffers (they are
+// sized for the caller's frame) and, unless the stage keeps them, without shadow rays
+static svo_trace_params own_list_params(const svo_trace_params &prm, bool keep_shadow)
+{
+    svo_trace_params march = prm;
+    if (!keep_shadow) march.shadow = 0;
+    march.counters_dev = nullptr; march.tile_cost_dev = nullptr; march.tile_order_dev = nullptr;
+    return march;
+}
+
 static int fill_common(svo_world *w, const svo_trace_params *prm, TraceArgs &A)
 {
     if (!w) return SVO_ERR_INVALID_ARG;
-    if (prm && prm->see_through > 0xFFFFu) { set_error("svo_trace: see_through is a 16-bit material"); return SVO_ERR_INVALID_ARG; }
+    if (const int rc = refuse_params("svo_trace", prm, PRM_SEE_THROUGH)) return rc;
     if (w->device < 0) { set_error("svo_trace: world is not uploaded"); return SVO_ERR_NOT_UPLOADED; }
+    if (const int rc = refuse_params("svo_trace", prm, PRM_SEMANTICS)) return rc;
     std::memset(&A, 0, sizeof A);
     const float cs = (float)w->chunksize;
     const int dims[3] = { w->width, w->height, w->depth };
@@ -803,7 +819,6 @@ static int fill_common(svo_world *w, const svo_trace_params *prm, TraceArgs &A)
     }
     A.chunks = w->hbm->chunks.p; A.tree = w->hbm->tree.p; A.twig = w->hbm->twig.p; A.mask = w->hbm->mask.p;
     A.wchunks = w->hbm->wchunks.p; A.wide = w->hbm->wide.p; A.wbase = w->hbm->wbase.p; A.bmat = w->hbm->bmat.p;
-    if (prm && prm->semantics != SVO_SEMANTICS_CPU && prm->semantics != SVO_SEMANTICS_GLSL) { set_error("svo_trace: unknown semantics"); return SVO_ERR_INVALID_ARG; }
     const bool glsl = prm && prm->semantics == SVO_SEMANTICS_GLSL;      // defaults: src/Traverse.cpp:8,54,79,142 / shaders/Chunkmarch.glsl:1-3,17
     A.glsl = glsl ? 1 : 0;
     A.eps = (prm && prm->eps != 0.0f) ? prm->eps : (glsl ? 1.0f / 4096.0f : 1.0f / 8192.0f);
@@ -843,6 +858,7 @@ static bool stack_needs_big(const svo_world *w)
 
 static int pick_kernel(const svo_world *w, const svo_trace_params *prm, const TraceArgs &A)
 {
+    if (const int rc = refuse_params("svo_trace", prm, PRM_KERNEL)) return rc;
     const int want = prm ? prm->kernel : SVO_KERNEL_AUTO;
     // (brick indices and wide node indices are 32-bit in the kernel at any size: fewer than 2^32 bricks / wide nodes per world)
     // (... and chunk indices are formed with 24-bit multiplies, kernel_stack.hip.h chunk_index_u24: fewer than 2^24 chunks)
@@ -853,7 +869,6 @@ static int pick_kernel(const svo_world *w, const svo_trace_params *prm, const Tr
         if (!stack_ok) { set_error("svo_trace: SVO_KERNEL_STACK needs exact geometry, chunk depth <= 24, fewer than 2^24 chunks and the world's wide trees (svo_world_info.wide_nodes)"); return SVO_ERR_UNSUPPORTED; }
         return SVO_KERNEL_STACK;
     }
-    if (want != SVO_KERNEL_AUTO) { set_error("svo_trace: unknown kernel id"); return SVO_ERR_INVALID_ARG; }
     return (stack_ok && !A.counters) ? SVO_KERNEL_STACK : SVO_KERNEL_LITERAL;
 }
 
@@ -903,12 +918,11 @@ static int use_view(svo_world *w, uint32_t m, TraceArgs &A, hipStream_t s)
             for (Event &e : d.work_done) if (e.e) if (const int rc = e.wait(s)) return rc;
         }
         d.view_material = 0;                                            // (until the build below is issued)
-        if ((n4 + 255) / 256 > 0x7FFFFFFFull || (bricks * 8 + 255) / 256 > 0x7FFFFFFFull) { set_error("svo_trace: pools too large for one view launch"); return SVO_ERR_UNSUPPORTED; }
-        if (n4) hipLaunchKernelGGL(k_view_wide, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const uint4 *>(d.wide.p),
-                                   reinterpret_cast<uint4 *>(d.view_wide.p), n4, m);
-        if (bricks) hipLaunchKernelGGL(k_view_mask, dim3((unsigned)((bricks * 8 + 255) / 256)), dim3(256), 0, s, d.twig.p, d.mask.p, d.view_mask.p, bricks, m);
-        HIP_TRY(hipGetLastError());
-        if (const int rc = d.view_built.record(s)) return rc;
+        int rc;                                                         // (both sizes before either launch: a view is never half built)
+        if ((rc = launch_fits("svo_trace", (int64_t)n4)) != SVO_OK || (rc = launch_fits("svo_trace", (int64_t)bricks * 8)) != SVO_OK) return rc;
+        if ((rc = launch_per_element("svo_trace", (int64_t)n4, s, k_view_wide, reinterpret_cast<const uint4 *>(d.wide.p), reinterpret_cast<uint4 *>(d.view_wide.p), n4, m)) != SVO_OK ||
+            (rc = launch_per_element("svo_trace", (int64_t)bricks * 8, s, k_view_mask, d.twig.p, d.mask.p, d.view_mask.p, bricks, m)) != SVO_OK) return rc;
+        if ((rc = d.view_built.record(s)) != SVO_OK) return rc;
         d.view_material = m;
     } else {
         if (const int rc = d.view_built.wait(s)) return rc;
@@ -939,17 +953,15 @@ static int launch(svo_world *w, const svo_trace_params *prm, TraceArgs &A, hipSt
     HIP_TRY(hipMemsetAsync(A.work, 0, WORK_SLOT_WORDS * sizeof(unsigned long long), s));
     if (A.n <= 0) return ev.record(s) == SVO_OK ? SVO_OK : SVO_ERR_HIP;
     if (kernel == SVO_KERNEL_LITERAL) {
-        const int64_t blocks = (A.n + 255) / 256;
-        if (blocks > 0x7FFFFFFF) { set_error("svo_trace: too many rays for one launch"); return SVO_ERR_UNSUPPORTED; }
         const auto literal = see ? (A.tmax ? k_trace_literal<true, true> : k_trace_literal<true, false>) : (A.tmax ? k_trace_literal<false, true> : k_trace_literal<false, false>);
-        hipLaunchKernelGGL(literal, dim3((unsigned)blocks), dim3(256), 0, s, A, see);      // (see == 0: ST is off and `ignore` is not read)
+        if (const int rc = launch_per_element("svo_trace", A.n, s, literal, A, see)) return rc;      // (see == 0: ST is off and `ignore` is not read)
     } else {
         if (A.ntiles > (1 << 25)) { set_error("svo_trace: more than 2^31 rays in one stack-kernel launch"); return SVO_ERR_UNSUPPORTED; }
         if (A.tile_cost) HIP_TRY(hipMemsetAsync(A.tile_cost, 0, (size_t)A.ntiles * (size_t)(A.from_camera ? A.nframes : 1) * 2 * sizeof(uint32_t), s));
         const int rc = launch_stack(w, A, prm ? prm->tiles_per_wave : 0, prm ? prm->launches_in_flight : 0, s);
         if (rc != SVO_OK) { set_error("svo_trace: device query failed"); return rc; }
+        HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipGetLastError());
     return ev.record(s);
 }
 
@@ -1079,24 +1091,20 @@ int svo_trace_translucent(svo_world *w, const svo_camera *cam, const svo_trace_p
     hipStream_t s = (hipStream_t)stream;
     svo_trace_params surface = *prm;
     surface.see_through = 0;
-    int rc = svo_trace(w, cam, &surface, x0, y0, rw, rh, surface_dev, stream);
+    const int rc = svo_trace(w, cam, &surface, x0, y0, rw, rh, surface_dev, stream);
     if (rc != SVO_OK) return rc;
     const int64_t n = (int64_t)rw * rh;
     if (n == 0) return SVO_OK;
     HIP_TRY(hipSetDevice(w->device));
-    // the list lives in the world's scratch: calls on different streams are ordered behind one another (as svo_tile_order's sort)
-    OrderedScratch<float> &list = w->hbm->cont;
-    if ((rc = list.reserve((size_t)n * 6, "svo_trace_translucent")) != SVO_OK) return rc;
-    if ((rc = list.done.wait(s)) != SVO_OK) return rc;
-    float *origins = list.buf.p, *dirs = list.buf.p + 3 * n;
-    rc = launch_per_element("svo_trace_translucent", n, s, k_continuation, make_frame(*cam, x0, y0, rw, rh), m, miss_ray_origin(w),
-                            reinterpret_cast<uint4 *>(surface_dev), origins, dirs);
-    if (rc != SVO_OK) return rc;
-    svo_trace_params behind = *prm;                                     // (the caller's per-ray and per-tile buffers are sized for the surface)
-    behind.counters_dev = nullptr; behind.tile_cost_dev = nullptr; behind.tile_order_dev = nullptr;
-    rc = svo_trace_rays(w, origins, dirs, n, &behind, behind_dev, stream);
-    if (rc != SVO_OK) return rc;
-    return list.done.record(s);
+    // the list lives in the world's scratch: calls on different streams are ordered behind one another
+    return w->hbm->cont.use(RayList::floats(n, false), "svo_trace_translucent", s, [&](float *scratch) {
+        const RayList list(scratch, n, false);
+        const int rc = launch_per_element("svo_trace_translucent", n, s, k_continuation, make_frame(*cam, x0, y0, rw, rh), m, miss_ray_origin(w),
+                                          reinterpret_cast<uint4 *>(surface_dev), list.origins, list.dirs);
+        if (rc != SVO_OK) return rc;
+        const svo_trace_params behind = own_list_params(*prm, true);
+        return svo_trace_rays(w, list.origins, list.dirs, n, &behind, behind_dev, stream);
+    });
 }
 
 // Shadows from the point light and the spotlight (local_shadows.hip.h): the ray list of every light asked for, ONE ray-list launch
@@ -1119,25 +1127,20 @@ int svo_trace_local_shadows(svo_world *w, const svo_camera *cam, const svo_trace
     if (rays > 0x7FFFFFFF) { set_error("svo_trace_local_shadows: image too large"); return SVO_ERR_UNSUPPORTED; }
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(w->device));
-    // the records and the list live in the world's scratch: calls on different streams are ordered behind one another (as svo_trace_translucent's)
-    OrderedScratch<float> &list = w->hbm->local;
-    if ((rc = list.reserve((size_t)rays * 14, "svo_trace_local_shadows")) != SVO_OK) return rc;
-    if ((rc = list.done.wait(s)) != SVO_OK) return rc;
-    float *records = list.buf.p, *origins = records + 8 * rays, *dirs = origins + 3 * rays;
-    const PixelFrame F = make_frame(*cam, x0, y0, rw, rh);
-    rc = launch_per_element("svo_trace_local_shadows", n, s, k_local_rays, F, A.eps, L, miss_ray_origin(w), reinterpret_cast<const uint4 *>(gbuffer_dev),
-                            origins, dirs);
-    if (rc != SVO_OK) return rc;
-    svo_trace_params march = *prm;                                      // (the caller's per-ray and per-tile buffers are sized for the frame)
-    march.shadow = 0;
-    march.counters_dev = nullptr; march.tile_cost_dev = nullptr; march.tile_order_dev = nullptr;
-    // (unbounded on purpose: ending each ray at its light through svo_trace_segments was measured and is slower)
-    rc = svo_trace_rays(w, origins, dirs, rays, &march, reinterpret_cast<svo_hit *>(records), stream);
-    if (rc != SVO_OK) return rc;
-    rc = launch_per_element("svo_trace_local_shadows", n, s, k_local_resolve, F, A.eps, L, reinterpret_cast<const uint4 *>(records),
-                            reinterpret_cast<uint4 *>(gbuffer_dev));
-    if (rc != SVO_OK) return rc;
-    return list.done.record(s);
+    // the records and the list live in the world's scratch: calls on different streams are ordered behind one another
+    return w->hbm->local.use(RayList::floats(rays, true), "svo_trace_local_shadows", s, [&](float *scratch) {
+        const RayList list(scratch, rays, true);
+        const PixelFrame F = make_frame(*cam, x0, y0, rw, rh);
+        int rc = launch_per_element("svo_trace_local_shadows", n, s, k_local_rays, F, A.eps, L, miss_ray_origin(w), reinterpret_cast<const uint4 *>(gbuffer_dev),
+                                    list.origins, list.dirs);
+        if (rc != SVO_OK) return rc;
+        const svo_trace_params march = own_list_params(*prm, false);
+        // (unbounded on purpose: ending each ray at its light through svo_trace_segments was measured and is slower)
+        rc = svo_trace_rays(w, list.origins, list.dirs, rays, &march, reinterpret_cast<svo_hit *>(list.records), stream);
+        if (rc != SVO_OK) return rc;
+        return launch_per_element("svo_trace_local_shadows", n, s, k_local_resolve, F, A.eps, L, reinterpret_cast<const uint4 *>(list.records),
+                                  reinterpret_cast<uint4 *>(gbuffer_dev));
+    });
 }
 
 // ---- the directional light's shadow map (shadowmap.hip.h) -------------------------------------------------------------------------
@@ -1211,9 +1214,7 @@ int svo_shadowmap_fit(const svo_world *w, const float direction[3], int width, i
 int svo_shadowmap_render(svo_world *w, const svo_shadowmap *map, const svo_trace_params *prm, void *stream)
 {
     if (!w || !prm || !map_ok(map)) { set_error("svo_shadowmap_render: bad argument"); return SVO_ERR_INVALID_ARG; }
-    svo_trace_params march = *prm;                                      // (the caller's per-ray and per-tile buffers are sized for its frames)
-    march.shadow = 0;
-    march.counters_dev = nullptr; march.tile_cost_dev = nullptr; march.tile_order_dev = nullptr;
+    const svo_trace_params march = own_list_params(*prm, false);
     TraceArgs A;                                                        // (checks see_through, semantics, residency and the kernel id before any device work)
     int rc = fill_common(w, &march, A);
     if (rc != SVO_OK) return rc;
@@ -1222,16 +1223,14 @@ int svo_shadowmap_render(svo_world *w, const svo_shadowmap *map, const svo_trace
     const int64_t n = M.count();                                        // (<= 2^28)
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(w->device));
-    // the records and the list live in the world's scratch: calls on different streams are ordered behind one another (as svo_trace_local_shadows')
-    OrderedScratch<float> &list = w->hbm->shadowmap;
-    if ((rc = list.reserve((size_t)n * 14, "svo_shadowmap_render")) != SVO_OK) return rc;
-    if ((rc = list.done.wait(s)) != SVO_OK) return rc;
-    float *records = list.buf.p, *origins = records + 8 * n, *dirs = origins + 3 * n;
-    if ((rc = launch_per_element("svo_shadowmap_render", n, s, k_shadowmap_rays, M, origins, dirs)) != SVO_OK) return rc;
-    if ((rc = svo_trace_rays(w, origins, dirs, n, &march, reinterpret_cast<svo_hit *>(records), stream)) != SVO_OK) return rc;
-    rc = launch_per_element("svo_shadowmap_render", n, s, k_shadowmap_depth, M, reinterpret_cast<const uint4 *>(records), map->depth_dev);
-    if (rc != SVO_OK) return rc;
-    return list.done.record(s);
+    // the records and the list live in the world's scratch: calls on different streams are ordered behind one another
+    return w->hbm->shadowmap.use(RayList::floats(n, true), "svo_shadowmap_render", s, [&](float *scratch) {
+        const RayList list(scratch, n, true);
+        int rc;
+        if ((rc = launch_per_element("svo_shadowmap_render", n, s, k_shadowmap_rays, M, list.origins, list.dirs)) != SVO_OK) return rc;
+        if ((rc = svo_trace_rays(w, list.origins, list.dirs, n, &march, reinterpret_cast<svo_hit *>(list.records), stream)) != SVO_OK) return rc;
+        return launch_per_element("svo_shadowmap_render", n, s, k_shadowmap_depth, M, reinterpret_cast<const uint4 *>(list.records), map->depth_dev);
+    });
 }
 
 int svo_shadowmap_apply(const svo_camera *cam, const svo_shadowmap *map, float eps, float bias, int x0, int y0, int rw, int rh,
@@ -1250,26 +1249,20 @@ int svo_shadowmap_apply(const svo_camera *cam, const svo_shadowmap *map, float e
 int svo_world_locate(svo_world *w, const float *points_dev, int64_t n, const svo_trace_params *prm, svo_voxel *out_dev, void *stream)
 {
     if (!w || n < 0 || (n > 0 && (!points_dev || !out_dev))) { set_error("svo_world_locate: bad point list or output"); return SVO_ERR_INVALID_ARG; }
-    if (prm && prm->see_through > 0xFFFFu) { set_error("svo_world_locate: see_through is a 16-bit material"); return SVO_ERR_INVALID_ARG; }
-    if (prm && prm->semantics != SVO_SEMANTICS_CPU && prm->semantics != SVO_SEMANTICS_GLSL) { set_error("svo_world_locate: unknown semantics"); return SVO_ERR_INVALID_ARG; }
-    if (prm && prm->kernel != SVO_KERNEL_AUTO && prm->kernel != SVO_KERNEL_LITERAL && prm->kernel != SVO_KERNEL_STACK) { set_error("svo_world_locate: unknown kernel id"); return SVO_ERR_INVALID_ARG; }
-    TraceArgs A;
-    const int rc = fill_common(w, prm, A);                              // (residency; the world box, the tables and the pools)
+    int rc = refuse_params("svo_world_locate", prm);
     if (rc != SVO_OK) return rc;
+    TraceArgs A;
+    if ((rc = fill_common(w, prm, A)) != SVO_OK) return rc;             // (residency; the world box, the tables and the pools)
     A.counters = nullptr; A.tile_cost = nullptr; A.tile_order = nullptr;   // only kernel, semantics and see_through are read
     const int kernel = pick_kernel(w, prm, A);
     if (kernel < 0) return kernel;
     if (n == 0) return SVO_OK;
-    const int64_t blocks = (n + 255) / 256;
-    if (blocks > 0x7FFFFFFF) { set_error("svo_world_locate: too many points for one launch"); return SVO_ERR_UNSUPPORTED; }
+    if ((rc = launch_fits("svo_world_locate", n)) != SVO_OK) return rc;
     HIP_TRY(hipSetDevice(w->device));
     A.from_camera = 0; A.nframes = 1;
     A.origins = points_dev; A.n = n; A.out = out_dev;
     const uint32_t see = prm ? prm->see_through : 0u;
-    if (kernel == SVO_KERNEL_STACK) hipLaunchKernelGGL(k_locate_wide, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A, see);
-    else hipLaunchKernelGGL(k_locate_literal, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, A, see);
-    HIP_TRY(hipGetLastError());
-    return SVO_OK;
+    return launch_per_element("svo_world_locate", n, (hipStream_t)stream, kernel == SVO_KERNEL_STACK ? k_locate_wide : k_locate_literal, A, see);
 }
 
 // Voxel ambient occlusion (ao.hip.h): svo_world_locate's walks on the eight lattice cells around the open cell in front of every hit's
@@ -1280,12 +1273,10 @@ int svo_hit_ao(svo_world *w, const svo_camera *cam, const svo_trace_params *prm,
     if (!w || !rect_ok(cam, x0, y0, rw, rh) || !(cell >= 0.0f && cell < INFINITY)) { set_error("svo_hit_ao: bad world, camera, rectangle or cell"); return SVO_ERR_INVALID_ARG; }
     const int64_t n = (int64_t)rw * rh;
     if (n > 0 && (!gbuffer_dev || !voxels_dev || !ao_dev)) { set_error("svo_hit_ao: NULL buffer"); return SVO_ERR_INVALID_ARG; }
-    if (prm && prm->see_through > 0xFFFFu) { set_error("svo_hit_ao: see_through is a 16-bit material"); return SVO_ERR_INVALID_ARG; }
-    if (prm && prm->semantics != SVO_SEMANTICS_CPU && prm->semantics != SVO_SEMANTICS_GLSL) { set_error("svo_hit_ao: unknown semantics"); return SVO_ERR_INVALID_ARG; }
-    if (prm && prm->kernel != SVO_KERNEL_AUTO && prm->kernel != SVO_KERNEL_LITERAL && prm->kernel != SVO_KERNEL_STACK) { set_error("svo_hit_ao: unknown kernel id"); return SVO_ERR_INVALID_ARG; }
-    TraceArgs A;
-    const int rc = fill_common(w, prm, A);                              // (residency; the world box, the tables, the pools and the resolved eps)
+    int rc = refuse_params("svo_hit_ao", prm);
     if (rc != SVO_OK) return rc;
+    TraceArgs A;
+    if ((rc = fill_common(w, prm, A)) != SVO_OK) return rc;             // (residency; the world box, the tables, the pools and the resolved eps)
     A.counters = nullptr; A.tile_cost = nullptr; A.tile_order = nullptr;   // only eps, kernel, semantics and see_through are read
     const int kernel = pick_kernel(w, prm, A);
     if (kernel < 0) return kernel;
@@ -1296,11 +1287,8 @@ int svo_hit_ao(svo_world *w, const svo_camera *cam, const svo_trace_params *prm,
     const PixelFrame F = make_frame(*cam, x0, y0, rw, rh);
     const uint32_t see = prm ? prm->see_through : 0u;
     const uint4 *g = reinterpret_cast<const uint4 *>(gbuffer_dev), *v = reinterpret_cast<const uint4 *>(voxels_dev);
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)((n + 31) / 32));                         // eight lanes per pixel
-    if (kernel == SVO_KERNEL_STACK) hipLaunchKernelGGL(k_hit_ao<true>, grid, dim3(256), 0, s, A, F, cell, see, g, v, ao_dev);
-    else hipLaunchKernelGGL(k_hit_ao<false>, grid, dim3(256), 0, s, A, F, cell, see, g, v, ao_dev);
-    return launch_status("svo_hit_ao");
+    // eight lanes per pixel
+    return launch_per_element("svo_hit_ao", n * 8, (hipStream_t)stream, kernel == SVO_KERNEL_STACK ? k_hit_ao<true> : k_hit_ao<false>, A, F, cell, see, g, v, ao_dev);
 }
 
 // The parent index for a svo_hit_voxels call on `s`: built on the device at the first call after a change to the pools - level 0
@@ -1323,7 +1311,7 @@ static int use_parents(svo_world *w, hipStream_t s)
     }
     HIP_TRY(hipMemcpy(d.chunk_trees.p, trees.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemsetAsync(d.parent_level.p, 0, blocks, s));
-    hipLaunchKernelGGL(k_parent_roots, dim3(blocks_for(n, 256)), dim3(256), 0, s, d.chunks.p, d.chunk_trees.p, (uint32_t)n, d.tree.p, d.parent.p, d.parent_level.p);
+    if (const int rc = launch_per_element("svo_hit_voxels", (int64_t)n, s, k_parent_roots, d.chunks.p, d.chunk_trees.p, (uint32_t)n, d.tree.p, d.parent.p, d.parent_level.p)) return rc;
     if (most) {
         const dim3 grid(blocks_for(most, 256), (unsigned)std::min<size_t>(n, 65535));
         for (int L = 1; L < w->max_levels; ++L)
@@ -1342,18 +1330,15 @@ int svo_hit_voxels(svo_world *w, const svo_hit *gbuffer_dev, int64_t n, svo_voxe
     if (!w || n < 0 || (n > 0 && (!gbuffer_dev || !out_dev))) { set_error("svo_hit_voxels: bad G-buffer or output"); return SVO_ERR_INVALID_ARG; }
     if (w->device < 0) { set_error("svo_hit_voxels: world is not uploaded"); return SVO_ERR_NOT_UPLOADED; }
     if (n == 0) return SVO_OK;
-    const int64_t blocks = (n + 255) / 256;
-    if (blocks > 0x7FFFFFFF) { set_error("svo_hit_voxels: too many records for one launch"); return SVO_ERR_UNSUPPORTED; }
+    if (const int rc = launch_fits("svo_hit_voxels", n)) return rc;
     HIP_TRY(hipSetDevice(w->device));
     hipStream_t s = (hipStream_t)stream;
     try {
         if (const int rc = use_parents(w, s)) return rc;
     } catch (const std::bad_alloc &) { set_error("svo_hit_voxels: out of host memory"); return SVO_ERR_OUT_OF_MEMORY; }
     const Hbm &d = *w->hbm;
-    hipLaunchKernelGGL(k_hit_voxels, dim3((unsigned)blocks), dim3(256), 0, s, reinterpret_cast<const uint4 *>(gbuffer_dev), out_dev, n, d.chunks.p,
-                       d.chunk_trees.p, (uint32_t)w->chunks.size(), d.tree.p, d.parent.p, d.parent_level.p, (float)w->chunksize);
-    HIP_TRY(hipGetLastError());
-    return SVO_OK;
+    return launch_per_element("svo_hit_voxels", n, s, k_hit_voxels, reinterpret_cast<const uint4 *>(gbuffer_dev), out_dev, n, d.chunks.p,
+                              d.chunk_trees.p, (uint32_t)w->chunks.size(), d.tree.p, d.parent.p, d.parent_level.p, (float)w->chunksize);
 }
 
 int svo_tile_order(svo_world *w, const uint32_t *cost_dev, uint32_t *order_dev, int ntiles, void *stream)
@@ -1368,16 +1353,14 @@ int svo_tile_order(svo_world *w, const uint32_t *cost_dev, uint32_t *order_dev, 
     uint32_t *nul = nullptr;
     if (hipcub::DeviceRadixSort::SortPairsDescending(nullptr, cub_bytes, nul, nul, nul, nul, ntiles, 0, 32, s) != hipSuccess) return SVO_ERR_HIP;
     const size_t need = (size_t)ntiles * 3 * sizeof(uint32_t) + cub_bytes + 256;
-    OrderedScratch<unsigned char> &sort = w->hbm->sort;
-    if (const int rc = sort.reserve(need, "svo_tile_order")) return rc;
     // calls on different streams (one cost / order pair per launch in flight) share it: a sort that shared its keys need not even yield a permutation
-    if (const int rc = sort.done.wait(s)) return rc;
-    uint32_t *keys = reinterpret_cast<uint32_t *>(sort.buf.p), *keys_out = keys + ntiles, *idx = keys_out + ntiles;
-    void *tmp = reinterpret_cast<char *>(idx + ntiles) + ((256 - ((size_t)ntiles * 12) % 256) % 256);
-    hipLaunchKernelGGL(k_tile_keys, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, s, cost_dev, keys, idx, ntiles);
-    HIP_TRY(hipGetLastError());
-    if (hipcub::DeviceRadixSort::SortPairsDescending(tmp, cub_bytes, keys, keys_out, idx, order_dev, ntiles, 0, 32, s) != hipSuccess) { set_error("svo_tile_order: sort failed"); return SVO_ERR_HIP; }
-    return sort.done.record(s);
+    return w->hbm->sort.use(need, "svo_tile_order", s, [&](unsigned char *scratch) -> int {
+        uint32_t *keys = reinterpret_cast<uint32_t *>(scratch), *keys_out = keys + ntiles, *idx = keys_out + ntiles;
+        void *tmp = reinterpret_cast<char *>(idx + ntiles) + ((256 - ((size_t)ntiles * 12) % 256) % 256);
+        if (const int rc = launch_per_element("svo_tile_order", ntiles, s, k_tile_keys, cost_dev, keys, idx, ntiles)) return rc;
+        if (hipcub::DeviceRadixSort::SortPairsDescending(tmp, cub_bytes, keys, keys_out, idx, order_dev, ntiles, 0, 32, s) != hipSuccess) { set_error("svo_tile_order: sort failed"); return SVO_ERR_HIP; }
+        return SVO_OK;
+    });
 }
 
 int svo_trace_last_ray_count(svo_world *w, void *stream, uint64_t *rays)

@@ -1,5 +1,6 @@
-// hip_own.h — what the .hip files share: the HIP status mapping, block_take for the numbering kernels, the owners of HIP resources
-// and svo::Hbm, the device half of a world (the struct behind svo_world::hbm).  HIP only: world.h stays free of it.
+// hip_own.h — what the .hip files share: the HIP status mapping, the "one thread per element, blocks of 256" launch with its size
+// check and error mapping, block_take for the numbering kernels, the owners of HIP resources and svo::Hbm, the device half of a world
+// (the struct behind svo_world::hbm).  HIP only: world.h stays free of it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -21,6 +22,33 @@ inline int hip_status(hipError_t e)
     do { if (hipError_t e_ = (expr); e_ != hipSuccess) { svo::set_error(std::string(#expr) + ": " + hipGetErrorString(e_)); return svo::hip_status(e_); } } while (0)
 
 inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
+
+// what a launch left behind, as the status and the message of `who`
+inline int launch_status(const char *who)
+{
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return SVO_OK;
+    set_error(std::string(who) + ": " + hipGetErrorString(e));
+    return hip_status(e);
+}
+
+// n elements at one thread each in blocks of 256 are a grid one launch can have; refused for `who` otherwise (HIP is not touched)
+inline int launch_fits(const char *who, int64_t n)
+{
+    if ((n + 255) / 256 <= 0x7FFFFFFF) return SVO_OK;
+    set_error(std::string(who) + ": too many elements for one launch");
+    return SVO_ERR_UNSUPPORTED;
+}
+
+// kernel(args...), one thread per element of n >= 0 in blocks of 256: nothing for n == 0, launch_fits' refusal, the launch, its status
+template <typename... Params, typename... Args>
+int launch_per_element(const char *who, int64_t n, hipStream_t s, void (*kernel)(Params...), Args... args)
+{
+    if (n == 0) return SVO_OK;
+    if (const int rc = launch_fits(who, n)) return rc;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, args...);
+    return launch_status(who);
+}
 
 // Consecutive values from *ctr for the threads of a block of BLOCK threads that raise `pred` - ONE global atomic per block.  The
 // level-synchronous sweeps number millions of nodes through a handful of counters, and same-address atomics are served one after the
@@ -121,17 +149,30 @@ struct Event : NoCopy {
     int record(hipStream_t s) { if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); HIP_TRY(hipEventRecord(e, s)); return SVO_OK; }
 };
 
-// A scratch buffer of the world that calls on any stream use one after the other: reserve(), done.wait(s), the work, done.record(s).
-template <typename T> struct OrderedScratch {
+// A scratch buffer of the world that calls on any stream use one after the other.  use() is the only way to it: at least n elements,
+// `s` ordered behind the call that used it last, work(buffer), and - if that returned SVO_OK - the mark the next call waits for.
+template <typename T> class OrderedScratch {
     DevBuf<T> buf; Event done;
-    int reserve(size_t n, const char *who)                  // too small: replaced by one of n elements, once the device is through with the old one
+public:
+    template <typename Work> int use(size_t n, const char *who, hipStream_t s, Work &&work)
     {
-        if (n <= buf.cap) return SVO_OK;
-        if (buf.p) HIP_TRY(hipDeviceSynchronize());
-        buf = DevBuf<T>();
-        if (buf.reserve(n, false, nullptr) != SVO_OK) { set_error(std::string(who) + ": hipMalloc failed"); return SVO_ERR_OUT_OF_MEMORY; }
-        return SVO_OK;
+        if (n > buf.cap) {                                  // too small: replaced by one of n elements, once the device is through with the old one
+            if (buf.p) HIP_TRY(hipDeviceSynchronize());
+            buf = DevBuf<T>();
+            if (buf.reserve(n, false, nullptr) != SVO_OK) { set_error(std::string(who) + ": hipMalloc failed"); return SVO_ERR_OUT_OF_MEMORY; }
+        }
+        if (const int rc = done.wait(s)) return rc;
+        if (const int rc = work(buf.p)) return rc;
+        return done.record(s);
     }
+};
+
+// A float scratch as the ray list of `rays` rays a stage marches on its own: [rays] records of 8 words where the stage keeps the
+// march's output there too, then the origins and the directions, [2][rays][3]
+struct RayList {
+    float *records, *origins, *dirs;
+    static size_t floats(int64_t rays, bool with_records) { return (size_t)rays * (with_records ? 14 : 6); }
+    RayList(float *p, int64_t rays, bool with_records) : records(with_records ? p : nullptr), origins(p + (with_records ? 8 * rays : 0)), dirs(origins + 3 * rays) {}
 };
 
 // The wide-tree builder's scratch in uint32 words from its start (device.hip: wide_layout is the one place that knows it); the
@@ -150,9 +191,9 @@ struct Hbm {
     unsigned work_next = 0, work_last = 0;                  // ring cursor; slot of the most recent launch
     Event work_done[WORK_SLOTS];                            // recorded behind the launch that used the slot
     OrderedScratch<unsigned char> sort;                     // svo_tile_order
-    OrderedScratch<float> cont;                             // svo_trace_translucent: continuation origins and directions, [2][rays][3]
-    OrderedScratch<float> local;                            // svo_trace_local_shadows: per light asked for, [rays] records of 8 words, then origins and directions [2][rays][3]
-    OrderedScratch<float> shadowmap;                        // svo_shadowmap_render: [texels] records of 8 words, then origins and directions [2][texels][3], in tile order
+    OrderedScratch<float> cont;                             // svo_trace_translucent: a RayList without records, one ray per pixel
+    OrderedScratch<float> local;                            // svo_trace_local_shadows: a RayList with records, one ray per pixel and light asked for
+    OrderedScratch<float> shadowmap;                        // svo_shadowmap_render: a RayList with records, one ray per texel in tile order
     // see-through view (svo_trace_params.see_through, see_through.hip.h): the wide and mask pools with one material taken out, built
     // on the device at the first launch that asks for it, dropped by every change to the pools
     Pooled<uint32_t> view_wide; Pooled<uint64_t> view_mask;

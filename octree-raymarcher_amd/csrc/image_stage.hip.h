@@ -1,7 +1,7 @@
 // image_stage.hip.h — what the per-pixel stages behind the march share (shade.hip, sky.hip, boxes.hip, see_through.hip.h,
 // local_shadows.hip.h): the rectangle of the camera image a launch covers and the ray of each of its pixels, the decode of a G-buffer
-// record in its two forms, leafUV from both, and on the host the rectangle's validity test and the "one thread per element, blocks of
-// 256" launch with its size check and error mapping.
+// record in its two forms, leafUV from both, and on the host the rectangle's validity test (the launch itself: hip_own.h,
+// launch_per_element).
 #pragma once
 #include <cstring>
 #include <string>
@@ -99,25 +99,6 @@ inline PixelFrame make_frame(const svo_camera &cam, int x0, int y0, int w, int h
     F.cam = frame_cam(cam);
     F.imgw = cam.width; F.imgh = cam.height; F.x0 = x0; F.y0 = y0; F.w = w; F.h = h;
     return F;
-}
-
-// what a launch left behind, as the status and the message of `who`
-inline int launch_status(const char *who)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return SVO_OK;
-    set_error(std::string(who) + ": " + hipGetErrorString(e));
-    return hip_status(e);
-}
-
-// kernel(args...), one thread per element of n >= 0 in blocks of 256; a grid that does not fit one launch is refused before HIP is touched
-template <typename... Params, typename... Args>
-int launch_per_element(const char *who, int64_t n, hipStream_t s, void (*kernel)(Params...), Args... args)
-{
-    if (n == 0) return SVO_OK;
-    if ((n + 255) / 256 > 0x7FFFFFFF) { set_error(std::string(who) + ": image too large"); return SVO_ERR_UNSUPPORTED; }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, args...);
-    return launch_status(who);
 }
 
 } // namespace svo

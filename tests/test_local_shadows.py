@@ -4,6 +4,7 @@ ow.trace_rays and applies the `t < dist` rule), and svo_shade's use of the flags
 
 Run as a script - python tests/test_local_shadows.py <libsvo_*.so> - it puts one variant build of the library through the flags case
 (one library per process, as tests/variant_check.py)."""
+import ctypes as C
 import os
 import subprocess
 import sys
@@ -238,6 +239,54 @@ def test_translucent_surface(svo, oracle, scene, kernel):
     # the occlusion rays are marched with the caller's params: through the water
     ow6 = oracle.OracleWorld.from_chunks([svo.see_through_chunk(W.chunk(i), WATER) for i in range(4)], 2, 1, 2, 128)
     assert_gbuffer_equal(after, M.expected(oracle, ow6, cam, rect, surface, M.POINT, M.SPOT, 0), f"translucent surface {kernel}")
+
+
+def test_two_streams_share_the_scratch(svo, oracle, scene):
+    """Four frames (svo_trace, then svo_trace_local_shadows behind it) on two streams, nothing in between: the ray lists and their
+    records live in one scratch of the world.  Job A asks for both lights, job B for the point light alone, so the two lay the scratch
+    out differently (twice as many rays), and they look through different cameras (the two of test_see_through.py's two-stream test,
+    64 x 48: 1775 and 3072 usable hits by the oracle)."""
+    W, ow, _ = scene
+    hip = C.CDLL("libamdhip64.so.7")                        # the runtime the library is already linked against
+    w, h = 64, 48
+    rect, n = (0, 0, w, h), w * h
+    jobs_of = {"A": (svo.default_camera(2, 2, 128, w, h), M.POINT, M.SPOT),
+               "B": (svo.make_camera((20.0, 50.0, 64.0), (0.7, -0.7, 0.0), (0.0, 1.0, 0.0), 60.0, w, h), M.POINT, None)}
+    prm = svo.trace_params(shadow=True)
+
+    def issue(which, stream=0):
+        cam, point, spot = jobs_of[which]
+        g = svo.DeviceBuffer(n * 32)
+        W.trace(cam, prm, rect, g.ptr, stream=stream)
+        W.trace_local_shadows(cam, prm, rect, g.ptr, point=point, spot=spot, stream=stream)
+        return g
+
+    def fetch(g):
+        out = g.to_numpy(svo.HIT_DTYPE, n)
+        g.free()
+        return out
+
+    single = {}
+    for which, (cam, point, spot) in jobs_of.items():
+        g = issue(which)
+        svo.lib.svo_stream_synchronize(None)
+        single[which] = fetch(g)
+        frame = ow.trace_image(cam, params=oracle.make_params(shadow=True), threads=8)
+        assert M.usable(frame).sum() >= 32, which
+        assert_gbuffer_equal(single[which], M.expected(oracle, ow, cam, rect, frame, point, spot, 0), f"single stream, job {which}")
+    assert np.count_nonzero(np.any(single["A"].view(np.uint8).reshape(n, 32) != single["B"].view(np.uint8).reshape(n, 32), axis=1)) >= 32
+    streams = []
+    for _ in range(2):
+        s = C.c_void_p()
+        assert hip.hipStreamCreateWithFlags(C.byref(s), 1) == 0            # hipStreamNonBlocking
+        streams.append(s.value)
+    jobs = [(which, issue(which, stream=streams[k % 2])) for k, which in enumerate(("B", "A", "A", "B"))]
+    for s in streams:
+        svo.lib.svo_stream_synchronize(s)
+    for which, g in jobs:
+        assert np.array_equal(fetch(g).view(np.uint8), single[which].view(np.uint8)), f"two streams, job {which}"
+    for s in streams:
+        hip.hipStreamDestroy(C.c_void_p(s))
 
 
 def test_across_a_world_change(svo, oracle):

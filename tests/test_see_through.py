@@ -125,6 +125,58 @@ def test_trace_translucent(svo, oracle, water_world, kernel, shadow):
     assert np.count_nonzero(b[cont]["flags"] & 1) > 0.1 * cont.sum()      # a lake bed is seen (the rest leave through the world's floor)
 
 
+def test_two_streams_share_the_continuation_list(svo, oracle, water_world):
+    """Four svo_trace_translucent calls on two streams, nothing in between: the continuation lists live in one scratch of the world, and
+    a call that did not wait for the one before it would march the other camera's rays.  Two cameras at 64 x 48; the second is not the
+    cam2 of test_trace_and_frames_see_through, which sees no water at this size (the oracle says), but one over the lake: 484 and 1459
+    pixels continue."""
+    W, ow = water_world
+    hip = C.CDLL("libamdhip64.so.7")                        # the runtime the library is already linked against
+    w, h = 64, 48
+    rect, n = (0, 0, w, h), w * h
+    cams = {"A": svo.default_camera(2, 2, 128, w, h), "B": svo.make_camera((20.0, 50.0, 64.0), (0.7, -0.7, 0.0), (0.0, 1.0, 0.0), 60.0, w, h)}
+    prm = svo.trace_params(see_through=WATER)
+
+    def issue(which, stream=0):
+        bufs = svo.DeviceBuffer(n * 32), svo.DeviceBuffer(n * 32)
+        W.trace_translucent(cams[which], prm, rect, bufs[0].ptr, bufs[1].ptr, stream=stream)
+        return bufs
+
+    def fetch(bufs):
+        out = tuple(b.to_numpy(svo.HIT_DTYPE, n) for b in bufs)
+        for b in bufs:
+            b.free()
+        return out
+
+    single = {}
+    for which, cam in cams.items():
+        bufs = issue(which)
+        svo.lib.svo_stream_synchronize(None)
+        surface, behind = single[which] = fetch(bufs)
+        plain = W.draw(cam).reshape(-1)
+        cont = ((plain["flags"] & 1) != 0) & ((plain["flags"] & svo.ERR_FLAG) == 0) & (plain["material"] == WATER)
+        assert cont.sum() >= 32, f"camera {which}: only {cont.sum()} pixels see water"
+        assert np.array_equal((surface["flags"] & svo.SEE_THROUGH) != 0, cont)
+        p1, d = _continuations(svo, oracle, cam, surface, rect)
+        assert_gbuffer_equal(behind[cont], ow.trace_rays(p1[cont], d[cont], params=oracle.make_params(), threads=8), f"single stream, camera {which}")
+        assert np.all(behind[~cont].view(np.uint8).reshape(-1, 32) == 0), "pixels that are not continued are all-zero"
+    for k in (0, 1):                                            # the two jobs differ: records of one cannot pass for the other's
+        assert np.count_nonzero(np.any(single["A"][k].view(np.uint8).reshape(n, 32) != single["B"][k].view(np.uint8).reshape(n, 32), axis=1)) >= 32
+    streams = []
+    for _ in range(2):
+        s = C.c_void_p()
+        assert hip.hipStreamCreateWithFlags(C.byref(s), 1) == 0            # hipStreamNonBlocking
+        streams.append(s.value)
+    jobs = [(which, issue(which, stream=streams[k % 2])) for k, which in enumerate(("B", "A", "A", "B"))]
+    for s in streams:
+        svo.lib.svo_stream_synchronize(s)
+    for which, bufs in jobs:
+        for name, got, want in zip(("surface", "behind"), fetch(bufs), single[which]):
+            assert np.array_equal(got.view(np.uint8), want.view(np.uint8)), f"two streams, camera {which}: {name}"
+    for s in streams:
+        hip.hipStreamDestroy(C.c_void_p(s))
+
+
 def test_view_follows_edits(svo, oracle):
     W = svo.World.generate(2, 1, 2, 128, 8)
     W.upload(0)
