@@ -61,6 +61,9 @@
  *   svo_hit_ao           <- (a departure: the reference has no ambient occlusion; its ambient term is one constant per material,
  *                           shaders/World.Fragment.glsl:63-73) contact darkening from the eight lattice cells around each hit's face
  *   svo_shade_ao         <- (a departure, with it) that factor on the shaded image
+ *   svo_trace_reflections <- (a departure: the reference has no reflections) one mirror ray per hit of a material, off the axis-aligned
+ *                           face of the voxel that was hit
+ *   svo_shade_reflections <- (a departure, with it) what those rays saw, blended over the shaded image by a Fresnel term
  *
  * Conventions
  *   - plain C, opaque handle, caller owns every buffer it passes in;
@@ -111,7 +114,8 @@ extern "C" {
                                           svo_chunk_from_grid, svo_world_chunk_from_grid and svo_world_chunk_to_grid,
                                           svo_world_edit_ball and svo_world_edit_ball_all,
                                           svo_shadowmap, svo_shadowmap_fit, svo_shadowmap_render and svo_shadowmap_apply,
-                                          svo_hit_ao and svo_shade_ao */
+                                          svo_hit_ao and svo_shade_ao,
+                                          svo_trace_reflections, svo_shade_reflections and svo_mirror */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -857,6 +861,63 @@ int svo_shade_sky(const svo_camera *cam, const svo_sky *sky, int x0, int y0, int
  * A is 255 for every pixel (shaders/GBuffer.Fragment.glsl:10); the depth float does not enter the colour.
  * n < 0, or a NULL pointer with n > 0: SVO_ERR_INVALID_ARG; n == 0: SVO_OK.  Asynchronous on `stream`. */
 int svo_frame_rgba8(const float *rgba_dev, int64_t n, uint32_t *out_dev, void *stream);
+
+/* ---- mirror reflections: one bounce off axis-aligned voxel faces --------------------------------------------
+ * Not in the reference: an opt-in departure, as svo_trace_local_shadows and svo_hit_ao are.  Every generated world has a lake
+ * (svo_terrain_params.water_material); a voxel face is axis-aligned, so its mirror ray is the incoming ray with one sign flipped, and
+ * svo_trace_rays marches it.  svo_trace_reflections marches the mirror rays of a rectangle, svo_shade_reflections blends what they saw
+ * over the shaded image.  One bounce, no roughness, no refraction direction, no packed-record variant (the voxel boxes need the ids).
+ * gbuffer_dev holds the w*h records that svo_trace(cam, params, x0, y0, w, h) wrote (or the surface records of svo_trace_translucent),
+ * voxels_dev what svo_hit_voxels wrote for them; both calls only read them.
+ * A pixel is a MIRROR PIXEL iff its record has SVO_HIT_FLAG and no SVO_ERR_FLAG, `material` is 0 or the record's material, and its voxel
+ * record has SVO_LOCATE_INSIDE.  Its mirror ray, in float, every operation separately rounded - both calls form it with the same code:
+ *   1. sample point   (o, d) the pixel's camera ray as the march forms it; P = o + d * (t - eps).  svo_trace_reflections: eps is the
+ *                     launch's (0 = 1/8192, or 1/4096 under SVO_SEMANTICS_GLSL, as in svo_trace_local_shadows); svo_shade_reflections:
+ *                     p->eps (0 = 1/8192) - pass the launch's;
+ *   2. face           lo = bmin, hi = bmin + size of the voxel record; the SVO_NORMAL_FACE rule exactly as svo_hit_ao step 2 states it:
+ *                     an axis k and sgn = +1 or -1;
+ *   3. origin         O = P with O[k] = (sgn > 0 ? hi[k] : lo[k]) + sgn * eps: on the face plane, pushed out by eps.  P itself lies on
+ *                     or inside the closed box of its voxel, and a ray from there hits that voxel again at t = 0;
+ *   4. direction      R = d with R[k] = sgn * fabsf(d[k]): the ray always leaves the face; R is not re-normalised.
+ *
+ * svo_trace_reflections: reflect_dev[k] is, byte for byte, what svo_trace_rays writes for (O, R) under params without counters_dev,
+ * tile_cost_dev and tile_order_dev (eps, caps, semantics, kernel, see_through, normal_mode and shadow are honoured), and all zero for a
+ * pixel that is not a mirror pixel (it gets a ray that misses the world).  All rays go through ONE ray-list launch
+ * (svo_trace_last_ray_count then reports it: w*h rays); the list lives in the world's scratch, 24 bytes per pixel.  Asynchronous on
+ * `stream`; calls of one world on different streams are ordered behind one another on the device.  Nothing is cached.
+ * A NULL world, cam or params, a NULL buffer with w*h > 0, a rectangle that starts or extends backwards, material > 0xFFFF:
+ * SVO_ERR_INVALID_ARG; then what svo_trace refuses in params and the world (see_through > 0xFFFF, SVO_ERR_NOT_UPLOADED, an unknown
+ * semantics or kernel, SVO_KERNEL_STACK where it is unsupported); then w*h == 0: SVO_OK; w*h >= 2^31: SVO_ERR_UNSUPPORTED.  All settled
+ * before any device work. */
+int svo_trace_reflections(svo_world *, const svo_camera *cam, const svo_trace_params *params, uint32_t material,
+                          int x0, int y0, int w, int h,
+                          const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, svo_hit *reflect_dev, void *stream);
+
+/* svo_shade_reflections: over an image that svo_shade, svo_shade_textured or svo_shade_translucent wrote for the same rectangle; after
+ * svo_shade_ao, before svo_shade_boxes and svo_frame_rgba8 (svo_shade_sky writes other pixels: their order does not matter).
+ * For a mirror pixel (above; reflect_dev is what svo_trace_reflections wrote for the same records), with k the face's axis:
+ *   c = fabsf(d[k]), x = 1.0f - c;  F = f0 if fresnel == 0, else Schlick's f0 + (1.0f - f0) * (((x*x) * (x*x)) * x);
+ *   C = if reflect_dev[k] has SVO_HIT_FLAG: the r, g, b of svo_shade's hit formula for that record with the pixel's eye replaced by O,
+ *         its direction by R and t the record's - the point is O + R * (t - eps), the view vector -R; material table, shadow bits and
+ *         gamma as in svo_shade; the depth is dropped;
+ *       else if sky: svo_shade_sky's lookup with d := R;
+ *       else background - also where the sky has no answer, !(ma > 0);
+ *   F == 0: the pixel is not written.  Otherwise rgb = rgb * (1.0f - F) + C * F per channel; the depth float is never written.
+ * A pixel that is not a mirror pixel is not written at all.
+ * A NULL cam, p or mirror, a NULL buffer with w*h > 0, f0 outside [0, 1] or NaN, material > 0xFFFF, a background that is not finite,
+ * a sky that svo_shade_sky would refuse, a rectangle that starts or extends backwards: SVO_ERR_INVALID_ARG, settled before any device
+ * work.  w*h == 0 is SVO_OK.  Takes no world; asynchronous on `stream`. */
+typedef struct svo_mirror {
+    uint32_t material;              /* as svo_trace_reflections' */
+    float    f0;                    /* reflectance at normal incidence, in [0, 1] */
+    int32_t  fresnel;               /* 0: F = f0 everywhere; != 0: Schlick */
+    float    background[3];         /* colour of a mirror ray that leaves the world when sky == NULL (or the sky has no answer) */
+    const svo_sky *sky;             /* optional: svo_shade_sky's cube map, looked up along the MIRROR ray */
+} svo_mirror;
+int svo_shade_reflections(const svo_camera *cam, const svo_shade_params *p, const svo_mirror *mirror,
+                          int x0, int y0, int w, int h,
+                          const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, const svo_hit *reflect_dev,
+                          float *rgba_dev, void *stream);
 
 /* ---- the edit cursor and the light markers: cubes over the finished image ----------------------------------
  * One overlay record, 48 bytes, on the device.  The reference has four: the cursor cube (ImagCube: translucent grey, black edges) and one

@@ -20,6 +20,7 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     World.edit_cube                           <- modify()                                  src/Main.cpp:321-368
     World.edit_ball / edit_ball_all           <- (none: the reference edits cubes only)    destroyCube / buildCube over a closed ball
     World.hit_ao / ao_image, shade_ao         <- (none: the reference has no ambient occlusion)   the eight lattice cells around each hit's face
+    World.trace_reflections / reflect_image, shade_reflections, Mirror   <- (none: the reference has no reflections)   one mirror ray per hit, off its voxel's face
 
 There is NO CPU fallback: if libsvo_amd.so is missing the import raises, and every device call
 raises SvoError when HIP reports no device.
@@ -159,6 +160,20 @@ class Sky(C.Structure):
         self.size, self.filter = int(size), int(filter)
 
 
+class Mirror(C.Structure):
+    """svo_mirror: what svo_shade_reflections blends with.  Mirror(material, f0, fresnel, background, sky): sky a Sky or None; the
+    struct keeps a reference to it."""
+    _fields_ = [("material", C.c_uint32), ("f0", C.c_float), ("fresnel", C.c_int32), ("background", C.c_float * 3), ("sky", C.POINTER(Sky))]
+
+    def __init__(self, material: int = 0, f0: float = 0.02, fresnel: bool = True, background=(0.0, 0.0, 0.0), sky: Optional[Sky] = None):
+        super().__init__()
+        self.material, self.f0, self.fresnel = int(material), float(f0), int(bool(fresnel))
+        self.background[:] = [float(c) for c in background]
+        self._sky = sky                                      # (the pointer below does not keep it alive)
+        if sky is not None:
+            self.sky = C.pointer(sky)
+
+
 class Box(C.Structure):
     """svo_box: one overlay cube of svo_shade_boxes (48 bytes; BOX_DTYPE is its numpy twin)."""
     _fields_ = [("bmin", C.c_float * 3), ("size", C.c_float), ("color", C.c_float * 3), ("alpha", C.c_float), ("style", C.c_uint32),
@@ -184,6 +199,7 @@ ABI_SYMBOLS = [
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_edit_cube", "svo_world_edit_ball", "svo_world_edit_ball_all", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_cursor_place", "svo_shade_boxes", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_shadowmap_fit", "svo_shadowmap_render", "svo_shadowmap_apply", "svo_hit_ao", "svo_shade_ao",
+    "svo_trace_reflections", "svo_shade_reflections",
     "svo_device_count", "svo_device_alloc", "svo_device_free", "svo_device_cache_trim", "svo_memcpy_h2d", "svo_memcpy_d2h",
     "svo_stream_synchronize", "svo_last_error", "svo_abi_version",
 ]
@@ -243,6 +259,8 @@ lib.svo_hit_uv.argtypes = [C.POINTER(Camera), C.c_float, C.c_int, C.c_int, C.c_i
 lib.svo_shade_textured.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams), C.POINTER(Atlas), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
 lib.svo_hit_ao.argtypes = [_P, C.POINTER(Camera), C.POINTER(TraceParams), C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
 lib.svo_shade_ao.argtypes = [_P, C.c_float, C.c_int64, _P, _P]
+lib.svo_trace_reflections.argtypes = [_P, C.POINTER(Camera), C.POINTER(TraceParams), C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
+lib.svo_shade_reflections.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams), C.POINTER(Mirror), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]
 lib.svo_shade_sky.argtypes = [C.POINTER(Camera), C.POINTER(Sky), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
 lib.svo_frame_rgba8.argtypes = [_P, C.c_int64, _P, _P]
 lib.svo_cursor_place.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), _P, C.c_float, _P, _P]
@@ -474,6 +492,16 @@ def shade_sky(cam: Camera, sky: Sky, rect, rgba_ptr: int, gbuffer_ptr: Optional[
     x0, y0, w, h = rect
     _check(lib.svo_shade_sky(C.byref(cam) if cam is not None else None, C.byref(sky) if sky is not None else None, x0, y0, w, h,
                              gbuffer_ptr, packed_ptr, rgba_ptr, stream), "svo_shade_sky")
+
+
+def shade_reflections(cam: Camera, params: ShadeParams, mirror: Mirror, rect, gbuffer_ptr: int, voxels_ptr: int, reflect_ptr: int, rgba_ptr: int,
+                      stream: int = 0):
+    """svo_shade_reflections: what the mirror rays of World.trace_reflections saw (reflect_ptr), blended by mirror's Fresnel term over
+    the image a shade call wrote for the same records; behind shade_ao, before shade_boxes and frame_rgba8.  params.eps is the launch's."""
+    x0, y0, w, h = rect
+    _check(lib.svo_shade_reflections(C.byref(cam) if cam is not None else None, C.byref(params) if params is not None else None,
+                                     C.byref(mirror) if mirror is not None else None, x0, y0, w, h, gbuffer_ptr, voxels_ptr, reflect_ptr, rgba_ptr,
+                                     stream), "svo_shade_reflections")
 
 
 def frame_rgba8(rgba_ptr: int, n: int, out_ptr: int, stream: int = 0):
@@ -730,6 +758,14 @@ class World:
         _check(lib.svo_hit_ao(self._h, C.byref(cam) if cam is not None else None, C.byref(params) if params is not None else None, cell,
                               x0, y0, w, h, gbuffer_ptr, voxels_ptr, ao_ptr, stream), "svo_hit_ao")
 
+    def trace_reflections(self, cam: Camera, params: TraceParams, rect, gbuffer_ptr: int, voxels_ptr: int, reflect_ptr: int, material: int = 0,
+                          stream: int = 0):
+        """svo_trace_reflections on the G-buffer svo_trace(cam, params, rect) filled and the records hit_voxels wrote for it: the record
+        of the mirror ray of every usable hit of `material` (0 = any) into reflect_ptr (w*h HIT_DTYPE records), all zero elsewhere."""
+        x0, y0, w, h = rect
+        _check(lib.svo_trace_reflections(self._h, C.byref(cam) if cam is not None else None, C.byref(params) if params is not None else None,
+                                         material, x0, y0, w, h, gbuffer_ptr, voxels_ptr, reflect_ptr, stream), "svo_trace_reflections")
+
     def trace_translucent(self, cam: Camera, params: TraceParams, rect, surface_ptr: int, behind_ptr: int, stream: int = 0):
         """svo_trace_translucent: the surface G-buffer and, behind every hit of material params.see_through, the continuation's."""
         x0, y0, w, h = rect
@@ -879,6 +915,31 @@ class World:
                         gd.ptr, vd.ptr, out.ptr, cell=cell)
             _check(lib.svo_stream_synchronize(None), "svo_stream_synchronize")
             return out.to_numpy(np.float32, n).reshape(h, w)
+        finally:
+            for b in (gd, vd, out):
+                b.free()
+
+    def reflect_image(self, cam: Camera, records, rect=None, voxels=None, material: int = 0, shadow: bool = False, kernel: int = KERNEL_AUTO,
+                      semantics: int = 0, see_through: int = 0, eps: float = 0.0, light_dir=(1.0, -1.0, 0.0), normal_mode: int = 0):
+        """World.trace_reflections over host records (HIT_DTYPE[h, w], as World.draw(cam, rect) returns them); voxels: their VOXEL_DTYPE
+        records (None = hit_voxels').  Returns HIT_DTYPE[h, w]."""
+        x0, y0, w, h = rect if rect is not None else (0, 0, cam.width, cam.height)
+        g = np.ascontiguousarray(records, dtype=HIT_DTYPE).reshape(-1)
+        n = w * h
+        assert g.shape[0] == n
+        gd, vd, out = DeviceBuffer.from_numpy(g), DeviceBuffer(max(n, 1) * 32), DeviceBuffer(max(n, 1) * 32)
+        try:
+            if voxels is None:
+                self.hit_voxels(gd.ptr, n, vd.ptr)
+            elif n:
+                v = np.ascontiguousarray(voxels, dtype=VOXEL_DTYPE).reshape(-1)
+                assert v.shape[0] == n
+                _check(lib.svo_memcpy_h2d(vd.ptr, v.ctypes.data, v.nbytes), "svo_memcpy_h2d")
+            prm = trace_params(shadow=shadow, kernel=kernel, semantics=semantics, see_through=see_through, eps=eps, light_dir=light_dir,
+                               normal_mode=normal_mode)
+            self.trace_reflections(cam, prm, (x0, y0, w, h), gd.ptr, vd.ptr, out.ptr, material=material)
+            _check(lib.svo_stream_synchronize(None), "svo_stream_synchronize")
+            return out.to_numpy(HIT_DTYPE, n).reshape(h, w)
         finally:
             for b in (gd, vd, out):
                 b.free()

@@ -15,9 +15,6 @@
 
 namespace svo {
 
-__device__ __forceinline__ float axis_of(V3 v, int k) { return k == 0 ? v.x : k == 1 ? v.y : v.z; }
-__device__ __forceinline__ V3 with_axis(V3 v, int k, float s) { return mk(k == 0 ? s : v.x, k == 1 ? s : v.y, k == 2 ? s : v.z); }
-
 // Steps 1-4 for pixel k: false where the pixel gets 1.0f without a walk.  Q: the centre of the open cell, (u, v): the face's two
 // other axes, e: the lattice pitch, (fu, fv): where the sample point lies in its lattice cell.
 template <bool WIDE>
@@ -31,11 +28,9 @@ __device__ __forceinline__ bool ao_cell(const TraceArgs &A, const PixelFrame &F,
     V3 o, d;
     camera_ray(F.cam, F.imgw, F.imgh, F.x0 + (int)(k % (uint32_t)F.w), F.y0 + (int)(k / (uint32_t)F.w), o, d);     // (PixelFrame::ray; k < 2^31)
     const V3 P = o + d * (t - A.eps);                                           // 1.
-    const V3 lo = mk(__uint_as_float(v0.x), __uint_as_float(v0.y), __uint_as_float(v0.z));
-    const V3 hi = lo + __uint_as_float(v0.w);
-    const V3 n = face_normal(P, lo, hi, d);                                     // 2.
-    const int ax = n.x != 0.0f ? 0 : n.y != 0.0f ? 1 : 2;
-    const float sgn = axis_of(n, ax);
+    const HitFace face = hit_face(P, v0, d);                                    // 2. (image_stage.hip.h)
+    const int ax = face.axis;
+    const float sgn = face.sgn;
     e = cell;                                                                   // 3.
     if (!(cell > 0.0f)) {
         const uint32_t levels = WIDE ? A.wchunks[v1.y].levels : A.chunks[v1.y].levels;
@@ -48,7 +43,7 @@ __device__ __forceinline__ bool ao_cell(const TraceArgs &A, const PixelFrame &F,
     Q = mk(0.0f, 0.0f, 0.0f);
     Q = with_axis(Q, u, (gu + 0.5f) * e);
     Q = with_axis(Q, v, (gv + 0.5f) * e);
-    Q = with_axis(Q, ax, (sgn > 0.0f ? axis_of(hi, ax) : axis_of(lo, ax)) + sgn * (e * 0.5f));
+    Q = with_axis(Q, ax, (sgn > 0.0f ? axis_of(face.hi, ax) : axis_of(face.lo, ax)) + sgn * (e * 0.5f));
     return isfinite(ru) && isfinite(rv);
 }
 

@@ -5,6 +5,7 @@
 //   svo_trace*        <- World::draw / draw_shadowmap             src/World.cpp:162-266
 //   svo_world_locate  <- traverse over a point list               src/Traverse.cpp:34-48 (locate.hip.h)
 //   svo_hit_ao        <- (none: the reference has no ambient occlusion)                    (ao.hip.h)
+//   svo_trace_reflections <- (none: the reference has no reflections)                      (reflect.hip.h)
 //
 // The reference's first-fit free-list allocator over GL buffers is not reproduced: a world is
 // packed into one flat pool per kind with per-chunk slots sized by the chunk's host capacity
@@ -28,6 +29,7 @@
 #include "kernel_stack.hip.h"
 #include "see_through.hip.h"
 #include "local_shadows.hip.h"
+#include "reflect.hip.h"
 #include "shadowmap.hip.h"
 #include "locate.hip.h"
 #include "ao.hip.h"
@@ -1104,6 +1106,33 @@ int svo_trace_translucent(svo_world *w, const svo_camera *cam, const svo_trace_p
         if (rc != SVO_OK) return rc;
         const svo_trace_params behind = own_list_params(*prm, true);
         return svo_trace_rays(w, list.origins, list.dirs, n, &behind, behind_dev, stream);
+    });
+}
+
+// Mirror reflections (reflect.hip.h): the mirror ray of every pixel that hit `material` on a voxel with a box, ONE ray-list launch into
+// reflect_dev.  svo_shade_reflections (shade.hip) rebuilds the rays from the same records and blends what they saw.
+int svo_trace_reflections(svo_world *w, const svo_camera *cam, const svo_trace_params *prm, uint32_t material, int x0, int y0, int rw, int rh,
+                          const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, svo_hit *reflect_dev, void *stream)
+{
+    if (!w || !prm || !rect_ok(cam, x0, y0, rw, rh) || material > 0xFFFFu) { set_error("svo_trace_reflections: bad world, camera, params, rectangle or material"); return SVO_ERR_INVALID_ARG; }
+    const int64_t n = (int64_t)rw * rh;
+    if (n > 0 && (!gbuffer_dev || !voxels_dev || !reflect_dev)) { set_error("svo_trace_reflections: NULL buffer"); return SVO_ERR_INVALID_ARG; }
+    const svo_trace_params march = own_list_params(*prm, true);
+    TraceArgs A;                                                        // (for the launch's resolved eps; checks see_through, semantics, residency and the kernel id)
+    int rc = fill_common(w, &march, A);
+    if (rc != SVO_OK) return rc;
+    if ((rc = pick_kernel(w, &march, A)) < 0) return rc;
+    if (n == 0) return SVO_OK;
+    if (n > 0x7FFFFFFF) { set_error("svo_trace_reflections: image too large"); return SVO_ERR_UNSUPPORTED; }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(w->device));
+    // the list lives in the world's scratch: calls on different streams are ordered behind one another
+    return w->hbm->mirror.use(RayList::floats(n, false), "svo_trace_reflections", s, [&](float *scratch) {
+        const RayList list(scratch, n, false);
+        const int rc = launch_per_element("svo_trace_reflections", n, s, k_mirror_rays, make_frame(*cam, x0, y0, rw, rh), A.eps, material, miss_ray_origin(w),
+                                          reinterpret_cast<const uint4 *>(gbuffer_dev), reinterpret_cast<const uint4 *>(voxels_dev), list.origins, list.dirs);
+        if (rc != SVO_OK) return rc;
+        return svo_trace_rays(w, list.origins, list.dirs, n, &march, reflect_dev, stream);
     });
 }
 

@@ -192,6 +192,7 @@ struct Hbm {
     Event work_done[WORK_SLOTS];                            // recorded behind the launch that used the slot
     OrderedScratch<unsigned char> sort;                     // svo_tile_order
     OrderedScratch<float> cont;                             // svo_trace_translucent: a RayList without records, one ray per pixel
+    OrderedScratch<float> mirror;                           // svo_trace_reflections: a RayList without records, one ray per pixel
     OrderedScratch<float> local;                            // svo_trace_local_shadows: a RayList with records, one ray per pixel and light asked for
     OrderedScratch<float> shadowmap;                        // svo_shadowmap_render: a RayList with records, one ray per texel in tile order
     // see-through view (svo_trace_params.see_through, see_through.hip.h): the wide and mask pools with one material taken out, built

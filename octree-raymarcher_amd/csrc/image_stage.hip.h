@@ -1,7 +1,7 @@
 // image_stage.hip.h — what the per-pixel stages behind the march share (shade.hip, sky.hip, boxes.hip, see_through.hip.h,
 // local_shadows.hip.h): the rectangle of the camera image a launch covers and the ray of each of its pixels, the decode of a G-buffer
-// record in its two forms, leafUV from both, and on the host the rectangle's validity test (the launch itself: hip_own.h,
-// launch_per_element).
+// record in its two forms, leafUV from both, the entered face of a hit's voxel, and on the host the rectangle's validity test (the
+// launch itself: hip_own.h, launch_per_element).
 #pragma once
 #include <cstring>
 #include <string>
@@ -75,6 +75,24 @@ __device__ __forceinline__ bool hit_uv(const PixelFrame &F, int64_t k, float eps
     const V3 p = o + d * (h.t - eps);           // the point cubeNormal is taken at, shaders/World.Fragment.glsl:174
     leaf_uv(p, mk(__uint_as_float(v0.x), __uint_as_float(v0.y), __uint_as_float(v0.z)), __uint_as_float(v0.w), h.material, eps, u, v);
     return true;
+}
+
+// ---- device: the face of its voxel a hit entered (ao.hip.h, reflect.hip.h) ----------------------------------------------------------
+__device__ __forceinline__ float axis_of(V3 v, int k) { return k == 0 ? v.x : k == 1 ? v.y : v.z; }
+__device__ __forceinline__ V3 with_axis(V3 v, int k, float s) { return mk(k == 0 ? s : v.x, k == 1 ? s : v.y, k == 2 ? s : v.z); }
+
+// The box [lo, hi] of a voxel record's first half (v0: bmin, size) and the face of it that the sample point P of a ray along d lies on:
+// the SVO_NORMAL_FACE rule (march.hip.h face_normal; include/svo.h svo_hit_ao step 2) as an axis and a sign of +1 or -1
+struct HitFace { V3 lo, hi; int axis; float sgn; };
+__device__ __forceinline__ HitFace hit_face(V3 P, uint4 v0, V3 d)
+{
+    HitFace f;
+    f.lo = mk(__uint_as_float(v0.x), __uint_as_float(v0.y), __uint_as_float(v0.z));
+    f.hi = f.lo + __uint_as_float(v0.w);
+    const V3 n = face_normal(P, f.lo, f.hi, d);
+    f.axis = n.x != 0.0f ? 0 : n.y != 0.0f ? 1 : 2;
+    f.sgn = axis_of(n, f.axis);
+    return f;
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 // shaders/World.Fragment.glsl:63-138,180-197, as one coalesced kernel (32 B read + 16 B written per pixel:
 // HBM-bound).  Albedo from the material table (svo_shade) or from the caller's texture atlas at the hit's leafUV
 // (svo_shade_textured, :5-15,178-182; svo_hit_uv hands that leafUV to callers with a sampler of their own) — see include/svo.h.
+// svo_shade_reflections blends what the mirror rays of svo_trace_reflections saw into the image (reflect.hip.h; not in the reference).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -9,6 +10,8 @@
 #include <string>
 
 #include "image_stage.hip.h"
+#include "reflect.hip.h"
+#include "sky_lookup.hip.h"
 
 namespace svo {
 namespace {
@@ -49,21 +52,13 @@ __device__ __forceinline__ float pow_shiny(float x, float y)
 }
 __device__ __forceinline__ int material_index(uint32_t material) { return material < 8 ? (int)material : 0; }
 
-// One pixel's {r, g, b, depth} from its record (a hit: SVO_HIT_FLAG) and its gamma-decoded albedo (:181-182) - the body of every
-// shading kernel
-__device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, const HitRecord &h, V3 diffuse, V3 specular)
+// {r, g, b, depth} of the record h (a hit: SVO_HIT_FLAG) of a ray from `eye` along the unit vector `beta`, with its gamma-decoded
+// albedo (:181-182) - the body of every shading kernel.  The shaded point is alpha + beta * (sigma - EPS), :174.
+// MIRROR: the ray is a mirror ray (k_shade_reflections): the view vector is -beta whatever sigma is, and there is no depth.
+template <bool MIRROR>
+__device__ __forceinline__ float4 shade_ray(const ShadeArgs &A, V3 eye, V3 beta, const HitRecord &h, V3 diffuse, V3 specular)
 {
     const svo_shade_params &P = A.P;
-    const FrameCam &cam = A.frame.cam;
-    // the ray of this pixel (same generation as the march) and the shaded point alpha + beta * (sigma - EPS), :174
-    // (not PixelFrame::ray: the host-made reciprocals and normalize_fast above, within this stage's tolerance and not bit for bit)
-    int px, py;
-    A.frame.pixel(k, px, py);
-    const float fx = (float)px + 0.5f, fy = (float)py + 0.5f;
-    const float u = ((fx * A.inv_imgw) * 2.0f - 1.0f) * cam.tanx;
-    const float v = (1.0f - (fy * A.inv_imgh) * 2.0f) * cam.tany;
-    const V3 eye = ld3(cam.eye);
-    const V3 beta = normalize_fast((ld3(cam.fwd) + ld3(cam.right) * u) + ld3(cam.up) * v);
     const float sdist = h.t - P.eps;
     const V3 p = eye + beta * sdist;
     const float shininess = P.materials[material_index(h.material)].shininess;
@@ -73,7 +68,7 @@ __device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, const
     const float lit_point = local ? ((h.flags & SVO_SHADOWED_POINT) ? 0.0f : 1.0f) : lit;
     const float lit_spot = local ? ((h.flags & SVO_SHADOWED_SPOT) ? 0.0f : 1.0f) : lit;
     // normalize(eye - p) = -beta and |p - eye| = sigma - EPS (beta is a unit vector) while the hit lies in front of the eye
-    const bool front = sdist > 1.0e-3f;
+    const bool front = MIRROR || sdist > 1.0e-3f;
     const V3 vdir = front ? mk(-beta.x, -beta.y, -beta.z) : normalize_fast(eye - p);
     const float zdist = front ? sdist : sqrtf(dot3(p - eye, p - eye));
     V3 color = mk(0.0f, 0.0f, 0.0f);
@@ -117,7 +112,21 @@ __device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, const
         const V3 spe = ((ld3(P.spot.specular) * s) * specular) * lit_spot;
         color = color + (amb + (dif + spe) * intensity) * att;
     }
-    return make_float4(color.x, color.y, color.z, (rcp_fast(zdist) - A.inv_near) * A.inv_depth_range);     // :193-197
+    return make_float4(color.x, color.y, color.z, MIRROR ? 0.0f : (rcp_fast(zdist) - A.inv_near) * A.inv_depth_range);     // :193-197
+}
+
+// One pixel's {r, g, b, depth} from its record: shade_ray along the ray of this pixel (same generation as the march)
+__device__ __forceinline__ float4 shade_hit(const ShadeArgs &A, int64_t k, const HitRecord &h, V3 diffuse, V3 specular)
+{
+    const FrameCam &cam = A.frame.cam;
+    // (not PixelFrame::ray: the host-made reciprocals and normalize_fast above, within this stage's tolerance and not bit for bit)
+    int px, py;
+    A.frame.pixel(k, px, py);
+    const float fx = (float)px + 0.5f, fy = (float)py + 0.5f;
+    const float u = ((fx * A.inv_imgw) * 2.0f - 1.0f) * cam.tanx;
+    const float v = (1.0f - (fy * A.inv_imgh) * 2.0f) * cam.tany;
+    const V3 beta = normalize_fast((ld3(cam.fwd) + ld3(cam.right) * u) + ld3(cam.up) * v);
+    return shade_ray<false>(A, ld3(cam.eye), beta, h, diffuse, specular);
 }
 
 // svo_shade's albedo: the material table's (:183-184 with the table in the atlas's place)
@@ -242,6 +251,40 @@ __global__ __launch_bounds__(256) void k_shade_ao(const float *ao, float strengt
     if (f == 1.0f || f != f) return;
     float *px = reinterpret_cast<float *>(rgba + k);
     px[0] = px[0] * f; px[1] = px[1] * f; px[2] = px[2] * f;
+}
+
+// svo_shade_reflections: what a mirror pixel's ray saw, blended over the pixel by the reflectance F.  A.gbuffer and `voxels` are the
+// records the ray list was made from - mirror_ray() rebuilds the ray that was marched -, `reflect` what the march wrote for it.
+struct MirrorArgs {
+    uint32_t material;
+    float f0;
+    int32_t fresnel, has_sky;
+    float background[3];
+    SkyMap sky;
+};
+
+__global__ __launch_bounds__(256) void k_shade_reflections(ShadeArgs A, MirrorArgs M, const uint4 *voxels, const uint4 *reflect)
+{
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= A.frame.count()) return;
+    V3 O, R;
+    float c;
+    if (!mirror_ray(A.frame, k, A.P.eps, M.material, A.gbuffer, voxels, O, R, c)) return;
+    const float x = 1.0f - c;
+    const float F = M.fresnel ? M.f0 + (1.0f - M.f0) * (((x * x) * (x * x)) * x) : M.f0;        // Schlick
+    if (F == 0.0f) return;
+    const HitRecord h = load_hit(reflect, k);
+    V3 C = ld3(M.background);
+    if (h.flags & SVO_HIT_FLAG) {
+        const int mi = material_index(h.material);
+        const float4 s = shade_ray<true>(A, O, R, h, ld3(A.gdiffuse[mi]), ld3(A.gspecular[mi]));      // (R is d with one sign flipped: a unit vector)
+        C = mk(s.x, s.y, s.z);
+    } else if (M.has_sky) {
+        sky_lookup(M.sky, R, C);                // (no answer: C stays the background)
+    }
+    const float keep = 1.0f - F;
+    float *px = reinterpret_cast<float *>(A.rgba + k);
+    px[0] = px[0] * keep + C.x * F; px[1] = px[1] * keep + C.y * F; px[2] = px[2] * keep + C.z * F;
 }
 
 } // namespace
@@ -379,6 +422,29 @@ int svo_shade_ao(const float *ao_dev, float strength, int64_t n, float *rgba_dev
 {
     if (!(strength >= 0.0f && strength <= 1.0f) || n < 0 || (n > 0 && (!ao_dev || !rgba_dev))) { set_error("svo_shade_ao: bad argument"); return SVO_ERR_INVALID_ARG; }
     return launch_per_element("svo_shade_ao", n, (hipStream_t)stream, k_shade_ao, ao_dev, strength, n, reinterpret_cast<float4 *>(rgba_dev));
+}
+
+// Mirror reflections over an image a shade call has written: svo_trace_reflections' records shaded along their mirror rays
+int svo_shade_reflections(const svo_camera *cam, const svo_shade_params *p, const svo_mirror *mirror, int x0, int y0, int w, int h,
+                          const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, const svo_hit *reflect_dev, float *rgba_dev, void *stream)
+{
+    const auto refuse = [](const char *what) { set_error(std::string("svo_shade_reflections: ") + what); return SVO_ERR_INVALID_ARG; };
+    if (!p || !mirror || !rect_ok(cam, x0, y0, w, h)) return refuse("bad camera, params, mirror or rectangle");
+    const int64_t n = (int64_t)w * h;
+    if (n > 0 && (!gbuffer_dev || !voxels_dev || !reflect_dev || !rgba_dev)) return refuse("NULL buffer");
+    if (!(mirror->f0 >= 0.0f && mirror->f0 <= 1.0f) || mirror->material > 0xFFFFu) return refuse("f0 is in [0, 1], material a 16-bit material");
+    for (int c = 0; c < 3; ++c) if (!std::isfinite(mirror->background[c])) return refuse("the background is not finite");
+    if (mirror->sky && !sky_ok(mirror->sky)) return refuse("bad sky");
+    if (n == 0) return SVO_OK;
+    ShadeArgs A;
+    if (const int rc = shade_args(cam, p, x0, y0, w, h, gbuffer_dev, rgba_dev, A)) return rc;
+    MirrorArgs M;
+    std::memset(&M, 0, sizeof M);
+    M.material = mirror->material; M.f0 = mirror->f0; M.fresnel = mirror->fresnel != 0;
+    std::memcpy(M.background, mirror->background, sizeof M.background);
+    if (mirror->sky) { M.has_sky = 1; M.sky = sky_map(*mirror->sky); }
+    return launch_per_element("svo_shade_reflections", n, (hipStream_t)stream, k_shade_reflections, A, M, reinterpret_cast<const uint4 *>(voxels_dev),
+                              reinterpret_cast<const uint4 *>(reflect_dev));
 }
 
 } // extern "C"

@@ -19,6 +19,7 @@
 //   svo::World::hit_voxels(...)      <- hit.bmin / hit.size of fragment main (svo_hit_voxels)   shaders/World.Fragment.glsl:168-172
 //   svo::World::hit_uv / shade_textured  <- leafUV, texture(Diffuse / Specular, uv) (svo_hit_uv, svo_shade_textured)   shaders/World.Fragment.glsl:5-15,178-182
 //   svo::World::hit_ao / shade_ao    <- (none: the reference has no ambient occlusion) svo_hit_ao, svo_shade_ao
+//   svo::World::trace_reflections / shade_reflections  <- (none: the reference has no reflections) svo_trace_reflections, svo_shade_reflections
 //   svo::World::shade_sky / frame_rgba8  <- Skybox::draw and the RGBA8 colour attachment (svo_shade_sky, svo_frame_rgba8)   src/Skybox.cpp, src/GBuffer.cpp
 //   svo::World::cursor_place / shade_boxes / edit_cube  <- computeTarget, ImaginaryCube::draw, modify() (svo_cursor_place, svo_shade_boxes,
 //                                       svo_world_edit_cube)   src/Main.cpp:314-368, src/ImaginaryCube.cpp:59-87
@@ -295,6 +296,21 @@ public:
     void shade_ao(const float *ao_dev, float strength, int64_t n, float *rgba_dev, void *stream = nullptr) const
     {
         check(svo_shade_ao(ao_dev, strength, n, rgba_dev, stream), "World::shade_ao");
+    }
+
+    // Mirror reflections off the axis-aligned faces of the voxels that were hit (not in the reference).  trace_reflections marches the
+    // mirror ray of every usable hit of `material` (0 = any) of the rectangle draw() filled - params: that frame's -, reflect_dev gets
+    // w*h records (svo_trace_reflections); shade_reflections blends what they saw over the image a shade call wrote, by mirror's Fresnel
+    // term (svo_shade_reflections: behind shade_ao, before shade_boxes and frame_rgba8; p.eps is the launch's).
+    void trace_reflections(const svo_camera &cam, const svo_trace_params &params, uint32_t material, int x0, int y0, int w, int h,
+                           const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, svo_hit *reflect_dev, void *stream = nullptr)
+    {
+        check(svo_trace_reflections(world_, &cam, &params, material, x0, y0, w, h, gbuffer_dev, voxels_dev, reflect_dev, stream), "World::trace_reflections");
+    }
+    void shade_reflections(const svo_camera &cam, const svo_shade_params &p, const svo_mirror &mirror, int x0, int y0, int w, int h,
+                           const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, const svo_hit *reflect_dev, float *rgba_dev, void *stream = nullptr) const
+    {
+        check(svo_shade_reflections(&cam, &p, &mirror, x0, y0, w, h, gbuffer_dev, voxels_dev, reflect_dev, rgba_dev, stream), "World::shade_reflections");
     }
 
     // The skybox behind the misses (svo_shade_sky; src/Skybox.cpp, src/Main.cpp:227) over an image a shade call has written for the same

@@ -1,7 +1,9 @@
 """Render one shaded frame (svo_trace + svo_shade) to a PNG — a human-readable sanity check of the whole path.
-    python scripts/render_png.py out.png [depth] [width] [height] [--ao STRENGTH]
+    python scripts/render_png.py out.png [depth] [width] [height] [--ao STRENGTH] [--reflect]
 --ao STRENGTH (0..1): a ball of radius 12 is carved out of the terrain under the image's centre and the frame gets voxel ambient occlusion
 (svo_hit_ao + svo_shade_ao) at that strength: the ball reads as a hole, creases and the foot of walls darken.
+--reflect: the lake (material 6) mirrors the terrain and the picture's sky colour (svo_trace_reflections + svo_shade_reflections,
+f0 = 0.02 with the Fresnel term).
 """
 import importlib, os, struct, sys, zlib
 import numpy as np
@@ -24,6 +26,9 @@ if "--ao" in sys.argv:
     i = sys.argv.index("--ao")
     ao = float(sys.argv[i + 1])
     del sys.argv[i:i + 2]
+reflect = "--reflect" in sys.argv
+if reflect:
+    sys.argv.remove("--reflect")
 out = sys.argv[1] if len(sys.argv) > 1 else "frame.png"
 depth = int(sys.argv[2]) if len(sys.argv) > 2 else 9
 w = int(sys.argv[3]) if len(sys.argv) > 3 else 960
@@ -47,11 +52,17 @@ if ao is not None:
     W.hit_voxels(gb.ptr, w * h, vox.ptr)
     W.hit_ao(cam, None, (0, 0, w, h), gb.ptr, vox.ptr, aod.ptr)
     svo.shade_ao(aod.ptr, ao, w * h, rgba.ptr)
+SKY = (0.45, 0.65, 0.9)
+if reflect:
+    vox, refl = svo.DeviceBuffer(w * h * 32), svo.DeviceBuffer(w * h * 32)
+    W.hit_voxels(gb.ptr, w * h, vox.ptr)
+    W.trace_reflections(cam, svo.trace_params(shadow=True), (0, 0, w, h), gb.ptr, vox.ptr, refl.ptr, material=6)
+    svo.shade_reflections(cam, P, svo.Mirror(6, 0.02, True, SKY), (0, 0, w, h), gb.ptr, vox.ptr, refl.ptr, rgba.ptr)
 svo.lib.svo_stream_synchronize(None)
 img = rgba.to_numpy(np.float32, w * h * 4).reshape(h, w, 4)
 rgb = np.nan_to_num(img[..., :3], nan=0.0)
 hit = (g["flags"] & 1) != 0
-sky = np.array([0.45, 0.65, 0.9], np.float32)
+sky = np.array(SKY, np.float32)
 rgb = np.where(hit[..., None], rgb, sky)
 rgb = np.clip(rgb, 0, 1) ** (1 / 2.2)
 write_png(out, (rgb * 255 + 0.5).astype(np.uint8))
