@@ -115,7 +115,9 @@ extern "C" {
                                           svo_world_edit_ball and svo_world_edit_ball_all,
                                           svo_shadowmap, svo_shadowmap_fit, svo_shadowmap_render and svo_shadowmap_apply,
                                           svo_hit_ao and svo_shade_ao,
-                                          svo_trace_reflections, svo_shade_reflections and svo_mirror */
+                                          svo_trace_reflections, svo_shade_reflections and svo_mirror,
+                                          svo_world_prepare_light, svo_world_prepared_light and SVO_SHADOW_NO_CLEARANCE (a bit of
+                                          svo_trace_params.shadow, which was any non-zero value: such callers keep their results) */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -204,7 +206,9 @@ typedef struct svo_trace_params {
     int32_t  max_chunk_steps;       /* 0 = 1000   (src/Traverse.cpp:142) */
     int32_t  max_tree_steps;        /* 0 = 1000   (src/Traverse.cpp:79) */
     int32_t  max_twig_steps;        /* 0 = 1000   (src/Traverse.cpp:54) */
-    int32_t  shadow;                /* !=0: one shadow ray per primary hit toward -light_dir */
+    int32_t  shadow;                /* !=0: one shadow ray per primary hit toward -light_dir.  Bit SVO_SHADOW_NO_CLEARANCE (2 or 3 instead
+                                       of 1): the same shadow rays, never ended early by svo_world_prepare_light's bits - the same records,
+                                       more steps; for A/B runs */
     float    light_dir[3];          /* directionalLight.direction, default normalize(1,-1,0) (src/Main.cpp:116) */
     int32_t  kernel;                /* SVO_KERNEL_* */
     int32_t  tiles_per_wave;        /* SVO_KERNEL_STACK launch shape: every persistent wave is handed at least this
@@ -253,6 +257,7 @@ typedef struct svo_trace_params {
                                        (svo_world_info does not count it; at most 1.4 GB at C3 size); every change to the pools drops it */
 } svo_trace_params;
 enum { SVO_NORMAL_CUBE = 0, SVO_NORMAL_FACE = 1 };
+enum { SVO_SHADOW_NO_CLEARANCE = 2 };
 enum { SVO_SEMANTICS_CPU = 0, SVO_SEMANTICS_GLSL = 1 };
 
 /* G-buffer record, 32 bytes per pixel / per ray. */
@@ -985,6 +990,36 @@ int svo_shade_boxes(const svo_camera *cam, const svo_box *boxes_dev, int nboxes,
  * svo_trace_frames launch; a multi-frame call served by a kernel other than SVO_KERNEL_STACK is one launch per
  * frame and reports its last frame); synchronises `stream` internally — call it outside timed regions. */
 int svo_trace_last_ray_count(svo_world *, void *stream, uint64_t *rays);
+
+/* Light clearance: shadow rays of the directional light stop at the first empty cell with a clear way to the light.
+ * A shadow ray adds one bit to its record, SVO_SHADOWED, and a lit one marches on through ever larger empty cells and out of the world
+ * to report nothing.  Whether the way from an EMPTY node to the light is free depends only on the world and the light's direction, so
+ * it is decided once, for every EMPTY node, by a sweep on the device (csrc/light_clearance.hip.h; DESIGN.md 6t has the rule and its
+ * proof) and kept as one bit of the stack kernel's wide tree; a shadow ray of SVO_KERNEL_STACK that locates such a node ends there.
+ * The records are the same bit for bit, svo_trace_last_ray_count too; only the steps taken differ.
+ *   svo_world_prepare_light   decides the bits for light_dir (as svo_trace_params.light_dir: (0,0,0) or NULL = the default light).
+ *                             Asynchronous on `stream`, ordered on the device behind every launch of the world issued before; launches
+ *                             that use the bits wait for it.  One light at a time: a second call replaces the first.  Costs a sweep over
+ *                             the wide pool per call (README quotes it beside the world build).
+ *   automatic                 the first svo_trace / svo_trace_frames / svo_trace_rows(_frames) launch with shadow rays on a world that has
+ *                             not changed since its upload (or its generation on the device) prepares the bits for its own light_dir.
+ *   dropped by                every change to the pools (svo_world_update / _edit_* / _shift / _compact / _coarsen / _chunk_from_grid /
+ *                             _upload).  After a change only svo_world_prepare_light brings them back: a caller who edits every frame
+ *                             never pays a sweep per frame.
+ *   used by                   camera launches of SVO_SEMANTICS_CPU with shadow rays whose light_dir equals the prepared one bit for bit and
+ *                             whose eps is a power of two of at least twice the float spacing at the world's largest coordinate.  Ray lists,
+ *                             segments, local lights, reflections, see_through, tile_cost_dev, SVO_SEMANTICS_GLSL, the literal kernel and
+ *                             SVO_SHADOW_NO_CLEARANCE march every step as before.  A direction with a non-zero component below 1/64 in
+ *                             magnitude is accepted and never used (a ray that grazes a chunk face defeats the proof).
+ *   svo_world_prepared_light  the prepared shadow direction, normalize(-light_dir) ((0,0,0) if none is), and the number of EMPTY reference
+ *                             nodes found clear (0 if the direction is never used); waits for `stream` and for the pass, whichever stream
+ *                             it was issued on.
+ * The pass keeps 16 bytes of scratch per wide node (41 MB on the 4x1x4 depth-12 world; svo_world_info does not count it) until the next change
+ * to the pools, so that a second light costs no allocation.  A launch prepares a world on its own only while wide entries x chunks <= 1e10
+ * (four times that world: a few seconds); larger worlds are prepared by the call alone.
+ * SVO_ERR_INVALID_ARG (NULL world / outputs), SVO_ERR_NOT_UPLOADED, SVO_ERR_OUT_OF_MEMORY (the scratch). */
+int svo_world_prepare_light(svo_world *, const float light_dir[3], void *stream);
+int svo_world_prepared_light(svo_world *, void *stream, float shadow_dir[3], uint64_t *clear_nodes);
 
 /* ---- small device helpers so that C/C++ callers need no HIP headers --------------------- */
 int   svo_device_count(void);

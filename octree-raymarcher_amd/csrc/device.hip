@@ -36,6 +36,7 @@
 #include "hit_voxels.hip.h"
 #include "hip_own.h"
 #include "wide_tree.hip.h"
+#include "light_clearance.hip.h"
 
 using namespace svo;
 
@@ -151,6 +152,15 @@ static void drop_parents(svo_world &w)
     if (d.parent.p || d.parent_level.p || d.chunk_trees.p) (void)hipDeviceSynchronize();
     d.parent = Pooled<uint32_t>(); d.parent_level = Pooled<uint8_t>(); d.chunk_trees = DevBuf<uint32_t>();
     d.parents_ok = false;
+}
+
+// the light clearance bits (light_clearance.hip.h): every change to the pools drops them - a rebuilt chunk has none, and those of the
+// other chunks were decided against matter that may have changed - until svo_world_prepare_light is called again
+static void drop_clearance(svo_world &w)
+{
+    Hbm &d = *w.hbm;
+    if (d.clear_place.p) { (void)hipDeviceSynchronize(); d.clear_place = Pooled<uint4>(); }     // (the pass's scratch: 16 bytes per wide node)
+    d.clear_state = Hbm::CLEAR_DROPPED; d.clear_usable = false;
 }
 
 int release_device(svo_world &w, bool keep_builder)
@@ -391,6 +401,7 @@ static bool wide_fits(const svo_world &w, int chunk)
 static void drop_wide(svo_world &w)
 {
     drop_view(w);
+    if (w.hbm->clear_state == Hbm::CLEAR_READY) drop_clearance(w);
     if (w.hbm->wide.p || w.hbm->wbase.p) (void)hipDeviceSynchronize();
     w.hbm->wide = Pooled<uint32_t>(); w.hbm->wbase = Pooled<uint32_t>();
     w.wide_ok = false;
@@ -596,6 +607,7 @@ static int install_chunk(svo_world &w, int chunk, const uint32_t *tree, const ui
     HIP_TRY(hipDeviceSynchronize());
     drop_view(w);                                                       // rebuilt from the new pools at the next see-through launch
     drop_parents(w);                                                    // ... and at the next svo_hit_voxels call
+    drop_clearance(w);                                                  // ... and only by svo_world_prepare_light
     ChunkPools &c = w.chunks[(size_t)chunk];
     DevChunk &e = w.table[(size_t)chunk];
     const uint64_t trees = c.tree_count(), twigs = c.twig_count();
@@ -615,7 +627,9 @@ static int install_chunk(svo_world &w, int chunk, const uint32_t *tree, const ui
                 HIP_TRY(hipMemcpy(c.tree.data(), tree, trees * sizeof(uint32_t), hipMemcpyDeviceToHost));
                 if (twigs) HIP_TRY(hipMemcpy(c.twig.data(), twig, twigs * TWIG_WORDS * sizeof(uint16_t), hipMemcpyDeviceToHost));
             }
-            return world_upload_impl(&w, w.device, true);
+            const int rc = world_upload_impl(&w, w.device, true);
+            if (w.hbm) drop_clearance(w);                               // (the re-pack is part of an edit, not a fresh upload)
+            return rc;
         }
         if (!tree_fits) { e.tree_off = tbase; w.tree_slot[(size_t)chunk] = need_t; w.tree_pool_len = tbase + need_t; }
         if (!twig_fits) { e.twig_off = w.twig_pool_len; w.twig_slot[(size_t)chunk] = need_b; w.twig_pool_len += need_b; }
@@ -799,6 +813,17 @@ static svo_trace_params own_list_params(const svo_trace_params &prm, bool keep_s
     return march;
 }
 
+// shadow direction = normalize(-light_dir), glm::normalize semantics; no direction or (0, 0, 0): the reference's light
+static void shadow_direction(const float *light_dir, float sdir[3])
+{
+    float l[3] = { 1.0f, -1.0f, 0.0f };                                  // src/Main.cpp:116 (normalised below)
+    if (light_dir && (light_dir[0] != 0.0f || light_dir[1] != 0.0f || light_dir[2] != 0.0f))
+        std::memcpy(l, light_dir, sizeof l);
+    const float nx = -l[0], ny = -l[1], nz = -l[2];
+    const float inv = 1.0f / std::sqrt(nx * nx + ny * ny + nz * nz);
+    sdir[0] = nx * inv; sdir[1] = ny * inv; sdir[2] = nz * inv;
+}
+
 static int fill_common(svo_world *w, const svo_trace_params *prm, TraceArgs &A)
 {
     if (!w) return SVO_ERR_INVALID_ARG;
@@ -831,13 +856,7 @@ static int fill_common(svo_world *w, const svo_trace_params *prm, TraceArgs &A)
     A.leaf_back = glsl ? 0.0f : A.eps;
     A.shadow = (prm && prm->shadow) ? 1 : 0;
     A.normal_mode = (prm && prm->normal_mode == SVO_NORMAL_FACE) ? SVO_NORMAL_FACE : SVO_NORMAL_CUBE;
-    float l[3] = { 1.0f, -1.0f, 0.0f };                                  // src/Main.cpp:116 (normalised below)
-    if (prm && (prm->light_dir[0] != 0.0f || prm->light_dir[1] != 0.0f || prm->light_dir[2] != 0.0f))
-        std::memcpy(l, prm->light_dir, sizeof l);
-    // shadow direction = normalize(-light_dir), glm::normalize semantics
-    const float nx = -l[0], ny = -l[1], nz = -l[2];
-    const float inv = 1.0f / std::sqrt(nx * nx + ny * ny + nz * nz);
-    A.sdir[0] = nx * inv; A.sdir[1] = ny * inv; A.sdir[2] = nz * inv;
+    shadow_direction(prm ? prm->light_dir : nullptr, A.sdir);
     A.counters = prm ? prm->counters_dev : nullptr;
     A.exact_geometry = w->exact_geometry ? 1 : 0;
     A.tile_cost = prm ? prm->tile_cost_dev : nullptr;
@@ -934,6 +953,91 @@ static int use_view(svo_world *w, uint32_t m, TraceArgs &A, hipStream_t s)
     return SVO_OK;
 }
 
+// Light clearance (light_clearance.hip.h).  The rule's premises: every component of the shadow direction is 0 or at
+// least CLEAR_S_MIN in magnitude (a smaller one lets a ray graze a chunk face for a long way: the chunk march then resumes far behind
+// the tree march's last sample), the world's largest coordinate has a float spacing u of at most eps / 2, and eps is a power of two.
+constexpr double CLEAR_S_MIN = 1.0 / 64.0;
+// The sweep looks at every chunk's root per EMPTY entry: its cost grows with entries x chunks.  The 4x1x4 depth-12 world (163 M entries,
+// 16 chunks: 2.6e9) takes 0.86 s (profiles/light_clearance_ab.txt); a launch prepares a world on its own up to four times that product,
+// a few seconds by proportion.  Larger worlds - the 10x1x10 one of scripts/bigworld_check.py is at 1.3e11 - are prepared on request only.
+constexpr double CLEAR_AUTO_WORK = 1.0e10;
+
+static float clear_spacing(const svo_world &w)
+{
+    const int dims[3] = { w.width, w.height, w.depth };
+    float m = 1.0f;
+    for (int a = 0; a < 3; ++a)
+        for (int k = 0; k < 2; ++k) m = std::max(m, std::fabs((float)(w.chunkcoordmin[a] + k * dims[a]) * (float)w.chunksize));
+    return std::nextafter(m, INFINITY) - m;
+}
+static bool eps_is_pow2(float eps)
+{
+    uint32_t b;
+    std::memcpy(&b, &eps, sizeof b);
+    return (b & 0x807FFFFFu) == 0u && b >= 0x00800000u && b < 0x7F800000u;
+}
+
+// The bits for shadow direction `sdir`, issued on `s` behind every launch of the world in flight (one of them may be reading the
+// bits of another light); launches that use them wait for clear_built.
+static int prepare_light(svo_world &w, const float sdir[3], hipStream_t s)
+{
+    Hbm &d = *w.hbm;
+    d.clear_usable = false;
+    if (!w.wide_ok || w.wide_pool_len == 0) return SVO_OK;              // the literal kernel marches this world: nothing reads the bits
+    HIP_TRY(hipSetDevice(w.device));
+    bool premises = true;
+    for (int a = 0; a < 3; ++a) premises &= std::isfinite(sdir[a]) && (sdir[a] == 0.0f || std::fabs((double)sdir[a]) >= CLEAR_S_MIN);
+    std::memcpy(d.clear_sdir, sdir, sizeof d.clear_sdir);
+    d.clear_state = Hbm::CLEAR_READY;
+    if (!premises || !w.exact_geometry) return SVO_OK;                  // prepared, and never used
+    d.clear_state = Hbm::CLEAR_DROPPED;                                 // (until everything below is issued)
+    const uint64_t nodes = w.wide_pool_len;
+    if (d.clear_place.bytes < nodes * sizeof(uint4)) {
+        if (d.clear_place.p) HIP_TRY(hipDeviceSynchronize());
+        if (d.clear_place.alloc(nodes, w.device) != hipSuccess) { set_error("svo_world_prepare_light: hipMalloc failed"); return SVO_ERR_OUT_OF_MEMORY; }
+    }
+    if (const int rc = d.clear_count.reserve(1, false, nullptr)) return rc;
+    for (Event &e : d.work_done) if (e.e) if (const int rc = e.wait(s)) return rc;
+    if (d.clear_built.e) if (const int rc = d.clear_built.wait(s)) return rc;
+    const double u = (double)clear_spacing(w);
+    ClearArgs K;
+    K.wchunks = d.wchunks.p; K.wide = d.wide.p; K.place = d.clear_place.p; K.pool_nodes = nodes;
+    K.n_chunks = (int32_t)w.chunks.size(); K.chunksize = (double)w.chunksize;
+    for (int a = 0; a < 3; ++a) K.s[a] = (double)sdir[a];
+    K.d1 = 4.0 * u;
+    K.d2 = (8.0 / CLEAR_S_MIN + 6.0 + 4.0 * (double)(w.width + w.height + w.depth + 2)) * u;
+    K.clear_nodes = d.clear_count.p;
+    HIP_TRY(hipMemsetAsync(d.clear_place.p, 0xFF, nodes * sizeof(uint4), s));
+    HIP_TRY(hipMemsetAsync(d.clear_count.p, 0, sizeof(unsigned long long), s));
+    int rc = launch_per_element("svo_world_prepare_light", K.n_chunks, s, k_clear_seed, K);
+    const int nw_max = w.max_levels ? (w.max_levels + 1) / 2 : 1;
+    for (int r = 0; rc == SVO_OK && r + 1 < nw_max; ++r) rc = launch_per_element("svo_world_prepare_light", (int64_t)nodes * 64, s, k_clear_boxes, K, (uint32_t)r);
+    if (rc == SVO_OK) rc = launch_per_element("svo_world_prepare_light", (int64_t)nodes * 64, s, k_clear_sweep, K);
+    if (rc != SVO_OK) return rc;
+    if ((rc = d.clear_built.record(s)) != SVO_OK) return rc;
+    d.clear_state = Hbm::CLEAR_READY;
+    d.clear_usable = true;
+    d.clear_eps = 2.0f * (float)u;                                      // the smallest eps the bits hold for
+    return SVO_OK;
+}
+
+// Does this stack-kernel launch let its shadow rays retire at clear cells?  Camera frames of the CPU march with shadow rays and
+// nothing that looks at a ray's later steps (tile costs) or marches another world (the see-through view); the world's first such
+// launch after its upload prepares the bits for its own light.
+static int use_light_clearance(svo_world *w, const svo_trace_params *prm, TraceArgs &A, uint32_t see, hipStream_t s)
+{
+    A.light_clear = 0;
+    if (!A.shadow || !A.from_camera || A.tmax || see || A.glsl || A.tile_cost || (prm && (prm->shadow & SVO_SHADOW_NO_CLEARANCE))) return SVO_OK;
+    Hbm &d = *w->hbm;
+    if (d.clear_state == Hbm::CLEAR_FRESH && (double)w->wide_pool_len * 64.0 * (double)w->chunks.size() <= CLEAR_AUTO_WORK)
+        if (const int rc = prepare_light(*w, A.sdir, s)) return rc;
+    if (d.clear_state != Hbm::CLEAR_READY || !d.clear_usable) return SVO_OK;
+    if (std::memcmp(d.clear_sdir, A.sdir, sizeof d.clear_sdir) != 0 || !eps_is_pow2(A.eps) || A.eps < d.clear_eps) return SVO_OK;
+    if (const int rc = d.clear_built.wait(s)) return rc;
+    A.light_clear = 1;
+    return SVO_OK;
+}
+
 static int launch(svo_world *w, const svo_trace_params *prm, TraceArgs &A, hipStream_t s)
 {
     const int kernel = pick_kernel(w, prm, A);
@@ -944,6 +1048,7 @@ static int launch(svo_world *w, const svo_trace_params *prm, TraceArgs &A, hipSt
         const int rc = use_view(w, see, A, s);
         if (rc != SVO_OK) return rc;
     }
+    if (kernel == SVO_KERNEL_STACK) if (const int rc = use_light_clearance(w, prm, A, see, s)) return rc;
     // every launch gets its own {tile cursor, ray count} slot so that launches on different streams may overlap
     Hbm &d = *w->hbm;
     d.work_last = d.work_next;
@@ -1401,6 +1506,34 @@ int svo_trace_last_ray_count(svo_world *w, void *stream, uint64_t *rays)
     unsigned long long v[2] = { 0, 0 };
     HIP_TRY(hipMemcpy(v, w->hbm->work.p + WORK_SLOT_WORDS * w->hbm->work_last, sizeof v, hipMemcpyDeviceToHost));
     *rays = v[1];
+    return SVO_OK;
+}
+
+int svo_world_prepare_light(svo_world *w, const float light_dir[3], void *stream)
+{
+    if (!w) return SVO_ERR_INVALID_ARG;
+    if (w->device < 0) { set_error("svo_world_prepare_light: world is not uploaded"); return SVO_ERR_NOT_UPLOADED; }
+    float sdir[3];
+    shadow_direction(light_dir, sdir);
+    return prepare_light(*w, sdir, (hipStream_t)stream);
+}
+
+int svo_world_prepared_light(svo_world *w, void *stream, float shadow_dir[3], uint64_t *clear_nodes)
+{
+    if (!w || !shadow_dir || !clear_nodes) return SVO_ERR_INVALID_ARG;
+    if (w->device < 0) { set_error("svo_world_prepared_light: world is not uploaded"); return SVO_ERR_NOT_UPLOADED; }
+    const Hbm &d = *w->hbm;
+    shadow_dir[0] = shadow_dir[1] = shadow_dir[2] = 0.0f;
+    *clear_nodes = 0;
+    if (d.clear_state != Hbm::CLEAR_READY) return SVO_OK;
+    std::memcpy(shadow_dir, d.clear_sdir, sizeof d.clear_sdir);
+    if (!d.clear_usable) return SVO_OK;
+    HIP_TRY(hipSetDevice(w->device));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    if (d.clear_built.e) HIP_TRY(hipEventSynchronize(d.clear_built.e));    // (the pass may have been issued on another stream)
+    unsigned long long v = 0;
+    HIP_TRY(hipMemcpy(&v, d.clear_count.p, sizeof v, hipMemcpyDeviceToHost));
+    *clear_nodes = v;
     return SVO_OK;
 }
 

@@ -206,6 +206,15 @@ struct Hbm {
     Pooled<uint32_t> parent; Pooled<uint8_t> parent_level; DevBuf<uint32_t> chunk_trees;
     bool parents_ok = false;                                // the build has been issued
     Event parents_built;                                    // calls on other streams wait for it
+    // light clearance (svo_world_prepare_light, light_clearance.hip.h): WIDE_CLEAR_BIT of the wide pool's EMPTY entries holds for
+    // clear_sdir while clear_state == CLEAR_READY; every change to the pools drops it (the bits of untouched chunks are stale then),
+    // and only a world unchanged since its upload (CLEAR_FRESH) is prepared by a launch on its own
+    enum { CLEAR_FRESH = 0, CLEAR_READY = 1, CLEAR_DROPPED = 2 };
+    int clear_state = CLEAR_FRESH;
+    bool clear_usable = false;                              // the prepared direction and the world meet the rule's premises
+    float clear_sdir[3] = { 0.0f, 0.0f, 0.0f }; float clear_eps = 0.0f;
+    Pooled<uint4> clear_place; DevBuf<unsigned long long> clear_count;
+    Event clear_built;                                      // launches that use the bits wait for it
     int stack_blocks[24] = {};                              // persistent-grid size per k_trace_stack instantiation (device.hip: STACK_KERNELS); 0 = not queried yet
 };
 

@@ -325,6 +325,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
     stk[0][threadIdx.x] = 0u;              // o, d, 1/d, world-entry t, output index (as int; -1 = no ray)
     const int lane = threadIdx.x;
     const bool want_cost = A.tile_cost != nullptr;      // (one SGPR held; the blocks below must not re-read the kernel arguments for a feature that is off)
+    [[maybe_unused]] const bool light_clear = A.light_clear != 0;      // shadow rays retire at clear cells (light_clearance.hip.h); the C++ step ignores the bit, which is always right
     const int n_chunks = A.dimw * A.dimh * A.dimd;
     const bool chunks_in_lds = n_chunks <= CHUNK_TAB;
     if (lane == 0) {
@@ -624,6 +625,10 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
         int pass = 0;
         // in the bulk: STEP_EXTRA more steps, decided once per pass of the outer loop (n_busy: before the chunk step)
         const int fixed_steps = (n_busy >= STEP_LANES && vote(creepn > 0 || creepn <= -4 * CREEP_SERIOUS) == 0ull) ? STEP_EXTRA : 0;
+#ifndef SVO_CXX_STEP
+        // the lanes that march a shadow ray: they change kind only in the hit block, so once per pass of the outer loop
+        const unsigned long long shadow_lanes = light_clear ? vote(outk < 0) : 0ull;
+#endif
         for (;;) {
 #ifdef SVO_STACK_TIMING
         n_lane_twig += mode == M_TWIG ? (pass == 0 ? 1u + (unsigned)fixed_steps : (unsigned)DRAIN_STEPS) : 0u;        // ... of them started inside a brick
@@ -635,7 +640,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
         const int nsteps = pass == 0 ? 1 + fixed_steps : DRAIN_STEPS;
         const int sure_miss = SVO_SURE_MISS_WHEN;      // (step_asm_body.inc: bricks whose march is bound to miss are not entered)
         march_steps_asm<BIG, GLSL>(mode, O, Blo, bsize, res, t, cnt, tt_saved, t_miss, it_saved, tw, cw, pux, puy, puz, valid, plev, bmask, creepn,
-                                   beta, g, clo, alpha, levels, nw_chunk, res_tree, wide_b, twig_off, lds_lane, SU, nsteps | (sure_miss << 16), step_stats);
+                                   beta, g, clo, alpha, levels, nw_chunk, res_tree, wide_b, twig_off, lds_lane, SU, nsteps | (sure_miss << 16), shadow_lanes, step_stats);
         pass += nsteps - 1;
 #else
         if (mode == M_TREE || mode == M_TWIG) {

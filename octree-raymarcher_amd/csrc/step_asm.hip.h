@@ -79,14 +79,16 @@ struct StepUniform {            // wave-uniform inputs (SGPRs)
 template <bool BIG> using WideRef = typename std::conditional<BIG, unsigned long long, uint32_t>::type;
 
 // `nsteps` (>= 1, wave-uniform; bit 16: the wave is draining) steps of every marching lane.  All lanes of the wave must call this
-// together (EXEC is saved and restored inside).  BIG: 64-bit addressing; GLSL: the shader twin's semantics.  One explicit
+// together (EXEC is saved and restored inside).  `shadow_lanes`: the lanes that march a shadow ray and may retire at a clear EMPTY entry
+// (light_clearance.hip.h), 0 = none may.  BIG: 64-bit addressing; GLSL: the shader twin's semantics.  One explicit
 // specialization per variant, each defined by step_asm_body.inc below.
 template <bool BIG, bool GLSL>
 __device__ void march_steps_asm(
     int &mode, V3 &O, V3 &Blo, float &bsize, float &res, float &t, int &cnt, float &tt_saved, float &t_miss, int &it_saved,
     float &tw, int &cw, int &pux, int &puy, int &puz, int &valid, int &plev, unsigned long long &bmask, int &creepn,
     const V3 beta, const V3 g, const V3 clo, const V3 alpha, const int levels, const int nw, const float res_tree,
-    const WideRef<BIG> wide_b, const uint32_t twig_off, const uint32_t lds_lane, const StepUniform U, const int nsteps_sure, StepStats &stats);
+    const WideRef<BIG> wide_b, const uint32_t twig_off, const uint32_t lds_lane, const StepUniform U, const int nsteps_sure,
+    const unsigned long long shadow_lanes, StepStats &stats);
 
 // The statement's variants (step_asm_body.inc is included once per variant):
 //   addressing   32-bit offsets against scalar bases / 64-bit addresses (entry: index * 4 + the lane's wide-tree address; mask:

@@ -7,7 +7,8 @@ __device__ __forceinline__ void march_steps_asm<SVO_STEP_BIG, SVO_STEP_GLSL>(
     int &mode, V3 &O, V3 &Blo, float &bsize, float &res, float &t, int &cnt, float &tt_saved, float &t_miss, int &it_saved,
     float &tw, int &cw, int &pux, int &puy, int &puz, int &valid, int &plev, unsigned long long &bmask, int &creepn,
     const V3 beta, const V3 g, const V3 clo, const V3 alpha, const int levels, const int nw, const float res_tree,
-    const WideRef<SVO_STEP_BIG> wide_b, const uint32_t twig_off, const uint32_t lds_lane, const StepUniform U, const int nsteps_sure, StepStats &stats)
+    const WideRef<SVO_STEP_BIG> wide_b, const uint32_t twig_off, const uint32_t lds_lane, const StepUniform U, const int nsteps_sure,
+    const unsigned long long shadow_lanes, StepStats &stats)
 {
     float px, py, pz, q1, q2, q3, q4, q5, q6, q7, r1, r2, r3;     // (r1..r3 double as the lattice quotients, low as 1/res, q7 as the brick cell index)
     int ux, uy, uz, low;
@@ -190,6 +191,20 @@ __device__ __forceinline__ void march_steps_asm<SVO_STEP_BIG, SVO_STEP_GLSL>(
         "v_cmp_le_u32_e64 %[sent], -2.0, %[w]\n\t"             // TWIG  (type bits 11)
         "v_sub_u32 %[q1], %[lev], %[plv]\n\t"
         "v_bfm_b32 %[low], %[q1], 0\n\t"                       // the node spans low + 1 cells
+        // ---- light clearance (light_clearance.hip.h): a shadow ray that has located an EMPTY node whose way to the light is clear
+        //      can only go on to report "lit" - its record says so already - and retires here; shm = the wave's shadow lanes, 0
+        //      where the launch does not use the bits (one scalar compare and a branch then).  Bit 0 rotated into the sign, the type
+        //      bits below it: a clear EMPTY entry is 100..., the smallest signed values
+        "s_cmp_eq_u64 %[shm], 0\n\t"
+        "s_cbranch_scc1 41f\n\t"
+        "v_alignbit_b32 %[q2], %[w], %[w], 1\n\t"
+        "v_cmp_gt_i32 vcc, 0xa0000000, %[q2]\n\t"
+        "s_and_b64 vcc, vcc, %[shm]\n\t"
+        "s_andn2_b64 %[sstay], %[sstay], vcc\n\t"              // (they do not advance)
+        "s_mov_b64 exec, vcc\n\t"
+        "v_mov_b32 %[md], 0\n\t"
+        "s_mov_b64 exec, %[smar]\n\t"
+        "41:\n\t"
         "s_or_b64 %[sadv], %[sadv], %[sstay]\n\t"
         "v_cmpx_le_i32 vcc, 2.0, %[w]\n\t"                     // LEAF (type bits 01): hit, src/Traverse.cpp:93,160
         SVO_STEP_LEAF_DISTANCE                                 // s = t - EPS (src/Traverse.cpp:93), or t for the GLSL twin
@@ -438,7 +453,7 @@ __device__ __forceinline__ void march_steps_asm<SVO_STEP_BIG, SVO_STEP_GLSL>(
         : [bx] "v"(beta.x), [by] "v"(beta.y), [bz] "v"(beta.z), [gx] "v"(g.x), [gy] "v"(g.y), [gz] "v"(g.z),
           [clx] "v"(clo.x), [cly] "v"(clo.y), [clz] "v"(clo.z), [ax] "v"(alpha.x), [ay] "v"(alpha.y), [az] "v"(alpha.z),
           [lev] "v"(levels), [nw] "v"(nw), [rtr] "v"(res_tree), [wb] "v"(wide_b), [tof] "v"(twig_off), [lds] "v"(lds_lane),
-          [csz] "s"(U.csize), [eps] "s"(U.eps), [eps2] "s"(U.eps2), [captw] "s"(U.cap_twig), [wide] "s"(U.wide), [maskp] "s"(U.mask), [nst] "s"(nsteps_sure), [dsh] "s"(U.descend_shift)
+          [csz] "s"(U.csize), [eps] "s"(U.eps), [eps2] "s"(U.eps2), [captw] "s"(U.cap_twig), [wide] "s"(U.wide), [maskp] "s"(U.mask), [nst] "s"(nsteps_sure), [dsh] "s"(U.descend_shift), [shm] "s"(shadow_lanes)
         : "vcc", "scc", "memory");
 #ifdef SVO_STACK_TIMING
     stats.steps = st_steps; stats.lanes = st_lanes; stats.stalls = st_stalls; stats.chased = st_chased;

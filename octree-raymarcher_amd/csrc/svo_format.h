@@ -116,7 +116,8 @@ struct TraceArgs {
     int32_t  exact_geometry;    // every voxel corner is an exact float (svo_world_info.exact_geometry): the literal kernel's closed-form creep runs rely on it
     uint32_t *tile_cost;        // optional [nframes][ntiles][2]: largest primary / shadow step count per tile (stack kernel)
     const uint32_t *tile_order; // optional [ntiles]: the order in which a frame's tiles are handed out (stack kernel)
-    const float *tmax;          // svo_trace_segments: [n] far end per ray (list mode; read by the bounded instantiations only).  Last: no other field moves
+    const float *tmax;          // svo_trace_segments: [n] far end per ray (list mode; read by the bounded instantiations only).  Last but one: no other field moves
+    int32_t  light_clear;       // stack kernel: a shadow ray retires at an EMPTY entry that carries WIDE_CLEAR_BIT (device.hip use_light_clearance decides)
 };
 
 } // namespace svo

@@ -185,6 +185,12 @@ public:
         check(svo_trace_frames(world_, plain.data(), (int)plain.size(), &p, 0, 0, w, h, out.device(), stream), "World::draw_frames");
     }
 
+    // A fixed sun: decide once, for every empty node, whether its way to the light is clear (svo_world_prepare_light); the shadow rays of
+    // draw() / draw_frames() with this light_dir then end at the first such node they locate - the same records in fewer steps.  A world
+    // that has not changed since its upload is prepared by its first draw(shadow = true) on its own; after modify() or any other edit only
+    // this call brings the bits back.  Asynchronous on `stream`.
+    void prepare_light(const float light_dir[3] = nullptr, void *stream = nullptr) { check(svo_world_prepare_light(world_, light_dir, stream), "World::prepare_light"); }
+
     // Shadows from the point light and the spotlight on a G-buffer that draw() filled with the same camera, shadow flag and light
     // direction (svo_trace_local_shadows): one flag per light, a null position leaves that light with the directional light's term.
     // Not in the reference, whose three lights share one shadow term (shaders/World.Fragment.glsl:186-190).

@@ -1,0 +1,281 @@
+"""Light clearance on the device (svo_world_prepare_light, csrc/light_clearance.hip.h, the retire at label 4 of step_asm_body.inc):
+shadow rays of the stack kernel end at the first EMPTY node whose way to the light is clear, and every record still equals the
+oracle's bit for bit - whatever the light, across chunk seams, after edits, with a light other than the prepared one, and on every
+path that has to ignore the bits.  Worlds of 2x1x2 chunks at depth 5-6, images of 64x48.
+
+`python tests/test_light_clearance.py <library>` runs the scenes against a variant build (tests/variant_check.py's mechanism)."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from helpers import assert_gbuffer_equal, random_rays
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DIMS, CHUNK = (2, 1, 2), 128
+W_IMG, H_IMG = 64, 48
+LIGHTS = {"default": (1.0, -1.0, 0.0), "oblique": (0.5, -1.0, 0.3), "down": (0.0, -1.0, 0.0), "up": (0.0, 1.0, 0.0)}
+FLAT = dict(amplitude=0.0, yshift=16.0, water=False)
+STRUCTURES = [  # (chunk, lo, hi): on the voxel lattice, so that under the 45-degree default light their corners lie exactly on prism boundaries
+    (0, (96.0, 0.0, 32.0), (112.0, 96.0, 48.0)),            # a tower: it shades chunk 0 and, over the seam x = 128, nothing of chunk 1 ...
+    (2, (112.0, 0.0, 160.0), (128.0, 112.0, 176.0)),        # ... one on the seam itself: it shades chunk 3 only
+    (0, (112.0, 0.0, 80.0), (128.0, 64.0, 96.0)), (1, (128.0, 0.0, 80.0), (144.0, 64.0, 96.0)),     # an arch across the seam: legs ...
+    (0, (120.0, 64.0, 80.0), (128.0, 72.0, 96.0)), (1, (128.0, 64.0, 80.0), (136.0, 72.0, 96.0)),   # ... and lintel
+    (1, (160.0, 40.0, 16.0), (224.0, 44.0, 48.0)),          # a roof two voxels thick: bricks with empty cells
+]
+
+
+def cameras(svo):
+    return [svo.make_camera((128.3, 120.2, -70.1), (0.0, -0.55, 0.83), (0.0, 1.0, 0.0), 60.0, W_IMG, H_IMG),
+            svo.make_camera((200.7, 90.4, 40.2), (-0.5, -0.6, 0.62), (0.0, 1.0, 0.0), 60.0, W_IMG, H_IMG)]
+
+
+def build_both(svo, ob, O, W, boxes, material=5):
+    for ci, lo, hi in boxes:
+        dt, dw = ob.Delta(), ob.Delta()
+        ob.lib.orc_build(C.byref(O.w.chunk[ci]), ob.vec3(lo), ob.vec3(hi), material, C.byref(dt), C.byref(dw))
+        W.edit_box(ci, svo.EDIT_BUILD, lo, hi, material)
+
+
+def pair(svo, ob, depth=6, **terrain):
+    O = ob.OracleWorld.generate(*DIMS, chunksize=CHUNK, depth=depth, **terrain)
+    W = svo.World.generate(*DIMS, CHUNK, depth, build_device=0, **terrain)
+    return O, W
+
+
+def march(svo, W, cams, light, **prm):
+    out = svo.DeviceBuffer(len(cams) * W_IMG * H_IMG * 32)
+    p = svo.trace_params(shadow=True, kernel=svo.KERNEL_STACK, light_dir=light, **prm)
+    if len(cams) == 1:
+        W.trace(cams[0], p, (0, 0, W_IMG, H_IMG), out.ptr)
+    else:
+        W.trace_frames(cams, p, (0, 0, W_IMG, H_IMG), out.ptr)
+    svo.lib.svo_stream_synchronize(None)
+    got = out.to_numpy(svo.HIT_DTYPE, len(cams) * W_IMG * H_IMG)
+    out.free()
+    return got
+
+
+def want_of(ob, O, cams, light, **prm):
+    want = np.concatenate([O.trace_image(c, params=ob.make_params(shadow=True, light_dir=light, **prm), threads=8).reshape(-1) for c in cams])
+    assert not np.any(want["flags"] & 0x8000), "the scene makes the oracle give a ray up"
+    assert np.count_nonzero(want["flags"] & 1) > 500
+    return want
+
+
+def check(svo, ob, O, W, light, what, expect_clear=True):
+    """Prepared explicitly for `light`: clear nodes exist, and one frame and two frames per launch equal the oracle."""
+    cams = cameras(svo)
+    W.prepare_light(light)
+    sdir, clear = W.prepared_light()
+    assert np.array_equal(np.array(sdir, np.float32), np.array(ob_sdir(light), np.float32)), what
+    assert (clear > 0) == expect_clear, (what, clear)
+    want = want_of(ob, O, cams, light)
+    assert_gbuffer_equal(march(svo, W, cams, light), want, f"{what}: two frames per launch")
+    assert_gbuffer_equal(march(svo, W, cams[:1], light), want[:W_IMG * H_IMG], f"{what}: one frame")
+    O.trace_image(cams[0], params=ob.make_params(shadow=True, light_dir=light))
+    assert W.last_ray_count() == O.last_rays, "a retired shadow ray was counted when it was set up"
+    return want, clear
+
+
+def ob_sdir(light):
+    import clearance_model
+    return clearance_model.shadow_dir(light)
+
+
+def scene(svo, ob, name):
+    if name == "open":
+        return pair(svo, ob, **FLAT)
+    if name == "structures":
+        O, W = pair(svo, ob, **FLAT)
+        build_both(svo, ob, O, W, STRUCTURES)
+        return O, W
+    if name == "lake":
+        return pair(svo, ob)                                # terrain with the water plane at y = 6
+    assert name == "mixed"
+    gen = {d: ob.OracleWorld.generate(*DIMS, chunksize=CHUNK, depth=d) for d in (4, 6, 5)}
+    chunks = [gen[d].chunk(i) for i, d in enumerate((4, 6, 5, 6))]
+    W = svo.World.create(chunks, *DIMS, CHUNK)
+    W.upload(0)
+    return ob.OracleWorld.from_chunks(chunks, *DIMS, CHUNK), W
+
+
+@pytest.mark.parametrize("light", sorted(LIGHTS))
+@pytest.mark.parametrize("name", ["open", "structures", "lake", "mixed"])
+def test_records_equal_the_oracle(svo, oracle, name, light):
+    O, W = scene(svo, oracle, name)
+    want, clear = check(svo, oracle, O, W, LIGHTS[light], f"{name}/{light}", expect_clear=light != "up")
+    if name == "structures" and light == "default":
+        lit = (want["flags"] & 7) == 3
+        assert lit.sum() > 200 and ((want["flags"] & 4) != 0).sum() > 100       # both kinds of shadow ray are in the picture
+    W.destroy()
+
+
+def test_first_launch_prepares_an_edit_drops_and_the_call_restores(svo, oracle):
+    O, W = pair(svo, oracle, **FLAT)
+    light, cams = LIGHTS["default"], cameras(svo)
+    assert W.prepared_light() == ((0.0, 0.0, 0.0), 0)
+    before = want_of(oracle, O, cams, light)
+    assert_gbuffer_equal(march(svo, W, cams, light), before, "first launch")
+    sdir, clear = W.prepared_light()
+    assert clear > 0 and sdir[1] > 0.7, "the first shadowed launch of an unchanged world prepares its light"
+    build_both(svo, oracle, O, W, [(0, (64.0, 48.0, 0.0), (128.0, 56.0, 128.0))])      # a slab in the way of the light
+    assert W.prepared_light() == ((0.0, 0.0, 0.0), 0), "an edit drops the bits"
+    after = want_of(oracle, O, cams, light)
+    assert ((after["flags"] & 4) != 0).sum() > ((before["flags"] & 4) != 0).sum() + 50, "the slab's shadow"
+    assert_gbuffer_equal(march(svo, W, cams, light), after, "after the edit, bits dropped")
+    assert W.prepared_light() == ((0.0, 0.0, 0.0), 0), "no launch prepares an edited world on its own"
+    check(svo, oracle, O, W, light, "after the edit, prepared again")
+    W.destroy()
+
+
+def test_another_light_than_the_prepared_one(svo, oracle):
+    O, W = scene(svo, oracle, "structures")
+    a, b, cams = LIGHTS["default"], LIGHTS["oblique"], cameras(svo)
+    check(svo, oracle, O, W, a, "light A")
+    assert_gbuffer_equal(march(svo, W, cams, b), want_of(oracle, O, cams, b), "prepared for A, traced with B")
+    assert W.prepared_light()[0][2] == 0.0                  # still A's
+    check(svo, oracle, O, W, b, "light B")
+    assert_gbuffer_equal(march(svo, W, cams, a), want_of(oracle, O, cams, a), "prepared for B, traced with A")
+    W.prepare_light((1.0, -1.0, 1e-4))                      # a component below 1/64: accepted, never used
+    assert W.prepared_light()[1] == 0
+    W.destroy()
+
+
+def test_paths_that_ignore_the_bits(svo, oracle):
+    O, W = scene(svo, oracle, "lake")
+    light, cams = LIGHTS["default"], cameras(svo)
+    _, clear = check(svo, oracle, O, W, light, "lake")
+    assert clear > 0
+    one = cams[:1]
+    assert_gbuffer_equal(march(svo, W, one, light, light_clearance=False), want_of(oracle, O, one, light), "the off switch")
+    assert_gbuffer_equal(march(svo, W, one, light, semantics=svo.SEMANTICS_GLSL), want_of(oracle, O, one, light, semantics=1), "GLSL semantics")
+    cost = svo.DeviceBuffer(((W_IMG + 7) // 8) * ((H_IMG + 7) // 8) * 2 * 4)
+    assert_gbuffer_equal(march(svo, W, one, light, tile_cost_dev=cost.ptr), want_of(oracle, O, one, light), "tile costs recorded")
+    assert cost.to_numpy(np.uint32, ((W_IMG + 7) // 8) * ((H_IMG + 7) // 8) * 2).reshape(-1, 2)[:, 1].max() > 10, "shadow rays' full step counts"
+    cost.free()
+    o, d = random_rays(np.random.default_rng(5), 6000, (0, 0, 0), (256, 128, 256))
+    prm = oracle.make_params(shadow=True, light_dir=light)
+    assert_gbuffer_equal(W.chunkmarch(o, d, shadow=True, kernel=svo.KERNEL_STACK, light_dir=light), O.trace_rays(o, d, params=prm, threads=8), "a ray list")
+    far = W.chunkmarch(o, d, shadow=True, kernel=svo.KERNEL_STACK, light_dir=light, tmax=1e30)
+    assert_gbuffer_equal(far, O.trace_rays(o, d, params=prm, threads=8), "segments with a far end beyond everything")
+    see = W.draw(one[0], shadow=True, kernel=svo.KERNEL_STACK, light_dir=light, see_through=6)
+    lit = W.draw(one[0], shadow=True, kernel=svo.KERNEL_LITERAL, light_dir=light, see_through=6)
+    assert_gbuffer_equal(see, lit, "the see-through view (stack kernel against the literal kernel)")
+    assert np.count_nonzero(see["material"] == 6) == 0
+    W.destroy()
+
+
+@pytest.mark.parametrize("variant", ["cxxstep", "wide64"])
+def test_variant_builds(variant):
+    lib = os.path.join(ROOT, "octree-raymarcher_amd", "build", f"libsvo_{variant}.so")
+    assert os.path.exists(lib), f"{lib} missing: __graft_entry__.build() makes it"
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), lib, "scenes"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+def model_of_scene(ob, O, light):
+    import clearance_model
+    return clearance_model.model_of(O, DIMS, CHUNK, light)
+
+
+@pytest.mark.parametrize("light", ["default", "oblique", "down"])
+@pytest.mark.parametrize("name", ["open", "structures", "lake", "mixed"])
+def test_the_pass_finds_the_models_clear_nodes(svo, oracle, name, light):
+    """The device sweep and tests/clearance_model.py are two statements of one predicate: over every reachable EMPTY node of the
+    scene - odd level counts with their padded top wide node, child-level terminals that fill 8 slots, mixed depths, seams - they
+    must find the same number clear.  (Both evaluate the same float64 expressions, so no tolerance.)"""
+    O, W = scene(svo, oracle, name)
+    model = model_of_scene(oracle, O, LIGHTS[light])
+    want = sum(1 for ci in range(4) for off, lo, size in model.empty_nodes(ci) if model.is_clear(ci, off, lo, size))
+    W.prepare_light(LIGHTS[light])
+    got = W.prepared_light()[1]
+    print(f"{name}/{light}: device {got} clear nodes, model {want}")
+    assert got == want and want > 0
+    W.destroy()
+
+
+def lane_steps(svo, ob):
+    """(script mode, a timing build) the open scene's first camera with the bits on and off: records against the oracle and the asm
+    step's own count of marching lanes summed over its wave-steps (StepStats.lanes, sixth uint4 of a wave's counters)."""
+    O, W = scene(svo, ob, "open")
+    light, cam = LIGHTS["default"], cameras(svo)[0]
+    W.prepare_light(light)
+    want = want_of(ob, O, [cam], light)
+    waves = 256 * 32
+    out = {}
+    for name, on in (("on", True), ("off", False)):
+        ctr = svo.DeviceBuffer.from_numpy(np.zeros(waves * 6 * 4, np.uint32))
+        buf = svo.DeviceBuffer(W_IMG * H_IMG * 32)
+        W.trace(cam, svo.trace_params(shadow=True, kernel=svo.KERNEL_STACK, light_dir=light, counters_dev=ctr.ptr, light_clearance=on), (0, 0, W_IMG, H_IMG), buf.ptr)
+        svo.lib.svo_stream_synchronize(None)
+        assert_gbuffer_equal(buf.to_numpy(svo.HIT_DTYPE, W_IMG * H_IMG), want, f"timing build, bits {name}")
+        out[name] = int(ctr.to_numpy(np.uint32, waves * 6 * 4).reshape(waves, 6, 4)[:, 5, 1].astype(np.int64).sum())
+        ctr.free(); buf.free()
+    W.destroy()
+    print(f"LANE_STEPS {out['on']} {out['off']}")
+
+
+_removed = {}
+
+
+def removed_by_the_model(svo, ob):
+    """Oracle steps (tree steps + brick cells) that the lit shadow rays of the open scene's first camera take after the step that first
+    locates a clear cell, and all steps of the frame: tests/clearance_model.py re-marches them with the reference's arithmetic."""
+    if not _removed:
+        import clearance_model
+        O = ob.OracleWorld.generate(*DIMS, chunksize=CHUNK, depth=6, **FLAT)
+        light, cam = LIGHTS["default"], cameras(svo)[0]
+        model = clearance_model.model_of(O, DIMS, CHUNK, light)
+        rec, cnt = O.trace_image(cam, params=ob.make_params(shadow=True, light_dir=light), counters=True, threads=8)
+        flags, t = rec["flags"].reshape(-1), rec["t"].reshape(-1)
+        cd = dict(eye=tuple(cam.eye), forward=tuple(cam.forward), right=tuple(cam.right), up=tuple(cam.up),
+                  tan_half_x=cam.tan_half_x, tan_half_y=cam.tan_half_y, width=cam.width, height=cam.height)
+        P, removed = clearance_model.P, 0
+        for k in np.nonzero((flags & 7) == 3)[0]:                              # hit, shadow traced, lit
+            alpha, beta = P.camera_ray(cd, int(k % W_IMG), int(k // W_IMG))
+            r = model.march_lit(P.vadd(alpha, P.vmuls(beta, np.float32(t[k]) - model.eps)))
+            assert not r["hit"]
+            if r["first_clear"]:
+                removed += r["tree_steps"] + r["brick_cells"] - r["first_clear"]
+        _removed.update(removed=removed, total=int(cnt[..., 3].sum() + cnt[..., 1].sum()))
+    return _removed["removed"], _removed["total"]
+
+
+@pytest.mark.parametrize("variant", ["timing", "timing64"])
+def test_shadow_lanes_do_retire(svo, oracle, variant):
+    """No comparison above notices a retire that never fires.  The timing builds count the asm step's marching lanes per wave-step:
+    with the bits on, the open scene must take clearly fewer lane-steps than with SVO_SHADOW_NO_CLEARANCE, on both addressing variants.
+    The bound comes from the model, not from the kernel: every oracle step a lit ray takes after its first clear cell is a lane-step the
+    kernel takes with the bits off and not with them on.  The kernel may take an oracle step in closed form (creep block) or skip a
+    brick that is bound to miss, so half of the model's figure is asked for."""
+    removed, total = removed_by_the_model(svo, oracle)
+    assert removed > 0.05 * total, (removed, total)
+    lib = os.path.join(ROOT, "octree-raymarcher_amd", "build", f"libsvo_{variant}.so")
+    assert os.path.exists(lib), f"{lib} missing: __graft_entry__.build() makes it"
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), lib, "lanes"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    on, off = [int(v) for v in r.stdout.split("LANE_STEPS")[1].split()[:2]]
+    print(f"{variant}: {off} lane-steps with the bits off, {on} with them on ({off - on} fewer); the model removes {removed} of {total} oracle steps")
+    assert off - on >= removed // 2, (on, off, removed)
+
+
+if __name__ == "__main__":
+    import variant_check
+    svo_, ob_ = variant_check.load(os.path.abspath(sys.argv[1]))
+    if svo_.device_count() < 1:
+        print("no HIP device"); sys.exit(3)
+    if sys.argv[2] == "lanes":
+        lane_steps(svo_, ob_)
+        sys.exit(0)
+    for name_ in ("structures", "lake"):
+        for light_ in ("default", "oblique"):
+            O_, W_ = scene(svo_, ob_, name_)
+            check(svo_, ob_, O_, W_, LIGHTS[light_], f"{name_}/{light_}")
+            W_.destroy()
+    print("light clearance: structures and lake under two lights equal the oracle")
