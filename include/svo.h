@@ -117,7 +117,8 @@ extern "C" {
                                           svo_hit_ao and svo_shade_ao,
                                           svo_trace_reflections, svo_shade_reflections and svo_mirror,
                                           svo_world_prepare_light, svo_world_prepared_light and SVO_SHADOW_NO_CLEARANCE (a bit of
-                                          svo_trace_params.shadow, which was any non-zero value: such callers keep their results) */
+                                          svo_trace_params.shadow, which was any non-zero value: such callers keep their results),
+                                          svo_world_prepared_bricks and SVO_SHADOW_NO_BRICK_CLEARANCE (another such bit) */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -208,7 +209,8 @@ typedef struct svo_trace_params {
     int32_t  max_twig_steps;        /* 0 = 1000   (src/Traverse.cpp:54) */
     int32_t  shadow;                /* !=0: one shadow ray per primary hit toward -light_dir.  Bit SVO_SHADOW_NO_CLEARANCE (2 or 3 instead
                                        of 1): the same shadow rays, never ended early by svo_world_prepare_light's bits - the same records,
-                                       more steps; for A/B runs */
+                                       more steps; for A/B runs.  Bit SVO_SHADOW_NO_BRICK_CLEARANCE (5 instead of 1): the bits are used, the
+                                       per-brick flags that settle a lit shadow ray at its primary hit are not */
     float    light_dir[3];          /* directionalLight.direction, default normalize(1,-1,0) (src/Main.cpp:116) */
     int32_t  kernel;                /* SVO_KERNEL_* */
     int32_t  tiles_per_wave;        /* SVO_KERNEL_STACK launch shape: every persistent wave is handed at least this
@@ -257,7 +259,7 @@ typedef struct svo_trace_params {
                                        (svo_world_info does not count it; at most 1.4 GB at C3 size); every change to the pools drops it */
 } svo_trace_params;
 enum { SVO_NORMAL_CUBE = 0, SVO_NORMAL_FACE = 1 };
-enum { SVO_SHADOW_NO_CLEARANCE = 2 };
+enum { SVO_SHADOW_NO_CLEARANCE = 2, SVO_SHADOW_NO_BRICK_CLEARANCE = 4 };
 enum { SVO_SEMANTICS_CPU = 0, SVO_SEMANTICS_GLSL = 1 };
 
 /* G-buffer record, 32 bytes per pixel / per ray. */
@@ -1014,12 +1016,22 @@ int svo_trace_last_ray_count(svo_world *, void *stream, uint64_t *rays);
  *   svo_world_prepared_light  the prepared shadow direction, normalize(-light_dir) ((0,0,0) if none is), and the number of EMPTY reference
  *                             nodes found clear (0 if the direction is never used); waits for `stream` and for the pass, whichever stream
  *                             it was issued on.
+ *   svo_world_prepared_bricks the number of bricks that carry the clear flag (0 if the flags are never used).  Behind the sweep the pass
+ *                             decides one flag per brick, bit 15 of its 16-bit material word: every EMPTY cell of the brick has a clear way
+ *                             to the light, bricks seen cell by cell.  A primary hit in a cell of such a brick whose shadow
+ *                             origin lies in an empty cell of the same brick is lit without a step of its shadow ray; the record and
+ *                             svo_trace_last_ray_count are what they were.  Same lifecycle and the same launches as the bits; in addition
+ *                             the world must have no negative coordinate and no voxel below the float spacing at its largest coordinate,
+ *                             and a brick of several materials, or of one material of 0x8000 and above, carries no flag.
+ *                             SVO_SHADOW_NO_BRICK_CLEARANCE switches the flags off alone, SVO_SHADOW_NO_CLEARANCE both.
  * The pass keeps 16 bytes of scratch per wide node (41 MB on the 4x1x4 depth-12 world; svo_world_info does not count it) until the next change
  * to the pools, so that a second light costs no allocation.  A launch prepares a world on its own only while wide entries x chunks <= 1e10
- * (four times that world: a few seconds); larger worlds are prepared by the call alone.
+ * (four times that world: a few seconds for the bits; the brick flags take seventeen times as long, 15 s on that world and 0.8 s at depth 10);
+ * larger worlds are prepared by the call alone.
  * SVO_ERR_INVALID_ARG (NULL world / outputs), SVO_ERR_NOT_UPLOADED, SVO_ERR_OUT_OF_MEMORY (the scratch). */
 int svo_world_prepare_light(svo_world *, const float light_dir[3], void *stream);
 int svo_world_prepared_light(svo_world *, void *stream, float shadow_dir[3], uint64_t *clear_nodes);
+int svo_world_prepared_bricks(svo_world *, void *stream, uint64_t *flagged);
 
 /* ---- small device helpers so that C/C++ callers need no HIP headers --------------------- */
 int   svo_device_count(void);

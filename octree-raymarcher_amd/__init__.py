@@ -63,6 +63,7 @@ HIT_FLAG, SHADOW_TRACED, SHADOWED, FACE_NORMAL, SEE_THROUGH, ERR_FLAG = 1, 2, 4,
 LOCAL_SHADOWS, SHADOWED_POINT, SHADOWED_SPOT = 1 << 5, 1 << 6, 1 << 7     # svo_trace_local_shadows
 NORMAL_CUBE, NORMAL_FACE = 0, 1
 SHADOW_NO_CLEARANCE = 2          # bit of TraceParams.shadow: shadow rays as ever, World.prepare_light's bits ignored
+SHADOW_NO_BRICK_CLEARANCE = 4    # bit of TraceParams.shadow: the bits are used, the per-brick flags that settle a lit shadow ray at its hit are not
 SEMANTICS_CPU, SEMANTICS_GLSL = 0, 1
 CELL_NONE = 0xFF
 SKY_LINEAR, SKY_NEAREST = 0, 1                           # svo_sky.filter
@@ -200,7 +201,7 @@ ABI_SYMBOLS = [
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_edit_cube", "svo_world_edit_ball", "svo_world_edit_ball_all", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_cursor_place", "svo_shade_boxes", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_shadowmap_fit", "svo_shadowmap_render", "svo_shadowmap_apply", "svo_hit_ao", "svo_shade_ao",
-    "svo_trace_reflections", "svo_shade_reflections", "svo_world_prepare_light", "svo_world_prepared_light",
+    "svo_trace_reflections", "svo_shade_reflections", "svo_world_prepare_light", "svo_world_prepared_light", "svo_world_prepared_bricks",
     "svo_device_count", "svo_device_alloc", "svo_device_free", "svo_device_cache_trim", "svo_memcpy_h2d", "svo_memcpy_d2h",
     "svo_stream_synchronize", "svo_last_error", "svo_abi_version",
 ]
@@ -269,6 +270,7 @@ lib.svo_shade_boxes.argtypes = [C.POINTER(Camera), _P, C.c_int, C.c_float, C.c_f
 lib.svo_trace_last_ray_count.argtypes = [_P, _P, C.POINTER(C.c_uint64)]
 lib.svo_world_prepare_light.argtypes = [_P, C.POINTER(C.c_float), _P]
 lib.svo_world_prepared_light.argtypes = [_P, _P, C.POINTER(C.c_float), C.POINTER(C.c_uint64)]
+lib.svo_world_prepared_bricks.argtypes = [_P, _P, C.POINTER(C.c_uint64)]
 lib.svo_device_count.restype = C.c_int
 lib.svo_device_alloc.argtypes = [C.c_size_t]
 lib.svo_device_alloc.restype = _P
@@ -367,7 +369,7 @@ def c5_scene() -> dict:
 def trace_params(shadow: bool = False, kernel: int = KERNEL_AUTO, light_dir=(1.0, -1.0, 0.0), eps: float = 0.0,
                  caps=(0, 0, 0), counters_dev: Optional[int] = None, tiles_per_wave: int = 0, normal_mode: int = 0,
                  tile_cost_dev: Optional[int] = None, tile_order_dev: Optional[int] = None, launches_in_flight: int = 0,
-                 semantics: int = 0, see_through: int = 0, light_clearance: bool = True) -> TraceParams:
+                 semantics: int = 0, see_through: int = 0, light_clearance: bool = True, brick_clearance: bool = True) -> TraceParams:
     """semantics: SEMANTICS_CPU (src/Traverse.cpp) / SEMANTICS_GLSL (shaders/Chunkmarch.glsl); eps / caps 0 = that twin's own constants.
     see_through: a material (1..0xFFFF) every ray marches through as if it were empty; 0 = off."""
     p = TraceParams()
@@ -377,6 +379,8 @@ def trace_params(shadow: bool = False, kernel: int = KERNEL_AUTO, light_dir=(1.0
     p.eps = eps
     p.max_chunk_steps, p.max_tree_steps, p.max_twig_steps = caps
     p.shadow = (1 if light_clearance else 1 | SHADOW_NO_CLEARANCE) if shadow else 0    # (light_clearance=False: World.prepare_light's bits are ignored)
+    if shadow and not brick_clearance:
+        p.shadow |= SHADOW_NO_BRICK_CLEARANCE                                           # (... =False: the bits are used, the brick flags are not)
     p.light_dir[:] = [float(x) for x in light_dir]
     p.kernel = kernel
     p.counters_dev = counters_dev
@@ -810,6 +814,12 @@ class World:
         sdir, n = (C.c_float * 3)(), C.c_uint64()
         _check(lib.svo_world_prepared_light(self._h, stream, sdir, C.byref(n)), "svo_world_prepared_light")
         return tuple(sdir), n.value
+
+    def prepared_bricks(self, stream: int = 0) -> int:
+        """svo_world_prepared_bricks: bricks that carry the clear flag (every empty cell has a clear way to the prepared light)."""
+        n = C.c_uint64()
+        _check(lib.svo_world_prepared_bricks(self._h, stream, C.byref(n)), "svo_world_prepared_bricks")
+        return n.value
 
     def last_ray_count(self, stream: int = 0) -> int:
         n = C.c_uint64()

@@ -45,7 +45,9 @@ namespace svo {
 // bit w of mask[b] = (brick b cell w != 0).  One thread per 16-byte eighth of a brick (8 cells -> one mask byte):
 // 16 B per lane, fully coalesced reads of the twig pool, byte stores into the little-endian uint64 masks.  The eight lanes of
 // a brick also agree on bmat[b]: the brick's material if all its non-empty cells hold the same one (what grow() produces), 0 for an
-// empty brick, 0xFFFF if it holds several (the hit block then reads the cell itself).
+// empty brick, 0xFFFF if it holds several (the hit block then reads the cell itself).  Bit 15 is the brick's clear flag
+// (light_clearance.hip.h k_clear_bricks), written 0 here: a rebuilt chunk has none; a brick of one material of 0x8000 and above is
+// stored as 0xFFFF, which is right and only slower for such a brick.
 __global__ __launch_bounds__(256) void k_brick_masks(const uint16_t *twig, uint64_t *mask, uint16_t *bmat, uint64_t first, uint64_t count)
 {
     const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;      // eighth-of-brick index
@@ -69,7 +71,7 @@ __global__ __launch_bounds__(256) void k_brick_masks(const uint16_t *twig, uint6
     }
     if (!live) return;
     reinterpret_cast<uint8_t *>(mask + first)[i] = (uint8_t)bits;
-    if ((i & 7u) == 0u) bmat[first + (i >> 3)] = (uint16_t)(hi == 0u ? 0u : (lo == hi ? lo : 0xFFFFu));
+    if ((i & 7u) == 0u) bmat[first + (i >> 3)] = (uint16_t)(hi == 0u ? 0u : (lo == hi && lo < BMAT_CLEAR_BIT ? lo : BMAT_SEVERAL));
 }
 
 // svo_tile_order: key = primary + shadow step maxima of the tile (saturating), value = the tile's index
@@ -160,7 +162,7 @@ static void drop_clearance(svo_world &w)
 {
     Hbm &d = *w.hbm;
     if (d.clear_place.p) { (void)hipDeviceSynchronize(); d.clear_place = Pooled<uint4>(); }     // (the pass's scratch: 16 bytes per wide node)
-    d.clear_state = Hbm::CLEAR_DROPPED; d.clear_usable = false;
+    d.clear_state = Hbm::CLEAR_DROPPED; d.clear_usable = d.clear_bricks_usable = false;     // (the flags in bmat stay and are ignored)
 }
 
 int release_device(svo_world &w, bool keep_builder)
@@ -959,7 +961,8 @@ static int use_view(svo_world *w, uint32_t m, TraceArgs &A, hipStream_t s)
 constexpr double CLEAR_S_MIN = 1.0 / 64.0;
 // The sweep looks at every chunk's root per EMPTY entry: its cost grows with entries x chunks.  The 4x1x4 depth-12 world (163 M entries,
 // 16 chunks: 2.6e9) takes 0.86 s (profiles/light_clearance_ab.txt); a launch prepares a world on its own up to four times that product,
-// a few seconds by proportion.  Larger worlds - the 10x1x10 one of scripts/bigworld_check.py is at 1.3e11 - are prepared on request only.
+// a few seconds by proportion - and seventeen times that with the brick flags behind it (k_clear_bricks: 14.9 s on that world, 0.8 s at
+// depth 10; DESIGN.md 6u "Not done").  Larger worlds - the 10x1x10 one of scripts/bigworld_check.py is at 1.3e11 - are prepared on request only.
 constexpr double CLEAR_AUTO_WORK = 1.0e10;
 
 static float clear_spacing(const svo_world &w)
@@ -982,7 +985,7 @@ static bool eps_is_pow2(float eps)
 static int prepare_light(svo_world &w, const float sdir[3], hipStream_t s)
 {
     Hbm &d = *w.hbm;
-    d.clear_usable = false;
+    d.clear_usable = d.clear_bricks_usable = false;
     if (!w.wide_ok || w.wide_pool_len == 0) return SVO_OK;              // the literal kernel marches this world: nothing reads the bits
     HIP_TRY(hipSetDevice(w.device));
     bool premises = true;
@@ -996,7 +999,7 @@ static int prepare_light(svo_world &w, const float sdir[3], hipStream_t s)
         if (d.clear_place.p) HIP_TRY(hipDeviceSynchronize());
         if (d.clear_place.alloc(nodes, w.device) != hipSuccess) { set_error("svo_world_prepare_light: hipMalloc failed"); return SVO_ERR_OUT_OF_MEMORY; }
     }
-    if (const int rc = d.clear_count.reserve(1, false, nullptr)) return rc;
+    if (const int rc = d.clear_count.reserve(2, false, nullptr)) return rc;
     for (Event &e : d.work_done) if (e.e) if (const int rc = e.wait(s)) return rc;
     if (d.clear_built.e) if (const int rc = d.clear_built.wait(s)) return rc;
     const double u = (double)clear_spacing(w);
@@ -1007,16 +1010,24 @@ static int prepare_light(svo_world &w, const float sdir[3], hipStream_t s)
     K.d1 = 4.0 * u;
     K.d2 = (8.0 / CLEAR_S_MIN + 6.0 + 4.0 * (double)(w.width + w.height + w.depth + 2)) * u;
     K.clear_nodes = d.clear_count.p;
+    // the brick flags ask more of the world: no negative coordinate and no voxel below u, so that a sample's cell
+    // contains it exactly (exact_geometry has the power-of-two chunk size); where that fails every flag is written 0
+    bool bricks = true;
+    for (int a = 0; a < 3; ++a) bricks &= w.chunkcoordmin[a] >= 0;
+    for (const ChunkPools &c : w.chunks) bricks &= std::ldexp((double)w.chunksize, -(int)c.depth) >= u;
+    K.mask = d.mask.p; K.bmat = d.bmat.p; K.clear_bricks = d.clear_count.p + 1; K.brick_premises = bricks ? 1 : 0;
     HIP_TRY(hipMemsetAsync(d.clear_place.p, 0xFF, nodes * sizeof(uint4), s));
-    HIP_TRY(hipMemsetAsync(d.clear_count.p, 0, sizeof(unsigned long long), s));
+    HIP_TRY(hipMemsetAsync(d.clear_count.p, 0, 2 * sizeof(unsigned long long), s));
     int rc = launch_per_element("svo_world_prepare_light", K.n_chunks, s, k_clear_seed, K);
     const int nw_max = w.max_levels ? (w.max_levels + 1) / 2 : 1;
     for (int r = 0; rc == SVO_OK && r + 1 < nw_max; ++r) rc = launch_per_element("svo_world_prepare_light", (int64_t)nodes * 64, s, k_clear_boxes, K, (uint32_t)r);
     if (rc == SVO_OK) rc = launch_per_element("svo_world_prepare_light", (int64_t)nodes * 64, s, k_clear_sweep, K);
+    if (rc == SVO_OK) rc = launch_per_element("svo_world_prepare_light", (int64_t)nodes * 64, s, k_clear_bricks, K);
     if (rc != SVO_OK) return rc;
     if ((rc = d.clear_built.record(s)) != SVO_OK) return rc;
     d.clear_state = Hbm::CLEAR_READY;
     d.clear_usable = true;
+    d.clear_bricks_usable = bricks;
     d.clear_eps = 2.0f * (float)u;                                      // the smallest eps the bits hold for
     return SVO_OK;
 }
@@ -1034,7 +1045,8 @@ static int use_light_clearance(svo_world *w, const svo_trace_params *prm, TraceA
     if (d.clear_state != Hbm::CLEAR_READY || !d.clear_usable) return SVO_OK;
     if (std::memcmp(d.clear_sdir, A.sdir, sizeof d.clear_sdir) != 0 || !eps_is_pow2(A.eps) || A.eps < d.clear_eps) return SVO_OK;
     if (const int rc = d.clear_built.wait(s)) return rc;
-    A.light_clear = 1;
+    A.light_clear = LIGHT_CLEAR_NODES;
+    if (d.clear_bricks_usable && !(prm && (prm->shadow & SVO_SHADOW_NO_BRICK_CLEARANCE))) A.light_clear |= LIGHT_CLEAR_BRICKS;
     return SVO_OK;
 }
 
@@ -1534,6 +1546,22 @@ int svo_world_prepared_light(svo_world *w, void *stream, float shadow_dir[3], ui
     unsigned long long v = 0;
     HIP_TRY(hipMemcpy(&v, d.clear_count.p, sizeof v, hipMemcpyDeviceToHost));
     *clear_nodes = v;
+    return SVO_OK;
+}
+
+int svo_world_prepared_bricks(svo_world *w, void *stream, uint64_t *flagged)
+{
+    if (!w || !flagged) return SVO_ERR_INVALID_ARG;
+    if (w->device < 0) { set_error("svo_world_prepared_bricks: world is not uploaded"); return SVO_ERR_NOT_UPLOADED; }
+    const Hbm &d = *w->hbm;
+    *flagged = 0;
+    if (d.clear_state != Hbm::CLEAR_READY || !d.clear_usable || !d.clear_bricks_usable) return SVO_OK;
+    HIP_TRY(hipSetDevice(w->device));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    if (d.clear_built.e) HIP_TRY(hipEventSynchronize(d.clear_built.e));    // (the pass may have been issued on another stream)
+    unsigned long long v = 0;
+    HIP_TRY(hipMemcpy(&v, d.clear_count.p + 1, sizeof v, hipMemcpyDeviceToHost));
+    *flagged = v;
     return SVO_OK;
 }
 

@@ -183,7 +183,7 @@ struct WideLayout { uint64_t next = 0, flag = 0, rank = 0, wref = 0, wide = 0, w
 struct Hbm {
     DevBuf<DevChunk> chunks; DevBuf<DevWide> wchunks;       // the chunk tables (host mirrors: svo_world::table / wtable)
     Pooled<uint32_t> tree; Pooled<uint64_t> mask;
-    Pooled<uint16_t> twig, bmat;                            // bmat: per brick its one material / 0 (empty) / 0xFFFF (several), written with the masks
+    Pooled<uint16_t> twig, bmat;                            // bmat: per brick its one material / 0 (empty) / 0xFFFF (several), written with the masks; bit 15: the clear flag
     Pooled<uint32_t> wide, wbase;                           // wide tree of every chunk (wide_tree.hip.h) and, per wide node, the reference blocks it expands
     Pooled<uint32_t> wscratch; WideLayout wlayout;          // the wide builder's scratch and how it is laid out
     Pinned<uint32_t> wide_tail;                             // the wide builder's per-level read-back
@@ -212,6 +212,7 @@ struct Hbm {
     enum { CLEAR_FRESH = 0, CLEAR_READY = 1, CLEAR_DROPPED = 2 };
     int clear_state = CLEAR_FRESH;
     bool clear_usable = false;                              // the prepared direction and the world meet the rule's premises
+    bool clear_bricks_usable = false;                       // ... and those of the per-brick flags in bmat's bit 15 (k_clear_bricks) as well
     float clear_sdir[3] = { 0.0f, 0.0f, 0.0f }; float clear_eps = 0.0f;
     Pooled<uint4> clear_place; DevBuf<unsigned long long> clear_count;
     Event clear_built;                                      // launches that use the bits wait for it

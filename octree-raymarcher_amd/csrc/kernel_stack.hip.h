@@ -820,7 +820,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
             const uint32_t hitc = (uint32_t)cnt;                    // which brick cell (or SVO_CELL_NONE: a LEAF)
             V3 vlo;
             float vsize;
-            uint32_t material;
+            uint32_t material;                                      // (bit 16: the hit brick's clear flag, which store_hit cuts off)
             if (hitc == SVO_CELL_NONE) {                            // LEAF node: frame = tree level (Blo = clo, res = cell)
                 const int low = (1 << (levels - plev)) - 1;
                 vlo = mk(Blo.x + (float)(pux & ~low) * res, Blo.y + (float)(puy & ~low) * res, Blo.z + (float)(puz & ~low) * res);
@@ -832,8 +832,9 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
                 // most bricks hold one material (grow() fills a brick with its node's): it is kept per brick next to the masks, 64
                 // bricks to a cache line; only a brick of several materials (0xFFFF) is read itself, 128 B for one cell
                 const unsigned long long brick = (unsigned long long)twig_off + (word & WIDE_PAYLOAD);
-                material = A.bmat[brick];
-                if (material == 0xFFFFu) material = A.twig[brick * TWIG_WORDS + hitc];
+                // (bit 15 of the word is the brick's clear flag, light_clearance.hip.h; 0xFFFF carries none)
+                const uint32_t bw = A.bmat[brick];
+                material = bw == 0xFFFFu ? A.twig[brick * TWIG_WORDS + hitc] : (bw & 0x7FFFu) | ((bw & 0x8000u) << 1);
             }
             const V3 point = alpha + beta * (tw - eps);
             const bool face = A.normal_mode == SVO_NORMAL_FACE;
@@ -849,7 +850,21 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
                 tw = 0.0f; cw = 0; guard = 0; creepn = 0;
                 bool hit = true;
                 if (!inside(alpha, wlo, whi)) tw = (GLSL ? enter_glsl(alpha, g, wlo, whi, hit) : enter(alpha, beta, wlo, whi, hit)) + eps;
-                mode = hit ? M_WORLD : M_DONE;          // a shadow ray that misses the world box stays "lit"
+                // Every empty cell of the hit brick has a clear way to the light (its flag), and the shadow ray's first sample - the
+                // origin itself: tw = 0, t = 0, p = alpha - is located in one of them, by the brick step's own arithmetic (the frame
+                // still is the brick's: Blo its box, res its voxel; bmask its cells): inside the box, a cell of 0..3 per axis (a
+                // difference rounded up to the far face gives 4), that cell empty.  The record is final as store_hit wrote it.
+                // (read from the arguments here, as A.shadow is: a wave-uniform bool kept from the kernel's top costs a scalar spill; the
+                // shader's twin and bounded rays never use the flags: no code in their instantiations)
+                bool settled = !GLSL && !SEG && (A.light_clear & LIGHT_CLEAR_BRICKS) != 0 && (material >> 16) != 0u;
+                if (settled) {
+                    const float inv_res = recip_pow2(res);
+                    const float fx = (point.x - Blo.x) * inv_res, fy = (point.y - Blo.y) * inv_res, fz = (point.z - Blo.z) * inv_res;
+                    const uint32_t ux = (uint32_t)(int)fx, uy = (uint32_t)(int)fy, uz = (uint32_t)(int)fz;
+                    settled = (fx >= 0.0f) & (fy >= 0.0f) & (fz >= 0.0f) & ((ux | uy | uz) <= 3u);
+                    settled = settled && ((bmask >> ((uz * 16u + uy * 4u + ux) & 63u)) & 1ull) == 0ull;
+                }
+                mode = hit && !settled ? M_WORLD : M_DONE;  // a shadow ray that misses the world box stays "lit"
                 rays_marched++;
             }
         } }

@@ -16,6 +16,11 @@
 // its low corner, wide level, chunk) level by level - a wide node's index says nothing about where it sits -, k_clear_sweep decides
 // every EMPTY terminal entry and writes WIDE_CLEAR_BIT.  All slots of one reference node get the same answer: a child-level
 // terminal fills 8 slots, its first slot decides for all of them.
+//
+// Behind the sweep, k_clear_bricks decides one flag per brick (bit 15 of its bmat word, BMAT_CLEAR_BIT): every EMPTY
+// cell of the brick is clear under the same rule with the cell in the place of C and with bricks seen cell by cell - occupied is
+// every LEAF node and every occupied cell of every brick, the brick's own among them.  The stack kernel's hit block settles a
+// shadow ray whose origin lies in an empty cell of such a brick without a step.  tests/brick_clearance_model.py is its model.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,7 +38,14 @@ struct ClearArgs {
     double s[3];                // the shadow direction, float32 values
     double d1, d2;
     unsigned long long *clear_nodes;    // count of reference nodes found clear
+    // k_clear_bricks
+    const uint64_t *mask;               // the mask pool: bit w of mask[b] = cell w of brick b is occupied
+    uint16_t *bmat;                     // per brick: material | BMAT_CLEAR_BIT (0xFFFF carries no flag)
+    unsigned long long *clear_bricks;   // count of bricks flagged (clear_nodes + 1)
+    int32_t brick_premises;             // the premises of 6u hold: otherwise every flag is written 0
 };
+
+constexpr uint32_t BMAT_CLEAR_BIT = 0x8000u, BMAT_SEVERAL = 0xFFFFu;
 
 constexpr uint32_t CLEAR_NO_PLACE = 0xFFFFFFFFu;
 constexpr int CLEAR_MAX_WIDE_LEVELS = (WIDE_MAX_LEVELS + 1) / 2;
@@ -107,7 +119,9 @@ __device__ __forceinline__ bool clear_meets(const ClearArgs &K, const ClearCell 
     return clear_prism(K, C, lo, hi, K.d2);
 }
 
-// depth-first walk of chunk j's wide tree: does a LEAF or TWIG entry's box meet the region of C?
+// depth-first walk of chunk j's wide tree: does a LEAF or TWIG entry's box meet the region of C?  CELLS: a TWIG entry counts by its
+// occupied cells, each a box of its own
+template <bool CELLS = false>
 __device__ bool clear_occupied(const ClearArgs &K, const ClearCell &C, int j, bool own)
 {
     const DevWide ch = K.wchunks[j];
@@ -138,6 +152,23 @@ __device__ bool clear_occupied(const ClearArgs &K, const ClearCell &C, int j, bo
         const double edge = res * (double)span;
         for (int a = 0; a < 3; ++a) { lo[a] = base[a] + (double)(c[a] & ~(span - 1u)) * res; hi[a] = lo[a] + edge; }
         if (!clear_meets(K, C, own, inner_lo, inner_hi, lo, hi)) continue;
+        if constexpr (CELLS) {
+            if (type == TWIG) {
+                if (((c[0] | c[1] | c[2]) & (span - 1u)) != 0u) continue;   // (a node that fills several slots: its first one looks at the cells)
+                unsigned long long m = K.mask[ch.twig_off + (word & WIDE_PAYLOAD_MASK)];
+                const double leaf = edge * 0.25, blo[3] = { lo[0], lo[1], lo[2] };
+                bool met = false;
+                while (m != 0ull && !met) {
+                    const uint32_t w = (uint32_t)__ffsll((long long)m) - 1u;
+                    m &= m - 1ull;
+                    lo[0] = blo[0] + leaf * (double)(w & 3u); lo[1] = blo[1] + leaf * (double)((w >> 2) & 3u); lo[2] = blo[2] + leaf * (double)(w >> 4);
+                    for (int a = 0; a < 3; ++a) hi[a] = lo[a] + leaf;
+                    met = clear_meets(K, C, own, inner_lo, inner_hi, lo, hi);
+                }
+                if (met) return true;
+                continue;
+            }
+        }
         if (type != BRANCH || k + 1 >= nw) return true;
         ++k;
         node[k] = word & WIDE_PAYLOAD_MASK; cur[k] = 0u; bx[k] = c[0]; by[k] = c[1]; bz[k] = c[2];
@@ -181,6 +212,54 @@ __global__ __launch_bounds__(256) void k_clear_sweep(ClearArgs K)
     if (level == 0 && !child && slot != 0u) clear = false;              // (a chunk that is one EMPTY node fills all 64 slots: counted once)
     const unsigned long long voted = __ballot(clear);                   // (one atomic per wave)
     if (clear && (int)(threadIdx.x & 63u) == __ffsll((long long)voted) - 1) atomicAdd(K.clear_nodes, (unsigned long long)__popcll(voted));
+}
+
+// one wave per wide node: its TWIG entries one after the other, one lane per cell of the brick, a vote at the end
+__global__ __launch_bounds__(256) void k_clear_bricks(ClearArgs K)
+{
+    const uint64_t wn = ((uint64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
+    if (wn >= K.pool_nodes) return;
+    const uint4 b = K.place[wn];
+    if (b.w == CLEAR_NO_PLACE) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const int own = (int)(b.w >> 4), k = (int)(b.w & 15u);
+    const DevWide ch = K.wchunks[own];
+    const int levels = (int)ch.levels, nw = levels ? (levels + 1) >> 1 : 1;
+    const int sh = 2 * (nw - 1 - k);
+    const double res = K.chunksize / (double)(1u << levels);
+    unsigned long long twigs = __ballot(node_type(K.wide[wn * 64u + lane]) == TWIG);
+    unsigned flagged = 0;
+    while (twigs != 0ull) {
+        const uint32_t slot = (uint32_t)__ffsll((long long)twigs) - 1u;
+        twigs &= twigs - 1ull;
+        const uint32_t word = K.wide[wn * 64u + slot];
+        const uint32_t c[3] = { b.x | ((slot & 3u) << sh), b.y | (((slot >> 2) & 3u) << sh), b.z | ((slot >> 4) << sh) };
+        if (((c[0] | c[1] | c[2]) >> levels) != 0u) continue;
+        const int level = (int)((word >> WIDE_LEVEL_SHIFT) & ((1u << WIDE_LEVEL_BITS) - 1u));
+        if (level > levels) continue;
+        const uint32_t span = 1u << (levels - level);
+        if (((c[0] | c[1] | c[2]) & (span - 1u)) != 0u) continue;          // a node that fills 8 (or all 64) slots: decided in its first
+        const uint64_t brick = ch.twig_off + (word & WIDE_PAYLOAD_MASK);
+        bool clear = K.brick_premises != 0;
+        if (clear && ((K.mask[brick] >> lane) & 1ull) == 0ull) {            // an EMPTY cell: the rule of the sweep, the cell in the place of C
+            const double leaf = res * (double)span * 0.25;
+            ClearCell C;
+            const uint32_t w3[3] = { lane & 3u, (lane >> 2) & 3u, lane >> 4 };
+            for (int a = 0; a < 3; ++a) { C.lo[a] = (double)ch.bmin[a] + (double)c[a] * res + leaf * (double)w3[a]; C.hi[a] = C.lo[a] + leaf; }
+            clear = !clear_occupied<true>(K, C, own, true);
+            for (int j = 0; clear && j < K.n_chunks; ++j)
+                if (j != own) clear = !clear_occupied<true>(K, C, j, false);
+        }
+        const bool all_clear = __ballot(!clear) == 0ull;
+        if (lane == 0u) {
+            const uint32_t m = K.bmat[brick];
+            if (m != BMAT_SEVERAL) {
+                K.bmat[brick] = (uint16_t)((m & ~BMAT_CLEAR_BIT) | (all_clear ? BMAT_CLEAR_BIT : 0u));
+                flagged += all_clear;
+            }
+        }
+    }
+    if (flagged) atomicAdd(K.clear_bricks, (unsigned long long)flagged);
 }
 
 } // namespace svo

@@ -81,7 +81,7 @@ struct TraceArgs {
     const DevWide  *wchunks;    // stack kernel: chunk table over the wide pool
     const uint32_t *wide;       // wide pool: 64 entries per wide node (wide_tree.hip.h)
     const uint32_t *wbase;      // per wide node: reference index of the child block and of the 8 grandchild blocks it expands (for svo_hit.node)
-    const uint16_t *bmat;       // per brick: its one material, 0 if empty, 0xFFFF if it holds several
+    const uint16_t *bmat;       // per brick: its one material (below 0x8000), 0 if empty, 0xFFFF if it holds several; bit 15: every empty cell of the brick has a clear way to the prepared light
     const uint32_t *tree;
     const uint16_t *twig;
     const uint64_t *mask;
@@ -117,7 +117,8 @@ struct TraceArgs {
     uint32_t *tile_cost;        // optional [nframes][ntiles][2]: largest primary / shadow step count per tile (stack kernel)
     const uint32_t *tile_order; // optional [ntiles]: the order in which a frame's tiles are handed out (stack kernel)
     const float *tmax;          // svo_trace_segments: [n] far end per ray (list mode; read by the bounded instantiations only).  Last but one: no other field moves
-    int32_t  light_clear;       // stack kernel: a shadow ray retires at an EMPTY entry that carries WIDE_CLEAR_BIT (device.hip use_light_clearance decides)
+    int32_t  light_clear;       // stack kernel, LIGHT_CLEAR_*: a shadow ray retires at an EMPTY entry that carries WIDE_CLEAR_BIT / is settled at its primary hit by the brick's flag (device.hip use_light_clearance decides)
 };
+enum : int32_t { LIGHT_CLEAR_NODES = 1, LIGHT_CLEAR_BRICKS = 2 };
 
 } // namespace svo

@@ -190,6 +190,9 @@ public:
     // that has not changed since its upload is prepared by its first draw(shadow = true) on its own; after modify() or any other edit only
     // this call brings the bits back.  Asynchronous on `stream`.
     void prepare_light(const float light_dir[3] = nullptr, void *stream = nullptr) { check(svo_world_prepare_light(world_, light_dir, stream), "World::prepare_light"); }
+    // ... and, with it, for every brick whether all its empty cells are (svo_world_prepared_bricks counts them): a hit whose shadow ray would
+    // start in an empty cell of such a brick is lit without a step.  Waits for `stream` and for the pass.
+    uint64_t prepared_bricks(void *stream = nullptr) { uint64_t n = 0; check(svo_world_prepared_bricks(world_, stream, &n), "World::prepared_bricks"); return n; }
 
     // Shadows from the point light and the spotlight on a G-buffer that draw() filled with the same camera, shadow flag and light
     // direction (svo_trace_local_shadows): one flag per light, a null position leaves that light with the directional light's term.

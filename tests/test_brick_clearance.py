@@ -1,0 +1,258 @@
+"""The per-brick clear flag on the device (k_clear_bricks of csrc/light_clearance.hip.h, the hit block of kernel_stack.hip.h):
+a lit shadow ray whose origin lies in an empty cell of the brick its primary ray hit is settled at that hit, without a step, when the
+brick's every empty cell has a clear way to the light - and every record still equals the oracle's bit for bit, whatever the light,
+across chunk seams, in bricks of several materials or of a material that leaves the flag no room, after edits, with a light other
+than the prepared one, under both switches and on every path that has to ignore the flags.  Worlds of 2x1x2 chunks at depth 6-7
+(the pass-against-model scenes are those of tests/test_light_clearance.py), images of 64x48.
+
+`python tests/test_brick_clearance.py <library> scenes|lanes` runs against a variant build (tests/variant_check.py's mechanism)."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from helpers import assert_gbuffer_equal, random_rays
+import test_light_clearance as T
+
+pytestmark = pytest.mark.gpu
+
+ROOT, DIMS, CHUNK, W_IMG, H_IMG, LIGHTS = T.ROOT, T.DIMS, T.CHUNK, T.W_IMG, T.H_IMG, T.LIGHTS
+
+
+def scene(svo, ob, name):
+    """open ground, structures with an arch across the seam x = 128, the lake: depth 6, as tests/test_light_clearance.py builds them;
+    mixed: chunks of depth 6 and 7 side by side."""
+    if name != "mixed":
+        return T.scene(svo, ob, name)
+    gen = {d: ob.OracleWorld.generate(*DIMS, chunksize=CHUNK, depth=d) for d in (6, 7)}
+    chunks = [gen[d].chunk(i) for i, d in enumerate((6, 7, 7, 6))]
+    W = svo.World.create(chunks, *DIMS, CHUNK)
+    W.upload(0)
+    return ob.OracleWorld.from_chunks(chunks, *DIMS, CHUNK), W
+
+
+def check(svo, ob, O, W, light, what, expect_flags=True):
+    """Prepared explicitly for `light`: flagged bricks exist, and one frame and two frames per launch equal the oracle."""
+    cams = T.cameras(svo)
+    W.prepare_light(light)
+    flagged = W.prepared_bricks()
+    if expect_flags is not None:
+        assert (flagged > 0) == expect_flags, (what, flagged)
+    want = T.want_of(ob, O, cams, light)
+    assert_gbuffer_equal(T.march(svo, W, cams, light), want, f"{what}: two frames per launch")
+    assert_gbuffer_equal(T.march(svo, W, cams[:1], light), want[:W_IMG * H_IMG], f"{what}: one frame")
+    O.trace_image(cams[0], params=ob.make_params(shadow=True, light_dir=light))
+    assert W.last_ray_count() == O.last_rays, "a settled shadow ray must still be counted"
+    return want, flagged
+
+
+@pytest.mark.parametrize("light", sorted(LIGHTS))
+@pytest.mark.parametrize("name", ["open", "structures", "lake", "mixed"])
+def test_records_equal_the_oracle(svo, oracle, name, light):
+    O, W = scene(svo, oracle, name)
+    check(svo, oracle, O, W, LIGHTS[light], f"{name}/{light}", expect_flags=None if light == "up" else True)
+    W.destroy()
+
+
+def brick_model(ob, O, light):
+    import brick_clearance_model
+    return brick_clearance_model.model_of(O, DIMS, CHUNK, light)
+
+
+def test_bricks_of_several_materials_and_of_a_material_without_room_for_the_flag(svo, oracle):
+    """A brick of several materials is stored as 0xFFFF and so is one whose only material is 0x8000 or above: neither carries a flag,
+    both are hit with the right material, and the pass counts the flags it could store."""
+    light = LIGHTS["default"]
+    O, W = T.pair(svo, oracle, **T.FLAT)
+    T.build_both(svo, oracle, O, W, [(0, (32.0, 16.0, 32.0), (64.0, 20.0, 64.0)), (1, (160.0, 16.0, 32.0), (192.0, 20.0, 64.0))], material=0x9000)
+    T.build_both(svo, oracle, O, W, [(0, (34.0, 20.0, 34.0), (62.0, 22.0, 62.0)), (2, (40.0, 16.0, 160.0), (90.0, 18.0, 200.0))], material=7)
+    T.build_both(svo, oracle, O, W, [(2, (42.0, 18.0, 160.0), (88.0, 20.0, 200.0))], material=9)
+    want, flagged = check(svo, oracle, O, W, light, "special bricks")
+    mats = set(np.unique(want["material"]).tolist())
+    assert {0x9000, 7, 9} <= mats, mats
+    model = brick_model(oracle, O, light)
+    stored, ruled = model.flagged_bricks(stored_only=True), model.flagged_bricks()
+    print(f"special bricks: device {flagged} flags, model {stored} stored of {ruled} that the rule grants")
+    assert flagged == stored < ruled
+    W.destroy()
+
+
+def test_first_launch_prepares_an_edit_drops_and_the_call_restores(svo, oracle):
+    O, W = T.pair(svo, oracle, **T.FLAT)
+    light, cams = LIGHTS["default"], T.cameras(svo)
+    assert W.prepared_bricks() == 0
+    before = T.want_of(oracle, O, cams, light)
+    assert_gbuffer_equal(T.march(svo, W, cams, light), before, "first launch")
+    first = W.prepared_bricks()
+    assert first > 0, "the first shadowed launch of an unchanged world prepares the flags with the bits"
+    T.build_both(svo, oracle, O, W, [(0, (64.0, 48.0, 0.0), (128.0, 56.0, 128.0))])        # a slab in the way of the light
+    assert W.prepared_bricks() == 0, "an edit drops the flags"
+    after = T.want_of(oracle, O, cams, light)
+    assert ((after["flags"] & 4) != 0).sum() > ((before["flags"] & 4) != 0).sum() + 50, "the slab's shadow"
+    assert_gbuffer_equal(T.march(svo, W, cams, light), after, "after the edit: the stale flags of the untouched chunks are ignored")
+    assert W.prepared_bricks() == 0, "no launch prepares an edited world on its own"
+    check(svo, oracle, O, W, light, "after the edit, prepared again")
+    W.destroy()
+
+
+def test_another_light_than_the_prepared_one_and_both_switches(svo, oracle):
+    O, W = scene(svo, oracle, "structures")
+    a, b, cams = LIGHTS["default"], LIGHTS["oblique"], T.cameras(svo)
+    check(svo, oracle, O, W, a, "light A")
+    assert_gbuffer_equal(T.march(svo, W, cams, b), T.want_of(oracle, O, cams, b), "prepared for A, traced with B")
+    check(svo, oracle, O, W, b, "light B")
+    want = T.want_of(oracle, O, cams, a)
+    assert_gbuffer_equal(T.march(svo, W, cams, a), want, "prepared for B, traced with A")
+    W.prepare_light(a)
+    assert_gbuffer_equal(T.march(svo, W, cams, a, brick_clearance=False), want, "SVO_SHADOW_NO_BRICK_CLEARANCE")
+    assert_gbuffer_equal(T.march(svo, W, cams, a, light_clearance=False), want, "SVO_SHADOW_NO_CLEARANCE")
+    assert_gbuffer_equal(T.march(svo, W, cams, a, light_clearance=False, brick_clearance=False), want, "both switches")
+    W.prepare_light((1.0, -1.0, 1e-4))                      # a component below 1/64: accepted, never used
+    assert W.prepared_bricks() == 0
+    assert_gbuffer_equal(T.march(svo, W, cams, a), want, "a light that is never used: the flags of light A are still in the pool")
+    W.destroy()
+
+
+def test_paths_that_ignore_the_flags(svo, oracle):
+    """Every path of DESIGN 6t's "Off" list, on a world whose pool holds flags."""
+    O, W = scene(svo, oracle, "lake")
+    light, cams = LIGHTS["default"], T.cameras(svo)
+    check(svo, oracle, O, W, light, "lake")
+    one = cams[:1]
+    want = T.want_of(oracle, O, one, light)
+    assert_gbuffer_equal(T.march(svo, W, one, light, semantics=svo.SEMANTICS_GLSL), T.want_of(oracle, O, one, light, semantics=1), "GLSL semantics")
+    ntiles = ((W_IMG + 7) // 8) * ((H_IMG + 7) // 8)
+    cost = svo.DeviceBuffer(ntiles * 2 * 4)
+    assert_gbuffer_equal(T.march(svo, W, one, light, tile_cost_dev=cost.ptr), want, "tile costs recorded")
+    assert cost.to_numpy(np.uint32, ntiles * 2).reshape(-1, 2)[:, 1].max() > 10, "shadow rays' full step counts"
+    cost.free()
+    assert_gbuffer_equal(T.march(svo, W, one, light, eps=1.0 / 4096 * 1.5), T.want_of(oracle, O, one, light, eps=1.0 / 4096 * 1.5), "an eps that is no power of two")
+    o, d = random_rays(np.random.default_rng(7), 6000, (0, 0, 0), (256, 128, 256))
+    prm = oracle.make_params(shadow=True, light_dir=light)
+    assert_gbuffer_equal(W.chunkmarch(o, d, shadow=True, kernel=svo.KERNEL_STACK, light_dir=light), O.trace_rays(o, d, params=prm, threads=8), "a ray list")
+    far = W.chunkmarch(o, d, shadow=True, kernel=svo.KERNEL_STACK, light_dir=light, tmax=1e30)
+    assert_gbuffer_equal(far, O.trace_rays(o, d, params=prm, threads=8), "segments with a far end beyond everything")
+    see = W.draw(one[0], shadow=True, kernel=svo.KERNEL_STACK, light_dir=light, see_through=6)
+    lit = W.draw(one[0], shadow=True, kernel=svo.KERNEL_LITERAL, light_dir=light, see_through=6)
+    assert_gbuffer_equal(see, lit, "the see-through view (stack kernel against the literal kernel)")
+    assert np.count_nonzero(see["material"] == 6) == 0
+    assert_gbuffer_equal(W.draw(one[0], shadow=True, kernel=svo.KERNEL_LITERAL, light_dir=light), want.reshape(H_IMG, W_IMG), "the literal kernel")
+    W.destroy()
+
+
+@pytest.mark.parametrize("light", ["default", "oblique", "down"])
+@pytest.mark.parametrize("name", ["open", "structures", "lake", "mixed"])
+def test_the_pass_finds_the_models_flagged_bricks(svo, oracle, name, light):
+    """k_clear_bricks and tests/brick_clearance_model.py are two statements of one predicate: over every reachable brick of the scene -
+    odd level counts, TWIG nodes that fill 8 slots of a wide node, mixed depths, seams - they must flag the same number.  (Both
+    evaluate the same float64 expressions, so no tolerance.)"""
+    O, W = T.scene(svo, oracle, name)
+    want = brick_model(oracle, O, LIGHTS[light]).flagged_bricks(stored_only=True)
+    W.prepare_light(LIGHTS[light])
+    got = W.prepared_bricks()
+    print(f"{name}/{light}: device {got} flagged bricks, model {want}")
+    assert got == want and want > 0
+    W.destroy()
+
+
+@pytest.mark.parametrize("variant", ["cxxstep", "wide64"])
+def test_variant_builds(variant):
+    lib = os.path.join(ROOT, "octree-raymarcher_amd", "build", f"libsvo_{variant}.so")
+    assert os.path.exists(lib), f"{lib} missing: __graft_entry__.build() makes it"
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), lib, "scenes"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+
+
+def lane_steps(svo, ob):
+    """(script mode, a timing build) the open scene's first camera with the flags on and off, the bits on both times: records against
+    the oracle, the asm step's own count of marching lanes summed over its wave-steps (StepStats.lanes, sixth uint4 of a wave's
+    counters) and svo_trace_last_ray_count."""
+    O, W = T.scene(svo, ob, "open")
+    light, cam = LIGHTS["default"], T.cameras(svo)[0]
+    W.prepare_light(light)
+    assert W.prepared_bricks() > 0
+    want = T.want_of(ob, O, [cam], light)
+    waves = 256 * 32
+    steps, rays = {}, {}
+    for name, on in (("on", True), ("off", False)):
+        ctr = svo.DeviceBuffer.from_numpy(np.zeros(waves * 6 * 4, np.uint32))
+        buf = svo.DeviceBuffer(W_IMG * H_IMG * 32)
+        W.trace(cam, svo.trace_params(shadow=True, kernel=svo.KERNEL_STACK, light_dir=light, counters_dev=ctr.ptr, brick_clearance=on), (0, 0, W_IMG, H_IMG), buf.ptr)
+        svo.lib.svo_stream_synchronize(None)
+        assert_gbuffer_equal(buf.to_numpy(svo.HIT_DTYPE, W_IMG * H_IMG), want, f"timing build, flags {name}")
+        steps[name] = int(ctr.to_numpy(np.uint32, waves * 6 * 4).reshape(waves, 6, 4)[:, 5, 1].astype(np.int64).sum())
+        rays[name] = W.last_ray_count()
+        ctr.free(); buf.free()
+    W.destroy()
+    O.trace_image(cam, params=ob.make_params(shadow=True, light_dir=light))
+    print(f"LANE_STEPS {steps['on']} {steps['off']} RAYS {rays['on']} {rays['off']} {O.last_rays}")
+
+
+_settled = {}
+
+
+def settled_by_the_model(svo, ob):
+    """(rays, oracle steps) of the open scene's first camera that the flags settle: lit shadow rays whose origin lies in an empty cell
+    of the hit brick, that brick flagged; their steps are those they take TODAY, up to the first clear EMPTY node of 6t (the bits stay
+    on), re-marched by tests/clearance_model.py with the reference's arithmetic."""
+    if not _settled:
+        import clearance_model
+        O = ob.OracleWorld.generate(*DIMS, chunksize=CHUNK, depth=6, **T.FLAT)
+        light, cam = LIGHTS["default"], T.cameras(svo)[0]
+        model = brick_model(ob, O, light)
+        P = clearance_model.P
+        rec, cnt = O.trace_image(cam, params=ob.make_params(shadow=True, light_dir=light), counters=True, threads=8)
+        rec = rec.reshape(-1)
+        cd = dict(eye=tuple(cam.eye), forward=tuple(cam.forward), right=tuple(cam.right), up=tuple(cam.up),
+                  tan_half_x=cam.tan_half_x, tan_half_y=cam.tan_half_y, width=cam.width, height=cam.height)
+        rays = steps = 0
+        for k in np.nonzero(((rec["flags"] & 7) == 3) & (rec["cell"] != P.CELL_NONE))[0]:      # hit in a brick cell, shadow traced, lit
+            alpha, beta = P.camera_ray(cd, int(k % W_IMG), int(k // W_IMG))
+            origin = P.vadd(alpha, P.vmuls(beta, np.float32(rec["t"][k]) - model.eps))
+            if model.settles(origin, int(rec["chunk"][k]), int(rec["node"][k]))[2]:
+                r = model.march_lit(origin)
+                assert not r["hit"]
+                rays += 1
+                steps += r["first_clear"] or (r["tree_steps"] + r["brick_cells"])
+        _settled.update(rays=rays, steps=steps, total=int(cnt[..., 3].sum() + cnt[..., 1].sum()))
+        O.close()
+    return _settled["rays"], _settled["steps"], _settled["total"]
+
+
+@pytest.mark.parametrize("variant", ["timing", "timing64"])
+def test_settled_rays_take_no_steps(svo, oracle, variant):
+    """No comparison above notices a flag that never settles a ray.  The timing builds count the asm step's marching lanes per
+    wave-step: with the flags on, the open scene must take fewer lane-steps than with SVO_SHADOW_NO_BRICK_CLEARANCE (the bits on both
+    times), on both addressing variants, and count the same rays.  The bound comes from the model, not from the kernel: every oracle
+    step a settled ray takes today, up to its first clear EMPTY node, is a lane-step the kernel takes with the flags off and not with
+    them on.  The kernel may take an oracle step in closed form (creep block) or skip a brick that is bound to miss, so half of the
+    model's figure is asked for."""
+    rays, steps, total = settled_by_the_model(svo, oracle)
+    assert rays > 100 and steps > 0.05 * total, (rays, steps, total)
+    lib = os.path.join(ROOT, "octree-raymarcher_amd", "build", f"libsvo_{variant}.so")
+    assert os.path.exists(lib), f"{lib} missing: __graft_entry__.build() makes it"
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), lib, "lanes"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    on, off, rays_on, rays_off, rays_oracle = [int(v) for v in r.stdout.split("LANE_STEPS")[1].replace("RAYS", " ").split()[:5]]
+    print(f"{variant}: {off} lane-steps with the flags off, {on} with them on ({off - on} fewer); the model settles {rays} rays "
+          f"that take {steps} of {total} oracle steps; {rays_on} rays counted")
+    assert off - on >= steps // 2, (on, off, steps)
+    assert rays_on == rays_off == rays_oracle, "svo_trace_last_ray_count counts a settled shadow ray as the oracle does"
+
+
+if __name__ == "__main__":
+    import variant_check
+    svo_, ob_ = variant_check.load(os.path.abspath(sys.argv[1]))
+    if svo_.device_count() < 1:
+        print("no HIP device"); sys.exit(3)
+    if sys.argv[2] == "lanes":
+        lane_steps(svo_, ob_)
+        sys.exit(0)
+    for name_ in ("structures", "lake", "mixed"):
+        for light_ in ("default", "oblique"):
+            O_, W_ = scene(svo_, ob_, name_)
+            check(svo_, ob_, O_, W_, LIGHTS[light_], f"{name_}/{light_}")
+            W_.destroy()
+    print("brick clearance: structures, lake and mixed depths under two lights equal the oracle")
