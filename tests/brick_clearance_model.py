@@ -224,7 +224,7 @@ class BrickClearanceModel(CM.ClearanceModel):
         return True, bool(empty), bool(empty) and self.brick_flag(hit_chunk, hit_node, at["bmin"], at["size"])
 
 
-def model_of(oracle_world, dims, chunksize, light_dir, chunkcoordmin=(0, 0, 0), faults=()):
+def model_of(oracle_world, dims, chunksize, light_dir, chunkcoordmin=(0, 0, 0), faults=(), eps=P.EPS):
     """BrickClearanceModel over an oracle_binding.OracleWorld."""
     n = dims[0] * dims[1] * dims[2]
-    return BrickClearanceModel([oracle_world.chunk(i) for i in range(n)], dims, chunksize, light_dir, chunkcoordmin, faults=faults)
+    return BrickClearanceModel([oracle_world.chunk(i) for i in range(n)], dims, chunksize, light_dir, chunkcoordmin, eps=eps, faults=faults)

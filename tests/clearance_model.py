@@ -249,10 +249,10 @@ class ClearanceModel:
         return finish()
 
 
-def model_of(oracle_world, dims, chunksize, light_dir, chunkcoordmin=(0, 0, 0), faults=()):
+def model_of(oracle_world, dims, chunksize, light_dir, chunkcoordmin=(0, 0, 0), faults=(), eps=P.EPS):
     """ClearanceModel over an oracle_binding.OracleWorld."""
     n = dims[0] * dims[1] * dims[2]
-    return ClearanceModel([oracle_world.chunk(i) for i in range(n)], dims, chunksize, light_dir, chunkcoordmin, faults=faults)
+    return ClearanceModel([oracle_world.chunk(i) for i in range(n)], dims, chunksize, light_dir, chunkcoordmin, eps=eps, faults=faults)
 
 
 def shadow_origins(cam_rays, records, eps=P.EPS):

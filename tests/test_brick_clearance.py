@@ -5,7 +5,8 @@ across chunk seams, in bricks of several materials or of a material that leaves 
 than the prepared one, under both switches and on every path that has to ignore the flags.  Worlds of 2x1x2 chunks at depth 6-7
 (the pass-against-model scenes are those of tests/test_light_clearance.py), images of 64x48.
 
-`python tests/test_brick_clearance.py <library> scenes|lanes` runs against a variant build (tests/variant_check.py's mechanism)."""
+`python tests/test_brick_clearance.py <library> scenes|lanes [position ...]` runs against a variant build (tests/variant_check.py's
+mechanism); a position is a name of tests/clearance_positions.py, none = the world at the origin."""
 import os
 import subprocess
 import sys
@@ -21,11 +22,12 @@ pytestmark = pytest.mark.gpu
 ROOT, DIMS, CHUNK, W_IMG, H_IMG, LIGHTS = T.ROOT, T.DIMS, T.CHUNK, T.W_IMG, T.H_IMG, T.LIGHTS
 
 
-def scene(svo, ob, name):
+def scene(svo, ob, name, dims=DIMS, chunkcoordmin=(0, 0, 0)):
     """open ground, structures with an arch across the seam x = 128, the lake: depth 6, as tests/test_light_clearance.py builds them;
-    mixed: chunks of depth 6 and 7 side by side."""
+    mixed: chunks of depth 6 and 7 side by side (at the origin only)."""
     if name != "mixed":
-        return T.scene(svo, ob, name)
+        return T.scene(svo, ob, name, dims, chunkcoordmin)
+    assert (tuple(dims), tuple(chunkcoordmin)) == (DIMS, (0, 0, 0))
     gen = {d: ob.OracleWorld.generate(*DIMS, chunksize=CHUNK, depth=d) for d in (6, 7)}
     chunks = [gen[d].chunk(i) for i, d in enumerate((6, 7, 7, 6))]
     W = svo.World.create(chunks, *DIMS, CHUNK)
@@ -33,9 +35,9 @@ def scene(svo, ob, name):
     return ob.OracleWorld.from_chunks(chunks, *DIMS, CHUNK), W
 
 
-def check(svo, ob, O, W, light, what, expect_flags=True):
+def check(svo, ob, O, W, light, what, expect_flags=True, cams=None):
     """Prepared explicitly for `light`: flagged bricks exist, and one frame and two frames per launch equal the oracle."""
-    cams = T.cameras(svo)
+    cams = cams or T.cameras(svo)
     W.prepare_light(light)
     flagged = W.prepared_bricks()
     if expect_flags is not None:
@@ -56,9 +58,9 @@ def test_records_equal_the_oracle(svo, oracle, name, light):
     W.destroy()
 
 
-def brick_model(ob, O, light):
+def brick_model(ob, O, light, dims=DIMS, chunkcoordmin=(0, 0, 0), eps=0.0):
     import brick_clearance_model
-    return brick_clearance_model.model_of(O, DIMS, CHUNK, light)
+    return brick_clearance_model.model_of(O, dims, CHUNK, light, chunkcoordmin, eps=eps or T.CP.EPS)
 
 
 def test_bricks_of_several_materials_and_of_a_material_without_room_for_the_flag(svo, oracle):
@@ -165,12 +167,13 @@ def test_variant_builds(variant):
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
 
 
-def lane_steps(svo, ob):
+def lane_steps(svo, ob, position=None):
     """(script mode, a timing build) the open scene's first camera with the flags on and off, the bits on both times: records against
     the oracle, the asm step's own count of marching lanes summed over its wave-steps (StepStats.lanes, sixth uint4 of a wave's
     counters) and svo_trace_last_ray_count."""
-    O, W = T.scene(svo, ob, "open")
-    light, cam = LIGHTS["default"], T.cameras(svo)[0]
+    dims, ccm = T.place(position)
+    O, W = T.scene(svo, ob, "open", dims, ccm)
+    light, cam = LIGHTS["default"], T.cameras(svo, ccm)[0]
     W.prepare_light(light)
     assert W.prepared_bricks() > 0
     want = T.want_of(ob, O, [cam], light)
@@ -193,15 +196,16 @@ def lane_steps(svo, ob):
 _settled = {}
 
 
-def settled_by_the_model(svo, ob):
+def settled_by_the_model(svo, ob, position=None):
     """(rays, oracle steps) of the open scene's first camera that the flags settle: lit shadow rays whose origin lies in an empty cell
     of the hit brick, that brick flagged; their steps are those they take TODAY, up to the first clear EMPTY node of 6t (the bits stay
     on), re-marched by tests/clearance_model.py with the reference's arithmetic."""
-    if not _settled:
+    if position not in _settled:
         import clearance_model
-        O = ob.OracleWorld.generate(*DIMS, chunksize=CHUNK, depth=6, **T.FLAT)
-        light, cam = LIGHTS["default"], T.cameras(svo)[0]
-        model = brick_model(ob, O, light)
+        dims, ccm = T.place(position)
+        O = ob.OracleWorld.generate(*dims, chunksize=CHUNK, depth=6, chunkcoordmin=ccm, **T.FLAT)
+        light, cam = LIGHTS["default"], T.cameras(svo, ccm)[0]
+        model = brick_model(ob, O, light, dims, ccm)
         P = clearance_model.P
         rec, cnt = O.trace_image(cam, params=ob.make_params(shadow=True, light_dir=light), counters=True, threads=8)
         rec = rec.reshape(-1)
@@ -216,9 +220,9 @@ def settled_by_the_model(svo, ob):
                 assert not r["hit"]
                 rays += 1
                 steps += r["first_clear"] or (r["tree_steps"] + r["brick_cells"])
-        _settled.update(rays=rays, steps=steps, total=int(cnt[..., 3].sum() + cnt[..., 1].sum()))
+        _settled[position] = (rays, steps, int(cnt[..., 3].sum() + cnt[..., 1].sum()))
         O.close()
-    return _settled["rays"], _settled["steps"], _settled["total"]
+    return _settled[position]
 
 
 @pytest.mark.parametrize("variant", ["timing", "timing64"])
@@ -248,11 +252,14 @@ if __name__ == "__main__":
     if svo_.device_count() < 1:
         print("no HIP device"); sys.exit(3)
     if sys.argv[2] == "lanes":
-        lane_steps(svo_, ob_)
+        lane_steps(svo_, ob_, *sys.argv[3:4])
         sys.exit(0)
-    for name_ in ("structures", "lake", "mixed"):
-        for light_ in ("default", "oblique"):
-            O_, W_ = scene(svo_, ob_, name_)
-            check(svo_, ob_, O_, W_, LIGHTS[light_], f"{name_}/{light_}")
-            W_.destroy()
+    for position_ in sys.argv[3:] or [None]:
+        dims_, ccm_ = T.place(position_)
+        slab_ = position_ is not None and T.CP.POSITIONS[position_]["slab"]
+        for name_ in ("slab",) if slab_ else ("structures", "lake") + (("mixed",) if position_ is None else ()):
+            for light_ in ("default", "oblique"):
+                O_, W_ = scene(svo_, ob_, name_, dims_, ccm_)
+                check(svo_, ob_, O_, W_, LIGHTS[light_], f"{position_}: {name_}/{light_}", cams=T.cameras(svo_, ccm_, T.CP.SLAB_CAMERAS if slab_ else T.CP.CAMERAS))
+                W_.destroy()
     print("brick clearance: structures, lake and mixed depths under two lights equal the oracle")

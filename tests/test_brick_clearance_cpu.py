@@ -20,8 +20,8 @@ f32 = np.float32
 DIMS, CHUNK, LIGHTS, SCENES = T.DIMS, T.CHUNK, T.LIGHTS, T.SCENES
 
 
-def _violations(world, model):
-    """(flagged bricks, empty cells sampled, rays from them that the oracle finds occupied)."""
+def _violations(world, model, eps=0.0):
+    """(flagged bricks, empty cells sampled, rays from them that the oracle finds occupied); eps: the march's, 0 = its own 1/8192."""
     origins, bricks = [], 0
     for ci in range(len(model.chunks)):
         for off, lo, size in model.twig_nodes(ci):
@@ -35,7 +35,7 @@ def _violations(world, model):
         return bricks, 0, 0
     o = np.concatenate(origins)
     d = np.tile(np.array(model.sdir, f32), (len(o), 1))
-    rec = world.trace_rays(o, d, params=ob.make_params(shadow=False), threads=4)
+    rec = world.trace_rays(o, d, params=ob.make_params(shadow=False, eps=eps), threads=4)
     return bricks, len(origins), int(np.count_nonzero(rec["flags"] & 1))
 
 

@@ -3,7 +3,8 @@ shadow rays of the stack kernel end at the first EMPTY node whose way to the lig
 oracle's bit for bit - whatever the light, across chunk seams, after edits, with a light other than the prepared one, and on every
 path that has to ignore the bits.  Worlds of 2x1x2 chunks at depth 5-6, images of 64x48.
 
-`python tests/test_light_clearance.py <library>` runs the scenes against a variant build (tests/variant_check.py's mechanism)."""
+`python tests/test_light_clearance.py <library> scenes|lanes [position ...]` runs against a variant build (tests/variant_check.py's
+mechanism); a position is a name of tests/clearance_positions.py, none = the world at the origin."""
 import ctypes as C
 import os
 import subprocess
@@ -12,6 +13,7 @@ import sys
 import numpy as np
 import pytest
 
+import clearance_positions as CP
 from helpers import assert_gbuffer_equal, random_rays
 
 pytestmark = pytest.mark.gpu
@@ -30,21 +32,27 @@ STRUCTURES = [  # (chunk, lo, hi): on the voxel lattice, so that under the 45-de
 ]
 
 
-def cameras(svo):
-    return [svo.make_camera((128.3, 120.2, -70.1), (0.0, -0.55, 0.83), (0.0, 1.0, 0.0), 60.0, W_IMG, H_IMG),
-            svo.make_camera((200.7, 90.4, 40.2), (-0.5, -0.6, 0.62), (0.0, 1.0, 0.0), 60.0, W_IMG, H_IMG)]
+def cameras(svo, chunkcoordmin=(0, 0, 0), views=CP.CAMERAS):
+    """The two views, moved with the world."""
+    off = CP.offset(chunkcoordmin, CHUNK)
+    return [svo.make_camera(tuple(e + o for e, o in zip(eye, off)), fwd, up, 60.0, W_IMG, H_IMG) for eye, fwd, up in views]
 
 
 def build_both(svo, ob, O, W, boxes, material=5):
+    """boxes: (chunk, lo, hi); chunk None = the chunk World::index names for the box's centre, on the device and on the oracle (with
+    a chunkcoordmin that is no multiple of the grid that is not the chunk its position suggests, and a box sent there changes nothing)."""
     for ci, lo, hi in boxes:
+        if ci is None:
+            ci = W.index(*W.index_float(CP.centre(lo, hi)))
+            assert ci == CP.oracle_chunk_at(ob, O, CP.centre(lo, hi))
         dt, dw = ob.Delta(), ob.Delta()
         ob.lib.orc_build(C.byref(O.w.chunk[ci]), ob.vec3(lo), ob.vec3(hi), material, C.byref(dt), C.byref(dw))
         W.edit_box(ci, svo.EDIT_BUILD, lo, hi, material)
 
 
-def pair(svo, ob, depth=6, **terrain):
-    O = ob.OracleWorld.generate(*DIMS, chunksize=CHUNK, depth=depth, **terrain)
-    W = svo.World.generate(*DIMS, CHUNK, depth, build_device=0, **terrain)
+def pair(svo, ob, depth=6, dims=DIMS, chunkcoordmin=(0, 0, 0), **terrain):
+    O = ob.OracleWorld.generate(*dims, chunksize=CHUNK, depth=depth, chunkcoordmin=chunkcoordmin, **terrain)
+    W = svo.World.generate(*dims, CHUNK, depth, chunkcoordmin=chunkcoordmin, build_device=0, **terrain)
     return O, W
 
 
@@ -68,9 +76,9 @@ def want_of(ob, O, cams, light, **prm):
     return want
 
 
-def check(svo, ob, O, W, light, what, expect_clear=True):
+def check(svo, ob, O, W, light, what, expect_clear=True, cams=None):
     """Prepared explicitly for `light`: clear nodes exist, and one frame and two frames per launch equal the oracle."""
-    cams = cameras(svo)
+    cams = cams or cameras(svo)
     W.prepare_light(light)
     sdir, clear = W.prepared_light()
     assert np.array_equal(np.array(sdir, np.float32), np.array(ob_sdir(light), np.float32)), what
@@ -88,16 +96,22 @@ def ob_sdir(light):
     return clearance_model.shadow_dir(light)
 
 
-def scene(svo, ob, name):
+def scene(svo, ob, name, dims=DIMS, chunkcoordmin=(0, 0, 0)):
+    """dims / chunkcoordmin: the world elsewhere; its structures (CP.STRUCTURES, or the one slab of CP.SLAB over flat ground) move with it."""
+    at = dict(dims=dims, chunkcoordmin=chunkcoordmin)
+    moved = (tuple(dims), tuple(chunkcoordmin)) != (DIMS, (0, 0, 0))
     if name == "open":
-        return pair(svo, ob, **FLAT)
-    if name == "structures":
-        O, W = pair(svo, ob, **FLAT)
-        build_both(svo, ob, O, W, STRUCTURES)
+        return pair(svo, ob, **at, **FLAT)
+    if name in ("structures", "slab"):
+        O, W = pair(svo, ob, **at, **FLAT)
+        boxes = STRUCTURES if not moved else [(None, lo, hi) for lo, hi in CP.translated(CP.STRUCTURES, dims, chunkcoordmin, CHUNK)]
+        if name == "slab":
+            boxes = [(None, lo, hi) for lo, hi in CP.translated(CP.SLAB, dims, chunkcoordmin, CHUNK)]
+        build_both(svo, ob, O, W, boxes)
         return O, W
     if name == "lake":
-        return pair(svo, ob)                                # terrain with the water plane at y = 6
-    assert name == "mixed"
+        return pair(svo, ob, **at)                          # terrain with the water plane at y = 6
+    assert name == "mixed" and not moved
     gen = {d: ob.OracleWorld.generate(*DIMS, chunksize=CHUNK, depth=d) for d in (4, 6, 5)}
     chunks = [gen[d].chunk(i) for i, d in enumerate((4, 6, 5, 6))]
     W = svo.World.create(chunks, *DIMS, CHUNK)
@@ -179,9 +193,9 @@ def test_variant_builds(variant):
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
 
 
-def model_of_scene(ob, O, light):
+def model_of_scene(ob, O, light, dims=DIMS, chunkcoordmin=(0, 0, 0), eps=0.0):
     import clearance_model
-    return clearance_model.model_of(O, DIMS, CHUNK, light)
+    return clearance_model.model_of(O, dims, CHUNK, light, chunkcoordmin, eps=eps or CP.EPS)
 
 
 @pytest.mark.parametrize("light", ["default", "oblique", "down"])
@@ -200,11 +214,17 @@ def test_the_pass_finds_the_models_clear_nodes(svo, oracle, name, light):
     W.destroy()
 
 
-def lane_steps(svo, ob):
+def place(position):
+    """(dims, chunkcoordmin) of a position of tests/clearance_positions.py; None = the world at the origin."""
+    return (DIMS, (0, 0, 0)) if position is None else (CP.POSITIONS[position]["dims"], CP.POSITIONS[position]["ccm"])
+
+
+def lane_steps(svo, ob, position=None):
     """(script mode, a timing build) the open scene's first camera with the bits on and off: records against the oracle and the asm
     step's own count of marching lanes summed over its wave-steps (StepStats.lanes, sixth uint4 of a wave's counters)."""
-    O, W = scene(svo, ob, "open")
-    light, cam = LIGHTS["default"], cameras(svo)[0]
+    dims, ccm = place(position)
+    O, W = scene(svo, ob, "open", dims, ccm)
+    light, cam = LIGHTS["default"], cameras(svo, ccm)[0]
     W.prepare_light(light)
     want = want_of(ob, O, [cam], light)
     waves = 256 * 32
@@ -224,14 +244,18 @@ def lane_steps(svo, ob):
 _removed = {}
 
 
-def removed_by_the_model(svo, ob):
+def removed_by_the_model(svo, ob, position=None, sweep_eps=0.0):
     """Oracle steps (tree steps + brick cells) that the lit shadow rays of the open scene's first camera take after the step that first
-    locates a clear cell, and all steps of the frame: tests/clearance_model.py re-marches them with the reference's arithmetic."""
-    if not _removed:
+    locates a clear cell, and all steps of the frame: tests/clearance_model.py re-marches them with the reference's arithmetic.
+    sweep_eps: the eps the model decides the clear nodes with (0 = the march's own 1/8192, with which the rays are marched either way)."""
+    if (position, sweep_eps) not in _removed:
         import clearance_model
-        O = ob.OracleWorld.generate(*DIMS, chunksize=CHUNK, depth=6, **FLAT)
-        light, cam = LIGHTS["default"], cameras(svo)[0]
-        model = clearance_model.model_of(O, DIMS, CHUNK, light)
+        dims, ccm = place(position)
+        O = ob.OracleWorld.generate(*dims, chunksize=CHUNK, depth=6, chunkcoordmin=ccm, **FLAT)
+        light, cam = LIGHTS["default"], cameras(svo, ccm)[0]
+        model = clearance_model.model_of(O, dims, CHUNK, light, ccm, eps=sweep_eps or CP.EPS)
+        assert model.enabled
+        model.eps = np.float32(CP.EPS)
         rec, cnt = O.trace_image(cam, params=ob.make_params(shadow=True, light_dir=light), counters=True, threads=8)
         flags, t = rec["flags"].reshape(-1), rec["t"].reshape(-1)
         cd = dict(eye=tuple(cam.eye), forward=tuple(cam.forward), right=tuple(cam.right), up=tuple(cam.up),
@@ -243,8 +267,9 @@ def removed_by_the_model(svo, ob):
             assert not r["hit"]
             if r["first_clear"]:
                 removed += r["tree_steps"] + r["brick_cells"] - r["first_clear"]
-        _removed.update(removed=removed, total=int(cnt[..., 3].sum() + cnt[..., 1].sum()))
-    return _removed["removed"], _removed["total"]
+        _removed[(position, sweep_eps)] = (removed, int(cnt[..., 3].sum() + cnt[..., 1].sum()))
+        O.close()
+    return _removed[(position, sweep_eps)]
 
 
 @pytest.mark.parametrize("variant", ["timing", "timing64"])
@@ -271,11 +296,14 @@ if __name__ == "__main__":
     if svo_.device_count() < 1:
         print("no HIP device"); sys.exit(3)
     if sys.argv[2] == "lanes":
-        lane_steps(svo_, ob_)
+        lane_steps(svo_, ob_, *sys.argv[3:4])
         sys.exit(0)
-    for name_ in ("structures", "lake"):
-        for light_ in ("default", "oblique"):
-            O_, W_ = scene(svo_, ob_, name_)
-            check(svo_, ob_, O_, W_, LIGHTS[light_], f"{name_}/{light_}")
-            W_.destroy()
+    for position_ in sys.argv[3:] or [None]:
+        dims_, ccm_ = place(position_)
+        slab_ = position_ is not None and CP.POSITIONS[position_]["slab"]
+        for name_ in ("slab",) if slab_ else ("structures", "lake"):
+            for light_ in ("default", "oblique"):
+                O_, W_ = scene(svo_, ob_, name_, dims_, ccm_)
+                check(svo_, ob_, O_, W_, LIGHTS[light_], f"{position_}: {name_}/{light_}", cams=cameras(svo_, ccm_, CP.SLAB_CAMERAS if slab_ else CP.CAMERAS))
+                W_.destroy()
     print("light clearance: structures and lake under two lights equal the oracle")

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import clearance_model as CM
+import clearance_positions as CP
 import oracle_binding as ob
 
 f32 = np.float32
@@ -25,21 +26,17 @@ def _build(world, ci, lo, hi, material=5):
     ob.lib.orc_build(C.byref(world.w.chunk[ci]), ob.vec3(lo), ob.vec3(hi), material, C.byref(dt), C.byref(dw))
 
 
-def _terrain():
-    return ob.OracleWorld.generate(*DIMS, chunksize=CHUNK, depth=DEPTH)
+def _terrain(dims=DIMS, chunkcoordmin=(0, 0, 0)):
+    return ob.OracleWorld.generate(*dims, chunksize=CHUNK, depth=DEPTH, chunkcoordmin=chunkcoordmin)
 
 
-def _flat():
+def _flat(dims=DIMS, chunkcoordmin=(0, 0, 0), boxes=CP.STRUCTURES):
     """Flat ground under open sky, towers (the default light comes from -x: they shade the chunk beside them), an arch over the
-    seam x = 128 and a roof one voxel thick."""
-    w = ob.OracleWorld.generate(*DIMS, chunksize=CHUNK, depth=DEPTH, amplitude=0.0, yshift=16.0, water=False)
-    _build(w, 0, (96.0, 0.0, 32.0), (112.0, 96.0, 48.0))                       # tower: under the default light it shades x < 96
-    for ci, (x0, x1) in ((0, (112.0, 128.0)), (1, (128.0, 144.0))):             # arch: two legs and a lintel across the seam
-        _build(w, ci, (x0, 0.0, 80.0), (x1, 64.0, 96.0))
-    _build(w, 0, (120.0, 64.0, 80.0), (128.0, 72.0, 96.0))
-    _build(w, 1, (128.0, 64.0, 80.0), (136.0, 72.0, 96.0))
-    _build(w, 1, (160.0, 40.0, 16.0), (224.0, 44.0, 48.0))                      # roof one voxel thick: bricks with empty cells
-    _build(w, 2, (112.0, 0.0, 160.0), (128.0, 112.0, 176.0))                    # tower on the seam x = 128: it shades chunk 3 only
+    seam x = 128 and a roof one voxel thick - CP.STRUCTURES, moved with the world; each box goes to the chunk that World::index
+    names for it, which is chunk `position` only where chunkcoordmin is a multiple of the grid."""
+    w = ob.OracleWorld.generate(*dims, chunksize=CHUNK, depth=DEPTH, chunkcoordmin=chunkcoordmin, amplitude=0.0, yshift=16.0, water=False)
+    for lo, hi in CP.translated(boxes, dims, chunkcoordmin, CHUNK):
+        _build(w, CP.oracle_chunk_at(ob, w, CP.centre(lo, hi)), lo, hi)
     return w
 
 
@@ -55,8 +52,8 @@ def _cell_samples(lo, size):
     return np.array([(x, y, z) for x in axes[0] for y in axes[1] for z in axes[2]], f32)
 
 
-def _violations(world, model):
-    """(clear cells, rays from clear cells that the oracle finds occupied)."""
+def _violations(world, model, eps=0.0):
+    """(clear cells, rays from clear cells that the oracle finds occupied); eps: the march's, 0 = its own 1/8192."""
     origins = []
     for ci in range(len(model.chunks)):
         for off, lo, size in model.empty_nodes(ci):
@@ -66,7 +63,7 @@ def _violations(world, model):
         return 0, 0
     o = np.concatenate(origins)
     d = np.tile(np.array(model.sdir, f32), (len(o), 1))
-    rec = world.trace_rays(o, d, params=ob.make_params(shadow=False), threads=4)
+    rec = world.trace_rays(o, d, params=ob.make_params(shadow=False, eps=eps), threads=4)
     return len(origins), int(np.count_nonzero(rec["flags"] & 1))
 
 
