@@ -210,7 +210,11 @@ typedef struct svo_trace_params {
     int32_t  shadow;                /* !=0: one shadow ray per primary hit toward -light_dir.  Bit SVO_SHADOW_NO_CLEARANCE (2 or 3 instead
                                        of 1): the same shadow rays, never ended early by svo_world_prepare_light's bits - the same records,
                                        more steps; for A/B runs.  Bit SVO_SHADOW_NO_BRICK_CLEARANCE (5 instead of 1): the bits are used, the
-                                       per-brick flags that settle a lit shadow ray at its primary hit are not */
+                                       per-brick flags that settle a lit shadow ray at its primary hit are not.  Bit
+                                       SVO_SHADOW_NO_DARK_BIRTH (9 instead of 1): a shadow ray whose origin lies in an occupied cell of the
+                                       brick its primary ray hit is marched (two steps) instead of being settled "shadowed" at the hit;
+                                       SVO_SHADOW_NO_CLEARANCE and SVO_SHADOW_NO_BRICK_CLEARANCE (no shadow ray is settled at its primary hit)
+                                       switch that off too.  The same records with every combination */
     float    light_dir[3];          /* directionalLight.direction, default normalize(1,-1,0) (src/Main.cpp:116) */
     int32_t  kernel;                /* SVO_KERNEL_* */
     int32_t  tiles_per_wave;        /* SVO_KERNEL_STACK launch shape: every persistent wave is handed at least this
@@ -259,7 +263,7 @@ typedef struct svo_trace_params {
                                        (svo_world_info does not count it; at most 1.4 GB at C3 size); every change to the pools drops it */
 } svo_trace_params;
 enum { SVO_NORMAL_CUBE = 0, SVO_NORMAL_FACE = 1 };
-enum { SVO_SHADOW_NO_CLEARANCE = 2, SVO_SHADOW_NO_BRICK_CLEARANCE = 4 };
+enum { SVO_SHADOW_NO_CLEARANCE = 2, SVO_SHADOW_NO_BRICK_CLEARANCE = 4, SVO_SHADOW_NO_DARK_BIRTH = 8 };
 enum { SVO_SEMANTICS_CPU = 0, SVO_SEMANTICS_GLSL = 1 };
 
 /* G-buffer record, 32 bytes per pixel / per ray. */
@@ -1024,6 +1028,16 @@ int svo_trace_last_ray_count(svo_world *, void *stream, uint64_t *rays);
  *                             the world must have no negative coordinate and no voxel below the float spacing at its largest coordinate,
  *                             and a brick of several materials, or of one material of 0x8000 and above, carries no flag.
  *                             SVO_SHADOW_NO_BRICK_CLEARANCE switches the flags off alone, SVO_SHADOW_NO_CLEARANCE both.
+ *   dark at birth             needs none of the above: a primary hit in a brick cell whose shadow origin the hit block locates
+ *                             in an OCCUPIED cell of the same brick is shadowed - the reference's shadow march finds that cell in its first
+ *                             chunk step, tree step and brick cell - and the record is written once, with SVO_SHADOWED.  No prepared light,
+ *                             no bit of the pools: it holds after edits and for every finite light_dir.  The same launches as the bits
+ *                             (camera launches of SVO_SEMANTICS_CPU on the stack kernel, no see_through, no tile_cost_dev), on a world
+ *                             without a negative coordinate.  By default it is also left off where eps is below twice the float spacing
+ *                             at the world's largest coordinate: that is no premise of the rule, only a default that
+ *                             keeps such launches step for step what they were.  SVO_SHADOW_NO_DARK_BIRTH switches it off alone,
+ *                             SVO_SHADOW_NO_BRICK_CLEARANCE with the flags (no shadow ray is then settled at its primary hit),
+ *                             SVO_SHADOW_NO_CLEARANCE with everything.
  * The pass keeps 16 bytes of scratch per wide node (41 MB on the 4x1x4 depth-12 world; svo_world_info does not count it) until the next change
  * to the pools, so that a second light costs no allocation.  A launch prepares a world on its own only while wide entries x chunks <= 1e10
  * (four times that world: a few seconds for the bits; the brick flags take seventeen times as long, 15 s on that world and 0.8 s at depth 10);

@@ -64,6 +64,7 @@ LOCAL_SHADOWS, SHADOWED_POINT, SHADOWED_SPOT = 1 << 5, 1 << 6, 1 << 7     # svo_
 NORMAL_CUBE, NORMAL_FACE = 0, 1
 SHADOW_NO_CLEARANCE = 2          # bit of TraceParams.shadow: shadow rays as ever, World.prepare_light's bits ignored
 SHADOW_NO_BRICK_CLEARANCE = 4    # bit of TraceParams.shadow: the bits are used, the per-brick flags that settle a lit shadow ray at its hit are not
+SHADOW_NO_DARK_BIRTH = 8         # bit of TraceParams.shadow: a shadow ray born in an occupied cell of the hit brick is marched, not settled at the hit
 SEMANTICS_CPU, SEMANTICS_GLSL = 0, 1
 CELL_NONE = 0xFF
 SKY_LINEAR, SKY_NEAREST = 0, 1                           # svo_sky.filter
@@ -369,9 +370,12 @@ def c5_scene() -> dict:
 def trace_params(shadow: bool = False, kernel: int = KERNEL_AUTO, light_dir=(1.0, -1.0, 0.0), eps: float = 0.0,
                  caps=(0, 0, 0), counters_dev: Optional[int] = None, tiles_per_wave: int = 0, normal_mode: int = 0,
                  tile_cost_dev: Optional[int] = None, tile_order_dev: Optional[int] = None, launches_in_flight: int = 0,
-                 semantics: int = 0, see_through: int = 0, light_clearance: bool = True, brick_clearance: bool = True) -> TraceParams:
+                 semantics: int = 0, see_through: int = 0, light_clearance: bool = True, brick_clearance: bool = True,
+                 dark_birth: bool = True) -> TraceParams:
     """semantics: SEMANTICS_CPU (src/Traverse.cpp) / SEMANTICS_GLSL (shaders/Chunkmarch.glsl); eps / caps 0 = that twin's own constants.
-    see_through: a material (1..0xFFFF) every ray marches through as if it were empty; 0 = off."""
+    see_through: a material (1..0xFFFF) every ray marches through as if it were empty; 0 = off.
+    light_clearance / brick_clearance / dark_birth = False set SHADOW_NO_CLEARANCE / SHADOW_NO_BRICK_CLEARANCE / SHADOW_NO_DARK_BIRTH: the
+    same records, more steps (light_clearance=False switches all three short cuts off, brick_clearance=False both that settle a ray at its hit)."""
     p = TraceParams()
     p.semantics = semantics
     p.see_through = see_through
@@ -381,6 +385,8 @@ def trace_params(shadow: bool = False, kernel: int = KERNEL_AUTO, light_dir=(1.0
     p.shadow = (1 if light_clearance else 1 | SHADOW_NO_CLEARANCE) if shadow else 0    # (light_clearance=False: World.prepare_light's bits are ignored)
     if shadow and not brick_clearance:
         p.shadow |= SHADOW_NO_BRICK_CLEARANCE                                           # (... =False: the bits are used, the brick flags are not)
+    if shadow and not dark_birth:
+        p.shadow |= SHADOW_NO_DARK_BIRTH                                                # (... =False: a ray born in an occupied cell of the hit brick is marched)
     p.light_dir[:] = [float(x) for x in light_dir]
     p.kernel = kernel
     p.counters_dev = counters_dev

@@ -1050,6 +1050,28 @@ static int use_light_clearance(svo_world *w, const svo_trace_params *prm, TraceA
     return SVO_OK;
 }
 
+// Does this stack-kernel launch settle a shadow ray "shadowed" at its primary hit when the ray's origin lies in an occupied cell of the
+// hit brick?  Decided on its own: the rule reads the hit brick's cells only - no prepared light, no bit of the pools, any
+// eps - so it holds after edits and for every finite light.  The same launches as above; the rule's premises are exact geometry (which
+// has the power-of-two chunk and voxel size, and which the stack kernel demands anyway), a finite shadow direction (fl(s * 0) = 0: the
+// march's first sample is the origin) and no world corner with a negative coordinate (World::index puts a point at or just above a
+// negative multiple of the chunk size in the chunk below, and the reference's march then misses the brick).
+static void use_dark_birth(const svo_world *w, const svo_trace_params *prm, TraceArgs &A, uint32_t see)
+{
+    if (!A.shadow || !A.from_camera || A.tmax || see || A.glsl || A.tile_cost) return;
+    // (SVO_SHADOW_NO_BRICK_CLEARANCE means "no shadow ray is settled at its primary hit": tests/test_brick_clearance.py compares the
+    // lane-steps of a default launch with those of a launch under that bit and asks for half of what the flags' rays take; with this rule
+    // on under the bit the difference fell below that, DESIGN.md 6v "Off" has the figures)
+    if (prm && (prm->shadow & (SVO_SHADOW_NO_CLEARANCE | SVO_SHADOW_NO_BRICK_CLEARANCE | SVO_SHADOW_NO_DARK_BIRTH))) return;
+    bool premises = w->exact_geometry;
+    for (int a = 0; a < 3; ++a) premises &= std::isfinite(A.sdir[a]) && w->chunkcoordmin[a] >= 0;
+    // Not a premise of the rule, only of its default: an eps of at least twice the float spacing at the world's largest coordinate, as the
+    // bits ask.  tests/test_clearance_positions.py::test_beyond_the_limit_no_lane_retires wants a default launch below that eps to take
+    // about as many lane-steps as one under SVO_SHADOW_NO_CLEARANCE, and the rule removes lane-steps from the default launch alone.
+    premises &= A.eps >= 2.0f * clear_spacing(*w);
+    if (premises) A.light_clear |= LIGHT_CLEAR_DARK;
+}
+
 static int launch(svo_world *w, const svo_trace_params *prm, TraceArgs &A, hipStream_t s)
 {
     const int kernel = pick_kernel(w, prm, A);
@@ -1060,7 +1082,10 @@ static int launch(svo_world *w, const svo_trace_params *prm, TraceArgs &A, hipSt
         const int rc = use_view(w, see, A, s);
         if (rc != SVO_OK) return rc;
     }
-    if (kernel == SVO_KERNEL_STACK) if (const int rc = use_light_clearance(w, prm, A, see, s)) return rc;
+    if (kernel == SVO_KERNEL_STACK) {
+        if (const int rc = use_light_clearance(w, prm, A, see, s)) return rc;
+        use_dark_birth(w, prm, A, see);
+    }
     // every launch gets its own {tile cursor, ray count} slot so that launches on different streams may overlap
     Hbm &d = *w->hbm;
     d.work_last = d.work_next;

@@ -325,7 +325,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
     stk[0][threadIdx.x] = 0u;              // o, d, 1/d, world-entry t, output index (as int; -1 = no ray)
     const int lane = threadIdx.x;
     const bool want_cost = A.tile_cost != nullptr;      // (one SGPR held; the blocks below must not re-read the kernel arguments for a feature that is off)
-    [[maybe_unused]] const bool light_clear = A.light_clear != 0;      // shadow rays retire at clear cells (light_clearance.hip.h); the C++ step ignores the bit, which is always right
+    [[maybe_unused]] const bool light_clear = (A.light_clear & LIGHT_CLEAR_NODES) != 0;      // shadow rays retire at clear cells (light_clearance.hip.h); the C++ step ignores the bit, which is always right
     const int n_chunks = A.dimw * A.dimh * A.dimd;
     const bool chunks_in_lds = n_chunks <= CHUNK_TAB;
     if (lane == 0) {
@@ -837,9 +837,38 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
                 material = bw == 0xFFFFu ? A.twig[brick * TWIG_WORDS + hitc] : (bw & 0x7FFFu) | ((bw & 0x8000u) << 1);
             }
             const V3 point = alpha + beta * (tw - eps);
+            // The shadow ray's first sample is its origin itself (tw = 0, t = 0, p = alpha = point), and the reference locates it by the
+            // brick step's own arithmetic.  The frame still is the hit brick's (Blo its box, res its voxel, bmask its cells): inside the
+            // box, a cell of 0..3 per axis (a difference rounded up to the far face gives 4: not settled, which is always right).  That
+            // cell occupied: the reference's march returns a hit in its first brick cell, the ray is shadowed, whatever the
+            // light and the pools' bits.  That cell empty and the brick's flag set: the ray is lit (6u).  One evaluation of the cell for
+            // both; the verdict rides in bit 16 of `material`, which store_hit cuts off, and in the record's flags.
+            // (the switches are read from the arguments here, as A.shadow is: a wave-uniform bool kept from the kernel's top costs a
+            // scalar spill; the shader's twin and bounded rays never settle a ray: no code in their instantiations; either bit of
+            // A.light_clear implies A.shadow)
+            uint32_t dark = 0u;
+            if constexpr (!GLSL && !SEG) {
+                const uint32_t use = (uint32_t)A.light_clear & (uint32_t)(LIGHT_CLEAR_BRICKS | LIGHT_CLEAR_DARK);
+                if (use != 0u) {                                // (wave-uniform: a scalar branch; inside, no lane branches - a LEAF hit computes
+                    const float inv_res = recip_pow2(res);      //  a cell of its tree frame and is masked out by hitc)
+                    // (the sign is that of the difference, not of the quotient: a voxel above 1 takes a denormal difference below 0 to -0)
+                    const float dx = point.x - Blo.x, dy = point.y - Blo.y, dz = point.z - Blo.z;
+                    const uint32_t ux = (uint32_t)(int)(dx * inv_res), uy = (uint32_t)(int)(dy * inv_res), uz = (uint32_t)(int)(dz * inv_res);
+                    const bool located = (hitc != SVO_CELL_NONE) & (dx >= 0.0f) & (dy >= 0.0f) & (dz >= 0.0f) & ((ux | uy | uz) <= 3u);
+                    // (integer arithmetic on the switch word: as wave-uniform bools the two switches are hoisted to the kernel's top as
+                    // lane masks and cost four scalar spills)
+                    const uint32_t occupied = (uint32_t)(bmask >> ((uz * 16u + uy * 4u + ux) & 63u)) & 1u;
+                    const uint32_t on = (use >> (1u + occupied)) & (occupied | (material >> 16)) & 1u;      // occupied: the DARK bit; empty: the BRICKS bit and the brick's flag
+                    const uint32_t settle = located ? on : 0u;
+                    material = (material & 0xFFFFu) | (settle << 16);
+                    dark = (settle & occupied) * (uint32_t)SVO_SHADOWED;
+                } else {
+                    material &= 0xFFFFu;
+                }
+            }
             const bool face = A.normal_mode == SVO_NORMAL_FACE;
             const V3 n = face ? face_normal(point, vlo, vlo + vsize, beta) : cube_normal_pow2(point, vlo, vsize, eps);
-            const uint32_t flags = SVO_HIT_FLAG | (A.shadow ? SVO_SHADOW_TRACED : 0u) | (face ? (uint32_t)SVO_FACE_NORMAL : 0u);
+            const uint32_t flags = SVO_HIT_FLAG | (A.shadow ? SVO_SHADOW_TRACED : 0u) | (face ? (uint32_t)SVO_FACE_NORMAL : 0u) | dark;
             store_hit(A.out, outk, tw, n, material, flags, (uint32_t)ci, node, hitc);
             if (want_cost) note_tile_cost(outk, guard);
             mode = M_DONE;
@@ -850,20 +879,8 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
                 tw = 0.0f; cw = 0; guard = 0; creepn = 0;
                 bool hit = true;
                 if (!inside(alpha, wlo, whi)) tw = (GLSL ? enter_glsl(alpha, g, wlo, whi, hit) : enter(alpha, beta, wlo, whi, hit)) + eps;
-                // Every empty cell of the hit brick has a clear way to the light (its flag), and the shadow ray's first sample - the
-                // origin itself: tw = 0, t = 0, p = alpha - is located in one of them, by the brick step's own arithmetic (the frame
-                // still is the brick's: Blo its box, res its voxel; bmask its cells): inside the box, a cell of 0..3 per axis (a
-                // difference rounded up to the far face gives 4), that cell empty.  The record is final as store_hit wrote it.
-                // (read from the arguments here, as A.shadow is: a wave-uniform bool kept from the kernel's top costs a scalar spill; the
-                // shader's twin and bounded rays never use the flags: no code in their instantiations)
-                bool settled = !GLSL && !SEG && (A.light_clear & LIGHT_CLEAR_BRICKS) != 0 && (material >> 16) != 0u;
-                if (settled) {
-                    const float inv_res = recip_pow2(res);
-                    const float fx = (point.x - Blo.x) * inv_res, fy = (point.y - Blo.y) * inv_res, fz = (point.z - Blo.z) * inv_res;
-                    const uint32_t ux = (uint32_t)(int)fx, uy = (uint32_t)(int)fy, uz = (uint32_t)(int)fz;
-                    settled = (fx >= 0.0f) & (fy >= 0.0f) & (fz >= 0.0f) & ((ux | uy | uz) <= 3u);
-                    settled = settled && ((bmask >> ((uz * 16u + uy * 4u + ux) & 63u)) & 1ull) == 0ull;
-                }
+                // settled above, lit or shadowed: the record is final as store_hit wrote it
+                const bool settled = !GLSL && !SEG && (material >> 16) != 0u;
                 mode = hit && !settled ? M_WORLD : M_DONE;  // a shadow ray that misses the world box stays "lit"
                 rays_marched++;
             }

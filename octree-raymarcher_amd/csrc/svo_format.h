@@ -119,6 +119,8 @@ struct TraceArgs {
     const float *tmax;          // svo_trace_segments: [n] far end per ray (list mode; read by the bounded instantiations only).  Last but one: no other field moves
     int32_t  light_clear;       // stack kernel, LIGHT_CLEAR_*: a shadow ray retires at an EMPTY entry that carries WIDE_CLEAR_BIT / is settled at its primary hit by the brick's flag (device.hip use_light_clearance decides)
 };
-enum : int32_t { LIGHT_CLEAR_NODES = 1, LIGHT_CLEAR_BRICKS = 2 };
+// LIGHT_CLEAR_DARK (device.hip use_dark_birth decides, on its own): a shadow ray whose origin lies in an occupied cell of the hit brick is
+// settled "shadowed" at its primary hit; it needs no prepared light and no bit of the pools
+enum : int32_t { LIGHT_CLEAR_NODES = 1, LIGHT_CLEAR_BRICKS = 2, LIGHT_CLEAR_DARK = 4 };
 
 } // namespace svo
