@@ -156,15 +156,6 @@ static void drop_parents(svo_world &w)
     d.parents_ok = false;
 }
 
-// the light clearance bits (light_clearance.hip.h): every change to the pools drops them - a rebuilt chunk has none, and those of the
-// other chunks were decided against matter that may have changed - until svo_world_prepare_light is called again
-static void drop_clearance(svo_world &w)
-{
-    Hbm &d = *w.hbm;
-    if (d.clear_place.p) { (void)hipDeviceSynchronize(); d.clear_place = Pooled<uint4>(); }     // (the pass's scratch: 16 bytes per wide node)
-    d.clear_state = Hbm::CLEAR_DROPPED; d.clear_usable = d.clear_bricks_usable = false;     // (the flags in bmat stay and are ignored)
-}
-
 int release_device(svo_world &w, bool keep_builder)
 {
     if (w.hbm) {
@@ -403,7 +394,7 @@ static bool wide_fits(const svo_world &w, int chunk)
 static void drop_wide(svo_world &w)
 {
     drop_view(w);
-    if (w.hbm->clear_state == Hbm::CLEAR_READY) drop_clearance(w);
+    if (w.hbm->clear.prepared()) drop_clearance(w);
     if (w.hbm->wide.p || w.hbm->wbase.p) (void)hipDeviceSynchronize();
     w.hbm->wide = Pooled<uint32_t>(); w.hbm->wbase = Pooled<uint32_t>();
     w.wide_ok = false;
@@ -955,123 +946,6 @@ static int use_view(svo_world *w, uint32_t m, TraceArgs &A, hipStream_t s)
     return SVO_OK;
 }
 
-// Light clearance (light_clearance.hip.h).  The rule's premises: every component of the shadow direction is 0 or at
-// least CLEAR_S_MIN in magnitude (a smaller one lets a ray graze a chunk face for a long way: the chunk march then resumes far behind
-// the tree march's last sample), the world's largest coordinate has a float spacing u of at most eps / 2, and eps is a power of two.
-constexpr double CLEAR_S_MIN = 1.0 / 64.0;
-// The sweep looks at every chunk's root per EMPTY entry: its cost grows with entries x chunks.  The 4x1x4 depth-12 world (163 M entries,
-// 16 chunks: 2.6e9) takes 0.86 s (profiles/light_clearance_ab.txt); a launch prepares a world on its own up to four times that product,
-// a few seconds by proportion - and seventeen times that with the brick flags behind it (k_clear_bricks: 14.9 s on that world, 0.8 s at
-// depth 10; DESIGN.md 6u "Not done").  Larger worlds - the 10x1x10 one of scripts/bigworld_check.py is at 1.3e11 - are prepared on request only.
-constexpr double CLEAR_AUTO_WORK = 1.0e10;
-
-static float clear_spacing(const svo_world &w)
-{
-    const int dims[3] = { w.width, w.height, w.depth };
-    float m = 1.0f;
-    for (int a = 0; a < 3; ++a)
-        for (int k = 0; k < 2; ++k) m = std::max(m, std::fabs((float)(w.chunkcoordmin[a] + k * dims[a]) * (float)w.chunksize));
-    return std::nextafter(m, INFINITY) - m;
-}
-static bool eps_is_pow2(float eps)
-{
-    uint32_t b;
-    std::memcpy(&b, &eps, sizeof b);
-    return (b & 0x807FFFFFu) == 0u && b >= 0x00800000u && b < 0x7F800000u;
-}
-
-// The bits for shadow direction `sdir`, issued on `s` behind every launch of the world in flight (one of them may be reading the
-// bits of another light); launches that use them wait for clear_built.
-static int prepare_light(svo_world &w, const float sdir[3], hipStream_t s)
-{
-    Hbm &d = *w.hbm;
-    d.clear_usable = d.clear_bricks_usable = false;
-    if (!w.wide_ok || w.wide_pool_len == 0) return SVO_OK;              // the literal kernel marches this world: nothing reads the bits
-    HIP_TRY(hipSetDevice(w.device));
-    bool premises = true;
-    for (int a = 0; a < 3; ++a) premises &= std::isfinite(sdir[a]) && (sdir[a] == 0.0f || std::fabs((double)sdir[a]) >= CLEAR_S_MIN);
-    std::memcpy(d.clear_sdir, sdir, sizeof d.clear_sdir);
-    d.clear_state = Hbm::CLEAR_READY;
-    if (!premises || !w.exact_geometry) return SVO_OK;                  // prepared, and never used
-    d.clear_state = Hbm::CLEAR_DROPPED;                                 // (until everything below is issued)
-    const uint64_t nodes = w.wide_pool_len;
-    if (d.clear_place.bytes < nodes * sizeof(uint4)) {
-        if (d.clear_place.p) HIP_TRY(hipDeviceSynchronize());
-        if (d.clear_place.alloc(nodes, w.device) != hipSuccess) { set_error("svo_world_prepare_light: hipMalloc failed"); return SVO_ERR_OUT_OF_MEMORY; }
-    }
-    if (const int rc = d.clear_count.reserve(2, false, nullptr)) return rc;
-    for (Event &e : d.work_done) if (e.e) if (const int rc = e.wait(s)) return rc;
-    if (d.clear_built.e) if (const int rc = d.clear_built.wait(s)) return rc;
-    const double u = (double)clear_spacing(w);
-    ClearArgs K;
-    K.wchunks = d.wchunks.p; K.wide = d.wide.p; K.place = d.clear_place.p; K.pool_nodes = nodes;
-    K.n_chunks = (int32_t)w.chunks.size(); K.chunksize = (double)w.chunksize;
-    for (int a = 0; a < 3; ++a) K.s[a] = (double)sdir[a];
-    K.d1 = 4.0 * u;
-    K.d2 = (8.0 / CLEAR_S_MIN + 6.0 + 4.0 * (double)(w.width + w.height + w.depth + 2)) * u;
-    K.clear_nodes = d.clear_count.p;
-    // the brick flags ask more of the world: no negative coordinate and no voxel below u, so that a sample's cell
-    // contains it exactly (exact_geometry has the power-of-two chunk size); where that fails every flag is written 0
-    bool bricks = true;
-    for (int a = 0; a < 3; ++a) bricks &= w.chunkcoordmin[a] >= 0;
-    for (const ChunkPools &c : w.chunks) bricks &= std::ldexp((double)w.chunksize, -(int)c.depth) >= u;
-    K.mask = d.mask.p; K.bmat = d.bmat.p; K.clear_bricks = d.clear_count.p + 1; K.brick_premises = bricks ? 1 : 0;
-    HIP_TRY(hipMemsetAsync(d.clear_place.p, 0xFF, nodes * sizeof(uint4), s));
-    HIP_TRY(hipMemsetAsync(d.clear_count.p, 0, 2 * sizeof(unsigned long long), s));
-    int rc = launch_per_element("svo_world_prepare_light", K.n_chunks, s, k_clear_seed, K);
-    const int nw_max = w.max_levels ? (w.max_levels + 1) / 2 : 1;
-    for (int r = 0; rc == SVO_OK && r + 1 < nw_max; ++r) rc = launch_per_element("svo_world_prepare_light", (int64_t)nodes * 64, s, k_clear_boxes, K, (uint32_t)r);
-    if (rc == SVO_OK) rc = launch_per_element("svo_world_prepare_light", (int64_t)nodes * 64, s, k_clear_sweep, K);
-    if (rc == SVO_OK) rc = launch_per_element("svo_world_prepare_light", (int64_t)nodes * 64, s, k_clear_bricks, K);
-    if (rc != SVO_OK) return rc;
-    if ((rc = d.clear_built.record(s)) != SVO_OK) return rc;
-    d.clear_state = Hbm::CLEAR_READY;
-    d.clear_usable = true;
-    d.clear_bricks_usable = bricks;
-    d.clear_eps = 2.0f * (float)u;                                      // the smallest eps the bits hold for
-    return SVO_OK;
-}
-
-// Does this stack-kernel launch let its shadow rays retire at clear cells?  Camera frames of the CPU march with shadow rays and
-// nothing that looks at a ray's later steps (tile costs) or marches another world (the see-through view); the world's first such
-// launch after its upload prepares the bits for its own light.
-static int use_light_clearance(svo_world *w, const svo_trace_params *prm, TraceArgs &A, uint32_t see, hipStream_t s)
-{
-    A.light_clear = 0;
-    if (!A.shadow || !A.from_camera || A.tmax || see || A.glsl || A.tile_cost || (prm && (prm->shadow & SVO_SHADOW_NO_CLEARANCE))) return SVO_OK;
-    Hbm &d = *w->hbm;
-    if (d.clear_state == Hbm::CLEAR_FRESH && (double)w->wide_pool_len * 64.0 * (double)w->chunks.size() <= CLEAR_AUTO_WORK)
-        if (const int rc = prepare_light(*w, A.sdir, s)) return rc;
-    if (d.clear_state != Hbm::CLEAR_READY || !d.clear_usable) return SVO_OK;
-    if (std::memcmp(d.clear_sdir, A.sdir, sizeof d.clear_sdir) != 0 || !eps_is_pow2(A.eps) || A.eps < d.clear_eps) return SVO_OK;
-    if (const int rc = d.clear_built.wait(s)) return rc;
-    A.light_clear = LIGHT_CLEAR_NODES;
-    if (d.clear_bricks_usable && !(prm && (prm->shadow & SVO_SHADOW_NO_BRICK_CLEARANCE))) A.light_clear |= LIGHT_CLEAR_BRICKS;
-    return SVO_OK;
-}
-
-// Does this stack-kernel launch settle a shadow ray "shadowed" at its primary hit when the ray's origin lies in an occupied cell of the
-// hit brick?  Decided on its own: the rule reads the hit brick's cells only - no prepared light, no bit of the pools, any
-// eps - so it holds after edits and for every finite light.  The same launches as above; the rule's premises are exact geometry (which
-// has the power-of-two chunk and voxel size, and which the stack kernel demands anyway), a finite shadow direction (fl(s * 0) = 0: the
-// march's first sample is the origin) and no world corner with a negative coordinate (World::index puts a point at or just above a
-// negative multiple of the chunk size in the chunk below, and the reference's march then misses the brick).
-static void use_dark_birth(const svo_world *w, const svo_trace_params *prm, TraceArgs &A, uint32_t see)
-{
-    if (!A.shadow || !A.from_camera || A.tmax || see || A.glsl || A.tile_cost) return;
-    // (SVO_SHADOW_NO_BRICK_CLEARANCE means "no shadow ray is settled at its primary hit": tests/test_brick_clearance.py compares the
-    // lane-steps of a default launch with those of a launch under that bit and asks for half of what the flags' rays take; with this rule
-    // on under the bit the difference fell below that, DESIGN.md 6v "Off" has the figures)
-    if (prm && (prm->shadow & (SVO_SHADOW_NO_CLEARANCE | SVO_SHADOW_NO_BRICK_CLEARANCE | SVO_SHADOW_NO_DARK_BIRTH))) return;
-    bool premises = w->exact_geometry;
-    for (int a = 0; a < 3; ++a) premises &= std::isfinite(A.sdir[a]) && w->chunkcoordmin[a] >= 0;
-    // Not a premise of the rule, only of its default: an eps of at least twice the float spacing at the world's largest coordinate, as the
-    // bits ask.  tests/test_clearance_positions.py::test_beyond_the_limit_no_lane_retires wants a default launch below that eps to take
-    // about as many lane-steps as one under SVO_SHADOW_NO_CLEARANCE, and the rule removes lane-steps from the default launch alone.
-    premises &= A.eps >= 2.0f * clear_spacing(*w);
-    if (premises) A.light_clear |= LIGHT_CLEAR_DARK;
-}
-
 static int launch(svo_world *w, const svo_trace_params *prm, TraceArgs &A, hipStream_t s)
 {
     const int kernel = pick_kernel(w, prm, A);
@@ -1082,10 +956,8 @@ static int launch(svo_world *w, const svo_trace_params *prm, TraceArgs &A, hipSt
         const int rc = use_view(w, see, A, s);
         if (rc != SVO_OK) return rc;
     }
-    if (kernel == SVO_KERNEL_STACK) {
-        if (const int rc = use_light_clearance(w, prm, A, see, s)) return rc;
-        use_dark_birth(w, prm, A, see);
-    }
+    if (kernel == SVO_KERNEL_STACK)
+        if (const int rc = gate_light_clearance(*w, prm, A, see, s)) return rc;
     // every launch gets its own {tile cursor, ray count} slot so that launches on different streams may overlap
     Hbm &d = *w->hbm;
     d.work_last = d.work_next;
@@ -1559,35 +1431,20 @@ int svo_world_prepared_light(svo_world *w, void *stream, float shadow_dir[3], ui
 {
     if (!w || !shadow_dir || !clear_nodes) return SVO_ERR_INVALID_ARG;
     if (w->device < 0) { set_error("svo_world_prepared_light: world is not uploaded"); return SVO_ERR_NOT_UPLOADED; }
-    const Hbm &d = *w->hbm;
+    const LightClearance &c = w->hbm->clear;
     shadow_dir[0] = shadow_dir[1] = shadow_dir[2] = 0.0f;
     *clear_nodes = 0;
-    if (d.clear_state != Hbm::CLEAR_READY) return SVO_OK;
-    std::memcpy(shadow_dir, d.clear_sdir, sizeof d.clear_sdir);
-    if (!d.clear_usable) return SVO_OK;
-    HIP_TRY(hipSetDevice(w->device));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    if (d.clear_built.e) HIP_TRY(hipEventSynchronize(d.clear_built.e));    // (the pass may have been issued on another stream)
-    unsigned long long v = 0;
-    HIP_TRY(hipMemcpy(&v, d.clear_count.p, sizeof v, hipMemcpyDeviceToHost));
-    *clear_nodes = v;
-    return SVO_OK;
+    if (!c.prepared()) return SVO_OK;
+    std::memcpy(shadow_dir, c.sdir, sizeof c.sdir);
+    return c.state == ClearState::UNUSED ? SVO_OK : read_clear_count(*w, (hipStream_t)stream, 0, clear_nodes);
 }
 
 int svo_world_prepared_bricks(svo_world *w, void *stream, uint64_t *flagged)
 {
     if (!w || !flagged) return SVO_ERR_INVALID_ARG;
     if (w->device < 0) { set_error("svo_world_prepared_bricks: world is not uploaded"); return SVO_ERR_NOT_UPLOADED; }
-    const Hbm &d = *w->hbm;
     *flagged = 0;
-    if (d.clear_state != Hbm::CLEAR_READY || !d.clear_usable || !d.clear_bricks_usable) return SVO_OK;
-    HIP_TRY(hipSetDevice(w->device));
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-    if (d.clear_built.e) HIP_TRY(hipEventSynchronize(d.clear_built.e));    // (the pass may have been issued on another stream)
-    unsigned long long v = 0;
-    HIP_TRY(hipMemcpy(&v, d.clear_count.p + 1, sizeof v, hipMemcpyDeviceToHost));
-    *flagged = v;
-    return SVO_OK;
+    return w->hbm->clear.state == ClearState::BRICKS ? read_clear_count(*w, (hipStream_t)stream, 1, flagged) : SVO_OK;
 }
 
 } // extern "C"

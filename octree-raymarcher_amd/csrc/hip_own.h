@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "world.h"
+#include "light_gate.h"
 
 namespace svo {
 
@@ -179,6 +180,17 @@ struct RayList {
 // fronts begin at 0, the scan's own scratch is the tail
 struct WideLayout { uint64_t next = 0, flag = 0, rank = 0, wref = 0, wide = 0, wbase = 0, scan = 0, scan_words = 0, total = 0; };
 
+// Light clearance (svo_world_prepare_light; light_clearance.hip.h has the pass, light_gate.h the states, their transitions and the
+// launches' use of them): WIDE_CLEAR_BIT of the wide pool's EMPTY entries and BMAT_CLEAR_BIT of the bricks, as `state` says, for `sdir`
+struct LightClearance {
+    ClearState state = ClearState::FRESH;
+    float sdir[3] = { 0.0f, 0.0f, 0.0f };                   // the prepared shadow direction (UNUSED, NODES, BRICKS)
+    Pooled<uint4> place;                                    // the pass's scratch: 16 bytes per wide node, kept until the pools change
+    DevBuf<unsigned long long> count;                       // [0] EMPTY reference nodes found clear, [1] bricks flagged
+    Event built;                                            // launches that use the bits wait for it
+    bool prepared() const { return state == ClearState::UNUSED || state == ClearState::NODES || state == ClearState::BRICKS; }
+};
+
 // What an uploaded world keeps on the device.  release_device (device.hip) lets go of it as a whole.
 struct Hbm {
     DevBuf<DevChunk> chunks; DevBuf<DevWide> wchunks;       // the chunk tables (host mirrors: svo_world::table / wtable)
@@ -206,16 +218,7 @@ struct Hbm {
     Pooled<uint32_t> parent; Pooled<uint8_t> parent_level; DevBuf<uint32_t> chunk_trees;
     bool parents_ok = false;                                // the build has been issued
     Event parents_built;                                    // calls on other streams wait for it
-    // light clearance (svo_world_prepare_light, light_clearance.hip.h): WIDE_CLEAR_BIT of the wide pool's EMPTY entries holds for
-    // clear_sdir while clear_state == CLEAR_READY; every change to the pools drops it (the bits of untouched chunks are stale then),
-    // and only a world unchanged since its upload (CLEAR_FRESH) is prepared by a launch on its own
-    enum { CLEAR_FRESH = 0, CLEAR_READY = 1, CLEAR_DROPPED = 2 };
-    int clear_state = CLEAR_FRESH;
-    bool clear_usable = false;                              // the prepared direction and the world meet the rule's premises
-    bool clear_bricks_usable = false;                       // ... and those of the per-brick flags in bmat's bit 15 (k_clear_bricks) as well
-    float clear_sdir[3] = { 0.0f, 0.0f, 0.0f }; float clear_eps = 0.0f;
-    Pooled<uint4> clear_place; DevBuf<unsigned long long> clear_count;
-    Event clear_built;                                      // launches that use the bits wait for it
+    LightClearance clear;
     int stack_blocks[24] = {};                              // persistent-grid size per k_trace_stack instantiation (device.hip: STACK_KERNELS); 0 = not queried yet
 };
 

@@ -832,9 +832,9 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
                 // most bricks hold one material (grow() fills a brick with its node's): it is kept per brick next to the masks, 64
                 // bricks to a cache line; only a brick of several materials (0xFFFF) is read itself, 128 B for one cell
                 const unsigned long long brick = (unsigned long long)twig_off + (word & WIDE_PAYLOAD);
-                // (bit 15 of the word is the brick's clear flag, light_clearance.hip.h; 0xFFFF carries none)
+                // (BMAT_CLEAR_BIT of the word is the brick's clear flag, light_clearance.hip.h; BMAT_SEVERAL carries none)
                 const uint32_t bw = A.bmat[brick];
-                material = bw == 0xFFFFu ? A.twig[brick * TWIG_WORDS + hitc] : (bw & 0x7FFFu) | ((bw & 0x8000u) << 1);
+                material = bw == BMAT_SEVERAL ? A.twig[brick * TWIG_WORDS + hitc] : (bw & BMAT_MATERIAL_MASK) | ((bw & BMAT_CLEAR_BIT) << 1);
             }
             const V3 point = alpha + beta * (tw - eps);
             // The shadow ray's first sample is its origin itself (tw = 0, t = 0, p = alpha = point), and the reference locates it by the

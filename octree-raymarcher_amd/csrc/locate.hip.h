@@ -105,7 +105,7 @@ __device__ __forceinline__ bool walk_wide(const TraceArgs &A, V3 p, Terminal &T)
     const V3 clo = ld3(ch.bmin);
     if (!inside(p, clo, clo + A.chunksize)) return false;
     const int levels = (int)ch.levels;
-    const int nw = levels ? (levels + 1) >> 1 : 1;
+    const int nw = wide_levels(levels);
     V3 lo = clo, lo1 = clo;                         // box after both comparisons of a wide node / after the first one
     float size = A.chunksize, size1 = size;
     uint64_t wn = ch.wide_off;                      // the wide node's index in the pool
@@ -133,7 +133,7 @@ __device__ __forceinline__ bool walk_wide(const TraceArgs &A, V3 p, Terminal &T)
     }
     T.type = node_type(word);
     if (T.type == BRANCH) return false;                             // a BRANCH below the last wide level: malformed (never built)
-    const int plev = (int)((word >> WIDE_LEVEL_SHIFT) & ((1u << WIDE_LEVEL_BITS) - 1u));     // the reference node's level
+    const int plev = (int)wide_entry_level(word);     // the reference node's level
     uint32_t node = 0u;                                             // level 0 is the chunk's root
     if (plev == 0) { lo = clo; size = A.chunksize; }
     else {

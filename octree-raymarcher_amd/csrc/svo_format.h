@@ -56,6 +56,9 @@ struct DevWide {
 };
 static_assert(sizeof(DevWide) == 32, "wide chunk table entry is 32 bytes");
 
+// The bmat word of a brick (TraceArgs::bmat; written by device.hip k_brick_masks, the flag by light_clearance.hip.h k_clear_bricks)
+constexpr uint32_t BMAT_MATERIAL_MASK = 0x7FFFu, BMAT_CLEAR_BIT = 0x8000u, BMAT_SEVERAL = 0xFFFFu;
+
 // Everything a trace kernel needs, passed by value.
 // Launch slot (u64 words).  The stack kernel deals the image out as TILE_REGIONS screen regions, one per XCD (own L2),
 // each with its own cursor; a wave whose region is empty moves on to the next one.
@@ -81,7 +84,7 @@ struct TraceArgs {
     const DevWide  *wchunks;    // stack kernel: chunk table over the wide pool
     const uint32_t *wide;       // wide pool: 64 entries per wide node (wide_tree.hip.h)
     const uint32_t *wbase;      // per wide node: reference index of the child block and of the 8 grandchild blocks it expands (for svo_hit.node)
-    const uint16_t *bmat;       // per brick: its one material (below 0x8000), 0 if empty, 0xFFFF if it holds several; bit 15: every empty cell of the brick has a clear way to the prepared light
+    const uint16_t *bmat;       // per brick, BMAT_*: its one material (below 0x8000), 0 if empty, 0xFFFF if it holds several; bit 15: every empty cell of the brick has a clear way to the prepared light
     const uint32_t *tree;
     const uint16_t *twig;
     const uint64_t *mask;
@@ -117,10 +120,10 @@ struct TraceArgs {
     uint32_t *tile_cost;        // optional [nframes][ntiles][2]: largest primary / shadow step count per tile (stack kernel)
     const uint32_t *tile_order; // optional [ntiles]: the order in which a frame's tiles are handed out (stack kernel)
     const float *tmax;          // svo_trace_segments: [n] far end per ray (list mode; read by the bounded instantiations only).  Last but one: no other field moves
-    int32_t  light_clear;       // stack kernel, LIGHT_CLEAR_*: a shadow ray retires at an EMPTY entry that carries WIDE_CLEAR_BIT / is settled at its primary hit by the brick's flag (device.hip use_light_clearance decides)
+    int32_t  light_clear;       // stack kernel, LIGHT_CLEAR_*: a shadow ray retires at an EMPTY entry that carries WIDE_CLEAR_BIT / is settled at its primary hit by the brick's flag (light_gate.h decides)
 };
-// LIGHT_CLEAR_DARK (device.hip use_dark_birth decides, on its own): a shadow ray whose origin lies in an occupied cell of the hit brick is
-// settled "shadowed" at its primary hit; it needs no prepared light and no bit of the pools
+// LIGHT_CLEAR_DARK (light_gate.h decides it with the other two, from premises of its own): a shadow ray whose origin lies in an occupied cell
+// of the hit brick is settled "shadowed" at its primary hit; it needs no prepared light and no bit of the pools
 enum : int32_t { LIGHT_CLEAR_NODES = 1, LIGHT_CLEAR_BRICKS = 2, LIGHT_CLEAR_DARK = 4 };
 
 } // namespace svo

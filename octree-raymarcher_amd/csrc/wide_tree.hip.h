@@ -32,6 +32,11 @@ constexpr uint32_t WIDE_LEVEL_SHIFT = 25, WIDE_LEVEL_BITS = 5, WIDE_PAYLOAD_MASK
 constexpr uint32_t WIDE_CLEAR_BIT = 1u;          // payload bit 0 of an EMPTY terminal: the way from this node to the prepared light is clear (light_clearance.hip.h)
 constexpr uint32_t WIDE_MAX_LEVELS = 22;        // branch levels the stack kernel marches (chunk depth <= 24: cell coordinates stay exact floats)
 
+// nw: the wide levels of a chunk of `levels` branch levels
+__host__ __device__ constexpr int wide_levels(int levels) { return levels ? (levels + 1) >> 1 : 1; }
+// the level of the reference node a terminal entry stands for
+__host__ __device__ constexpr uint32_t wide_entry_level(uint32_t word) { return (word >> WIDE_LEVEL_SHIFT) & ((1u << WIDE_LEVEL_BITS) - 1u); }
+
 __device__ __forceinline__ uint32_t wide_terminal(uint32_t word, uint32_t level)
 {   // word: a reference node word that is not a BRANCH
     const uint32_t type = node_type(word);

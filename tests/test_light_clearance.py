@@ -155,9 +155,16 @@ def test_another_light_than_the_prepared_one(svo, oracle):
     assert_gbuffer_equal(march(svo, W, cams, b), want_of(oracle, O, cams, b), "prepared for A, traced with B")
     assert W.prepared_light()[0][2] == 0.0                  # still A's
     check(svo, oracle, O, W, b, "light B")
-    assert_gbuffer_equal(march(svo, W, cams, a), want_of(oracle, O, cams, a), "prepared for B, traced with A")
-    W.prepare_light((1.0, -1.0, 1e-4))                      # a component below 1/64: accepted, never used
+    want_a = want_of(oracle, O, cams, a)
+    assert_gbuffer_equal(march(svo, W, cams, a), want_a, "prepared for B, traced with A")
+    grazing = (1.0, -1.0, 1e-4)
+    W.prepare_light(grazing)                                # a component below 1/64: accepted, never used
     assert W.prepared_light()[1] == 0
+    sdir = W.prepared_light()[0]                            # prepared and unused: the direction is kept, nothing was decided
+    assert np.array_equal(np.array(sdir, np.float32), np.array(ob_sdir(grazing), np.float32))
+    assert W.prepared_bricks() == 0
+    assert_gbuffer_equal(march(svo, W, cams[:1], a), want_a[:W_IMG * H_IMG], "prepared and unused, traced with A")
+    assert W.prepared_light()[0] == sdir, "a launch has prepared a world that was prepared and unused"
     W.destroy()
 
 
