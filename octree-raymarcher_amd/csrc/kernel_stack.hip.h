@@ -40,6 +40,7 @@
 //  * The step itself is one hand-scheduled asm statement that runs the steps of a pass (step_asm.hip.h; the C++ step below
 //    is the readable statement of the same algorithm, built with -DSVO_CXX_STEP): what a wave-step costs is its chain of
 //    dependent loads and the instructions between them, and that chain is what the statement is arranged around.
+//  * The chunk step is a second hand-scheduled statement (chunk_step_asm.hip.h; its C++ block below is built with -DSVO_CXX_STEP as well).
 //  * Lane state is kept small (re-basing points pw/pt and the node box are recomputed with the
 //    reference's own expressions instead of being held): 80 VGPRs, 6 waves per SIMD, no spill inside the pass loop.
 //  * The chunk table of worlds of up to 64 chunks sits in LDS: the chunk step waits for no global load.
@@ -54,6 +55,7 @@
 #pragma once
 #include "march.hip.h"
 #include "step_asm.hip.h"
+#include "chunk_step_asm.hip.h"
 
 namespace svo {
 
@@ -414,6 +416,11 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
     const uint32_t lds_lane = (uint32_t)(size_t)(__attribute__((address_space(3))) uint32_t *)&stk[0][lane];
     StepUniform SU;
     SU.csize = csize; SU.eps = eps; SU.eps2 = 2.0f * eps; SU.cap_twig = A.cap_twig; SU.wide = A.wide; SU.mask = A.mask; SU.descend_shift = MAXLV <= 10 ? DESCEND_SHIFT_SHALLOW : DESCEND_SHIFT_DEEP;
+    // ... and the chunk step's (chunk_step_asm.hip.h)
+    const uint32_t lds_tab = (uint32_t)(size_t)(__attribute__((address_space(3))) uint32_t *)&chunk_tab[0][0];
+    ChunkStepUniform CU;
+    CU.wlo = wlo; CU.whi = whi; CU.csize = csize; CU.eps = eps; CU.cap_chunk = A.cap_chunk; CU.cap_tree = A.cap_tree; CU.wide = A.wide;
+    CU.kernarg = __builtin_amdgcn_kernarg_segment_ptr();
 #endif
     // creeping rays: |creepn| = consecutive advances of this ray by less than 2 EPS (kept across level changes: a ray pinned
     // on a chunk face creeps at every level); > 0 only while the cell located last is known to be empty (creep block armed)
@@ -554,6 +561,22 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
         // (the votes are wave-uniform: a scalar branch over a block that does not run - folded into the lane mask, a pass without the
         // block paid the mask's scalar arithmetic and an EXEC round trip; the empty statement keeps the two tests apart)
         if (SVO_LIKELY(run_world)) { asm volatile("");
+#ifndef SVO_CXX_STEP
+        // (chunk_step_asm.hip.h) the block below as one statement - the only place that writes the chunk's lane registers; the rays
+        // that end here come back as a mask, their records are stored behind it
+        const ChunkGrid G = chunk_grid;                 // (two LDS reads at a uniform address)
+        const unsigned long long missed = ChunkStepAsm<BIG, GLSL, SEG>::template run<CHUNK_TAB>(
+            mode, tw, cw, ci, valid, pux, puy, puz, clo, wide_b, twig_off, levels, O, t, cnt, Blo, res, bsize, res_tree, nw_chunk,
+            alpha, beta, g, far, G.inv, G.off[0], G.off[1], G.off[2], G.dimw, G.dimh, G.dimd,
+            (uint32_t)__builtin_amdgcn_readfirstlane((int)G.table_in_lds), lds_tab, CU);
+        if (__builtin_amdgcn_inverse_ballot_w64(missed)) {        // (the mask is the branch's EXEC: no lane value is formed)
+            int k = outk;
+            asm("" : "+v"(k));                      // (a value of its own: the record's 64-bit index is formed here, not held as a pair across the loop)
+            if (k >= 0) store_miss(A.out, k, 0);
+            if (want_cost) note_tile_cost(k, guard);
+            mode = M_DONE;                          // shadow miss: record already says "traced, lit"
+        }
+#else
         if (mode == M_WORLD) {
             if (cw < 0) {                               // left its chunk in the step: t += escape(chunk box) + EPS, src/Traverse.cpp:164-168
                 cw &= ~CW_ESCAPE_PENDING;
@@ -614,7 +637,9 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
                 if (want_cost) note_tile_cost(outk, guard);
                 mode = M_DONE;                          // shadow miss: record already says "traced, lit"
             }
-        } }
+        }
+#endif
+        }
 
         // ---- one step of the current level: tree (src/Traverse.cpp:79-111) or brick (:54-70) -----
         //      First decide what the step does (locate the cell, read its node / mask bit), then apply exactly one of
