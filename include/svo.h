@@ -54,6 +54,10 @@
  *   svo_world_edit_ball_all <- (no counterpart; the reference edits cubes only) one ball to every chunk whose box it touches
  *   svo_trace_local_shadows <- (a departure: the reference gives the directional light's shadow term to all three lights,
  *                           shaders/World.Fragment.glsl:186-190) one occlusion ray per hit towards the point light and the spotlight
+ *   svo_trace_lights     <- (a departure: the reference has three lights, src/Main.cpp:101-131) up to 32 point lights with a reach
+ *                           each, one occlusion ray per hit and light that can reach it, in one compacted ray list
+ *   svo_shade_lights     <- (a departure, with it) computePointLight_BlinnPhong (shaders/World.Fragment.glsl:80-97) per light of
+ *                           the list, windowed to the reach, added to the shaded image
  *   svo_shadowmap_render <- World::draw_shadowmap under the OrthoCamera (src/World.cpp:162-203, shaders/ShadowmapWorld.Fragment.glsl,
  *                           src/Main.cpp:149,190-198): the world marched once from the directional light into a depth image
  *   svo_shadowmap_apply  <- computeShadow                          shaders/World.Fragment.glsl:140-155,186
@@ -118,7 +122,8 @@ extern "C" {
                                           svo_trace_reflections, svo_shade_reflections and svo_mirror,
                                           svo_world_prepare_light, svo_world_prepared_light and SVO_SHADOW_NO_CLEARANCE (a bit of
                                           svo_trace_params.shadow, which was any non-zero value: such callers keep their results),
-                                          svo_world_prepared_bricks and SVO_SHADOW_NO_BRICK_CLEARANCE (another such bit) */
+                                          svo_world_prepared_bricks and SVO_SHADOW_NO_BRICK_CLEARANCE (another such bit),
+                                          svo_trace_lights, svo_shade_lights, svo_light and SVO_MAX_LIGHTS */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -929,6 +934,76 @@ int svo_shade_reflections(const svo_camera *cam, const svo_shade_params *p, cons
                           int x0, int y0, int w, int h,
                           const svo_hit *gbuffer_dev, const svo_voxel *voxels_dev, const svo_hit *reflect_dev,
                           float *rgba_dev, void *stream);
+
+/* ---- light lists: up to 32 point lights, each with a reach ---------------------------------------------------
+ * svo_shade has the reference's three lights, and svo_trace_local_shadows gives the two local ones a padded list of one ray per
+ * pixel and light.  A world lit by torches and lamps has dozens of small lights, each reaching a few percent of the screen:
+ * svo_trace_lights marches one occlusion ray per hit and light THAT CAN REACH IT, all of them in one compacted list, and
+ * svo_shade_lights adds the lights to an image a svo_shade* call has written.  Not in the reference: an opt-in departure. */
+#define SVO_MAX_LIGHTS 32
+typedef struct svo_light {          /* 64 bytes */
+    float position[3]; float reach;      /* reach > 0, finite: beyond it the light adds nothing and casts no ray */
+    float ambient[3];  float constant;
+    float diffuse[3];  float linear;
+    float specular[3]; float quadratic;  /* attenuation 1 / (constant + linear d + quadratic d^2), as svo_shade_params.point */
+} svo_light;
+
+/* One word per pixel: bit j of visible_dev[k] is set iff light j reaches pixel k's hit unoccluded.  `lights` is a host array of
+ * nlights lights (1..SVO_MAX_LIGHTS); gbuffer_dev holds the w*h records that svo_trace(cam, params, x0, y0, w, h) wrote (or the
+ * surface records of svo_trace_translucent, or any records of the caller's) and is not written; visible_dev receives w*h words.
+ * Every operation is in float and separately rounded; pixels k are row-major in the rectangle; eps is the launch's (0 = 1/8192,
+ * 1/4096 under SVO_SEMANTICS_GLSL), as in svo_trace_local_shadows.  For pixel k with SVO_HIT_FLAG and without SVO_ERR_FLAG and
+ * light j at L with reach R:
+ *   P = o + d * (t - eps)   (o, d) the pixel's camera ray: the point the directional shadow ray starts from;
+ *   v = L - P, q = v.x*v.x + v.y*v.y + v.z*v.z (left to right); q == 0 or not finite: no pair;
+ *   in reach   q <= R2, R2 = R * R in float (an R2 that overflows to +inf is legal: everything is in reach);
+ *   facing     s = n.x*v.x + n.y*v.y + n.z*v.z (left to right), n the record's normal as it stands; the test is !(s <= 0), so a
+ *              NaN normal (the SVO_NORMAL_CUBE hits whose integer vector is zero) faces every light;
+ *   (k, j) is a PAIR iff the hit is usable, in reach and facing.  Its ray is (P, v * (1 / sqrtf(q))); it is OCCLUDED iff that ray's
+ *   record, marched as svo_trace_rays marches it with `params` and shadow = 0 (eps, caps, semantics, kernel and see_through are
+ *   honoured), has SVO_HIT_FLAG, has no SVO_ERR_FLAG and its t < sqrtf(q) - svo_trace_local_shadows' rule word for word: terrain
+ *   behind the light does not shadow it, a runaway ray is not occluded.
+ * Order and capacity: the pairs are ranked light-major - all pairs of light 0 in ascending k, then light 1, and so on -, so the 64
+ * rays of a wave converge on one light.  cap = max_rays > 0 ? max_rays : w*h.  Pair r occupies slot r of the list if r < cap; pairs
+ * with r >= cap are DROPPED: not marched, and they count as not occluded (the library's rule for a ray it did not resolve).  Slots
+ * from the number of pairs up to cap hold a ray that misses the world.  ONE svo_trace_rays launch of cap rays marches the list
+ * (svo_trace_last_ray_count then reports cap).  No host synchronisation is made and the host never learns the number of pairs:
+ * that is the point of the cap.
+ *   visible_dev[k]  bit j set iff (k, j) is a pair and not occluded; every other bit, and the word of a pixel without a usable hit, is 0;
+ *   count_dev       optional (NULL): two uint32 on the device, [0] the number of pairs, [1] min(pairs, cap) - a caller feeds [0]
+ *                   into the next frame's max_rays, as it does with svo_tile_order's costs.
+ * In this order, all before any device work: a NULL world, cam, params, lights, gbuffer_dev or visible_dev, nlights outside
+ * 1..SVO_MAX_LIGHTS, max_rays < 0, a rectangle that starts or extends backwards, a position that is not finite, a reach that is not
+ * > 0 or not finite: SVO_ERR_INVALID_ARG; then what svo_trace refuses in params and a world that is not resident
+ * (SVO_ERR_NOT_UPLOADED); then w*h == 0: SVO_OK; nlights * w*h > 0x7FFFFFFF or cap > 0x7FFFFFFF: SVO_ERR_UNSUPPORTED.
+ * Asynchronous on `stream`.  The list, its records and the ranks live in the world's scratch, 56 bytes per slot plus 8 bytes per
+ * light and block of 256 pixels; calls of one world on different streams are ordered behind one another on the device. */
+int svo_trace_lights(svo_world *, const svo_camera *cam, const svo_trace_params *params,
+                     const svo_light *lights, int nlights, int64_t max_rays,
+                     int x0, int y0, int w, int h, const svo_hit *gbuffer_dev,
+                     uint32_t *visible_dev, uint32_t *count_dev, void *stream);
+
+/* The lights of a list added to an image that a svo_shade* call has written for the same rectangle (as svo_shade_ao and
+ * svo_shade_reflections work over the image): for every record with SVO_HIT_FLAG, rgb += sum over j of C_j.  The depth float, the
+ * misses and everything beyond w*h pixels are not written.  visible_dev (svo_trace_lights' words) == NULL: every light is
+ * unshadowed.  Albedo (the material table's), shininess, eps and gamma come from p exactly as svo_shade uses them; p's own three
+ * lights are ignored.  With pt = eye + beta * (t - eps), lv = L - pt, d = |lv|, l = lv / d, and vdir, hv as in
+ * computePointLight_BlinnPhong (shaders/World.Fragment.glsl:80-97):
+ *   if !(d > 0) or !(d < reach): C_j = 0
+ *   win = clamp(1 - (d / reach)^4, 0, 1)^2          the contribution falls to 0 at the reach, continuously
+ *   att = win / (constant + linear d + quadratic d d)
+ *   vis = bit j of visible_dev[k] ? 1 : 0
+ *   C_j = ((ambient * diffuse_albedo + diffuse * max(n.l, 0) * diffuse_albedo * vis)
+ *          + specular * pow(max(vdir.hv, 0), shininess) * specular_albedo * vis) * att
+ * The window is what lets svo_trace_lights cull by reach without a seam: outside the reach nothing is added whatever the bit says
+ * (such a pixel keeps its bits), and the boundary pixel's contribution is about 0 in both stages.  A NaN normal gives NaN colours, as
+ * in svo_shade.  In the stage's arithmetic (compared with a tolerance, not bit for bit).
+ * A NULL cam, p, lights, gbuffer_dev or rgba_dev, nlights outside 1..SVO_MAX_LIGHTS, a rectangle that starts or extends backwards:
+ * SVO_ERR_INVALID_ARG; a rectangle too large for one launch: SVO_ERR_UNSUPPORTED; an empty one: SVO_OK.  All before HIP is touched.
+ * Asynchronous on `stream`.  In a frame: svo_shade* -> svo_trace_lights -> svo_shade_lights -> svo_shade_ao, sky, boxes, RGBA8. */
+int svo_shade_lights(const svo_camera *cam, const svo_shade_params *p, const svo_light *lights, int nlights,
+                     int x0, int y0, int w, int h, const svo_hit *gbuffer_dev, const uint32_t *visible_dev,
+                     float *rgba_dev, void *stream);
 
 /* ---- the edit cursor and the light markers: cubes over the finished image ----------------------------------
  * One overlay record, 48 bytes, on the device.  The reference has four: the cursor cube (ImagCube: translucent grey, black edges) and one

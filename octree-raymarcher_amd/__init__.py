@@ -9,6 +9,7 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     World.chunkmarch(origins, dirs)           <- chunkmarch             src/Traverse.cpp:127-171
     World.draw_translucent(camera, m)         <- ParallaxAlpha's march past water   shaders/ParallaxAlpha.Fragment.glsl:141-199,276-335
     World.trace_local_shadows(camera, ...)    <- (none: the reference's three lights share the directional light's shadow term)
+    World.trace_lights, shade_lights, Light   <- (none: the reference has three lights)    up to 32 point lights with a reach, one compacted ray list
     World.shadowmap_fit / shadowmap_render, shadowmap_apply   <- OrthoCamera, World::draw_shadowmap, computeShadow   src/World.cpp:162-203, shaders/World.Fragment.glsl:140-155
     World.index / index_float                 <- World::index(_float)   src/World.cpp:288-293,323-332
     World.locate / locate_points              <- traverse               src/Traverse.cpp:34-48 (the voxel under each point)
@@ -70,6 +71,7 @@ CELL_NONE = 0xFF
 SKY_LINEAR, SKY_NEAREST = 0, 1                           # svo_sky.filter
 BOX_SOLID, BOX_CURSOR, BOX_HIDDEN = 0, 1, 1 << 8         # svo_box.style
 MAX_BOXES = 64                                           # SVO_MAX_BOXES
+MAX_LIGHTS = 32                                          # SVO_MAX_LIGHTS
 BOX_DTYPE = np.dtype([("bmin", "<f4", (3,)), ("size", "<f4"), ("color", "<f4", (3,)), ("alpha", "<f4"), ("style", "<u4"), ("_pad", "<u4", (3,))])
 assert BOX_DTYPE.itemsize == 48
 
@@ -177,6 +179,19 @@ class Mirror(C.Structure):
             self.sky = C.pointer(sky)
 
 
+class Light(C.Structure):
+    """svo_light: one point light of a light list (64 bytes).  Light(position, reach, ambient, diffuse, specular, attenuation)."""
+    _fields_ = [("position", C.c_float * 3), ("reach", C.c_float), ("ambient", C.c_float * 3), ("constant", C.c_float),
+                ("diffuse", C.c_float * 3), ("linear", C.c_float), ("specular", C.c_float * 3), ("quadratic", C.c_float)]
+
+    def __init__(self, position=(0.0, 0.0, 0.0), reach: float = 0.0, ambient=(0.0, 0.0, 0.0), diffuse=(0.0, 0.0, 0.0), specular=(0.0, 0.0, 0.0),
+                 attenuation=(1.0, 0.0, 0.0)):
+        super().__init__()
+        self.position[:], self.reach = [float(c) for c in position], float(reach)
+        self.ambient[:], self.diffuse[:], self.specular[:] = ([float(c) for c in v] for v in (ambient, diffuse, specular))
+        self.constant, self.linear, self.quadratic = (float(c) for c in attenuation)
+
+
 class Box(C.Structure):
     """svo_box: one overlay cube of svo_shade_boxes (48 bytes; BOX_DTYPE is its numpy twin)."""
     _fields_ = [("bmin", C.c_float * 3), ("size", C.c_float), ("color", C.c_float * 3), ("alpha", C.c_float), ("style", C.c_uint32),
@@ -202,7 +217,7 @@ ABI_SYMBOLS = [
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_edit_cube", "svo_world_edit_ball", "svo_world_edit_ball_all", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_cursor_place", "svo_shade_boxes", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_shadowmap_fit", "svo_shadowmap_render", "svo_shadowmap_apply", "svo_hit_ao", "svo_shade_ao",
-    "svo_trace_reflections", "svo_shade_reflections", "svo_world_prepare_light", "svo_world_prepared_light", "svo_world_prepared_bricks",
+    "svo_trace_reflections", "svo_shade_reflections", "svo_trace_lights", "svo_shade_lights", "svo_world_prepare_light", "svo_world_prepared_light", "svo_world_prepared_bricks",
     "svo_device_count", "svo_device_alloc", "svo_device_free", "svo_device_cache_trim", "svo_memcpy_h2d", "svo_memcpy_d2h",
     "svo_stream_synchronize", "svo_last_error", "svo_abi_version",
 ]
@@ -264,6 +279,9 @@ lib.svo_hit_ao.argtypes = [_P, C.POINTER(Camera), C.POINTER(TraceParams), C.c_fl
 lib.svo_shade_ao.argtypes = [_P, C.c_float, C.c_int64, _P, _P]
 lib.svo_trace_reflections.argtypes = [_P, C.POINTER(Camera), C.POINTER(TraceParams), C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
 lib.svo_shade_reflections.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams), C.POINTER(Mirror), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]
+lib.svo_trace_lights.argtypes = [_P, C.POINTER(Camera), C.POINTER(TraceParams), C.POINTER(Light), C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 _P, _P, _P, _P]
+lib.svo_shade_lights.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams), C.POINTER(Light), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
 lib.svo_shade_sky.argtypes = [C.POINTER(Camera), C.POINTER(Sky), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
 lib.svo_frame_rgba8.argtypes = [_P, C.c_int64, _P, _P]
 lib.svo_cursor_place.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), _P, C.c_float, _P, _P]
@@ -515,6 +533,26 @@ def shade_reflections(cam: Camera, params: ShadeParams, mirror: Mirror, rect, gb
     _check(lib.svo_shade_reflections(C.byref(cam) if cam is not None else None, C.byref(params) if params is not None else None,
                                      C.byref(mirror) if mirror is not None else None, x0, y0, w, h, gbuffer_ptr, voxels_ptr, reflect_ptr, rgba_ptr,
                                      stream), "svo_shade_reflections")
+
+
+def light_array(lights):
+    """A sequence of Light as the contiguous svo_light array the light-list calls take (None stays None); (array, count)."""
+    if lights is None:
+        return None, 0
+    lights = list(lights)
+    arr = (Light * max(len(lights), 1))()
+    for j, l in enumerate(lights):
+        C.memmove(C.byref(arr, j * C.sizeof(Light)), C.byref(l), C.sizeof(Light))
+    return arr, len(lights)
+
+
+def shade_lights(cam: Camera, params: ShadeParams, rect, gbuffer_ptr: int, lights, rgba_ptr: int, visible_ptr: Optional[int] = None, stream: int = 0):
+    """svo_shade_lights: the point lights of `lights` (a sequence of Light), each windowed to its reach, added to the image a shade call
+    wrote for the same records; visible_ptr: the words World.trace_lights wrote (None: every light unshadowed).  Before shade_ao."""
+    x0, y0, w, h = rect
+    arr, n = light_array(lights)
+    _check(lib.svo_shade_lights(C.byref(cam) if cam is not None else None, C.byref(params) if params is not None else None, arr, n,
+                                x0, y0, w, h, gbuffer_ptr, visible_ptr, rgba_ptr, stream), "svo_shade_lights")
 
 
 def frame_rgba8(rgba_ptr: int, n: int, out_ptr: int, stream: int = 0):
@@ -792,6 +830,16 @@ class World:
         vec = [None if v is None else (C.c_float * 3)(*[float(c) for c in v]) for v in (point, spot)]
         _check(lib.svo_trace_local_shadows(self._h, C.byref(cam) if cam is not None else None, C.byref(params) if params is not None else None,
                                            vec[0], vec[1], x0, y0, w, h, gbuffer_ptr, stream), "svo_trace_local_shadows")
+
+    def trace_lights(self, cam: Camera, params: TraceParams, rect, gbuffer_ptr: int, lights, visible_ptr: int, max_rays: int = 0, count_ptr: int = 0,
+                     stream: int = 0):
+        """svo_trace_lights on the G-buffer svo_trace(cam, params, rect) filled: one word per pixel into visible_ptr, bit j set where
+        light j of `lights` (a sequence of Light) reaches the hit unoccluded.  max_rays: the capacity of the compacted ray list (0 = one
+        slot per pixel); count_ptr: two uint32 on the device, (pairs, min(pairs, capacity))."""
+        x0, y0, w, h = rect
+        arr, n = light_array(lights)
+        _check(lib.svo_trace_lights(self._h, C.byref(cam) if cam is not None else None, C.byref(params) if params is not None else None, arr, n,
+                                    int(max_rays), x0, y0, w, h, gbuffer_ptr, visible_ptr, count_ptr or None, stream), "svo_trace_lights")
 
     def shadowmap_fit(self, direction, width: int, height: int, smap: Optional[ShadowMap] = None) -> ShadowMap:
         """svo_shadowmap_fit: a map of width x height texels that holds the whole world box, seen along `direction`; depth_dev of

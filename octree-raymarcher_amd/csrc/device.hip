@@ -29,6 +29,7 @@
 #include "kernel_stack.hip.h"
 #include "see_through.hip.h"
 #include "local_shadows.hip.h"
+#include "light_list.hip.h"
 #include "reflect.hip.h"
 #include "shadowmap.hip.h"
 #include "locate.hip.h"
@@ -1183,6 +1184,61 @@ int svo_trace_local_shadows(svo_world *w, const svo_camera *cam, const svo_trace
         if (rc != SVO_OK) return rc;
         return launch_per_element("svo_trace_local_shadows", n, s, k_local_resolve, F, A.eps, L, reinterpret_cast<const uint4 *>(list.records),
                                   reinterpret_cast<uint4 *>(gbuffer_dev));
+    });
+}
+
+// A list of point lights (light_list.hip.h): the candidate masks and their counts, the scan that ranks the pairs light-major, the
+// compacted ray list, ONE ray-list launch of `cap` rays - the host never learns how many pairs there are -, the fold into one word
+// per pixel.  The scratch: the RayList of cap slots, then the [light][block] counts, their exclusive sums, the two totals, the scan's own.
+int svo_trace_lights(svo_world *w, const svo_camera *cam, const svo_trace_params *prm, const svo_light *lights, int nlights, int64_t max_rays,
+                     int x0, int y0, int rw, int rh, const svo_hit *gbuffer_dev, uint32_t *visible_dev, uint32_t *count_dev, void *stream)
+{
+    if (!w || !prm || !lights || !gbuffer_dev || !visible_dev || nlights < 1 || nlights > MAX_LIGHTS || max_rays < 0 || !rect_ok(cam, x0, y0, rw, rh)) {
+        set_error("svo_trace_lights: bad argument"); return SVO_ERR_INVALID_ARG;
+    }
+    LightList L;
+    std::memset(&L, 0, sizeof L);
+    for (int j = 0; j < nlights; ++j) {
+        const svo_light &l = lights[j];
+        if (!std::isfinite(l.position[0]) || !std::isfinite(l.position[1]) || !std::isfinite(l.position[2]) || !(l.reach > 0.0f && l.reach < INFINITY)) {
+            set_error("svo_trace_lights: a light's position is not finite, or its reach is not a finite number above 0"); return SVO_ERR_INVALID_ARG;
+        }
+        std::memcpy(L.pos[j], l.position, sizeof L.pos[j]);
+        L.reach2[j] = l.reach * l.reach;
+    }
+    L.count = nlights;
+    TraceArgs A;                                                        // (for the launch's resolved eps; checks see_through, semantics and residency)
+    int rc = fill_common(w, prm, A);
+    if (rc != SVO_OK) return rc;
+    const int64_t n = (int64_t)rw * rh, cap = max_rays > 0 ? max_rays : n;
+    if (n == 0) return SVO_OK;
+    if (n * nlights > 0x7FFFFFFF || cap > 0x7FFFFFFF) { set_error("svo_trace_lights: image or list too large"); return SVO_ERR_UNSUPPORTED; }
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(w->device));
+    const uint32_t nblocks = blocks_for((uint64_t)n, LIGHT_BLOCK), items = nblocks * (uint32_t)nlights;
+    size_t scan_bytes = 0;
+    uint32_t *nul = nullptr;
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, nul, nul, (int)items, s) != hipSuccess) { set_error("svo_trace_lights: scan size query failed"); return SVO_ERR_HIP; }
+    const size_t list_words = RayList::floats(cap, true), head_words = (list_words + 2 * (size_t)items + 2 + 63) / 64 * 64;
+    // the records, the list and the ranks live in the world's scratch: calls on different streams are ordered behind one another
+    return w->hbm->lights.use(head_words + (scan_bytes + 3) / 4 + 64, "svo_trace_lights", s, [&](float *scratch) -> int {
+        const RayList list(scratch, cap, true);
+        uint32_t *counts = reinterpret_cast<uint32_t *>(scratch + list_words), *base = counts + items, *total = base + items;
+        const PixelFrame F = make_frame(*cam, x0, y0, rw, rh);
+        const uint4 *gbuffer = reinterpret_cast<const uint4 *>(gbuffer_dev);
+        const char *who = "svo_trace_lights";
+        int rc = launch_per_element(who, n, s, k_light_cull, F, A.eps, L, gbuffer, visible_dev, counts, nblocks);
+        if (rc != SVO_OK) return rc;
+        if (hipcub::DeviceScan::ExclusiveSum(scratch + head_words, scan_bytes, counts, base, (int)items, s) != hipSuccess) { set_error("svo_trace_lights: scan failed"); return SVO_ERR_HIP; }
+        hipLaunchKernelGGL(k_light_total, dim3(1), dim3(1), 0, s, counts, base, items, (uint32_t)cap, total, count_dev);
+        if ((rc = launch_status(who)) != SVO_OK) return rc;
+        rc = launch_per_element(who, n, s, k_light_emit, F, A.eps, L, miss_ray_origin(w), gbuffer, visible_dev, base, nblocks, total, (uint32_t)cap, list.origins, list.dirs);
+        if (rc != SVO_OK) return rc;
+        const svo_trace_params march = own_list_params(*prm, false);
+        // (unbounded on purpose, as svo_trace_local_shadows' launch is: DESIGN.md 6g)
+        rc = svo_trace_rays(w, list.origins, list.dirs, cap, &march, reinterpret_cast<svo_hit *>(list.records), stream);
+        if (rc != SVO_OK) return rc;
+        return launch_per_element(who, n, s, k_light_resolve, F, A.eps, L, gbuffer, base, nblocks, (uint32_t)cap, reinterpret_cast<const uint4 *>(list.records), visible_dev);
     });
 }
 

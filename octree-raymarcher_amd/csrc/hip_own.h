@@ -206,6 +206,7 @@ struct Hbm {
     OrderedScratch<float> cont;                             // svo_trace_translucent: a RayList without records, one ray per pixel
     OrderedScratch<float> mirror;                           // svo_trace_reflections: a RayList without records, one ray per pixel
     OrderedScratch<float> local;                            // svo_trace_local_shadows: a RayList with records, one ray per pixel and light asked for
+    OrderedScratch<float> lights;                           // svo_trace_lights: a RayList with records of `cap` slots, the block counts, their sums, the scan's own
     OrderedScratch<float> shadowmap;                        // svo_shadowmap_render: a RayList with records, one ray per texel in tile order
     // see-through view (svo_trace_params.see_through, see_through.hip.h): the wide and mask pools with one material taken out, built
     // on the device at the first launch that asks for it, dropped by every change to the pools

@@ -287,6 +287,62 @@ __global__ __launch_bounds__(256) void k_shade_reflections(ShadeArgs A, MirrorAr
     px[0] = px[0] * keep + C.x * F; px[1] = px[1] * keep + C.y * F; px[2] = px[2] * keep + C.z * F;
 }
 
+// svo_shade_lights: computePointLight_BlinnPhong (:80-97, the point-light block of shade_ray) for every light of a list, each windowed
+// to its reach and with its own bit of the pixel's word for the shadow factor, added to the pixel.  A pixel no light reaches is not written.
+struct ListLights {
+    svo_light light[SVO_MAX_LIGHTS];
+    float inv_reach[SVO_MAX_LIGHTS];            // 1 / reach, made on the host
+    int32_t count;
+};
+
+__global__ __launch_bounds__(256) void k_shade_lights(ShadeArgs A, ListLights L, const uint32_t *visible)
+{
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= A.frame.count()) return;
+    const HitRecord h = load_hit(A.gbuffer, k);
+    if (!(h.flags & SVO_HIT_FLAG)) return;
+    const FrameCam &cam = A.frame.cam;
+    int px, py;
+    A.frame.pixel(k, px, py);                   // the ray as shade_hit makes it, the point and the view vector as shade_ray does
+    const float fx = (float)px + 0.5f, fy = (float)py + 0.5f;
+    const float u = ((fx * A.inv_imgw) * 2.0f - 1.0f) * cam.tanx;
+    const float v = (1.0f - (fy * A.inv_imgh) * 2.0f) * cam.tany;
+    const V3 eye = ld3(cam.eye), beta = normalize_fast((ld3(cam.fwd) + ld3(cam.right) * u) + ld3(cam.up) * v);
+    const float sdist = h.t - A.P.eps;
+    const V3 p = eye + beta * sdist;
+    const V3 vdir = sdist > 1.0e-3f ? mk(-beta.x, -beta.y, -beta.z) : normalize_fast(eye - p);
+    const int mi = material_index(h.material);
+    const float shininess = A.P.materials[mi].shininess;
+    const V3 diffuse = ld3(A.gdiffuse[mi]), specular = ld3(A.gspecular[mi]);
+    const uint32_t word = visible ? visible[k] : 0xFFFFFFFFu;
+    V3 sum = mk(0.0f, 0.0f, 0.0f);
+    bool reached = false;
+    for (int j = 0; j < L.count; ++j) {
+        const svo_light &Lj = L.light[j];
+        const V3 lv = ld3(Lj.position) - p;
+        const float l2 = dot3(lv, lv), il = __builtin_amdgcn_rsqf(l2), dist = l2 * il;
+        if (!(dist > 0.0f) || !(dist < Lj.reach)) continue;         // (l2 == 0 or inf: dist is NaN)
+        reached = true;
+        const V3 l = lv * il;
+        const V3 hv = normalize_fast(l + vdir);
+        const float d = maxf0(dot3(h.n, l));
+        const float s = pow_shiny(maxf0(dot3(vdir, hv)), shininess);
+        const float x = dist * L.inv_reach[j], x2 = x * x;
+        float win = 1.0f - x2 * x2;
+        win = (win < 0.0f) ? 0.0f : win;
+        win = (1.0f < win) ? 1.0f : win;
+        const float att = (win * win) * attenuation(Lj.constant, Lj.linear, Lj.quadratic, dist);
+        const float vis = ((word >> j) & 1u) ? 1.0f : 0.0f;
+        const V3 amb = ld3(Lj.ambient) * diffuse;
+        const V3 dif = ((ld3(Lj.diffuse) * d) * diffuse) * vis;
+        const V3 spe = ((ld3(Lj.specular) * s) * specular) * vis;
+        sum = sum + ((amb + dif) + spe) * att;
+    }
+    if (!reached) return;
+    float *out = reinterpret_cast<float *>(A.rgba + k);
+    out[0] = out[0] + sum.x; out[1] = out[1] + sum.y; out[2] = out[2] + sum.z;
+}
+
 } // namespace
 } // namespace svo
 
@@ -445,6 +501,21 @@ int svo_shade_reflections(const svo_camera *cam, const svo_shade_params *p, cons
     if (mirror->sky) { M.has_sky = 1; M.sky = sky_map(*mirror->sky); }
     return launch_per_element("svo_shade_reflections", n, (hipStream_t)stream, k_shade_reflections, A, M, reinterpret_cast<const uint4 *>(voxels_dev),
                               reinterpret_cast<const uint4 *>(reflect_dev));
+}
+
+// The lights of a list (svo_trace_lights' words for their shadow factors) added to an image a shade call has written
+int svo_shade_lights(const svo_camera *cam, const svo_shade_params *p, const svo_light *lights, int nlights, int x0, int y0, int w, int h,
+                     const svo_hit *gbuffer_dev, const uint32_t *visible_dev, float *rgba_dev, void *stream)
+{
+    if (!lights || nlights < 1 || nlights > SVO_MAX_LIGHTS) { set_error("svo_shade_lights: between 1 and 32 lights"); return SVO_ERR_INVALID_ARG; }
+    ShadeArgs A;
+    if (const int rc = shade_args(cam, p, x0, y0, w, h, gbuffer_dev, rgba_dev, A)) return rc;
+    ListLights L;
+    std::memset(&L, 0, sizeof L);
+    std::memcpy(L.light, lights, (size_t)nlights * sizeof(svo_light));
+    for (int j = 0; j < nlights; ++j) L.inv_reach[j] = 1.0f / lights[j].reach;
+    L.count = nlights;
+    return launch_per_element("svo_shade_lights", A.frame.count(), (hipStream_t)stream, k_shade_lights, A, L, visible_dev);
 }
 
 } // extern "C"

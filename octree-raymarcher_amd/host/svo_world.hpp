@@ -9,6 +9,7 @@
 //   svo::World::load_gpu()           <- World::load_gpu        src/World.cpp:57-94
 //   svo::World::draw(camera, ...)    <- World::draw (+ draw_shadowmap as the fused shadow ray)  src/World.cpp:162-266
 //   svo::World::local_shadows(...)   <- (none: per-light shadows of the point light and the spotlight, svo_trace_local_shadows)
+//   svo::World::lights / shade_lights  <- (none: the reference has three lights) up to 32 point lights with a reach, svo_trace_lights, svo_shade_lights
 //   svo::World::shadowmap_fit / shadowmap_render / shadowmap_apply  <- the OrthoCamera, World::draw_shadowmap and computeShadow (svo_shadowmap_*):
 //                                       the directional light rendered once, looked up per frame   src/World.cpp:162-203, shaders/World.Fragment.glsl:140-155
 //   svo::World::modify(i, ...)       <- World::modify          src/World.cpp:268-274
@@ -207,6 +208,27 @@ public:
         if (light_dir) std::memcpy(p.light_dir, light_dir, sizeof p.light_dir);
         check(svo_trace_local_shadows(world_, &cam, &p, point_position, spot_position, 0, 0, cam.width, cam.height, gbuffer.device(), stream),
               "World::local_shadows");
+    }
+
+    // A list of up to SVO_MAX_LIGHTS point lights with a reach each (not in the reference, which has three lights).  lights() marches one
+    // occlusion ray per hit of the G-buffer draw() filled and light that can reach it, all in one compacted list of max_rays slots (0 =
+    // one per pixel; pairs beyond it count as lit), and writes one word per pixel: bit j set where light j reaches the hit unoccluded
+    // (svo_trace_lights; count_dev, optional: the number of pairs, for the next frame's max_rays).  shade_lights adds the lights, windowed
+    // to their reach, to the image a shade call wrote (svo_shade_lights: behind svo_shade*, before shade_ao; visible_dev null = unshadowed).
+    void lights(const Camera &cam, const GBuffer &gbuffer, const svo_light *list, int nlights, uint32_t *visible_dev, int64_t max_rays = 0,
+                uint32_t *count_dev = nullptr, uint32_t see_through = 0, void *stream = nullptr)
+    {
+        svo_trace_params p;
+        std::memset(&p, 0, sizeof p);
+        p.semantics = semantics;
+        p.see_through = see_through;
+        check(svo_trace_lights(world_, &cam, &p, list, nlights, max_rays, 0, 0, cam.width, cam.height, gbuffer.device(), visible_dev, count_dev, stream),
+              "World::lights");
+    }
+    void shade_lights(const svo_camera &cam, const svo_shade_params &p, const svo_light *list, int nlights, int x0, int y0, int w, int h,
+                      const svo_hit *gbuffer_dev, const uint32_t *visible_dev, float *rgba_dev, void *stream = nullptr) const
+    {
+        check(svo_shade_lights(&cam, &p, list, nlights, x0, y0, w, h, gbuffer_dev, visible_dev, rgba_dev, stream), "World::shade_lights");
     }
 
     // The shadow map of a fixed sun (svo_shadowmap_fit / _render / _apply; the reference's World::draw_shadowmap and computeShadow,
