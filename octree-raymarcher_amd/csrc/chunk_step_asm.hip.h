@@ -1,6 +1,6 @@
 // chunk_step_asm.hip.h — the chunk step of k_trace_stack (src/Traverse.cpp:142-168), hand-scheduled for gfx950 (one asm statement).
 //
-// Same arithmetic, operand for operand and in the same order, as the C++ block in kernel_stack.hip.h (`if (mode == M_WORLD)`, which
+// Same arithmetic, operand for operand and in the same order, as the C++ twin in chunk_step_cxx.hip.h (`if (mode == M_WORLD)`, which
 // stays the readable statement of the algorithm and the A/B partner: -DSVO_CXX_STEP builds it); what differs is what the compiler
 // puts around it - a s_and_saveexec / s_or pair per source-level `if` (six of them nested), three box tests whose six compares are
 // and-ed through scalar chains, and 23 lane registers copied at the joins.  Here, in the idiom of step_asm.hip.h:

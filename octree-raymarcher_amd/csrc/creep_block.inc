@@ -125,9 +125,7 @@
                         O = fO;
                         Blo = clo;
                         res = csize * __uint_as_float((uint32_t)(127 - levels) << 23);
-#ifndef SVO_CXX_STEP
                         bsize = csize;
-#endif
                         mode = M_TREE;
                     }
                 } else if (K > 0) {

@@ -37,10 +37,10 @@
 //    launch's last waves are alone on their SIMD, bound by their own instruction stream.  Scalar instructions and
 //    branches cost a SIMD what vector instructions do (scripts/microbench/valu_issue.hip): the step avoids them
 //    where a select or an unconditional LDS read does the same.
-//  * The step itself is one hand-scheduled asm statement that runs the steps of a pass (step_asm.hip.h; the C++ step below
-//    is the readable statement of the same algorithm, built with -DSVO_CXX_STEP): what a wave-step costs is its chain of
+//  * The step itself is one hand-scheduled asm statement that runs the steps of a pass (step_asm.hip.h; the C++ step of
+//    step_cxx.hip.h is the readable statement of the same algorithm, built with -DSVO_CXX_STEP): what a wave-step costs is its chain of
 //    dependent loads and the instructions between them, and that chain is what the statement is arranged around.
-//  * The chunk step is a second hand-scheduled statement (chunk_step_asm.hip.h; its C++ block below is built with -DSVO_CXX_STEP as well).
+//  * The chunk step is a second hand-scheduled statement (chunk_step_asm.hip.h; its C++ twin, chunk_step_cxx.hip.h, is built with -DSVO_CXX_STEP as well).
 //  * Lane state is kept small (re-basing points pw/pt and the node box are recomputed with the
 //    reference's own expressions instead of being held): 80 VGPRs, 6 waves per SIMD, no spill inside the pass loop.
 //  * The chunk table of worlds of up to 64 chunks sits in LDS: the chunk step waits for no global load.
@@ -298,6 +298,36 @@ __device__ __forceinline__ bool past_far_end(int mode, float t, float tt_saved, 
     return (mode == M_TREE || mode == M_TWIG) && tw + (GLSL ? tt : tt - eps) >= far;
 }
 
+// ---- what the blocks below write more than once ------------------------------------------------------------------------
+
+// the flag word of a shadow ray that ends with `verdict` (SVO_SHADOWED, SVO_ERR_FLAG) instead of leaving its record "traced, lit"
+__device__ __forceinline__ uint32_t shadow_flags(int normal_mode, uint32_t verdict)
+{
+    return SVO_HIT_FLAG | SVO_SHADOW_TRACED | verdict | (normal_mode == SVO_NORMAL_FACE ? (uint32_t)SVO_FACE_NORMAL : 0u);
+}
+// the lane's ray has ended and its record is written: its step count goes to its tile's cost (if the launch asks for it)
+__device__ __forceinline__ void retire(int &mode, bool want_cost, int outk, uint32_t guard)
+{
+    if (want_cost) note_tile_cost(outk, guard);
+    mode = M_DONE;
+}
+
+} // namespace svo
+
+#include "chunk_step_cxx.hip.h"
+#include "step_cxx.hip.h"
+
+namespace svo {
+
+// The two steps: the hand-scheduled statements, or (-DSVO_CXX_STEP) their C++ twins, behind one name each.
+#ifdef SVO_CXX_STEP
+template <bool BIG, bool GLSL, bool SEG> using ChunkStep = ChunkStepCxx<BIG, GLSL, SEG>;
+#define SVO_MARCH_STEPS march_steps_cxx
+#else
+template <bool BIG, bool GLSL, bool SEG> using ChunkStep = ChunkStepAsm<BIG, GLSL, SEG>;
+#define SVO_MARCH_STEPS march_steps_asm
+#endif
+
 // BIG: the large-world instantiation - the chunk's wide tree is a 64-bit address per lane and the brick masks are addressed with
 // 64 bits (step_asm.hip.h: march_steps_asm<true, GLSL>), for wide pools of 4 GiB and more and mask pools of 2^29 bricks and more; the same
 // kernel otherwise, the same results.
@@ -327,7 +357,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
     stk[0][threadIdx.x] = 0u;              // o, d, 1/d, world-entry t, output index (as int; -1 = no ray)
     const int lane = threadIdx.x;
     const bool want_cost = A.tile_cost != nullptr;      // (one SGPR held; the blocks below must not re-read the kernel arguments for a feature that is off)
-    [[maybe_unused]] const bool light_clear = (A.light_clear & LIGHT_CLEAR_NODES) != 0;      // shadow rays retire at clear cells (light_clearance.hip.h); the C++ step ignores the bit, which is always right
+    const bool light_clear = (A.light_clear & LIGHT_CLEAR_NODES) != 0;      // shadow rays retire at clear cells (light_clearance.hip.h); the C++ step ignores the bit, which is always right
     const int n_chunks = A.dimw * A.dimh * A.dimd;
     const bool chunks_in_lds = n_chunks <= CHUNK_TAB;
     if (lane == 0) {
@@ -409,8 +439,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
     int pux = 0, puy = 0, puz = 0, valid = 0, plev = 0;
     // brick
     unsigned long long bmask = 0;
-#ifndef SVO_CXX_STEP
-    // step_asm.hip.h keeps the level's box edge and the chunk's wide-level count / tree-level pitch instead of deriving them per step
+    // the steps (step_asm.hip.h) keep the level's box edge and the chunk's wide-level count / tree-level pitch instead of deriving them per step
     float bsize = 0.0f, res_tree = 1.0f;
     int nw_chunk = 1;
     const uint32_t lds_lane = (uint32_t)(size_t)(__attribute__((address_space(3))) uint32_t *)&stk[0][lane];
@@ -421,7 +450,6 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
     ChunkStepUniform CU;
     CU.wlo = wlo; CU.whi = whi; CU.csize = csize; CU.eps = eps; CU.cap_chunk = A.cap_chunk; CU.cap_tree = A.cap_tree; CU.wide = A.wide;
     CU.kernarg = __builtin_amdgcn_kernarg_segment_ptr();
-#endif
     // creeping rays: |creepn| = consecutive advances of this ray by less than 2 EPS (kept across level changes: a ray pinned
     // on a chunk face creeps at every level); > 0 only while the cell located last is known to be empty (creep block armed)
     int creepn = 0;
@@ -549,7 +577,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
         const bool run_hit = n_hit >= (few_busy ? 1 : VOTE_HIT);
 
         if (SVO_UNLIKELY(mode != M_DONE && mode != M_HIT && ++guard > STEP_GUARD)) {     // runaway ray: give up, flag it
-            if (outk < 0) store_flags(A.out, outk & 0x7FFFFFFF, SVO_HIT_FLAG | SVO_SHADOW_TRACED | SVO_ERR_FLAG | (A.normal_mode == SVO_NORMAL_FACE ? (uint32_t)SVO_FACE_NORMAL : 0u));
+            if (outk < 0) store_flags(A.out, outk & 0x7FFFFFFF, shadow_flags(A.normal_mode, SVO_ERR_FLAG));
             else store_miss(A.out, outk, SVO_ERR_FLAG);
             mode = M_DONE;
         }
@@ -561,11 +589,10 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
         // (the votes are wave-uniform: a scalar branch over a block that does not run - folded into the lane mask, a pass without the
         // block paid the mask's scalar arithmetic and an EXEC round trip; the empty statement keeps the two tests apart)
         if (SVO_LIKELY(run_world)) { asm volatile("");
-#ifndef SVO_CXX_STEP
-        // (chunk_step_asm.hip.h) the block below as one statement - the only place that writes the chunk's lane registers; the rays
+        // (chunk_step_asm.hip.h, or its C++ twin) the step as one statement - the only place that writes the chunk's lane registers; the rays
         // that end here come back as a mask, their records are stored behind it
         const ChunkGrid G = chunk_grid;                 // (two LDS reads at a uniform address)
-        const unsigned long long missed = ChunkStepAsm<BIG, GLSL, SEG>::template run<CHUNK_TAB>(
+        const unsigned long long missed = ChunkStep<BIG, GLSL, SEG>::template run<CHUNK_TAB>(
             mode, tw, cw, ci, valid, pux, puy, puz, clo, wide_b, twig_off, levels, O, t, cnt, Blo, res, bsize, res_tree, nw_chunk,
             alpha, beta, g, far, G.inv, G.off[0], G.off[1], G.off[2], G.dimw, G.dimh, G.dimd,
             (uint32_t)__builtin_amdgcn_readfirstlane((int)G.table_in_lds), lds_tab, CU);
@@ -573,214 +600,31 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
             int k = outk;
             asm("" : "+v"(k));                      // (a value of its own: the record's 64-bit index is formed here, not held as a pair across the loop)
             if (k >= 0) store_miss(A.out, k, 0);
-            if (want_cost) note_tile_cost(k, guard);
-            mode = M_DONE;                          // shadow miss: record already says "traced, lit"
+            retire(mode, want_cost, k, guard);      // shadow miss: record already says "traced, lit"
         }
-#else
-        if (mode == M_WORLD) {
-            if (cw < 0) {                               // left its chunk in the step: t += escape(chunk box) + EPS, src/Traverse.cpp:164-168
-                cw &= ~CW_ESCAPE_PENDING;
-                if constexpr (GLSL) tw += guarded(escape(O, g, clo, clo + csize), eps) + eps;       // (the guard's threshold IS the march's EPS, Chunkmarch.glsl:113)
-                else tw += escape(O, g, clo, clo + csize) + eps;
-            }
-            bool miss = cw >= A.cap_chunk;
-            if constexpr (SEG) miss |= (GLSL ? tw : tw - eps) >= far;          // every later hit lies at tw + s, s >= -leaf_back: the ray has passed its far end
-            if (!miss) {
-                cw++;
-                const V3 p = alpha + beta * tw;
-                miss = !inside(p, wlo, whi);
-                if (!miss) {
-                    const ChunkGrid G = chunk_grid;                 // (two LDS reads at a uniform address)
-                    const bool table_in_lds = __builtin_amdgcn_readfirstlane((int)G.table_in_lds) != 0;
-                    int mx, my, mz;
-                    chunk_cell_pow2(G, p, mx, my, mz);
-                    const int ci_new = chunk_index_u24(G, mx, my, mz);
-                    // The descent cache (stk column, pux/puy/puz, valid) is keyed by chunk and cell, not by ray: a ray that
-                    // enters the chunk this lane marched last - a shadow ray leaving its primary hit, the next pixel of the
-                    // tile, a ray pinned on a chunk face - restarts below the deepest common level instead of at the root.
-                    // Another chunk: nothing of the cache holds.  The cached cell goes too: chunks may differ in depth
-                    // (src/Octree.h:56-76: an Ocroot carries its own), and a cell of a deeper chunk would make the next
-                    // descent compute a common prefix above this chunk's top level (keep < 0).
-                    if (ci_new != ci) { valid = 0; pux = 0; puy = 0; puz = 0; }
-                    ci = ci_new;
-                    uint32_t ch_levels, ch_wide, ch_twig;
-                    if (table_in_lds) {
-                        clo = mk(__uint_as_float(chunk_tab[0][ci]), __uint_as_float(chunk_tab[1][ci]), __uint_as_float(chunk_tab[2][ci]));
-                        ch_levels = chunk_tab[3][ci]; ch_wide = chunk_tab[4][ci]; ch_twig = chunk_tab[5][ci];
-                    } else {
-                        const DevWide ch = A.wchunks[ci];
-                        clo = ld3(ch.bmin);
-                        ch_levels = ch.levels; ch_wide = ch.wide_off; ch_twig = (uint32_t)ch.twig_off;
-                    }
-                    bool contained = inside(p, clo, clo + csize);
-                    // src/Traverse.cpp:154-155: a position outside the box of the chunk found for it ends the ray.  The shader has no
-                    // such check (shaders/Chunkmarch.glsl:297-330): its treemarch fails at once, and rootmarch steps on out of that box
-                    if (GLSL && !contained) tw += guarded(escape(p, g, clo, clo + csize), eps) + eps;     // (stays M_WORLD; cw counts it)
-                    else miss = !contained;
-                    if (contained) {                    // treemarch(p, beta, chunk): a = p, t = 0 (src/Traverse.cpp:158,78)
-                        if constexpr (BIG) wide_b = (unsigned long long)(size_t)A.wide + ((unsigned long long)ch_wide << 8);
-                        else wide_b = ch_wide << 8;                  // 64 entries of 4 bytes per wide node
-                        twig_off = ch_twig;
-                        levels = (int)ch_levels;
-                        O = p; t = 0.0f; cnt = A.cap_tree;
-                        Blo = clo;
-                        res = csize * __uint_as_float((uint32_t)(127 - levels) << 23);     // csize / 2^levels, exact
-#ifndef SVO_CXX_STEP
-                        bsize = csize; res_tree = res; nw_chunk = levels ? (levels + 1) >> 1 : 1;
-#endif
-                        mode = M_TREE;
-                    }
-                }
-            }
-            if (miss) {
-                if (outk >= 0) store_miss(A.out, outk, 0);
-                if (want_cost) note_tile_cost(outk, guard);
-                mode = M_DONE;                          // shadow miss: record already says "traced, lit"
-            }
-        }
-#endif
         }
 
-        // ---- one step of the current level: tree (src/Traverse.cpp:79-111) or brick (:54-70) -----
-        //      First decide what the step does (locate the cell, read its node / mask bit), then apply exactly one of
-        //      the outcomes below as a flat sequence of predicated updates of the lane state.
+        // ---- the steps of the current level: tree (src/Traverse.cpp:79-111) or brick (:54-70); step_cxx.hip.h states what one step does.
         //      The step repeats at once, without the refill / vote / block checks around it, while every live lane of the
         //      wave is marching and nothing else can be due: that is the state of the waves that carry a launch's longest
         //      rays after the tile cursors ran dry, alone on their SIMD and bound by their own instruction stream.
         int pass = 0;
         // in the bulk: STEP_EXTRA more steps, decided once per pass of the outer loop (n_busy: before the chunk step)
         const int fixed_steps = (n_busy >= STEP_LANES && vote(creepn > 0 || creepn <= -4 * CREEP_SERIOUS) == 0ull) ? STEP_EXTRA : 0;
-#ifndef SVO_CXX_STEP
         // the lanes that march a shadow ray: they change kind only in the hit block, so once per pass of the outer loop
         const unsigned long long shadow_lanes = light_clear ? vote(outk < 0) : 0ull;
-#endif
         for (;;) {
+        // (step_asm.hip.h, or its C++ twin) the steps of this pass in one statement: 1 + fixed_steps at first, DRAIN_STEPS while the inner repeat lasts
 #ifdef SVO_STACK_TIMING
         n_lane_twig += mode == M_TWIG ? (pass == 0 ? 1u + (unsigned)fixed_steps : (unsigned)DRAIN_STEPS) : 0u;        // ... of them started inside a brick
         n_lane_busy += (mode == M_TREE || mode == M_TWIG) ? (pass == 0 ? 1u + (unsigned)fixed_steps : (unsigned)DRAIN_STEPS) : 0u;     // steps of the coming statement this lane starts as a marching lane (an upper bound on its own steps)
         { const int nm = __popcll(__ballot(mode == M_TREE || mode == M_TWIG)); n_wsteps += nm > 0; n_lsteps += nm; if (more) { n_wsteps_b += nm > 0; n_lsteps_b += nm; n_hit_wait += __popcll(__ballot(mode == M_HIT)); n_dead_wait += __popcll(__ballot(mode == M_DONE)); n_world_wait += __popcll(__ballot(mode == M_WORLD)); n_twig_b += __popcll(__ballot(mode == M_TWIG)); } }
 #endif
-#ifndef SVO_CXX_STEP
-        // (step_asm.hip.h) the steps of this pass in one statement: 1 + fixed_steps at first, single steps while the inner repeat lasts
         const int nsteps = pass == 0 ? 1 + fixed_steps : DRAIN_STEPS;
         const int sure_miss = SVO_SURE_MISS_WHEN;      // (step_asm_body.inc: bricks whose march is bound to miss are not entered)
-        march_steps_asm<BIG, GLSL>(mode, O, Blo, bsize, res, t, cnt, tt_saved, t_miss, it_saved, tw, cw, pux, puy, puz, valid, plev, bmask, creepn,
-                                   beta, g, clo, alpha, levels, nw_chunk, res_tree, wide_b, twig_off, lds_lane, SU, nsteps | (sure_miss << 16), shadow_lanes, step_stats);
+        SVO_MARCH_STEPS<BIG, GLSL>(mode, O, Blo, bsize, res, t, cnt, tt_saved, t_miss, it_saved, tw, cw, pux, puy, puz, valid, plev, bmask, creepn,
+                               beta, g, clo, alpha, levels, nw_chunk, res_tree, wide_b, twig_off, lds_lane, SU, nsteps | (sure_miss << 16), shadow_lanes, step_stats);
         pass += nsteps - 1;
-#else
-        if (mode == M_TREE || mode == M_TWIG) {
-            enum : int { S_LEAVE = 0, S_ADVANCE = 1, S_ENTER = 2, S_HIT_LEAF = 3, S_HIT_CELL = 4, S_BAD = 5 };
-            const bool twig = mode == M_TWIG;
-            const float Bsize = twig ? res * 4.0f : csize, inv_res = recip_pow2(res);
-            const int crept = creepn < 0 ? -creepn : creepn;
-            creepn = -crept;                                        // disarmed unless this step advances (see the creep block)
-            bool leave = cnt <= 0;                                  // the level's step cap (src/Traverse.cpp:54,79)
-            cnt -= 1;                                               // (a lane that leaves restores or resets cnt below)
-            const V3 p = O + beta * t;
-            leave |= !inside(p, Blo, Blo + Bsize);
-            // lattice coordinates of p inside the box.  Brick: truncation, as the reference (:58).  Tree: the number
-            // of cell boundaries <= p; truncation gives exactly that unless the quotient is integral (p on a lattice
-            // plane, or rounded onto one), which the rare branch below settles with the reference's own comparison.
-            const float fx = (p.x - Blo.x) * inv_res, fy = (p.y - Blo.y) * inv_res, fz = (p.z - Blo.z) * inv_res;
-            int ux = (int)fx, uy = (int)fy, uz = (int)fz;
-#ifdef SVO_STACK_TIMING
-            n_fix += __ballot(!twig && ((fx == (float)ux) | (fy == (float)uy) | (fz == (float)uz))) != 0;
-#endif
-            if (SVO_UNLIKELY(!twig && ((fx == (float)ux) | (fy == (float)uy) | (fz == (float)uz)))) {
-                const int nmax = (1 << levels) - 1;
-                ux = ux > nmax ? nmax : ux; uy = uy > nmax ? nmax : uy; uz = uz > nmax ? nmax : uz;
-                ux -= (Blo.x + (float)ux * res > p.x) ? 1 : 0;
-                uy -= (Blo.y + (float)uy * res > p.y) ? 1 : 0;
-                uz -= (Blo.z + (float)uz * res > p.z) ? 1 : 0;
-            }
-            if (twig) leave |= (ux > 3) | (uy > 3) | (uz > 3);      // isInsideCube(off, 0, 3), :59 (off >= 0 always: p >= Blo)
-
-            int what = S_LEAVE;
-            int low = 0;                                            // the located cell spans (low+1) lattice steps
-            uint32_t payload = 0;                                   // node word (tree) / cell index (brick)
-            if (SVO_LIKELY(!leave)) {
-                if (!twig) {
-                    // descend through the chunk's wide tree (wide_tree.hip.h: two reference levels per node) from the
-                    // deepest cached wide level whose node is unchanged: wide level k is selected by the coordinate bits
-                    // above 2 (nw - k), so it survives while the highest differing bit lies below that
-                    const uint32_t diff = (uint32_t)((ux ^ pux) | (uy ^ puy) | (uz ^ puz));
-                    const int nw = levels ? (levels + 1) >> 1 : 1;
-                    const int hb = 32 - __clz((int)(diff | 1u));    // (diff == 0 reads as "bit 0 differs": keep = nw - 1 >= valid either way)
-                    const int keep = nw - ((hb + 1) >> 1);
-                    int k;                                          // min(keep, valid), never below the top level (one v_med3_i32)
-                    asm("v_med3_i32 %0, %1, 0, %2" : "=v"(k) : "v"(keep), "v"(valid));
-                    uint32_t wnode = stk[k][lane];                  // (row 0 holds node 0: no branch for k == 0)
-                    int sh = 2 * (nw - 1 - k);                      // the two coordinate bits that select the entry
-                    uint32_t word = ld_wide((wnode << 6) + wide_slot(ux, uy, uz, sh));
-                    while (is_branch(word)) {
-                        wnode = word & WIDE_PAYLOAD;
-                        ++k;
-                        stk[k][lane] = wnode;
-                        sh -= 2;
-                        word = ld_wide((wnode << 6) + wide_slot(ux, uy, uz, sh));
-                    }
-                    valid = k; pux = ux; puy = uy; puz = uz;
-                    plev = (int)((word >> 25) & 31u);               // the reference node's level: it spans 2^(levels - level) cells
-                    low = (1 << (levels - plev)) - 1;
-                    const uint32_t type = node_type(word);
-                    what = type == EMPTY ? S_ADVANCE : type == LEAF ? S_HIT_LEAF : S_ENTER;
-                    payload = word;
-                } else {
-                    payload = (uint32_t)(uz * 16 + uy * 4 + ux);
-                    what = ((bmask >> payload) & 1ull) ? S_HIT_CELL : S_ADVANCE;
-                }
-            }
-
-            // ---- the one escape evaluation of the step, out of the located cell from p (src/Traverse.cpp:89,104-105,67):
-            //      an EMPTY node or an empty brick cell advances by it; a TWIG node about to be entered remembers where the
-            //      tree level goes on if the brick march misses - t + (escape(p, node box) + EPS), :104-105, the same
-            //      expression with the same operands - so that leaving the brick later costs no evaluation of its own.
-            //      A lane that leaves its level evaluates nothing here: out of a brick it resumes the tree level at the
-            //      remembered parameter; out of the chunk (:164-168) it only raises the "escape pending" bit of cw, and the
-            //      chunk step, for which it has to wait anyway, advances tw from the tree frame's origin, which stays put.
-            if (what == S_ADVANCE || what == S_ENTER) {
-                const V3 E_lo = mk(Blo.x + (float)(ux & ~low) * res, Blo.y + (float)(uy & ~low) * res, Blo.z + (float)(uz & ~low) * res);
-                const float E_size = res * (float)(low + 1);
-                const float e = (GLSL ? guarded(escape(p, g, E_lo, E_lo + E_size), eps) : escape(p, g, E_lo, E_lo + E_size)) + eps;
-                if (what == S_ADVANCE) {
-                    t += e;
-                    creepn = e < 2.0f * eps ? crept + 1 : 0;        // pinned on a lattice plane: see the creep block
-                } else {                                            // twigmarch(p, b, node box, ...): a = p, t = 0 (:99,53)
-                    bmask = A.mask[twig_off + (payload & WIDE_PAYLOAD)];
-                    tt_saved = t; t_miss = t + e; it_saved = cnt;
-                    O = p; t = 0.0f; cnt = A.cap_twig;
-                    Blo = E_lo;
-                    res = E_size * 0.25f;                           // leafsize = node size / 4, exact
-                    mode = M_TWIG;
-                }
-            }
-            if (leave) {
-                if (twig) {                                         // back to the tree level that entered the brick
-                    t = t_miss;
-                    cnt = it_saved;
-                    O = alpha + beta * tw;                          // the chunk march's p (src/Traverse.cpp:144,158)
-                    Blo = clo;
-                    res = csize * __uint_as_float((uint32_t)(127 - levels) << 23);
-                    mode = M_TREE;
-                } else {                                            // out of the chunk
-                    cw |= CW_ESCAPE_PENDING;
-                    mode = M_WORLD;
-                }
-            }
-            if (what == S_HIT_LEAF) {
-                tw = tw + (GLSL ? t : t - eps);                     // src/Traverse.cpp:93,160 (t - EPS); shaders/Chunkmarch.glsl:266 (t)
-                cnt = (int)SVO_CELL_NONE;
-                mode = M_HIT;
-            }
-            if (what == S_HIT_CELL) {
-                float sdist = t;                                    // src/Traverse.cpp:63
-                sdist += tt_saved;                                  // :101
-                tw = tw + sdist;                                    // :160
-                cnt = (int)payload;
-                mode = M_HIT;
-            }
-        }
-#endif
 
         // Loop control is wave-uniform (scalar compare and branch).  In the bulk the number of extra steps was fixed before
         // the loop: nothing is looked at between them - the checks around the step (refill, three votes, guard, creep vote,
@@ -809,15 +653,13 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
         // ---- hits.  A shadow ray only sets a flag; a primary hit waits (M_HIT) until the wave votes to
         //      resolve: G-buffer record, then the lane becomes its own shadow ray -------------------
         if (mode == M_HIT && outk < 0) {
-            store_flags(A.out, outk & 0x7FFFFFFF, SVO_HIT_FLAG | SVO_SHADOW_TRACED | SVO_SHADOWED | (A.normal_mode == SVO_NORMAL_FACE ? (uint32_t)SVO_FACE_NORMAL : 0u));
-            if (want_cost) note_tile_cost(outk, guard);
-            mode = M_DONE;
+            store_flags(A.out, outk & 0x7FFFFFFF, shadow_flags(A.normal_mode, SVO_SHADOWED));
+            retire(mode, want_cost, outk, guard);
         }
         if constexpr (SEG) {
             if (mode == M_HIT && !(tw < far)) {             // a hit at or behind the far end: the miss record, no shadow ray (no vote needed)
                 store_miss(A.out, outk, 0);
-                if (want_cost) note_tile_cost(outk, guard);
-                mode = M_DONE;
+                retire(mode, want_cost, outk, guard);
             }
         }
         if (run_hit) { asm volatile("");
@@ -895,8 +737,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void k_trace_stack(TraceArgs A)
             const V3 n = face ? face_normal(point, vlo, vlo + vsize, beta) : cube_normal_pow2(point, vlo, vsize, eps);
             const uint32_t flags = SVO_HIT_FLAG | (A.shadow ? SVO_SHADOW_TRACED : 0u) | (face ? (uint32_t)SVO_FACE_NORMAL : 0u) | dark;
             store_hit(A.out, outk, tw, n, material, flags, (uint32_t)ci, node, hitc);
-            if (want_cost) note_tile_cost(outk, guard);
-            mode = M_DONE;
+            retire(mode, want_cost, outk, guard);
             if (A.shadow) {                             // the lane becomes its own shadow ray
                 alpha = point; beta = sdir; g = sg;
                 outk |= (int)0x80000000;

@@ -1,6 +1,6 @@
 // step_asm.hip.h — the march step of k_trace_stack, hand-scheduled for gfx950 (one asm statement).
 //
-// Same arithmetic, operand for operand, as the C++ step in kernel_stack.hip.h (which stays the readable statement of the
+// Same arithmetic, operand for operand, as the C++ step in step_cxx.hip.h (which stays the readable statement of the
 // algorithm and the A/B partner: -DSVO_CXX_STEP); what differs is everything the compiler adds around it.  The step is
 // bound by instruction issue, and of the ~285 instructions hipcc emits for it about 70 are scalar EXEC
 // bookkeeping (one s_and_saveexec / s_or pair per source-level `if`, s_or chains that AND six compares together), 12 are
@@ -12,7 +12,7 @@
 //   * the three axes of the escape evaluation are interleaved so that each v_cndmask finds its compare two issue slots
 //     back (the VALU-writes-SGPR -> VALU-reads-it hazard of gfx940+ needs two wait states), two s_nop remain;
 //   * lanes that enter a brick ride along with the advancing lanes through the one escape evaluation (their t_miss),
-//     lanes that leave evaluate nothing (kernel_stack.hip.h, "the one escape evaluation of the step");
+//     lanes that leave evaluate nothing (step_cxx.hip.h, "the one escape evaluation of the step");
 //   * no value is copied at a join: each outcome writes the lane state in place under its own mask.
 //   * three values are reached by shorter integer routes than the C++ step's, four instructions fewer per step and bit for bit the same
 //     (one vector instruction per wave-step is ~0.4 % of the headline): the deepest cached wide level that survives,

@@ -96,7 +96,7 @@ __device__ __forceinline__ void march_steps_asm<SVO_STEP_BIG, SVO_STEP_GLSL>(
         "v_cmp_lt_i32 vcc, 3, %[low]\n\t"                      // brick: isInsideCube(off, 0, 3), :59
         "s_and_b64 vcc, vcc, %[stw]\n\t"
         "s_andn2_b64 %[sstay], exec, vcc\n\t"
-        // ---- lanes that leave their level: no escape evaluation here (see kernel_stack.hip.h)
+        // ---- lanes that leave their level: no escape evaluation here (see step_cxx.hip.h)
         "s_andn2_b64 exec, %[smar], %[sstay]\n\t"
         "s_cbranch_execz 8f\n\t"
         "s_andn2_b64 exec, exec, %[stw]\n\t"                   // out of the chunk (:164-168): the chunk step advances tw

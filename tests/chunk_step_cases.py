@@ -7,7 +7,7 @@
 marches every case with the stack kernel and compares every field with the oracle's records, which the test computed once and stored
 in <reference.npz>.  exit 0 = every check passed.
 
-What is marched is the chunk step of k_trace_stack (chunk_step_asm.hip.h; the C++ block of kernel_stack.hip.h in the `cxxstep` build),
+What is marched is the chunk step of k_trace_stack (chunk_step_asm.hip.h; the C++ twin of chunk_step_cxx.hip.h in the `cxxstep` build),
 on worlds of depth 3 - 5 and lists of 4,096 rays, beyond the grids of tests/blocks_cases.py:
 
   caps      cap_chunk 1, 2, 3 on the 3x1x2 world: rays end on the cap in each chunk of their path

@@ -1,4 +1,4 @@
-"""The chunk step of the stack kernel (chunk_step_asm.hip.h: one hand-scheduled statement; the C++ block of kernel_stack.hip.h in the
+"""The chunk step of the stack kernel (chunk_step_asm.hip.h: one hand-scheduled statement; the C++ twin of chunk_step_cxx.hip.h in the
 `cxxstep` build) on the cases the grids of tests/test_gpu_blocks.py do not reach - tests/chunk_step_cases.py lists them: rays that end on
 cap_chunk 1, 2, 3 in each chunk of their path, origins outside the world (beside it, in front of it, grazing, corners and edges), origins on chunk faces
 and on negative exact multiples of the chunk edge (the containment test ends them), zero direction components from a lattice plane, a

@@ -1,5 +1,5 @@
 """The variant builds of the library (octree-raymarcher_amd/Makefile `variants`, built by __graft_entry__.build()) must not rot
-unseen: the C++ march step that kernel_stack.hip.h calls the readable statement of the algorithm, the timing
+unseen: the C++ march step that step_cxx.hip.h calls the readable statement of the algorithm, the timing
 build whose lane counters DESIGN.md quotes, the large-pool kernel forced onto small worlds, and the test hooks the shipped library
 no longer reads.  Each runs in its own process (one library per process), one after the other."""
 import os
