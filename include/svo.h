@@ -58,6 +58,8 @@
  *                           each, one occlusion ray per hit and light that can reach it, in one compacted ray list
  *   svo_shade_lights     <- (a departure, with it) computePointLight_BlinnPhong (shaders/World.Fragment.glsl:80-97) per light of
  *                           the list, windowed to the reach, added to the shaded image
+ *   svo_trace_instances  <- (a departure: the reference's only moving object is a rasterised mesh, src/Worm.cpp) up to 32 placements
+ *                           of one voxel model, marched in the model's own space and folded into the frame; svo_trace_instance_shadows: their shadows
  *   svo_shadowmap_render <- World::draw_shadowmap under the OrthoCamera (src/World.cpp:162-203, shaders/ShadowmapWorld.Fragment.glsl,
  *                           src/Main.cpp:149,190-198): the world marched once from the directional light into a depth image
  *   svo_shadowmap_apply  <- computeShadow                          shaders/World.Fragment.glsl:140-155,186
@@ -123,7 +125,8 @@ extern "C" {
                                           svo_world_prepare_light, svo_world_prepared_light and SVO_SHADOW_NO_CLEARANCE (a bit of
                                           svo_trace_params.shadow, which was any non-zero value: such callers keep their results),
                                           svo_world_prepared_bricks and SVO_SHADOW_NO_BRICK_CLEARANCE (another such bit),
-                                          svo_trace_lights, svo_shade_lights, svo_light and SVO_MAX_LIGHTS */
+                                          svo_trace_lights, svo_shade_lights, svo_light and SVO_MAX_LIGHTS,
+                                          svo_trace_instances, svo_trace_instance_shadows, svo_instance and SVO_MAX_INSTANCES */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -1004,6 +1007,88 @@ int svo_trace_lights(svo_world *, const svo_camera *cam, const svo_trace_params 
 int svo_shade_lights(const svo_camera *cam, const svo_shade_params *p, const svo_light *lights, int nlights,
                      int x0, int y0, int w, int h, const svo_hit *gbuffer_dev, const uint32_t *visible_dev,
                      float *rgba_dev, void *stream);
+
+/* ---- voxel model instances: up to 32 placements of one model world in a frame ------------------------------
+ * Everything above renders ONE static voxel world; moving anything means editing it.  An instance is a rigid placement (rotation,
+ * position, uniform scale) of a second uploaded world, the MODEL - in practice a small one, a single chunk from a grid
+ * (svo_chunk_from_grid + svo_world_create); it may be the scene's own handle.  One call renders up to 32 placements of one model; a
+ * caller with several models calls once per model and feeds merged_dev back in as gbuffer_dev (merged_dev == gbuffer_dev is
+ * allowed).  Not in the reference, whose only moving object is a rasterised mesh (src/Worm.cpp): an opt-in departure. */
+#define SVO_MAX_INSTANCES 32
+typedef struct svo_instance {       /* 64 bytes */
+    float rot[9];                   /* R, row-major, model -> world; orthonormal is the caller's business, finite is checked */
+    float pos[3];                   /* world position of the model's origin */
+    float scale;                    /* > 0, finite: x_world = pos + scale * (R x_model) */
+    uint32_t _pad[3];               /* 0 */
+} svo_instance;
+
+/* Stage 1, visibility.  gbuffer_dev holds the w*h records that svo_trace(scene, cam, params, x0, y0, w, h) wrote (or any records of
+ * the caller's); it is only read, unless it is merged_dev.  merged_dev receives w*h records, owner_dev w*h words.  Every operation is
+ * in float and separately rounded; pixels k are row-major in the rectangle; (o, d) is the pixel's camera ray as the march forms it;
+ * inv = 1.0f / scale, rounded once on the host; bmin / bmax are the model world's box as floats (chunkcoordmin * chunksize, and that
+ * plus dims * chunksize); a record is USABLE when it has SVO_HIT_FLAG and no SVO_ERR_FLAG.  For pixel k and instance j:
+ *   1. into model space   u = o - pos;  om[i] = (R[0][i]*u.x + R[1][i]*u.y + R[2][i]*u.z) * inv;  dm[i] = R[0][i]*d.x + R[1][i]*d.y
+ *                         + R[2][i]*d.z   (R transposed, summed left to right; dm is not re-normalised, so a distance along the model
+ *                         ray is the world's times inv);
+ *   2. box rule           tn = 0, tf = +inf; per axis a in x, y, z order: dm[a] == 0: the axis fails unless bmin[a] <= om[a] &&
+ *                         om[a] <= bmax[a], and bounds nothing; otherwise r = 1.0f / dm[a], t0 = (bmin[a] - om[a]) * r,
+ *                         t1 = (bmax[a] - om[a]) * r, swapped if t1 < t0, then if (t0 > tn) tn = t0; if (t1 < tf) tf = t1 (a NaN
+ *                         compares false and bounds nothing).  The box is missed if an axis fails or tn > tf;
+ *   3. pair               far = gbuffer[k] usable ? gbuffer[k].t * inv : +inf.  (k, j) is a PAIR iff the box is not missed and
+ *                         tn < far.  Its ray is (om, dm) with far end `far`.
+ * Order and capacity are svo_trace_lights': the pairs are ranked instance-major - all pairs of instance 0 in ascending k, then
+ * instance 1, and so on; cap = max_rays > 0 ? max_rays : w*h; pair r occupies slot r of the list if r < cap, pairs with r >= cap are
+ * DROPPED and count as "no hit"; slots from the number of pairs up to cap hold a ray that misses the model, with far end 0.  ONE
+ * svo_trace_segments launch of cap rays marches the list on the MODEL world (svo_trace_last_ray_count of the model then reports cap),
+ * with `params` and shadow = 0, without counters_dev, tile_cost_dev and tile_order_dev; eps, caps, semantics, kernel, normal_mode and
+ * see_through are honoured, in model units.  No host synchronisation is made.
+ *   4. resolve            pair (k, j) HITS iff it has a slot and its record M is usable (the launch has applied M.t < far); its world
+ *                         distance is tw = M.t * scale.  Among the hitting pairs of pixel k the smallest tw wins, the lowest j among
+ *                         equals.  With a winner merged[k] is: t = tw; normal[i] = R[i][0]*n.x + R[i][1]*n.y + R[i][2]*n.z with n
+ *                         M's normal (a NaN stays NaN); material, chunk, node and cell from M; flags = SVO_HIT_FLAG |
+ *                         (M.flags & SVO_FACE_NORMAL); and owner[k] = j + 1.  Otherwise merged[k] = gbuffer[k] byte for byte and
+ *                         owner[k] = 0.
+ *   count_dev             optional (NULL): two uint32 on the device, [0] the number of pairs, [1] min(pairs, cap) - [0] feeds the
+ *                         next frame's max_rays.
+ * THE IDS OF AN OWNED PIXEL BELONG TO THE MODEL WORLD: a per-hit stage that takes a world (svo_hit_voxels, svo_hit_ao,
+ * svo_trace_reflections, svo_trace_lights, ...) is fed such pixels with `model` as its world, or not at all; svo_shade* take no world
+ * and work on merged_dev as it stands.
+ * In this order, all before any device work: a NULL scene, model, cam, params, inst, gbuffer_dev, merged_dev or owner_dev, ninst
+ * outside 1..SVO_MAX_INSTANCES, max_rays < 0, a rectangle that starts or extends backwards, a rot or pos entry that is not finite, a
+ * scale that is not > 0 or not finite, scene and model resident on different devices: SVO_ERR_INVALID_ARG; then what svo_trace
+ * refuses in params, for the scene and then the model, and a world that is not resident (SVO_ERR_NOT_UPLOADED); then w*h == 0:
+ * SVO_OK; then ninst * w*h > 0x7FFFFFFF or cap > 0x7FFFFFFF: SVO_ERR_UNSUPPORTED.
+ * Asynchronous on `stream`.  The list, its records and the ranks live in the MODEL's scratch, 60 bytes per slot plus 4 per pixel and
+ * 8 per instance and block of 256 pixels; calls that share a model are ordered behind one another on the device.
+ * The list is marched in MODEL units from the eye's place in model space: a distance d in the world is d / scale there.  Keep scale near
+ * 1 (author a small object as a small chunk): from t = 2048 model units on, t + eps no longer advances a float t and the march of such a
+ * ray costs about sixty times more. */
+int svo_trace_instances(svo_world *scene, svo_world *model, const svo_camera *cam, const svo_trace_params *params,
+                        const svo_instance *inst, int ninst, int64_t max_rays,
+                        int x0, int y0, int w, int h, const svo_hit *gbuffer_dev,
+                        svo_hit *merged_dev, uint32_t *owner_dev, uint32_t *count_dev, void *stream);
+
+/* Stage 2, shadows from the directional light, on what stage 1 wrote: instances shadow the terrain, the terrain shadows instances,
+ * instances shadow each other and themselves.  S = normalize(-params->light_dir), the direction svo_trace's own shadow rays have;
+ * b = bias > 0 ? bias : the launch's resolved eps (0 = 1/8192, 1/4096 under SVO_SEMANTICS_GLSL).
+ *   1. a pixel is CONSIDERED iff merged[k] is usable and has no SVO_SHADOWED; its point is P = o + d * (t - b);
+ *   2. model launch   (k, j) is a pair iff the ray (P, S), taken into instance j's space as in stage 1, does not miss the box
+ *                     (far = +inf).  Ranking, cap, dropping, count_dev and scratch as in stage 1; ONE svo_trace_rays launch of cap
+ *                     rays on the model with shadow = 0.  A pair is OCCLUDED iff it has a slot and its record is usable;
+ *   3. scene launch   ONE svo_trace_rays launch of w*h rays on the scene with shadow = 0: a considered pixel with owner != 0 gets
+ *                     (P, S), every other pixel the ray that misses the scene (svo_trace_reflections' padding); occluded iff the
+ *                     record is usable.  (The scene's own pixels had their shadow rays from svo_trace.)
+ *   4. fold           every considered pixel gets SVO_SHADOW_TRACED, and SVO_SHADOWED if anything occluded it.  No other byte of
+ *                     merged_dev changes.
+ * bias exists because P, re-derived in a rotated or scaled model space, can land a rounding error inside the voxel it left: at
+ * bias = 0 (the march's eps) a rotated instance may show shadow acne on itself; a few eps (1/256) cures it.
+ * Argument rules as for svo_trace_instances (the required buffers: merged_dev, owner_dev), and a bias that is negative or NaN is
+ * SVO_ERR_INVALID_ARG.  Asynchronous on `stream`; the model list lives in the model's scratch, the scene list (56 bytes per pixel) in
+ * the scene's, and calls that share a world are ordered behind one another on the device. */
+int svo_trace_instance_shadows(svo_world *scene, svo_world *model, const svo_camera *cam, const svo_trace_params *params,
+                               const svo_instance *inst, int ninst, int64_t max_rays, float bias,
+                               int x0, int y0, int w, int h,
+                               svo_hit *merged_dev, const uint32_t *owner_dev, uint32_t *count_dev, void *stream);
 
 /* ---- the edit cursor and the light markers: cubes over the finished image ----------------------------------
  * One overlay record, 48 bytes, on the device.  The reference has four: the cursor cube (ImagCube: translucent grey, black edges) and one

@@ -10,6 +10,7 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     World.draw_translucent(camera, m)         <- ParallaxAlpha's march past water   shaders/ParallaxAlpha.Fragment.glsl:141-199,276-335
     World.trace_local_shadows(camera, ...)    <- (none: the reference's three lights share the directional light's shadow term)
     World.trace_lights, shade_lights, Light   <- (none: the reference has three lights)    up to 32 point lights with a reach, one compacted ray list
+    World.trace_instances, trace_instance_shadows, Instance   <- (none: the reference's moving object is a rasterised mesh, src/Worm.cpp)   up to 32 placements of a model world
     World.shadowmap_fit / shadowmap_render, shadowmap_apply   <- OrthoCamera, World::draw_shadowmap, computeShadow   src/World.cpp:162-203, shaders/World.Fragment.glsl:140-155
     World.index / index_float                 <- World::index(_float)   src/World.cpp:288-293,323-332
     World.locate / locate_points              <- traverse               src/Traverse.cpp:34-48 (the voxel under each point)
@@ -72,6 +73,7 @@ SKY_LINEAR, SKY_NEAREST = 0, 1                           # svo_sky.filter
 BOX_SOLID, BOX_CURSOR, BOX_HIDDEN = 0, 1, 1 << 8         # svo_box.style
 MAX_BOXES = 64                                           # SVO_MAX_BOXES
 MAX_LIGHTS = 32                                          # SVO_MAX_LIGHTS
+MAX_INSTANCES = 32                                       # SVO_MAX_INSTANCES
 BOX_DTYPE = np.dtype([("bmin", "<f4", (3,)), ("size", "<f4"), ("color", "<f4", (3,)), ("alpha", "<f4"), ("style", "<u4"), ("_pad", "<u4", (3,))])
 assert BOX_DTYPE.itemsize == 48
 
@@ -192,6 +194,17 @@ class Light(C.Structure):
         self.constant, self.linear, self.quadratic = (float(c) for c in attenuation)
 
 
+class Instance(C.Structure):
+    """svo_instance: one placement of a model world (64 bytes): x_world = pos + scale * (R x_model).  Instance(rot, pos, scale), rot a
+    3x3 (or 9 floats, row-major), model -> world."""
+    _fields_ = [("rot", C.c_float * 9), ("pos", C.c_float * 3), ("scale", C.c_float), ("_pad", C.c_uint32 * 3)]
+
+    def __init__(self, rot=(1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0), pos=(0.0, 0.0, 0.0), scale: float = 1.0):
+        super().__init__()
+        self.rot[:] = [float(c) for c in np.asarray(rot, np.float64).reshape(9)]
+        self.pos[:], self.scale = [float(c) for c in pos], float(scale)
+
+
 class Box(C.Structure):
     """svo_box: one overlay cube of svo_shade_boxes (48 bytes; BOX_DTYPE is its numpy twin)."""
     _fields_ = [("bmin", C.c_float * 3), ("size", C.c_float), ("color", C.c_float * 3), ("alpha", C.c_float), ("style", C.c_uint32),
@@ -217,7 +230,7 @@ ABI_SYMBOLS = [
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_edit_cube", "svo_world_edit_ball", "svo_world_edit_ball_all", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_cursor_place", "svo_shade_boxes", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_shadowmap_fit", "svo_shadowmap_render", "svo_shadowmap_apply", "svo_hit_ao", "svo_shade_ao",
-    "svo_trace_reflections", "svo_shade_reflections", "svo_trace_lights", "svo_shade_lights", "svo_world_prepare_light", "svo_world_prepared_light", "svo_world_prepared_bricks",
+    "svo_trace_reflections", "svo_shade_reflections", "svo_trace_lights", "svo_shade_lights", "svo_trace_instances", "svo_trace_instance_shadows", "svo_world_prepare_light", "svo_world_prepared_light", "svo_world_prepared_bricks",
     "svo_device_count", "svo_device_alloc", "svo_device_free", "svo_device_cache_trim", "svo_memcpy_h2d", "svo_memcpy_d2h",
     "svo_stream_synchronize", "svo_last_error", "svo_abi_version",
 ]
@@ -282,6 +295,10 @@ lib.svo_shade_reflections.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams),
 lib.svo_trace_lights.argtypes = [_P, C.POINTER(Camera), C.POINTER(TraceParams), C.POINTER(Light), C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                  _P, _P, _P, _P]
 lib.svo_shade_lights.argtypes = [C.POINTER(Camera), C.POINTER(ShadeParams), C.POINTER(Light), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
+lib.svo_trace_instances.argtypes = [_P, _P, C.POINTER(Camera), C.POINTER(TraceParams), C.POINTER(Instance), C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    _P, _P, _P, _P, _P]
+lib.svo_trace_instance_shadows.argtypes = [_P, _P, C.POINTER(Camera), C.POINTER(TraceParams), C.POINTER(Instance), C.c_int, C.c_int64, C.c_float,
+                                           C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
 lib.svo_shade_sky.argtypes = [C.POINTER(Camera), C.POINTER(Sky), C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P]
 lib.svo_frame_rgba8.argtypes = [_P, C.c_int64, _P, _P]
 lib.svo_cursor_place.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), _P, C.c_float, _P, _P]
@@ -544,6 +561,17 @@ def light_array(lights):
     for j, l in enumerate(lights):
         C.memmove(C.byref(arr, j * C.sizeof(Light)), C.byref(l), C.sizeof(Light))
     return arr, len(lights)
+
+
+def instance_array(instances):
+    """A sequence of Instance as the contiguous svo_instance array the instance calls take (None stays None); (array, count)."""
+    if instances is None:
+        return None, 0
+    instances = list(instances)
+    arr = (Instance * max(len(instances), 1))()
+    for j, i in enumerate(instances):
+        C.memmove(C.byref(arr, j * C.sizeof(Instance)), C.byref(i), C.sizeof(Instance))
+    return arr, len(instances)
 
 
 def shade_lights(cam: Camera, params: ShadeParams, rect, gbuffer_ptr: int, lights, rgba_ptr: int, visible_ptr: Optional[int] = None, stream: int = 0):
@@ -840,6 +868,29 @@ class World:
         arr, n = light_array(lights)
         _check(lib.svo_trace_lights(self._h, C.byref(cam) if cam is not None else None, C.byref(params) if params is not None else None, arr, n,
                                     int(max_rays), x0, y0, w, h, gbuffer_ptr, visible_ptr, count_ptr or None, stream), "svo_trace_lights")
+
+    def trace_instances(self, model: "World", cam: Camera, params: TraceParams, rect, gbuffer_ptr: int, instances, merged_ptr: int, owner_ptr: int,
+                        max_rays: int = 0, count_ptr: int = 0, stream: int = 0):
+        """svo_trace_instances with this world as the scene: up to 32 placements (a sequence of Instance) of the uploaded world `model`
+        in front of the G-buffer svo_trace(cam, params, rect) filled.  merged_ptr gets w*h records (it may be gbuffer_ptr), owner_ptr w*h
+        uint32 (0: the scene's pixel, j + 1: instance j's, whose ids belong to `model`).  max_rays: the capacity of the compacted ray
+        list (0 = one slot per pixel); count_ptr: two uint32 on the device, (pairs, min(pairs, capacity))."""
+        x0, y0, w, h = rect
+        arr, n = instance_array(instances)
+        _check(lib.svo_trace_instances(self._h, model._h if model is not None else None, C.byref(cam) if cam is not None else None,
+                                       C.byref(params) if params is not None else None, arr, n, int(max_rays), x0, y0, w, h, gbuffer_ptr, merged_ptr,
+                                       owner_ptr, count_ptr or None, stream), "svo_trace_instances")
+
+    def trace_instance_shadows(self, model: "World", cam: Camera, params: TraceParams, rect, instances, merged_ptr: int, owner_ptr: int,
+                               max_rays: int = 0, bias: float = 0.0, count_ptr: int = 0, stream: int = 0):
+        """svo_trace_instance_shadows on what trace_instances wrote: SHADOW_TRACED, and SHADOWED where the way to the directional light
+        is blocked by an instance or (for an instance's pixel) by this world, on every usable record not yet shadowed.  bias: how far
+        the shadow ray starts in front of the hit (0 = the march's eps; a rotated instance wants a few eps, 1/256)."""
+        x0, y0, w, h = rect
+        arr, n = instance_array(instances)
+        _check(lib.svo_trace_instance_shadows(self._h, model._h if model is not None else None, C.byref(cam) if cam is not None else None,
+                                              C.byref(params) if params is not None else None, arr, n, int(max_rays), float(bias), x0, y0, w, h,
+                                              merged_ptr, owner_ptr, count_ptr or None, stream), "svo_trace_instance_shadows")
 
     def shadowmap_fit(self, direction, width: int, height: int, smap: Optional[ShadowMap] = None) -> ShadowMap:
         """svo_shadowmap_fit: a map of width x height texels that holds the whole world box, seen along `direction`; depth_dev of

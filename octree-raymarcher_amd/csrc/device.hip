@@ -6,6 +6,7 @@
 //   svo_world_locate  <- traverse over a point list               src/Traverse.cpp:34-48 (locate.hip.h)
 //   svo_hit_ao        <- (none: the reference has no ambient occlusion)                    (ao.hip.h)
 //   svo_trace_reflections <- (none: the reference has no reflections)                      (reflect.hip.h)
+//   svo_trace_instances   <- (none: the reference's one moving object is a rasterised mesh, src/Worm.cpp)   (instances.hip.h)
 //
 // The reference's first-fit free-list allocator over GL buffers is not reproduced: a world is
 // packed into one flat pool per kind with per-chunk slots sized by the chunk's host capacity
@@ -30,6 +31,7 @@
 #include "see_through.hip.h"
 #include "local_shadows.hip.h"
 #include "light_list.hip.h"
+#include "instances.hip.h"
 #include "reflect.hip.h"
 #include "shadowmap.hip.h"
 #include "locate.hip.h"
@@ -1239,6 +1241,148 @@ int svo_trace_lights(svo_world *w, const svo_camera *cam, const svo_trace_params
         rc = svo_trace_rays(w, list.origins, list.dirs, cap, &march, reinterpret_cast<svo_hit *>(list.records), stream);
         if (rc != SVO_OK) return rc;
         return launch_per_element(who, n, s, k_light_resolve, F, A.eps, L, gbuffer, base, nblocks, (uint32_t)cap, reinterpret_cast<const uint4 *>(list.records), visible_dev);
+    });
+}
+
+// ---- voxel model instances (instances.hip.h) ----------------------------------------------------------------------------------------
+// What both instance calls settle before any device work, in the ABI's order: the arguments, then what fill_common / pick_kernel
+// refuse for either world (As, Am: the scene's and the model's resolved launch), then the sizes.  SVO_OK with n == 0: nothing to do.
+static int instance_call(const char *who, svo_world *scene, svo_world *model, const svo_camera *cam, const svo_trace_params *prm, const svo_instance *inst,
+                         int ninst, int64_t max_rays, float bias, int x0, int y0, int rw, int rh, bool buffers, InstanceList &I, svo_trace_params &march,
+                         TraceArgs &As, int64_t &n, int64_t &cap)
+{
+    const auto refuse = [who](const char *what) { set_error(std::string(who) + what); return SVO_ERR_INVALID_ARG; };
+    if (!scene || !model || !prm || !inst || !buffers || ninst < 1 || ninst > MAX_INSTANCES || max_rays < 0 || !rect_ok(cam, x0, y0, rw, rh)) return refuse(": bad argument");
+    std::memset(&I, 0, sizeof I);
+    for (int j = 0; j < ninst; ++j) {
+        const svo_instance &in = inst[j];
+        for (int a = 0; a < 9; ++a) if (!std::isfinite(in.rot[a])) return refuse(": an instance's rotation is not finite");
+        for (int a = 0; a < 3; ++a) if (!std::isfinite(in.pos[a])) return refuse(": an instance's position is not finite");
+        if (!(in.scale > 0.0f && in.scale < INFINITY)) return refuse(": an instance's scale is not a finite number above 0");
+        std::memcpy(I.rot[j], in.rot, sizeof I.rot[j]);
+        std::memcpy(I.pos[j], in.pos, sizeof I.pos[j]);
+        I.scale[j] = in.scale;
+        I.inv[j] = 1.0f / in.scale;
+    }
+    I.count = ninst;
+    if (!(bias >= 0.0f)) return refuse(": bias is negative or not a number");
+    if (scene->device >= 0 && model->device >= 0 && scene->device != model->device) return refuse(": the scene and the model are on different devices");
+    march = own_list_params(*prm, false);
+    TraceArgs Am;
+    int rc = fill_common(scene, &march, As);
+    if (rc != SVO_OK) return rc;
+    if ((rc = pick_kernel(scene, &march, As)) < 0) return rc;
+    if ((rc = fill_common(model, &march, Am)) != SVO_OK) return rc;
+    if ((rc = pick_kernel(model, &march, Am)) < 0) return rc;
+    for (int a = 0; a < 3; ++a) { I.bmin[a] = Am.worldmin[a]; I.bmax[a] = Am.worldmax[a]; }
+    n = (int64_t)rw * rh; cap = max_rays > 0 ? max_rays : n;
+    if (n == 0) return SVO_OK;
+    if (n * ninst > 0x7FFFFFFF || cap > 0x7FFFFFFF) { set_error(std::string(who) + ": image or list too large"); return SVO_ERR_UNSUPPORTED; }
+    return SVO_OK;
+}
+
+// The model list's scratch, in floats from its start: the RayList of cap slots with records, stage 1's far ends, the pair masks,
+// the [instance][block] counts, their exclusive sums, the two totals; the scan's own follows at `head`
+struct InstanceScratch {
+    uint32_t nblocks, items;
+    size_t list, head, scan_bytes = 0;
+    InstanceScratch(int64_t n, int64_t cap, int ninst, bool far_ends) : nblocks(blocks_for((uint64_t)n, LIGHT_BLOCK)), items(nblocks * (uint32_t)ninst),
+        list(RayList::floats(cap, true) + (far_ends ? (size_t)cap : 0)), head((list + (size_t)n + 2 * (size_t)items + 2 + 63) / 64 * 64) {}
+    size_t floats() const { return head + (scan_bytes + 3) / 4 + 64; }
+};
+
+// Cull, scan, total and emit of either stage into the model list: what the two calls share up to the march
+static int instance_list(bool shadow, const char *who, const InstanceScratch &L, float *scratch, const PixelFrame &F, float bias, V3 S, const InstanceList &I, svo_world *model,
+                         const uint4 *records, int64_t n, int64_t cap, const uint32_t *owner, V3 scene_miss, float *scene_origins, float *scene_dirs,
+                         uint32_t *count_dev, hipStream_t s)
+{
+    const RayList list(scratch, cap, true);
+    float *tmax = shadow ? nullptr : list.dirs + 3 * cap;
+    uint32_t *masks = reinterpret_cast<uint32_t *>(scratch + L.list), *counts = masks + n, *base = counts + L.items, *total = base + L.items;
+    int rc = launch_per_element(who, n, s, shadow ? k_inst_cull<true> : k_inst_cull<false>, F, bias, S, I, records, masks, counts, L.nblocks, owner, scene_miss, scene_origins, scene_dirs);
+    if (rc != SVO_OK) return rc;
+    size_t scan_bytes = L.scan_bytes;
+    if (hipcub::DeviceScan::ExclusiveSum(scratch + L.head, scan_bytes, counts, base, (int)L.items, s) != hipSuccess) { set_error(std::string(who) + ": scan failed"); return SVO_ERR_HIP; }
+    hipLaunchKernelGGL(k_light_total, dim3(1), dim3(1), 0, s, counts, base, L.items, (uint32_t)cap, total, count_dev);
+    if ((rc = launch_status(who)) != SVO_OK) return rc;
+    return launch_per_element(who, n, s, shadow ? k_inst_emit<true> : k_inst_emit<false>, F, bias, S, I, miss_ray_origin(model), records, masks, base, L.nblocks, total, (uint32_t)cap,
+                              list.origins, list.dirs, tmax);
+}
+
+static int instance_scan_size(const char *who, InstanceScratch &L, hipStream_t s)
+{
+    uint32_t *nul = nullptr;
+    if (hipcub::DeviceScan::ExclusiveSum(nullptr, L.scan_bytes, nul, nul, (int)L.items, s) != hipSuccess) { set_error(std::string(who) + ": scan size query failed"); return SVO_ERR_HIP; }
+    return SVO_OK;
+}
+
+// Stage 1: the pixels' rays into each instance's space, ONE bounded ray-list launch of `cap` rays on the model - each ray ends at what
+// the G-buffer holds -, the nearest hit per pixel back into the frame.  The list lives in the MODEL's scratch.
+int svo_trace_instances(svo_world *scene, svo_world *model, const svo_camera *cam, const svo_trace_params *prm, const svo_instance *inst, int ninst, int64_t max_rays,
+                        int x0, int y0, int rw, int rh, const svo_hit *gbuffer_dev, svo_hit *merged_dev, uint32_t *owner_dev, uint32_t *count_dev, void *stream)
+{
+    const char *who = "svo_trace_instances";
+    InstanceList I;
+    svo_trace_params march;
+    TraceArgs As;
+    int64_t n, cap;
+    int rc = instance_call(who, scene, model, cam, prm, inst, ninst, max_rays, 0.0f, x0, y0, rw, rh, gbuffer_dev && merged_dev && owner_dev, I, march, As, n, cap);
+    if (rc != SVO_OK || n == 0) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(model->device));
+    InstanceScratch L(n, cap, ninst, true);
+    if ((rc = instance_scan_size(who, L, s)) != SVO_OK) return rc;
+    // the records, the list and the ranks live in the model's scratch: calls on different streams are ordered behind one another
+    return model->hbm->instances.use(L.floats(), who, s, [&](float *scratch) -> int {
+        const RayList list(scratch, cap, true);
+        const PixelFrame F = make_frame(*cam, x0, y0, rw, rh);
+        const uint4 *gbuffer = reinterpret_cast<const uint4 *>(gbuffer_dev);
+        const V3 none = V3{ 0.0f, 0.0f, 0.0f };
+        int rc = instance_list(false, who, L, scratch, F, 0.0f, none, I, model, gbuffer, n, cap, nullptr, none, nullptr, nullptr, count_dev, s);
+        if (rc != SVO_OK) return rc;
+        rc = trace_list(model, list.origins, list.dirs, list.dirs + 3 * cap, cap, &march, reinterpret_cast<svo_hit *>(list.records), stream);
+        if (rc != SVO_OK) return rc;
+        const uint32_t *masks = reinterpret_cast<const uint32_t *>(scratch + L.list), *base = masks + n + L.items;
+        return launch_per_element(who, n, s, k_inst_resolve, F, I, gbuffer, masks, base, L.nblocks, (uint32_t)cap, reinterpret_cast<const uint4 *>(list.records),
+                                  reinterpret_cast<uint4 *>(merged_dev), owner_dev);
+    });
+}
+
+// Stage 2: from every usable, not yet shadowed record of merged_dev the ray towards the directional light - into each instance's space
+// and ONE unbounded launch of `cap` rays on the model, and for the pixels an instance owns ONE launch of w*h rays on the scene (the
+// terrain's pixels had theirs from svo_trace) -, the fold into the flag words.  The model list lives in the model's scratch, the scene
+// list in the scene's.
+int svo_trace_instance_shadows(svo_world *scene, svo_world *model, const svo_camera *cam, const svo_trace_params *prm, const svo_instance *inst, int ninst,
+                               int64_t max_rays, float bias, int x0, int y0, int rw, int rh, svo_hit *merged_dev, const uint32_t *owner_dev, uint32_t *count_dev,
+                               void *stream)
+{
+    const char *who = "svo_trace_instance_shadows";
+    InstanceList I;
+    svo_trace_params march;
+    TraceArgs As;
+    int64_t n, cap;
+    int rc = instance_call(who, scene, model, cam, prm, inst, ninst, max_rays, bias, x0, y0, rw, rh, merged_dev && owner_dev, I, march, As, n, cap);
+    if (rc != SVO_OK || n == 0) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipSetDevice(model->device));
+    InstanceScratch L(n, cap, ninst, false);
+    if ((rc = instance_scan_size(who, L, s)) != SVO_OK) return rc;
+    const float b = bias > 0.0f ? bias : As.eps;
+    const V3 S = V3{ As.sdir[0], As.sdir[1], As.sdir[2] };
+    return scene->hbm->instance_scene.use(RayList::floats(n, true), who, s, [&](float *scene_scratch) -> int {
+        return model->hbm->instance_shadows.use(L.floats(), who, s, [&](float *scratch) -> int {
+            const RayList list(scratch, cap, true), scene_list(scene_scratch, n, true);
+            const PixelFrame F = make_frame(*cam, x0, y0, rw, rh);
+            uint4 *merged = reinterpret_cast<uint4 *>(merged_dev);
+            int rc = instance_list(true, who, L, scratch, F, b, S, I, model, merged, n, cap, owner_dev, miss_ray_origin(scene), scene_list.origins, scene_list.dirs,
+                                         count_dev, s);
+            if (rc != SVO_OK) return rc;
+            if ((rc = svo_trace_rays(model, list.origins, list.dirs, cap, &march, reinterpret_cast<svo_hit *>(list.records), stream)) != SVO_OK) return rc;
+            if ((rc = svo_trace_rays(scene, scene_list.origins, scene_list.dirs, n, &march, reinterpret_cast<svo_hit *>(scene_list.records), stream)) != SVO_OK) return rc;
+            const uint32_t *masks = reinterpret_cast<const uint32_t *>(scratch + L.list), *base = masks + n + L.items;
+            return launch_per_element(who, n, s, k_inst_fold, F, I, masks, base, L.nblocks, (uint32_t)cap, reinterpret_cast<const uint4 *>(list.records),
+                                      reinterpret_cast<const uint4 *>(scene_list.records), merged);
+        });
     });
 }
 

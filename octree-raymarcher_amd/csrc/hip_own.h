@@ -207,6 +207,9 @@ struct Hbm {
     OrderedScratch<float> mirror;                           // svo_trace_reflections: a RayList without records, one ray per pixel
     OrderedScratch<float> local;                            // svo_trace_local_shadows: a RayList with records, one ray per pixel and light asked for
     OrderedScratch<float> lights;                           // svo_trace_lights: a RayList with records of `cap` slots, the block counts, their sums, the scan's own
+    OrderedScratch<float> instances;                        // svo_trace_instances, on the MODEL: a RayList with records and far ends of `cap` slots, the pair masks, the ranks
+    OrderedScratch<float> instance_shadows;                 // svo_trace_instance_shadows, on the MODEL: the same without far ends
+    OrderedScratch<float> instance_scene;                   // svo_trace_instance_shadows, on the SCENE: a RayList with records, one ray per pixel
     OrderedScratch<float> shadowmap;                        // svo_shadowmap_render: a RayList with records, one ray per texel in tile order
     // see-through view (svo_trace_params.see_through, see_through.hip.h): the wide and mask pools with one material taken out, built
     // on the device at the first launch that asks for it, dropped by every change to the pools

@@ -10,6 +10,8 @@
 //   svo::World::draw(camera, ...)    <- World::draw (+ draw_shadowmap as the fused shadow ray)  src/World.cpp:162-266
 //   svo::World::local_shadows(...)   <- (none: per-light shadows of the point light and the spotlight, svo_trace_local_shadows)
 //   svo::World::lights / shade_lights  <- (none: the reference has three lights) up to 32 point lights with a reach, svo_trace_lights, svo_shade_lights
+//   svo::World::instances / instance_shadows  <- (none: the reference's one moving object is a rasterised mesh, src/Worm.cpp) up to 32 placements
+//                                       of a model world in the frame and their shadows, svo_trace_instances, svo_trace_instance_shadows
 //   svo::World::shadowmap_fit / shadowmap_render / shadowmap_apply  <- the OrthoCamera, World::draw_shadowmap and computeShadow (svo_shadowmap_*):
 //                                       the directional light rendered once, looked up per frame   src/World.cpp:162-203, shaders/World.Fragment.glsl:140-155
 //   svo::World::modify(i, ...)       <- World::modify          src/World.cpp:268-274
@@ -231,6 +233,28 @@ public:
         check(svo_shade_lights(&cam, &p, list, nlights, x0, y0, w, h, gbuffer_dev, visible_dev, rgba_dev, stream), "World::shade_lights");
     }
 
+    // Up to SVO_MAX_INSTANCES placements (rotation, position, uniform scale) of `model`, another resident world - in practice one chunk
+    // from a grid -, in front of the G-buffer draw() filled (not in the reference, whose worm is a rasterised mesh).  instances() marches
+    // the pixels' rays in each placement's own space, bounded by what the frame holds, and writes the merged frame (merged_dev may be the
+    // G-buffer itself) and per pixel 0 or 1 + the instance that owns it (svo_trace_instances); the chunk / node / cell of an owned pixel
+    // belong to `model`.  instance_shadows() then gives every record not yet shadowed its SVO_SHADOW_TRACED / SVO_SHADOWED from the
+    // instances and, for owned pixels, from this world (svo_trace_instance_shadows; bias 0 = the march's eps, a rotated instance wants 1/256).
+    // max_rays: the slots of the compacted ray list (0 = one per pixel; pairs beyond it count as no hit); count_dev, optional: the pairs.
+    void instances(World &model, const Camera &cam, const svo_instance *list, int ninst, const svo_hit *gbuffer_dev, svo_hit *merged_dev, uint32_t *owner_dev,
+                   int64_t max_rays = 0, uint32_t *count_dev = nullptr, bool shadow = false, const float light_dir[3] = nullptr, void *stream = nullptr)
+    {
+        const svo_trace_params p = instance_params(shadow, light_dir);
+        check(svo_trace_instances(world_, model.world_, &cam, &p, list, ninst, max_rays, 0, 0, cam.width, cam.height, gbuffer_dev, merged_dev, owner_dev, count_dev,
+                                  stream), "World::instances");
+    }
+    void instance_shadows(World &model, const Camera &cam, const svo_instance *list, int ninst, svo_hit *merged_dev, const uint32_t *owner_dev,
+                          int64_t max_rays = 0, float bias = 0.0f, uint32_t *count_dev = nullptr, const float light_dir[3] = nullptr, void *stream = nullptr)
+    {
+        const svo_trace_params p = instance_params(true, light_dir);
+        check(svo_trace_instance_shadows(world_, model.world_, &cam, &p, list, ninst, max_rays, bias, 0, 0, cam.width, cam.height, merged_dev, owner_dev, count_dev,
+                                         stream), "World::instance_shadows");
+    }
+
     // The shadow map of a fixed sun (svo_shadowmap_fit / _render / _apply; the reference's World::draw_shadowmap and computeShadow,
     // src/World.cpp:162-203, shaders/World.Fragment.glsl:140-155): fit a width x height map around the world along `direction`, render it
     // once - and again after every edit, a rendered map is stale behind one -, then per frame draw(cam, out, false) and shadowmap_apply:
@@ -436,6 +460,16 @@ private:
 public:
 
     int width = 0, height = 0, depth = 0, plane = 0, volume = 0, chunksize = 0;
+    svo_trace_params instance_params(bool shadow, const float light_dir[3]) const
+    {
+        svo_trace_params p;
+        std::memset(&p, 0, sizeof p);
+        p.semantics = semantics;
+        p.shadow = shadow ? 1 : 0;
+        if (light_dir) std::memcpy(p.light_dir, light_dir, sizeof p.light_dir);
+        return p;
+    }
+
 private:
     svo_world *world_ = nullptr;
 };
