@@ -12,6 +12,9 @@
  *   svo_world_create     <- a World whose chunk[] the caller already owns (Ocroot, src/Octree.h:56-76)
  *   svo_chunk_from_grid / svo_world_chunk_from_grid <- grow() (src/Octree.cpp:74-176) over a grid instead of the height pyramid
  *   svo_world_chunk_to_grid <- (no counterpart) the chunk's voxels back as a dense grid
+ *   svo_grid_add_mesh / svo_device_grid_add_mesh <- (no counterpart: the reference rasterises its one mesh, src/Worm.cpp, with GL) a
+ *                           triangle mesh voxelised into a dense grid, on the host or in device memory
+ *   svo_grid_fill_enclosed / svo_device_grid_fill_enclosed <- (no counterpart) the cells that such a shell encloses, filled
  *   svo_world_upload     <- World::load_gpu + RootAllocator::alloc src/World.cpp:57-94, src/Allocator.cpp:28-35
  *   svo_world_update     <- World::modify + RootAllocator::subst   src/World.cpp:268-274, src/Allocator.cpp:37-55
  *   svo_trace            <- World::draw (+ draw_shadowmap)         src/World.cpp:162-266
@@ -126,7 +129,9 @@ extern "C" {
                                           svo_trace_params.shadow, which was any non-zero value: such callers keep their results),
                                           svo_world_prepared_bricks and SVO_SHADOW_NO_BRICK_CLEARANCE (another such bit),
                                           svo_trace_lights, svo_shade_lights, svo_light and SVO_MAX_LIGHTS,
-                                          svo_trace_instances, svo_trace_instance_shadows, svo_instance and SVO_MAX_INSTANCES */
+                                          svo_trace_instances, svo_trace_instance_shadows, svo_instance and SVO_MAX_INSTANCES,
+                                          svo_grid_add_mesh, svo_device_grid_add_mesh, svo_grid_fill_enclosed,
+                                          svo_device_grid_fill_enclosed and svo_mesh (functions added, nothing changed) */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -491,6 +496,64 @@ int svo_world_chunk_from_grid(svo_world *, int chunk, const uint16_t *grid_dev, 
  * SVO_ERR_INVALID_ARG; then a world that is not resident: SVO_ERR_NOT_UPLOADED - settled before any device work.  Asynchronous on
  * `stream` and ordered against updates, edits and shifts like svo_world_locate; it takes no launch slot and no scratch. */
 int svo_world_chunk_to_grid(svo_world *, int chunk, uint32_t depth, uint16_t *grid_dev, void *stream);
+
+/* ---- grids from triangle meshes: a voxeliser and an interior fill ------------------------------------------------------
+ * svo_grid_add_mesh rasterises a triangle mesh into a grid as above (N = 2^depth cells per axis, x fastest, depth in
+ * [SVO_GRID_MIN_DEPTH, SVO_GRID_MAX_DEPTH]); svo_grid_fill_enclosed makes the shell it leaves solid.  Each has a host form (every
+ * pointer host memory) and a device form (svo_device_*: the svo_mesh struct on the host, its three arrays and the grid in device
+ * memory, the grid 16-byte aligned); neither the mesh nor the grid of a device call visits the host.  The two forms give the same
+ * grid, cell for cell.  The way on from the grid: svo_world_chunk_from_grid -> svo_trace_instances, or svo_chunk_from_grid ->
+ * svo_world_create.
+ *
+ * For every cell,  grid[cell] = max(what it held, the largest material of the triangles that overlap it);  no other cell changes.
+ * THE CALLER CLEARS THE GRID FIRST (or leaves in it what the mesh is to be merged with).  The result does not depend on the order of
+ * the triangles, two calls give what one call on the concatenated mesh gives, and a triangle of material 0 changes nothing.
+ *
+ * The overlap rule is conservative (a cell that the triangle touches is marked) and closed (touching counts).  Every operation below
+ * is a float operation, separately rounded (nothing is contracted into a fused multiply-add), and a comparison with a NaN is false:
+ *   inv = 1.0f / cell, rounded once on the host; a vertex v goes to grid units per axis as g = (v - origin) * inv;
+ *   dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z;   cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x);
+ *   e0 = v1 - v0, e1 = v2 - v1, e2 = v0 - v2, n = cross(e0, e1)     (v0, v1, v2 in grid units).
+ * A triangle is DROPPED - it overlaps nothing - if one of its three indices is >= nvertices (nothing is read out of range, whatever
+ * the index array holds), if one of its nine grid coordinates is not finite, or if n is (0, 0, 0).  Otherwise it overlaps the cell
+ * p = (x, y, z) (the integer min corner as floats; the cell's box is [p, p + 1]) iff all of these hold:
+ *   box     per axis k:  p[k] <= hi[k]  and  p[k] + 1 >= lo[k],   lo = min(min(v0, v1), v2) and hi likewise the max;
+ *   plane   c[k] = n[k] > 0 ? 1 : 0,  d1 = dot(c - v0, n),  d2 = dot((1 - c) - v0, n),  q = dot(p, n):   (q + d1) * (q + d2) <= 0;
+ *   edges   for (i, j, w) in ((x, y, z), (y, z, x), (z, x, y)):  s = n[w] >= 0 ? 1 : -1,  and for each edge k = 0, 1, 2:
+ *             a = -e_k[j] * s,  b = e_k[i] * s,  de = ((-(a*v_k[i] + b*v_k[j])) + max0(a)) + max0(b),  max0(t) = t > 0 ? t : 0:
+ *             (a*p[i] + b*p[j]) + de >= 0.
+ * "Closed" on the lattice: a face that lies exactly in a lattice plane marks the cells on BOTH of its sides.  An axis-aligned cube
+ * with its corners at cells 4 and 8 marks the cells 3 .. 8 per axis (6^3 - 2^3 = 208 cells), not 4 .. 7; a caller who wants 4 .. 7
+ * moves or shrinks the mesh by a fraction of a cell.
+ *
+ * The fill: an empty cell (value 0) is OUTSIDE iff a path of 6-neighbour steps through empty cells connects it to an empty cell with
+ * a coordinate of 0 or N - 1.  Every empty cell that is not outside becomes `material`; nothing else changes; *filled_out (may be
+ * NULL) receives how many cells were filled.
+ *
+ * Refusals, settled before any device work, nothing written: SVO_ERR_INVALID_ARG for a NULL mesh or grid, NULL vertices or indices
+ * with a non-zero count, a depth out of range, a misaligned device grid, a cell that is not finite or not > 0, an inv that is not
+ * finite, an origin that is not finite, a fill with material 0.  ntriangles == 0 is SVO_OK and touches nothing.
+ * The device forms are world-less, like svo_shade: they run on the calling thread's current device, on `stream`, take their working
+ * memory from the library's device buffer cache (svo_device_cache_trim returns it), HAVE COMPLETED WHEN THEY RETURN (they need
+ * totals on the host) and synchronise `stream` only, not the device - with the cache's two exceptions: a cache that is full of larger
+ * buffers gives the arena back with hipFree, and an allocation that fails is tried again after svo_device_cache_trim; both wait for
+ * the device.  SVO_ERR_NO_DEVICE, SVO_ERR_HIP, SVO_ERR_OUT_OF_MEMORY as elsewhere; svo_device_grid_add_mesh (the device form only)
+ * refuses a mesh of 2^31 - 1 triangles or more with SVO_ERR_UNSUPPORTED, before any device work. */
+typedef struct svo_mesh {
+    const float    *vertices;       /* [nvertices][3] */
+    const uint32_t *indices;        /* [ntriangles][3] */
+    const uint16_t *materials;      /* [ntriangles], or NULL: every triangle carries `material` */
+    uint32_t        nvertices, ntriangles;
+    float           origin[3];      /* the grid's min corner, in the mesh's coordinates */
+    float           cell;           /* edge of one grid cell, in the mesh's coordinates */
+    uint16_t        material;       /* used when materials == NULL */
+    uint16_t        _pad[3];        /* 56 bytes */
+} svo_mesh;
+
+int svo_grid_add_mesh(const svo_mesh *mesh, uint32_t depth, uint16_t *grid);
+int svo_device_grid_add_mesh(const svo_mesh *mesh, uint32_t depth, uint16_t *grid_dev, void *stream);
+int svo_grid_fill_enclosed(uint16_t *grid, uint32_t depth, uint16_t material, uint64_t *filled_out);
+int svo_device_grid_fill_enclosed(uint16_t *grid_dev, uint32_t depth, uint16_t material, uint64_t *filled_out, void *stream);
 
 /* ---- the hot path ------------------------------------------------------------------------ */
 

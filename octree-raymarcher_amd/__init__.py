@@ -23,6 +23,7 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     World.edit_ball / edit_ball_all           <- (none: the reference edits cubes only)    destroyCube / buildCube over a closed ball
     World.hit_ao / ao_image, shade_ao         <- (none: the reference has no ambient occlusion)   the eight lattice cells around each hit's face
     World.trace_reflections / reflect_image, shade_reflections, Mirror   <- (none: the reference has no reflections)   one mirror ray per hit, off its voxel's face
+    grid_add_mesh / grid_fill_enclosed, device_grid_add_mesh / device_grid_fill_enclosed, Mesh   <- (none: the reference rasterises its one mesh with GL)   a triangle mesh into a dense grid, its shell filled
 
 There is NO CPU fallback: if libsvo_amd.so is missing the import raises, and every device call
 raises SvoError when HIP reports no device.
@@ -205,6 +206,21 @@ class Instance(C.Structure):
         self.pos[:], self.scale = [float(c) for c in pos], float(scale)
 
 
+class Mesh(C.Structure):
+    """svo_mesh: a triangle mesh and the frame of the grid it is voxelised into (56 bytes).  Mesh(vertices, indices, materials, nvertices,
+    ntriangles, origin, cell, material): the three arrays as addresses (host for svo_grid_add_mesh, device for svo_device_grid_add_mesh;
+    None = NULL); the struct does not keep them alive."""
+    _fields_ = [("vertices", C.c_void_p), ("indices", C.c_void_p), ("materials", C.c_void_p), ("nvertices", C.c_uint32), ("ntriangles", C.c_uint32),
+                ("origin", C.c_float * 3), ("cell", C.c_float), ("material", C.c_uint16), ("_pad", C.c_uint16 * 3)]
+
+    def __init__(self, vertices=None, indices=None, materials=None, nvertices: int = 0, ntriangles: int = 0, origin=(0.0, 0.0, 0.0), cell: float = 1.0,
+                 material: int = 1):
+        super().__init__()
+        self.vertices, self.indices, self.materials = vertices, indices, materials
+        self.nvertices, self.ntriangles = int(nvertices), int(ntriangles)
+        self.origin[:], self.cell, self.material = [float(c) for c in origin], float(cell), int(material)
+
+
 class Box(C.Structure):
     """svo_box: one overlay cube of svo_shade_boxes (48 bytes; BOX_DTYPE is its numpy twin)."""
     _fields_ = [("bmin", C.c_float * 3), ("size", C.c_float), ("color", C.c_float * 3), ("alpha", C.c_float), ("style", C.c_uint32),
@@ -227,6 +243,7 @@ ABI_SYMBOLS = [
     "svo_world_generate", "svo_world_create", "svo_world_info_get", "svo_world_chunk", "svo_world_destroy",
     "svo_world_index_float", "svo_world_index", "svo_world_locate", "svo_hit_voxels", "svo_hit_uv", "svo_shade_textured", "svo_world_upload", "svo_world_update",
     "svo_chunk_from_grid", "svo_world_chunk_from_grid", "svo_world_chunk_to_grid",
+    "svo_grid_add_mesh", "svo_device_grid_add_mesh", "svo_grid_fill_enclosed", "svo_device_grid_fill_enclosed",
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_edit_cube", "svo_world_edit_ball", "svo_world_edit_ball_all", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_cursor_place", "svo_shade_boxes", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_shadowmap_fit", "svo_shadowmap_render", "svo_shadowmap_apply", "svo_hit_ao", "svo_shade_ao",
@@ -262,6 +279,10 @@ lib.svo_world_shift.argtypes = [_P, C.POINTER(C.c_int)]
 lib.svo_chunk_from_grid.argtypes = [_P, C.c_uint32, C.POINTER(C.c_float), C.c_float, C.POINTER(ChunkDesc)]
 lib.svo_world_chunk_from_grid.argtypes = [_P, C.c_int, _P, C.c_uint32]
 lib.svo_world_chunk_to_grid.argtypes = [_P, C.c_int, C.c_uint32, _P, _P]
+lib.svo_grid_add_mesh.argtypes = [C.POINTER(Mesh), C.c_uint32, _P]
+lib.svo_device_grid_add_mesh.argtypes = [C.POINTER(Mesh), C.c_uint32, _P, _P]
+lib.svo_grid_fill_enclosed.argtypes = [_P, C.c_uint32, C.c_uint16, C.POINTER(C.c_uint64)]
+lib.svo_device_grid_fill_enclosed.argtypes = [_P, C.c_uint32, C.c_uint16, C.POINTER(C.c_uint64), _P]
 lib.svo_gbuffer_pack.argtypes = [_P, _P, C.c_int64, _P]
 lib.svo_gbuffer_unpack.argtypes = [_P, _P, C.c_int64, _P]
 lib.svo_shade_defaults.argtypes = [C.POINTER(ShadeParams)]
@@ -478,6 +499,44 @@ def chunk_from_grid(grid, position=(0.0, 0.0, 0.0), size: float = 128.0) -> dict
         return {"position": tuple(d.position), "size": d.size, "depth": d.depth, "tree": tree, "twig": twig}
     finally:
         lib.svo_chunk_free(C.byref(d))
+
+
+def grid_add_mesh(grid: np.ndarray, vertices, indices, origin=(0.0, 0.0, 0.0), cell: float = 1.0, material: int = 1, materials=None) -> np.ndarray:
+    """svo_grid_add_mesh on the host: the triangles (vertices [nv, 3] float32, indices [nt, 3] uint32, materials [nt] uint16 or None:
+    every triangle carries `material`) raised into `grid`, a C-contiguous [z, y, x] uint16 array, in place.  Returns grid."""
+    if not (isinstance(grid, np.ndarray) and grid.dtype == np.uint16 and grid.flags.c_contiguous and grid.flags.writeable):
+        raise ValueError("grid_add_mesh writes into a C-contiguous uint16 array")
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    ix = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
+    mats = None if materials is None else np.ascontiguousarray(materials, dtype=np.uint16).reshape(ix.shape[0])
+    m = Mesh(v.ctypes.data if v.size else None, ix.ctypes.data if ix.size else None, None if mats is None else mats.ctypes.data,
+             v.shape[0], ix.shape[0], origin, cell, material)
+    _check(lib.svo_grid_add_mesh(C.byref(m), _grid_depth(grid), grid.ctypes.data), "svo_grid_add_mesh")
+    return grid
+
+
+def device_grid_add_mesh(grid_ptr: int, depth: int, vertices_ptr, nvertices: int, indices_ptr, ntriangles: int, origin=(0.0, 0.0, 0.0),
+                         cell: float = 1.0, material: int = 1, materials_ptr=None, stream: int = 0):
+    """svo_device_grid_add_mesh: the same on device pointers (the grid 16-byte aligned); complete when it returns."""
+    m = Mesh(vertices_ptr, indices_ptr, materials_ptr, nvertices, ntriangles, origin, cell, material)
+    return _check(lib.svo_device_grid_add_mesh(C.byref(m), int(depth), grid_ptr, stream), "svo_device_grid_add_mesh")
+
+
+def grid_fill_enclosed(grid: np.ndarray, material: int) -> int:
+    """svo_grid_fill_enclosed on the host: the empty cells of the [z, y, x] uint16 array that no path of empty cells connects to the
+    grid's faces become `material`, in place.  Returns how many."""
+    if not (isinstance(grid, np.ndarray) and grid.dtype == np.uint16 and grid.flags.c_contiguous and grid.flags.writeable):
+        raise ValueError("grid_fill_enclosed writes into a C-contiguous uint16 array")
+    filled = C.c_uint64(0)
+    _check(lib.svo_grid_fill_enclosed(grid.ctypes.data, _grid_depth(grid), int(material), C.byref(filled)), "svo_grid_fill_enclosed")
+    return int(filled.value)
+
+
+def device_grid_fill_enclosed(grid_ptr: int, depth: int, material: int, stream: int = 0) -> int:
+    """svo_device_grid_fill_enclosed: the same on a device grid (16-byte aligned); complete when it returns.  Returns how many."""
+    filled = C.c_uint64(0)
+    _check(lib.svo_device_grid_fill_enclosed(grid_ptr, int(depth), int(material), C.byref(filled), stream), "svo_device_grid_fill_enclosed")
+    return int(filled.value)
 
 
 def gbuffer_pack(gbuffer_ptr: int, packed_ptr: int, n: int, stream: int = 0):

@@ -19,6 +19,8 @@
 //   svo::World::locate(points, ...)  <- traverse over a point list (svo_world_locate)   src/Traverse.cpp:34-48
 //   svo::World::chunk_from_grid / chunk_to_grid  <- grow() over a dense voxel grid instead of the height pyramid (svo_world_chunk_from_grid),
 //                                       and the chunk's voxels back as a grid (svo_world_chunk_to_grid)   src/Octree.cpp:74-176
+//   svo::grid_add_mesh / grid_fill_enclosed, svo::device_grid_add_mesh / device_grid_fill_enclosed  <- (none: the reference rasterises its
+//                                       one mesh with GL) a triangle mesh voxelised into such a grid and its shell filled, on the host or in device memory
 //   svo::World::hit_voxels(...)      <- hit.bmin / hit.size of fragment main (svo_hit_voxels)   shaders/World.Fragment.glsl:168-172
 //   svo::World::hit_uv / shade_textured  <- leafUV, texture(Diffuse / Specular, uv) (svo_hit_uv, svo_shade_textured)   shaders/World.Fragment.glsl:5-15,178-182
 //   svo::World::hit_ao / shade_ao    <- (none: the reference has no ambient occlusion) svo_hit_ao, svo_shade_ao
@@ -499,6 +501,29 @@ inline bool chunkmarch(vec3 alpha, vec3 beta, const World *world, vec3 *sigma, s
     if (!(h.flags & SVO_HIT_FLAG)) return false;
     if (sigma) *sigma = { alpha.x + beta.x * h.t, alpha.y + beta.y * h.t, alpha.z + beta.z * h.t };   // src/Traverse.cpp:161
     return true;
+}
+
+// A triangle mesh into a dense grid ((2^depth)^3 uint16 materials, x fastest; the caller clears it first), and the cells its shell
+// encloses filled - world-less, like the shading stages; svo.h states both rules.  grid_add_mesh / grid_fill_enclosed: every pointer host
+// memory.  device_grid_add_mesh / device_grid_fill_enclosed: the mesh's three arrays and the grid in device memory (the grid 16-byte
+// aligned), on the calling thread's current device and on `stream`, complete at the return.  The fills return how many cells they filled.
+// From the grid on: World::chunk_from_grid, then World::instances; or svo_chunk_from_grid and a world created from it.
+inline void grid_add_mesh(const svo_mesh &mesh, uint32_t depth, uint16_t *grid) { check(svo_grid_add_mesh(&mesh, depth, grid), "grid_add_mesh"); }
+inline void device_grid_add_mesh(const svo_mesh &mesh, uint32_t depth, uint16_t *grid_dev, void *stream = nullptr)
+{
+    check(svo_device_grid_add_mesh(&mesh, depth, grid_dev, stream), "device_grid_add_mesh");
+}
+inline uint64_t grid_fill_enclosed(uint16_t *grid, uint32_t depth, uint16_t material)
+{
+    uint64_t filled = 0;
+    check(svo_grid_fill_enclosed(grid, depth, material, &filled), "grid_fill_enclosed");
+    return filled;
+}
+inline uint64_t device_grid_fill_enclosed(uint16_t *grid_dev, uint32_t depth, uint16_t material, void *stream = nullptr)
+{
+    uint64_t filled = 0;
+    check(svo_device_grid_fill_enclosed(grid_dev, depth, material, &filled, stream), "device_grid_fill_enclosed");
+    return filled;
 }
 
 } // namespace svo
