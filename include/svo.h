@@ -12,6 +12,8 @@
  *   svo_world_create     <- a World whose chunk[] the caller already owns (Ocroot, src/Octree.h:56-76)
  *   svo_chunk_from_grid / svo_world_chunk_from_grid <- grow() (src/Octree.cpp:74-176) over a grid instead of the height pyramid
  *   svo_world_chunk_to_grid <- (no counterpart) the chunk's voxels back as a dense grid
+ *   svo_chunk_from_mesh / svo_world_chunk_from_mesh <- (no counterpart) the tree of a triangle mesh's shell without the dense grid, to
+ *                           depth 16, on the host or on the device
  *   svo_grid_add_mesh / svo_device_grid_add_mesh <- (no counterpart: the reference rasterises its one mesh, src/Worm.cpp, with GL) a
  *                           triangle mesh voxelised into a dense grid, on the host or in device memory
  *   svo_grid_fill_enclosed / svo_device_grid_fill_enclosed <- (no counterpart) the cells that such a shell encloses, filled
@@ -88,7 +90,7 @@
  *     launch owns a private work-cursor slot from a 64-entry ring, and a launch that comes round
  *     to a slot still in use is ordered on the device behind that earlier launch;
  *   - svo_world_update / svo_world_shift / svo_world_edit_box / svo_world_edit_ball(_all) / svo_world_compact / svo_world_coarsen /
- *     svo_world_chunk_from_grid / svo_world_upload are ordered behind every launch issued before them on any stream
+ *     svo_world_chunk_from_grid / svo_world_chunk_from_mesh / svo_world_upload are ordered behind every launch issued before them on any stream
  *     (they drain the device before touching HBM, as World::modify is ordered on the GL queue) and have completed when they return: launches issued afterwards see
  *     the new world, launches issued before saw the old one, none sees a mixture.
  *
@@ -131,7 +133,9 @@ extern "C" {
                                           svo_trace_lights, svo_shade_lights, svo_light and SVO_MAX_LIGHTS,
                                           svo_trace_instances, svo_trace_instance_shadows, svo_instance and SVO_MAX_INSTANCES,
                                           svo_grid_add_mesh, svo_device_grid_add_mesh, svo_grid_fill_enclosed,
-                                          svo_device_grid_fill_enclosed and svo_mesh (functions added, nothing changed) */
+                                          svo_device_grid_fill_enclosed and svo_mesh,
+                                          svo_chunk_from_mesh, svo_world_chunk_from_mesh and SVO_MESH_MIN_DEPTH / SVO_MESH_MAX_DEPTH
+                                          (functions added, nothing changed) */
 
 typedef enum svo_status {
     SVO_OK                 =  0,
@@ -554,6 +558,46 @@ int svo_grid_add_mesh(const svo_mesh *mesh, uint32_t depth, uint16_t *grid);
 int svo_device_grid_add_mesh(const svo_mesh *mesh, uint32_t depth, uint16_t *grid_dev, void *stream);
 int svo_grid_fill_enclosed(uint16_t *grid, uint32_t depth, uint16_t material, uint64_t *filled_out);
 int svo_device_grid_fill_enclosed(uint16_t *grid_dev, uint32_t depth, uint16_t material, uint64_t *filled_out, void *stream);
+
+/* ---- chunks straight from triangle meshes: the sparse voxeliser ---------------------------------------------------------
+ * The tree of the grid that svo_grid_add_mesh would leave, built WITHOUT that grid, for depth in [SVO_MESH_MIN_DEPTH,
+ * SVO_MESH_MAX_DEPTH] - beyond SVO_GRID_MAX_DEPTH, where the grid would not fit.  Definition: let G be the (2^depth)^3 grid, all 0;
+ * every mesh of the list, in any order, is added to it by the rule stated above for svo_grid_add_mesh (the drop rules, the closed
+ * conservative overlap test, the largest material where triangles meet, material 0 changing nothing, inv = 1 / cell rounded once on
+ * the host; every mesh carries its own origin and cell); the result is the tree of G by the rule stated above for
+ * svo_chunk_from_grid (EMPTY / LEAF / BRANCH nodes and TWIGs at level depth-2, FIFO visiting order, a uniform 4^3 block a LEAF,
+ * minimal pools).  For depth <= SVO_GRID_MAX_DEPTH that is, index for index, svo_chunk_from_grid of svo_grid_add_mesh of a cleared
+ * grid; above it the same sentences define it.  G is never allocated: working memory is proportional to the number of (triangle,
+ * cell) overlaps - a cell's Morton key (3 * depth bits) and its material (16 bits) are one 64-bit word, which is why depth ends at 16.
+ * The host form and the device form give the same pools.
+ *
+ * THERE IS NO INTERIOR FILL: the result is the shell.  From outside it renders and shadows like the solid; an edit that cuts it open
+ * (svo_world_edit_box / _ball) finds it hollow.  The chunk is REPLACED, nothing is merged with what it held.  One call builds one
+ * chunk: a mesh that spans several chunks is passed to every one of them with origin = that chunk's min corner in the mesh's
+ * coordinates and cell = the chunk's size / 2^depth - the closed rule marks the cells on both sides of a chunk border alike.
+ * Cost: every triangle is tested against every cell of its clamped cell box (on the device: one wave per 4^3-cell tile of the box,
+ * up to (2^depth / 4)^3 tiles for one triangle that spans the grid; no tile is rejected early), so a few huge triangles at a high
+ * depth cost what their boxes hold, not what their surfaces hold.
+ *
+ * svo_chunk_from_mesh (host; every pointer host memory): malloc'ed pools in *out with the given frame, freed with svo_chunk_free -
+ * what svo_world_create takes.  It needs no device.
+ * svo_world_chunk_from_mesh (device; the svo_mesh structs on the host, their arrays device memory on the world's device): chunk
+ * `chunk` of an UPLOADED world is replaced; position and size stay, `depth` becomes the chunk's depth.  Ordered, complete and
+ * installed like svo_world_chunk_from_grid (it drains the device first; masks, wide tree, light-clearance state, svo_world_info and
+ * the host copy on request follow as there); SVO_OK, or SVO_OK_LITERAL_ONLY as for svo_world_edit_box.  Neither the meshes nor the
+ * pools visit the host; the working arrays come from the library's device buffer cache.
+ *
+ * nmeshes == 0, or meshes of which every triangle is dropped or misses the grid: SVO_OK, the chunk is the one word EMPTY, 0 bricks.
+ * Refusals, all before anything changes: SVO_ERR_INVALID_ARG for a NULL world / out / position, nmeshes < 0 or nmeshes > 0 with NULL
+ * meshes, a depth out of range, a chunk out of range, per mesh what svo_grid_add_mesh refuses of a mesh (NULL vertices or indices
+ * with a non-zero count, a cell that is not finite or not > 0, an inv or an origin that is not finite), on the host form a size that
+ * is not finite or not > 0; then SVO_ERR_NOT_UPLOADED (device form, a world that is not resident); SVO_ERR_UNSUPPORTED for 2^31 - 1
+ * triangles or more (device form: in one mesh or in the list), 2^31 - 1 overlaps or more, 2^30 nodes or bricks;
+ * SVO_ERR_OUT_OF_MEMORY when the working arrays do not fit (device: tried again after svo_device_cache_trim). */
+#define SVO_MESH_MIN_DEPTH 2
+#define SVO_MESH_MAX_DEPTH 16
+int svo_chunk_from_mesh(const svo_mesh *meshes, int nmeshes, uint32_t depth, const float position[3], float size, svo_chunk_desc *out);
+int svo_world_chunk_from_mesh(svo_world *, int chunk, const svo_mesh *meshes, int nmeshes, uint32_t depth);
 
 /* ---- the hot path ------------------------------------------------------------------------ */
 
@@ -1233,7 +1277,7 @@ int svo_trace_last_ray_count(svo_world *, void *stream, uint64_t *rays);
  *   automatic                 the first svo_trace / svo_trace_frames / svo_trace_rows(_frames) launch with shadow rays on a world that has
  *                             not changed since its upload (or its generation on the device) prepares the bits for its own light_dir.
  *   dropped by                every change to the pools (svo_world_update / _edit_* / _shift / _compact / _coarsen / _chunk_from_grid /
- *                             _upload).  After a change only svo_world_prepare_light brings them back: a caller who edits every frame
+ *                             _chunk_from_mesh / _upload).  After a change only svo_world_prepare_light brings them back: a caller who edits every frame
  *                             never pays a sweep per frame.
  *   used by                   camera launches of SVO_SEMANTICS_CPU with shadow rays whose light_dir equals the prepared one bit for bit and
  *                             whose eps is a power of two of at least twice the float spacing at the world's largest coordinate.  Ray lists,

@@ -23,6 +23,7 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     World.edit_ball / edit_ball_all           <- (none: the reference edits cubes only)    destroyCube / buildCube over a closed ball
     World.hit_ao / ao_image, shade_ao         <- (none: the reference has no ambient occlusion)   the eight lattice cells around each hit's face
     World.trace_reflections / reflect_image, shade_reflections, Mirror   <- (none: the reference has no reflections)   one mirror ray per hit, off its voxel's face
+    chunk_from_mesh, World.chunk_from_mesh   <- (none)   the tree of a mesh's shell without the dense grid, to depth 16
     grid_add_mesh / grid_fill_enclosed, device_grid_add_mesh / device_grid_fill_enclosed, Mesh   <- (none: the reference rasterises its one mesh with GL)   a triangle mesh into a dense grid, its shell filled
 
 There is NO CPU fallback: if libsvo_amd.so is missing the import raises, and every device call
@@ -244,6 +245,7 @@ ABI_SYMBOLS = [
     "svo_world_index_float", "svo_world_index", "svo_world_locate", "svo_hit_voxels", "svo_hit_uv", "svo_shade_textured", "svo_world_upload", "svo_world_update",
     "svo_chunk_from_grid", "svo_world_chunk_from_grid", "svo_world_chunk_to_grid",
     "svo_grid_add_mesh", "svo_device_grid_add_mesh", "svo_grid_fill_enclosed", "svo_device_grid_fill_enclosed",
+    "svo_chunk_from_mesh", "svo_world_chunk_from_mesh",
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_edit_cube", "svo_world_edit_ball", "svo_world_edit_ball_all", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_cursor_place", "svo_shade_boxes", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_shadowmap_fit", "svo_shadowmap_render", "svo_shadowmap_apply", "svo_hit_ao", "svo_shade_ao",
@@ -283,6 +285,8 @@ lib.svo_grid_add_mesh.argtypes = [C.POINTER(Mesh), C.c_uint32, _P]
 lib.svo_device_grid_add_mesh.argtypes = [C.POINTER(Mesh), C.c_uint32, _P, _P]
 lib.svo_grid_fill_enclosed.argtypes = [_P, C.c_uint32, C.c_uint16, C.POINTER(C.c_uint64)]
 lib.svo_device_grid_fill_enclosed.argtypes = [_P, C.c_uint32, C.c_uint16, C.POINTER(C.c_uint64), _P]
+lib.svo_chunk_from_mesh.argtypes = [C.POINTER(Mesh), C.c_int, C.c_uint32, C.POINTER(C.c_float), C.c_float, C.POINTER(ChunkDesc)]
+lib.svo_world_chunk_from_mesh.argtypes = [_P, C.c_int, C.POINTER(Mesh), C.c_int, C.c_uint32]
 lib.svo_gbuffer_pack.argtypes = [_P, _P, C.c_int64, _P]
 lib.svo_gbuffer_unpack.argtypes = [_P, _P, C.c_int64, _P]
 lib.svo_shade_defaults.argtypes = [C.POINTER(ShadeParams)]
@@ -537,6 +541,37 @@ def device_grid_fill_enclosed(grid_ptr: int, depth: int, material: int, stream: 
     filled = C.c_uint64(0)
     _check(lib.svo_device_grid_fill_enclosed(grid_ptr, int(depth), int(material), C.byref(filled), stream), "svo_device_grid_fill_enclosed")
     return int(filled.value)
+
+
+def _host_meshes(meshes):
+    """A list of dict(vertices, indices[, origin, cell, material, materials]) as an svo_mesh array over host arrays, and what keeps
+    those arrays alive."""
+    arr, keep = (Mesh * max(len(meshes), 1))(), []
+    for k, m in enumerate(meshes):
+        v = np.ascontiguousarray(m["vertices"], dtype=np.float32).reshape(-1, 3)
+        ix = np.ascontiguousarray(m["indices"], dtype=np.uint32).reshape(-1, 3)
+        mats = None if m.get("materials") is None else np.ascontiguousarray(m["materials"], dtype=np.uint16).reshape(ix.shape[0])
+        keep += [v, ix, mats]
+        arr[k].__init__(v.ctypes.data if v.size else None, ix.ctypes.data if ix.size else None, None if mats is None else mats.ctypes.data,
+                        v.shape[0], ix.shape[0], m.get("origin", (0.0, 0.0, 0.0)), m.get("cell", 1.0), m.get("material", 1))
+    return arr, keep
+
+
+def chunk_from_mesh(meshes, depth: int, position=(0.0, 0.0, 0.0), size: float = 128.0) -> dict:
+    """svo_chunk_from_mesh on the host: the tree of the shell of the meshes - a list of dict(vertices [nv, 3] float32, indices [nt, 3]
+    uint32, origin, cell, material, materials [nt] uint16 or None), the keyword arguments of grid_add_mesh - at `depth` (2 .. 16),
+    built without the dense grid, as a chunk dict (World.create takes it)."""
+    meshes = list(meshes)
+    arr, keep = _host_meshes(meshes)
+    d = ChunkDesc()
+    pos = None if position is None else (C.c_float * 3)(*[float(v) for v in position])
+    _check(lib.svo_chunk_from_mesh(arr, len(meshes), int(depth), pos, float(size), C.byref(d)), "svo_chunk_from_mesh")
+    try:
+        tree = np.ctypeslib.as_array(d.tree, shape=(d.trees,)).copy()
+        twig = np.ctypeslib.as_array(d.twig, shape=(d.twigs * 64,)).copy() if d.twigs else np.zeros(0, np.uint16)
+        return {"position": tuple(d.position), "size": d.size, "depth": d.depth, "tree": tree, "twig": twig}
+    finally:
+        lib.svo_chunk_free(C.byref(d))
 
 
 def gbuffer_pack(gbuffer_ptr: int, packed_ptr: int, n: int, stream: int = 0):
@@ -818,6 +853,15 @@ class World:
     def chunk_from_grid(self, chunk: int, grid_ptr: int, depth: int):
         """svo_world_chunk_from_grid: chunk replaced by the tree of the (2^depth)^3 uint16 grid at grid_ptr (device memory, x fastest)."""
         return _check(lib.svo_world_chunk_from_grid(self._h, int(chunk), grid_ptr, int(depth)), "svo_world_chunk_from_grid")
+
+    def chunk_from_mesh(self, chunk: int, meshes: Sequence[Mesh], depth: int):
+        """svo_world_chunk_from_mesh: chunk replaced by the tree of the shell of the meshes at `depth` (2 .. 16), built on the device
+        without the dense grid.  meshes: Mesh structs whose three arrays are device pointers."""
+        meshes = list(meshes)
+        arr = (Mesh * max(len(meshes), 1))()
+        for k, m in enumerate(meshes):
+            C.memmove(C.byref(arr[k]), C.byref(m), C.sizeof(Mesh))
+        return _check(lib.svo_world_chunk_from_mesh(self._h, int(chunk), arr, len(meshes), int(depth)), "svo_world_chunk_from_mesh")
 
     def chunk_to_grid(self, chunk: int, depth: int, out_ptr: int, stream: int = 0):
         """svo_world_chunk_to_grid: the chunk's voxels as a (2^depth)^3 uint16 grid at out_ptr (device memory), asynchronous on stream."""

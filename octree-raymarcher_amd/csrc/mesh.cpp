@@ -20,8 +20,14 @@ namespace svo {
 // the refusals of both add_mesh twins that do not depend on where the grid lives; *inv receives 1 / cell
 bool mesh_args_ok(const svo_mesh *m, uint32_t depth, const void *grid, float *inv)
 {
-    if (!m || !grid || depth < SVO_GRID_MIN_DEPTH || depth > SVO_GRID_MAX_DEPTH) return false;
-    if ((m->nvertices && !m->vertices) || (m->ntriangles && !m->indices)) return false;
+    if (!grid || depth < SVO_GRID_MIN_DEPTH || depth > SVO_GRID_MAX_DEPTH) return false;
+    return mesh_frame_ok(m, inv);
+}
+
+// the part of them that is about the mesh alone (sparse_mesh.cpp has no grid and a depth range of its own)
+bool mesh_frame_ok(const svo_mesh *m, float *inv)
+{
+    if (!m || (m->nvertices && !m->vertices) || (m->ntriangles && !m->indices)) return false;
     if (!std::isfinite(m->cell) || !(m->cell > 0.0f)) return false;
     *inv = 1.0f / m->cell;
     if (!std::isfinite(*inv)) return false;

@@ -3,7 +3,8 @@
 // the two share.  World-less: the calling thread's current device, the caller's stream, one arena from the device buffer cache per
 // call (at least 1 MiB, so that it goes back to the cache and not to hipFree, which would drain the device), complete at the return.
 //
-// The voxeliser - the same three launches for thousands of sub-cell triangles and for one triangle across a 1024^3 grid:
+// The voxeliser - the same three launches for thousands of sub-cell triangles and for one triangle across a 1024^3 grid (the setup
+// kernel and the decode of a tile job live in mesh_tiles.hip.h, which sparse_mesh.hip shares):
 //   k_mesh_setup     one thread per triangle: the record of mesh_setup (48 words: plane, box, nine edge functions, the clamped cell
 //                    box) and the number of 4x4x4-cell tiles its cell box touches; 0 for a dropped triangle
 //   hipcub scan      exclusive sum of the counts, 64-bit: where each triangle's tile jobs begin, and their total for the host
@@ -28,41 +29,13 @@
 
 #include "hip_own.h"
 #include "mesh_rule.h"
+#include "mesh_tiles.hip.h"
 
 namespace svo {
 
 namespace {
 
 constexpr unsigned FILL_BATCH = 16;                 // sweeps between two reads of the flag
-constexpr unsigned long long TILE_JOBS_PER_LAUNCH = 1ull << 30;
-
-struct MeshArgs {
-    const float *vertices; const uint32_t *indices; const uint16_t *materials;
-    uint32_t nvertices, ntriangles;
-    float origin[3], inv;
-    uint32_t material; int32_t N;
-};
-
-__device__ __forceinline__ uint32_t tiles_of(const MeshTri &T, int k) { return (uint32_t)((T.c1[k] >> 2) - (T.c0[k] >> 2) + 1); }
-
-// tri[t] and count[t] of triangle t; count[ntriangles] = 0 is the scan's last item, whose sum is the total
-__global__ __launch_bounds__(256) void k_mesh_setup(MeshArgs A, MeshTri *tri, unsigned long long *count)
-{
-    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t > A.ntriangles) return;
-    if (t == A.ntriangles) { count[t] = 0ull; return; }
-    const uint32_t i0 = A.indices[3ull * t], i1 = A.indices[3ull * t + 1], i2 = A.indices[3ull * t + 2];
-    MeshTri T = {};
-    bool live = false;
-    if (i0 < A.nvertices && i1 < A.nvertices && i2 < A.nvertices) {
-        const float *pa = A.vertices + 3ull * i0, *pb = A.vertices + 3ull * i1, *pc = A.vertices + 3ull * i2;
-        const float a[3] = { pa[0], pa[1], pa[2] }, b[3] = { pb[0], pb[1], pb[2] }, c[3] = { pc[0], pc[1], pc[2] };
-        live = mesh_setup(a, b, c, A.origin, A.inv, A.materials ? (uint32_t)A.materials[t] : A.material, A.N, T);
-    }
-    if (!live) T.material = 0u;
-    tri[t] = T;
-    count[t] = live ? (unsigned long long)tiles_of(T, 0) * tiles_of(T, 1) * tiles_of(T, 2) : 0ull;
-}
 
 // Tile job first + 4 * block + wave of `total`; start[t] = the first job of triangle t, start[ntriangles] = total
 __global__ __launch_bounds__(256) void k_mesh_tiles(const MeshTri *__restrict__ tri, const unsigned long long *__restrict__ start, uint32_t ntriangles,
@@ -71,17 +44,8 @@ __global__ __launch_bounds__(256) void k_mesh_tiles(const MeshTri *__restrict__ 
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
     const unsigned long long job = first + (unsigned long long)blockIdx.x * 4ull + wave;
     if (job >= total) return;
-    uint32_t lo = 0u, hi = ntriangles;                      // start[lo] <= job < start[hi]
-    while (hi - lo > 1u) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (start[mid] <= job) lo = mid; else hi = mid;
-    }
-    const MeshTri &T = tri[lo];
-    const uint32_t local = (uint32_t)(job - start[lo]);
-    const uint32_t nx = tiles_of(T, 0), ny = tiles_of(T, 1);
-    const uint32_t row = local / nx;
-    const uint32_t tx = (uint32_t)(T.c0[0] >> 2) + (local - row * nx), ty = (uint32_t)(T.c0[1] >> 2) + row % ny, tz = (uint32_t)(T.c0[2] >> 2) + row / ny;
-    const uint32_t x = tx * 4u + (lane & 3u), y = ty * 4u + ((lane >> 2) & 3u), z = tz * 4u + (lane >> 4);
+    uint32_t x, y, z;
+    const MeshTri &T = tile_job_cell(tri, start, ntriangles, job, lane, x, y, z);
     const float p[3] = { (float)x, (float)y, (float)z };
     const uint32_t m = mesh_overlaps(T, p) ? T.material : 0u;
     const uint32_t other = (uint32_t)__shfl_xor((int)m, 1, 64);
@@ -183,32 +147,7 @@ __global__ __launch_bounds__(256) void k_fill_write(uint16_t *grid, FillDims D, 
     if (((empty[w] & ~outside[w]) >> bit) & 1ull) grid[i] = material;
 }
 
-// ---- the host side --------------------------------------------------------------------------------------------------------------
-struct SyncAtExit { hipStream_t s; ~SyncAtExit() { (void)hipStreamSynchronize(s); } };     // the arena goes back to the cache behind the work
-
-int current_device(const char *who, int *device)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { set_error(std::string(who) + ": no HIP device"); return SVO_ERR_NO_DEVICE; }
-    HIP_TRY(hipGetDevice(device));
-    return SVO_OK;
-}
-
-// An arena of the pool cache carved into 256-byte aligned parts: add() every part, alloc(), then at<T>(k)
-struct Arena {
-    Pooled<unsigned char> mem;
-    std::vector<size_t> off;
-    size_t bytes = 0;
-    size_t add(size_t n) { off.push_back(bytes); bytes += (n + 255) & ~(size_t)255; return off.size() - 1; }
-    int alloc(const char *who, int device)
-    {
-        if (mem.alloc(std::max<size_t>(bytes, (size_t)1 << 20), device) == hipSuccess) return SVO_OK;
-        set_error(std::string(who) + ": no device memory for the working arrays");
-        return SVO_ERR_OUT_OF_MEMORY;
-    }
-    template <typename T> T *at(size_t k) const { return reinterpret_cast<T *>(mem.p + off[k]); }
-};
-
+// ---- the host side (mesh_tiles.hip.h: current_device, Arena, SyncAtExit) ------------------------------------------------------------
 int add_mesh_device(const svo_mesh &m, float inv, uint32_t depth, uint16_t *grid, hipStream_t s)
 {
     const char *who = "svo_device_grid_add_mesh";
@@ -223,11 +162,7 @@ int add_mesh_device(const svo_mesh &m, float inv, uint32_t depth, uint16_t *grid
     SyncAtExit sync{ s };
     MeshTri *tri = A.at<MeshTri>(k_tri);
     unsigned long long *count = A.at<unsigned long long>(k_count), *start = A.at<unsigned long long>(k_start);
-    MeshArgs K;
-    K.vertices = m.vertices; K.indices = m.indices; K.materials = m.materials;
-    K.nvertices = m.nvertices; K.ntriangles = n;
-    std::memcpy(K.origin, m.origin, sizeof K.origin);
-    K.inv = inv; K.material = m.material; K.N = 1 << depth;
+    const MeshArgs K = mesh_kernel_args(m, inv, depth);
     hipLaunchKernelGGL(k_mesh_setup, dim3(blocks_for((uint64_t)n + 1, 256)), dim3(256), 0, s, K, tri, count);
     if (const int rc = launch_status(who)) return rc;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(A.at<unsigned char>(k_tmp), need, count, start, (int)(n + 1), s));

@@ -18,6 +18,7 @@ namespace svo {
 
 // mesh.cpp: the refusals of both add_mesh twins that do not depend on where the grid lives; *inv receives 1 / cell
 bool mesh_args_ok(const svo_mesh *m, uint32_t depth, const void *grid, float *inv);
+bool mesh_frame_ok(const svo_mesh *m, float *inv);          // its part about the mesh alone: the arrays, cell, inv, origin
 
 // What the cell test needs of one triangle, in grid units: 48 words, the record the setup kernel leaves per triangle.
 struct MeshTri {
@@ -91,6 +92,20 @@ SVO_MESH_HD bool mesh_setup(const float a[3], const float b[3], const float c[3]
     }
     T.material = material;
     return true;
+}
+
+// Tile job `local` of a triangle whose cell box is nx x ny x nz tiles of 4^3 cells, x fastest: the tile (ox, oy, oz) within the box.
+// local < nx * ny * nz, which is up to 2^24 for a grid of depth 10 and up to 2^42 at depth 16: jobs below 2^32 - every job of a grid up
+// to depth 10 - are decoded in 32-bit divisions, the others in 64-bit ones (on the device the branch is wave-uniform).
+SVO_MESH_HD void mesh_tile_of_job(unsigned long long local, uint32_t nx, uint32_t ny, uint32_t &ox, uint32_t &oy, uint32_t &oz)
+{
+    if ((local >> 32) == 0ull) {
+        const uint32_t l = (uint32_t)local, row = l / nx;
+        ox = l - row * nx; oy = row % ny; oz = row / ny;
+    } else {
+        const unsigned long long row = local / nx, slab = row / ny;
+        ox = (uint32_t)(local - row * nx); oy = (uint32_t)(row - slab * ny); oz = (uint32_t)slab;
+    }
 }
 
 // Does the triangle overlap the cell whose integer min corner is p (as floats)?

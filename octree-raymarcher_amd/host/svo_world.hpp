@@ -17,6 +17,7 @@
 //   svo::World::modify(i, ...)       <- World::modify          src/World.cpp:268-274
 //   svo::World::index / index_float  <- src/World.cpp:288-293,323-332
 //   svo::World::locate(points, ...)  <- traverse over a point list (svo_world_locate)   src/Traverse.cpp:34-48
+//   svo::World::chunk_from_mesh  <- (none) a chunk from triangle meshes without the dense grid, to depth 16 (svo_world_chunk_from_mesh),
 //   svo::World::chunk_from_grid / chunk_to_grid  <- grow() over a dense voxel grid instead of the height pyramid (svo_world_chunk_from_grid),
 //                                       and the chunk's voxels back as a grid (svo_world_chunk_to_grid)   src/Octree.cpp:74-176
 //   svo::grid_add_mesh / grid_fill_enclosed, svo::device_grid_add_mesh / device_grid_fill_enclosed  <- (none: the reference rasterises its
@@ -315,6 +316,14 @@ public:
     void chunk_to_grid(int i, uint32_t depth, uint16_t *grid_dev, void *stream = nullptr)
     {
         check(svo_world_chunk_to_grid(world_, i, depth, grid_dev, stream), "World::chunk_to_grid");
+    }
+    // Chunk i replaced by the tree of the shell of nmeshes triangle meshes (their arrays in device memory), depth in [2, 16], built
+    // without the dense grid (svo_world_chunk_from_mesh; svo.h states the rule).  The shell only: an edit that cuts it open finds it hollow.
+    int chunk_from_mesh(int i, const svo_mesh *meshes, int nmeshes, uint32_t depth)
+    {
+        const int rc = svo_world_chunk_from_mesh(world_, i, meshes, nmeshes, depth);
+        check(rc, "World::chunk_from_mesh");
+        return rc;                                          // SVO_OK, or SVO_OK_LITERAL_ONLY
     }
 
     // The voxel box of each of n G-buffer records (svo_hit_voxels: hit.bmin / hit.size, shaders/World.Fragment.glsl:168-172) into out_dev;
