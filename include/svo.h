@@ -14,6 +14,8 @@
  *   svo_world_chunk_to_grid <- (no counterpart) the chunk's voxels back as a dense grid
  *   svo_chunk_from_mesh / svo_world_chunk_from_mesh <- (no counterpart) the tree of a triangle mesh's shell without the dense grid, to
  *                           depth 16, on the host or on the device
+ *   svo_chunk_fill_enclosed / svo_world_chunk_fill_enclosed <- (no counterpart) the cells a chunk's voxels enclose, filled on the tree
+ *                           without a dense grid, to depth 16, on the host or on the device
  *   svo_grid_add_mesh / svo_device_grid_add_mesh <- (no counterpart: the reference rasterises its one mesh, src/Worm.cpp, with GL) a
  *                           triangle mesh voxelised into a dense grid, on the host or in device memory
  *   svo_grid_fill_enclosed / svo_device_grid_fill_enclosed <- (no counterpart) the cells that such a shell encloses, filled
@@ -134,7 +136,8 @@ extern "C" {
                                           svo_trace_instances, svo_trace_instance_shadows, svo_instance and SVO_MAX_INSTANCES,
                                           svo_grid_add_mesh, svo_device_grid_add_mesh, svo_grid_fill_enclosed,
                                           svo_device_grid_fill_enclosed and svo_mesh,
-                                          svo_chunk_from_mesh, svo_world_chunk_from_mesh and SVO_MESH_MIN_DEPTH / SVO_MESH_MAX_DEPTH
+                                          svo_chunk_from_mesh, svo_world_chunk_from_mesh and SVO_MESH_MIN_DEPTH / SVO_MESH_MAX_DEPTH,
+                                          svo_chunk_fill_enclosed, svo_world_chunk_fill_enclosed and SVO_FILL_MIN_DEPTH / SVO_FILL_MAX_DEPTH
                                           (functions added, nothing changed) */
 
 typedef enum svo_status {
@@ -571,8 +574,9 @@ int svo_device_grid_fill_enclosed(uint16_t *grid_dev, uint32_t depth, uint16_t m
  * cell) overlaps - a cell's Morton key (3 * depth bits) and its material (16 bits) are one 64-bit word, which is why depth ends at 16.
  * The host form and the device form give the same pools.
  *
- * THERE IS NO INTERIOR FILL: the result is the shell.  From outside it renders and shadows like the solid; an edit that cuts it open
- * (svo_world_edit_box / _ball) finds it hollow.  The chunk is REPLACED, nothing is merged with what it held.  One call builds one
+ * THERE IS NO INTERIOR FILL IN THIS CALL: the result is the shell.  From outside it renders and shadows like the solid; an edit that
+ * cuts it open (svo_world_edit_box / _ball) finds it hollow until svo_world_chunk_fill_enclosed / svo_chunk_fill_enclosed (below) has
+ * made it solid, as svo_grid_fill_enclosed does behind svo_grid_add_mesh.  The chunk is REPLACED, nothing is merged with what it held.  One call builds one
  * chunk: a mesh that spans several chunks is passed to every one of them with origin = that chunk's min corner in the mesh's
  * coordinates and cell = the chunk's size / 2^depth - the closed rule marks the cells on both sides of a chunk border alike.
  * Cost: every triangle is tested against every cell of its clamped cell box (on the device: one wave per 4^3-cell tile of the box,
@@ -598,6 +602,42 @@ int svo_device_grid_fill_enclosed(uint16_t *grid_dev, uint32_t depth, uint16_t m
 #define SVO_MESH_MAX_DEPTH 16
 int svo_chunk_from_mesh(const svo_mesh *meshes, int nmeshes, uint32_t depth, const float position[3], float size, svo_chunk_desc *out);
 int svo_world_chunk_from_mesh(svo_world *, int chunk, const svo_mesh *meshes, int nmeshes, uint32_t depth);
+
+/* ---- the sparse interior fill: svo_grid_fill_enclosed's rule on the tree ------------------------------------------------------
+ * What svo_grid_fill_enclosed does to a dense grid, done to a chunk's pools WITHOUT that grid, for a chunk depth in
+ * [SVO_FILL_MIN_DEPTH, SVO_FILL_MAX_DEPTH]: a shell from svo_(world_)chunk_from_mesh becomes solid, and so does any other chunk - from
+ * a grid, generated, edited.  Definition: let D be the chunk's depth, N = 2^D and G the N^3 grid of the chunk's finest voxels, as
+ * svo_world_chunk_to_grid at depth D reports them (EMPTY: 0, LEAF: offset & 0xFFFF, TWIG: the brick cell; a value of 0 is empty however
+ * it is stored; only what the root reaches counts).  svo_grid_fill_enclosed's rule is applied to G: an empty cell is OUTSIDE iff
+ * 6-neighbour steps through empty cells connect it to an empty cell with a coordinate of 0 or N - 1; every other empty cell becomes
+ * `material`; nothing else changes; *filled_out (may be NULL) receives how many cells changed (at most 2^48).  The result is the tree
+ * of that grid by the rule stated above for svo_chunk_from_grid: FIFO visiting order, a uniform 4^3 block a LEAF, minimal pools.  It is
+ * ALWAYS rebuilt, also when nothing was filled: pools that were not minimal or not in FIFO order come back minimal and in FIFO order.
+ * For D <= SVO_GRID_MAX_DEPTH that is, index for index, svo_chunk_from_grid of svo_grid_fill_enclosed of the chunk's grid; above it
+ * the same sentences define it.  G is never allocated: working memory is proportional to the chunk's node words and bricks.  The
+ * host form and the device form give the same pools and the same count, and neither has more node words or bricks than the part of
+ * the input the root reaches.
+ * NEIGHBOURING CHUNKS ARE NOT CONSULTED: the chunk's own six faces are the outside.  A cavity that a neighbouring chunk would close
+ * stays open, and a shell that continues into the neighbour is open where it crosses the face.
+ *
+ * svo_chunk_fill_enclosed (host; `in` and `*out` host pools): *out receives malloc'ed pools with in's frame, freed with
+ * svo_chunk_free; `in` is not modified; out may not alias in.  It needs no device.
+ * svo_world_chunk_fill_enclosed (device): chunk `chunk` of an UPLOADED world is replaced by its filled form, built on the world's
+ * device; position, size and depth stay.  Ordered, complete and installed like svo_world_chunk_from_mesh (it drains the device first;
+ * masks, wide tree, light-clearance state, svo_world_info and the host copy on request follow as there); SVO_OK, or
+ * SVO_OK_LITERAL_ONLY as for svo_world_edit_box.  The pools do not visit the host; the working arrays come from the library's device
+ * buffer cache.
+ *
+ * Refusals, all before anything changes: SVO_ERR_INVALID_ARG for a NULL world / in / out, out == in, a chunk out of range, material 0,
+ * NULL pools in `in`, and (host form) pools that svo_world_create's validation would refuse; then SVO_ERR_NOT_UPLOADED (device form);
+ * SVO_ERR_UNSUPPORTED for a chunk depth outside [2, 16] and for a chunk that holds a TWIG above level depth-2 (the sparsely refined
+ * chunks of svo_terrain_params.coarse_depth: their bricks' cells are larger than a voxel, and the tree of the filled grid could be
+ * larger than the input); SVO_ERR_OUT_OF_MEMORY when the working arrays do not fit (device: tried again after
+ * svo_device_cache_trim). */
+#define SVO_FILL_MIN_DEPTH 2
+#define SVO_FILL_MAX_DEPTH 16
+int svo_chunk_fill_enclosed(const svo_chunk_desc *in, uint16_t material, svo_chunk_desc *out, uint64_t *filled_out);
+int svo_world_chunk_fill_enclosed(svo_world *, int chunk, uint16_t material, uint64_t *filled_out);
 
 /* ---- the hot path ------------------------------------------------------------------------ */
 

@@ -24,6 +24,7 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     World.hit_ao / ao_image, shade_ao         <- (none: the reference has no ambient occlusion)   the eight lattice cells around each hit's face
     World.trace_reflections / reflect_image, shade_reflections, Mirror   <- (none: the reference has no reflections)   one mirror ray per hit, off its voxel's face
     chunk_from_mesh, World.chunk_from_mesh   <- (none)   the tree of a mesh's shell without the dense grid, to depth 16
+    chunk_fill_enclosed, World.chunk_fill_enclosed   <- (none)   the cells a chunk's voxels enclose, filled on the tree, to depth 16
     grid_add_mesh / grid_fill_enclosed, device_grid_add_mesh / device_grid_fill_enclosed, Mesh   <- (none: the reference rasterises its one mesh with GL)   a triangle mesh into a dense grid, its shell filled
 
 There is NO CPU fallback: if libsvo_amd.so is missing the import raises, and every device call
@@ -245,7 +246,7 @@ ABI_SYMBOLS = [
     "svo_world_index_float", "svo_world_index", "svo_world_locate", "svo_hit_voxels", "svo_hit_uv", "svo_shade_textured", "svo_world_upload", "svo_world_update",
     "svo_chunk_from_grid", "svo_world_chunk_from_grid", "svo_world_chunk_to_grid",
     "svo_grid_add_mesh", "svo_device_grid_add_mesh", "svo_grid_fill_enclosed", "svo_device_grid_fill_enclosed",
-    "svo_chunk_from_mesh", "svo_world_chunk_from_mesh",
+    "svo_chunk_from_mesh", "svo_world_chunk_from_mesh", "svo_chunk_fill_enclosed", "svo_world_chunk_fill_enclosed",
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_edit_cube", "svo_world_edit_ball", "svo_world_edit_ball_all", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_cursor_place", "svo_shade_boxes", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_shadowmap_fit", "svo_shadowmap_render", "svo_shadowmap_apply", "svo_hit_ao", "svo_shade_ao",
@@ -287,6 +288,8 @@ lib.svo_grid_fill_enclosed.argtypes = [_P, C.c_uint32, C.c_uint16, C.POINTER(C.c
 lib.svo_device_grid_fill_enclosed.argtypes = [_P, C.c_uint32, C.c_uint16, C.POINTER(C.c_uint64), _P]
 lib.svo_chunk_from_mesh.argtypes = [C.POINTER(Mesh), C.c_int, C.c_uint32, C.POINTER(C.c_float), C.c_float, C.POINTER(ChunkDesc)]
 lib.svo_world_chunk_from_mesh.argtypes = [_P, C.c_int, C.POINTER(Mesh), C.c_int, C.c_uint32]
+lib.svo_chunk_fill_enclosed.argtypes = [C.POINTER(ChunkDesc), C.c_uint16, C.POINTER(ChunkDesc), C.POINTER(C.c_uint64)]
+lib.svo_world_chunk_fill_enclosed.argtypes = [_P, C.c_int, C.c_uint16, C.POINTER(C.c_uint64)]
 lib.svo_gbuffer_pack.argtypes = [_P, _P, C.c_int64, _P]
 lib.svo_gbuffer_unpack.argtypes = [_P, _P, C.c_int64, _P]
 lib.svo_shade_defaults.argtypes = [C.POINTER(ShadeParams)]
@@ -570,6 +573,26 @@ def chunk_from_mesh(meshes, depth: int, position=(0.0, 0.0, 0.0), size: float = 
         tree = np.ctypeslib.as_array(d.tree, shape=(d.trees,)).copy()
         twig = np.ctypeslib.as_array(d.twig, shape=(d.twigs * 64,)).copy() if d.twigs else np.zeros(0, np.uint16)
         return {"position": tuple(d.position), "size": d.size, "depth": d.depth, "tree": tree, "twig": twig}
+    finally:
+        lib.svo_chunk_free(C.byref(d))
+
+
+def chunk_fill_enclosed(chunk: dict, material: int):
+    """svo_chunk_fill_enclosed on the host: the chunk dict (position, size, depth, tree, twig) with every empty voxel that no path of
+    empty voxels connects to the chunk's six faces turned into `material`, rebuilt minimal and in FIFO order without a dense grid
+    (chunk depth 2 .. 16); `chunk` is left as it is.  Returns (the filled chunk dict, how many voxels were filled)."""
+    tree = np.ascontiguousarray(chunk["tree"], dtype=np.uint32)
+    twig = np.ascontiguousarray(chunk.get("twig", np.zeros(0, np.uint16)), dtype=np.uint16)
+    src, d, filled = ChunkDesc(), ChunkDesc(), C.c_uint64(0)
+    src.position[:] = [float(x) for x in chunk["position"]]
+    src.size, src.depth = float(chunk["size"]), int(chunk["depth"])
+    src.tree, src.trees = tree.ctypes.data_as(C.POINTER(C.c_uint32)), tree.size
+    src.twig, src.twigs = twig.ctypes.data_as(C.POINTER(C.c_uint16)), twig.size // 64
+    _check(lib.svo_chunk_fill_enclosed(C.byref(src), int(material), C.byref(d), C.byref(filled)), "svo_chunk_fill_enclosed")
+    try:
+        otree = np.ctypeslib.as_array(d.tree, shape=(d.trees,)).copy()
+        otwig = np.ctypeslib.as_array(d.twig, shape=(d.twigs * 64,)).copy() if d.twigs else np.zeros(0, np.uint16)
+        return {"position": tuple(d.position), "size": d.size, "depth": d.depth, "tree": otree, "twig": otwig}, int(filled.value)
     finally:
         lib.svo_chunk_free(C.byref(d))
 
@@ -862,6 +885,14 @@ class World:
         for k, m in enumerate(meshes):
             C.memmove(C.byref(arr[k]), C.byref(m), C.sizeof(Mesh))
         return _check(lib.svo_world_chunk_from_mesh(self._h, int(chunk), arr, len(meshes), int(depth)), "svo_world_chunk_from_mesh")
+
+    def chunk_fill_enclosed(self, chunk: int, material: int) -> int:
+        """svo_world_chunk_fill_enclosed: chunk replaced by its filled form - every empty voxel that no path of empty voxels connects to
+        the chunk's six faces becomes `material` -, built on the device on the tree (chunk depth 2 .. 16); complete when it returns.
+        Returns how many voxels were filled; the status (SVO_OK or SVO_OK_LITERAL_ONLY) is in self.fill_status."""
+        filled = C.c_uint64(0)
+        self.fill_status = _check(lib.svo_world_chunk_fill_enclosed(self._h, int(chunk), int(material), C.byref(filled)), "svo_world_chunk_fill_enclosed")
+        return int(filled.value)
 
     def chunk_to_grid(self, chunk: int, depth: int, out_ptr: int, stream: int = 0):
         """svo_world_chunk_to_grid: the chunk's voxels as a (2^depth)^3 uint16 grid at out_ptr (device memory), asynchronous on stream."""

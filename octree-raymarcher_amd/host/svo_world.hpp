@@ -18,6 +18,8 @@
 //   svo::World::index / index_float  <- src/World.cpp:288-293,323-332
 //   svo::World::locate(points, ...)  <- traverse over a point list (svo_world_locate)   src/Traverse.cpp:34-48
 //   svo::World::chunk_from_mesh  <- (none) a chunk from triangle meshes without the dense grid, to depth 16 (svo_world_chunk_from_mesh),
+//   svo::World::chunk_fill_enclosed / svo::chunk_fill_enclosed  <- (none) the voxels a chunk encloses filled on its tree, without a dense grid, to
+//                                       depth 16 (svo_world_chunk_fill_enclosed on the device, svo_chunk_fill_enclosed on host pools)
 //   svo::World::chunk_from_grid / chunk_to_grid  <- grow() over a dense voxel grid instead of the height pyramid (svo_world_chunk_from_grid),
 //                                       and the chunk's voxels back as a grid (svo_world_chunk_to_grid)   src/Octree.cpp:74-176
 //   svo::grid_add_mesh / grid_fill_enclosed, svo::device_grid_add_mesh / device_grid_fill_enclosed  <- (none: the reference rasterises its
@@ -325,6 +327,15 @@ public:
         check(rc, "World::chunk_from_mesh");
         return rc;                                          // SVO_OK, or SVO_OK_LITERAL_ONLY
     }
+    // Chunk i replaced by its filled form: every empty voxel that no path of empty voxels connects to the chunk's own six faces becomes
+    // `material`, on the tree, chunk depth in [2, 16] (svo_world_chunk_fill_enclosed; svo.h states the rule).  What makes the shell of
+    // chunk_from_mesh solid.  *filled_out (may be null) receives how many voxels were filled.
+    int chunk_fill_enclosed(int i, uint16_t material, uint64_t *filled_out = nullptr)
+    {
+        const int rc = svo_world_chunk_fill_enclosed(world_, i, material, filled_out);
+        check(rc, "World::chunk_fill_enclosed");
+        return rc;                                          // SVO_OK, or SVO_OK_LITERAL_ONLY
+    }
 
     // The voxel box of each of n G-buffer records (svo_hit_voxels: hit.bmin / hit.size, shaders/World.Fragment.glsl:168-172) into out_dev;
     // all zero for a record without a usable hit.  What the edit cursor is placed from (src/Main.cpp:317,340-367) and what leafUV needs.
@@ -532,6 +543,14 @@ inline uint64_t device_grid_fill_enclosed(uint16_t *grid_dev, uint32_t depth, ui
 {
     uint64_t filled = 0;
     check(svo_device_grid_fill_enclosed(grid_dev, depth, material, &filled, stream), "device_grid_fill_enclosed");
+    return filled;
+}
+// The same fill on a chunk's host pools, without the grid, chunk depth in [2, 16]: *out receives malloc'ed pools (svo_chunk_free), `in`
+// stays as it is.  Returns how many voxels were filled.
+inline uint64_t chunk_fill_enclosed(const svo_chunk_desc &in, uint16_t material, svo_chunk_desc *out)
+{
+    uint64_t filled = 0;
+    check(svo_chunk_fill_enclosed(&in, material, out, &filled), "chunk_fill_enclosed");
     return filled;
 }
 
