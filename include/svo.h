@@ -16,6 +16,8 @@
  *                           depth 16, on the host or on the device
  *   svo_chunk_fill_enclosed / svo_world_chunk_fill_enclosed <- (no counterpart) the cells a chunk's voxels enclose, filled on the tree
  *                           without a dense grid, to depth 16, on the host or on the device
+ *   svo_chunk_combine / svo_world_chunk_combine <- (no counterpart) two chunks of one depth combined cell by cell on their trees
+ *                           (union, B under / over A, subtraction, intersection), to depth 16, on the host or on the device
  *   svo_grid_add_mesh / svo_device_grid_add_mesh <- (no counterpart: the reference rasterises its one mesh, src/Worm.cpp, with GL) a
  *                           triangle mesh voxelised into a dense grid, on the host or in device memory
  *   svo_grid_fill_enclosed / svo_device_grid_fill_enclosed <- (no counterpart) the cells that such a shell encloses, filled
@@ -137,7 +139,8 @@ extern "C" {
                                           svo_grid_add_mesh, svo_device_grid_add_mesh, svo_grid_fill_enclosed,
                                           svo_device_grid_fill_enclosed and svo_mesh,
                                           svo_chunk_from_mesh, svo_world_chunk_from_mesh and SVO_MESH_MIN_DEPTH / SVO_MESH_MAX_DEPTH,
-                                          svo_chunk_fill_enclosed, svo_world_chunk_fill_enclosed and SVO_FILL_MIN_DEPTH / SVO_FILL_MAX_DEPTH
+                                          svo_chunk_fill_enclosed, svo_world_chunk_fill_enclosed and SVO_FILL_MIN_DEPTH / SVO_FILL_MAX_DEPTH,
+                                          svo_chunk_combine, svo_world_chunk_combine, SVO_COMBINE_* and SVO_COMBINE_MIN_DEPTH / SVO_COMBINE_MAX_DEPTH
                                           (functions added, nothing changed) */
 
 typedef enum svo_status {
@@ -576,7 +579,7 @@ int svo_device_grid_fill_enclosed(uint16_t *grid_dev, uint32_t depth, uint16_t m
  *
  * THERE IS NO INTERIOR FILL IN THIS CALL: the result is the shell.  From outside it renders and shadows like the solid; an edit that
  * cuts it open (svo_world_edit_box / _ball) finds it hollow until svo_world_chunk_fill_enclosed / svo_chunk_fill_enclosed (below) has
- * made it solid, as svo_grid_fill_enclosed does behind svo_grid_add_mesh.  The chunk is REPLACED, nothing is merged with what it held.  One call builds one
+ * made it solid, as svo_grid_fill_enclosed does behind svo_grid_add_mesh.  The chunk is REPLACED, nothing is merged with what it held (svo_(world_)chunk_combine, below, merges two chunks).  One call builds one
  * chunk: a mesh that spans several chunks is passed to every one of them with origin = that chunk's min corner in the mesh's
  * coordinates and cell = the chunk's size / 2^depth - the closed rule marks the cells on both sides of a chunk border alike.
  * Cost: every triangle is tested against every cell of its clamped cell box (on the device: one wave per 4^3-cell tile of the box,
@@ -638,6 +641,48 @@ int svo_world_chunk_from_mesh(svo_world *, int chunk, const svo_mesh *meshes, in
 #define SVO_FILL_MAX_DEPTH 16
 int svo_chunk_fill_enclosed(const svo_chunk_desc *in, uint16_t material, svo_chunk_desc *out, uint64_t *filled_out);
 int svo_world_chunk_fill_enclosed(svo_world *, int chunk, uint16_t material, uint64_t *filled_out);
+
+/* ---- chunk CSG: two chunks combined cell by cell, on their trees ----------------------------------------------------------------
+ * A mesh added into a terrain chunk, a solid carved out of the terrain, two models united, two solids intersected - at every depth
+ * the sparse voxeliser and the sparse fill reach, WITHOUT a dense grid.  Definition: A and B are two chunks of the same depth D in
+ * [SVO_COMBINE_MIN_DEPTH, SVO_COMBINE_MAX_DEPTH], N = 2^D, and G_A, G_B the N^3 grids of their finest voxels, as
+ * svo_world_chunk_to_grid at depth D reports them (EMPTY: 0, LEAF: offset & 0xFFFF, TWIG: the brick cell; a value of 0 is empty however
+ * it is stored; only what the root reaches counts).  CELLS CORRESPOND BY INDEX: the two chunks' positions and sizes are not consulted,
+ * and the result keeps A's frame.  For every cell c,  G[c] = f_op(G_A[c], G_B[c]),  with a = G_A[c] and b = G_B[c]:
+ *   SVO_COMBINE_MAX        max(a, b)          svo_grid_add_mesh's merge rule: B's voxels added to what A held
+ *   SVO_COMBINE_UNDER      a != 0 ? a : b     SVO_EDIT_BUILD's rule: B only where A is empty
+ *   SVO_COMBINE_OVER       b != 0 ? b : a     SVO_EDIT_REPLACE's rule: B on top
+ *   SVO_COMBINE_SUBTRACT   b != 0 ? 0 : a     SVO_EDIT_DESTROY's rule: B's shape carved out of A
+ *   SVO_COMBINE_INTERSECT  b != 0 ? a : 0     A where B is
+ * The result is the tree of G by the rule stated above for svo_chunk_from_grid: FIFO visiting order, a uniform 4^3 block a LEAF,
+ * minimal pools.  It is ALWAYS rebuilt, also when B is empty: pools that were not minimal or not in FIFO order come back minimal and
+ * in FIFO order.  *changed_out (may be NULL) receives the number of cells with G[c] != G_A[c] (at most 2^48).  For D <=
+ * SVO_GRID_MAX_DEPTH that is, index for index, svo_chunk_from_grid of the elementwise combination of the two chunks' grids; above it
+ * the same sentences define it.  No grid is allocated: working memory is proportional to the node words and bricks the two roots
+ * reach.  The host form and the device form give the same pools and the same count.  For minimal inputs the result has at most
+ * trees_A + trees_B node words and at most twigs_A + twigs_B bricks; UNLIKE THE FILL'S IT CAN BE LARGER THAN EITHER INPUT.
+ *
+ * svo_chunk_combine (host; `a`, `b` and `*out` host pools): *out receives malloc'ed pools with a's frame, freed with svo_chunk_free;
+ * `a` and `b` are not modified; out may alias neither; a == b is allowed.  It needs no device.
+ * svo_world_chunk_combine (device): A is chunk `chunk` of the UPLOADED world dst, B chunk `src_chunk` of the UPLOADED world src on the
+ * same device; A is replaced by the result, built on that device; position, size and depth stay.  src may be dst, and src_chunk ==
+ * chunk of the same world is defined (A = B): B is read completely before A is replaced, and src's chunk is never written.  Ordered,
+ * complete and installed like svo_world_chunk_fill_enclosed (it drains the device first; masks, wide tree, light-clearance state,
+ * svo_world_info and the host copy on request follow as there); SVO_OK, or SVO_OK_LITERAL_ONLY as for svo_world_edit_box.  The pools
+ * do not visit the host; the working arrays come from the library's device buffer cache.
+ *
+ * Refusals, all before anything changes: SVO_ERR_INVALID_ARG for a NULL world / a / b / out, out == a or out == b, a chunk out of range
+ * in either world, an unknown op, NULL pools, (host form) a size of `a` that is not finite or not > 0 and pools that svo_world_create's
+ * validation would refuse, (device form) two worlds resident on different devices; then SVO_ERR_NOT_UPLOADED for either world (device
+ * form); then SVO_ERR_UNSUPPORTED for depths that differ, a depth outside [2, 16], a TWIG above level depth-2 in either chunk (the
+ * sparsely refined chunks, refused for the fill's reason) and 2^30 nodes or bricks; SVO_ERR_OUT_OF_MEMORY when the working arrays do not
+ * fit (device: tried again after svo_device_cache_trim).  On the device a malformed pool found by the walk is SVO_ERR_MALFORMED_TREE,
+ * with nothing installed. */
+enum { SVO_COMBINE_MAX = 0, SVO_COMBINE_UNDER = 1, SVO_COMBINE_OVER = 2, SVO_COMBINE_SUBTRACT = 3, SVO_COMBINE_INTERSECT = 4 };
+#define SVO_COMBINE_MIN_DEPTH 2
+#define SVO_COMBINE_MAX_DEPTH 16
+int svo_chunk_combine(const svo_chunk_desc *a, const svo_chunk_desc *b, int op, svo_chunk_desc *out, uint64_t *changed_out);
+int svo_world_chunk_combine(svo_world *dst, int chunk, svo_world *src, int src_chunk, int op, uint64_t *changed_out);
 
 /* ---- the hot path ------------------------------------------------------------------------ */
 

@@ -25,6 +25,7 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     World.trace_reflections / reflect_image, shade_reflections, Mirror   <- (none: the reference has no reflections)   one mirror ray per hit, off its voxel's face
     chunk_from_mesh, World.chunk_from_mesh   <- (none)   the tree of a mesh's shell without the dense grid, to depth 16
     chunk_fill_enclosed, World.chunk_fill_enclosed   <- (none)   the cells a chunk's voxels enclose, filled on the tree, to depth 16
+    chunk_combine, World.chunk_combine   <- (none)   two chunks of one depth combined cell by cell on their trees (COMBINE_*), to depth 16
     grid_add_mesh / grid_fill_enclosed, device_grid_add_mesh / device_grid_fill_enclosed, Mesh   <- (none: the reference rasterises its one mesh with GL)   a triangle mesh into a dense grid, its shell filled
 
 There is NO CPU fallback: if libsvo_amd.so is missing the import raises, and every device call
@@ -64,6 +65,8 @@ ERR_NAMES = {0: "SVO_OK", -1: "SVO_ERR_INVALID_ARG", -2: "SVO_ERR_NO_DEVICE", -3
 EMPTY, LEAF, BRANCH, TWIG = 0, 1, 2, 3
 KERNEL_AUTO, KERNEL_LITERAL, KERNEL_STACK = 0, 1, 2
 EDIT_BUILD, EDIT_DESTROY, EDIT_REPLACE = 0, 1, 2     # svo_world_edit_box
+COMBINE_MAX, COMBINE_UNDER, COMBINE_OVER, COMBINE_SUBTRACT, COMBINE_INTERSECT = 0, 1, 2, 3, 4     # svo_chunk_combine / svo_world_chunk_combine
+COMBINE_MIN_DEPTH, COMBINE_MAX_DEPTH = 2, 16
 HIT_FLAG, SHADOW_TRACED, SHADOWED, FACE_NORMAL, SEE_THROUGH, ERR_FLAG = 1, 2, 4, 8, 16, 1 << 15
 LOCAL_SHADOWS, SHADOWED_POINT, SHADOWED_SPOT = 1 << 5, 1 << 6, 1 << 7     # svo_trace_local_shadows
 NORMAL_CUBE, NORMAL_FACE = 0, 1
@@ -247,6 +250,7 @@ ABI_SYMBOLS = [
     "svo_chunk_from_grid", "svo_world_chunk_from_grid", "svo_world_chunk_to_grid",
     "svo_grid_add_mesh", "svo_device_grid_add_mesh", "svo_grid_fill_enclosed", "svo_device_grid_fill_enclosed",
     "svo_chunk_from_mesh", "svo_world_chunk_from_mesh", "svo_chunk_fill_enclosed", "svo_world_chunk_fill_enclosed",
+    "svo_chunk_combine", "svo_world_chunk_combine",
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_edit_cube", "svo_world_edit_ball", "svo_world_edit_ball_all", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_cursor_place", "svo_shade_boxes", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_shadowmap_fit", "svo_shadowmap_render", "svo_shadowmap_apply", "svo_hit_ao", "svo_shade_ao",
@@ -290,6 +294,8 @@ lib.svo_chunk_from_mesh.argtypes = [C.POINTER(Mesh), C.c_int, C.c_uint32, C.POIN
 lib.svo_world_chunk_from_mesh.argtypes = [_P, C.c_int, C.POINTER(Mesh), C.c_int, C.c_uint32]
 lib.svo_chunk_fill_enclosed.argtypes = [C.POINTER(ChunkDesc), C.c_uint16, C.POINTER(ChunkDesc), C.POINTER(C.c_uint64)]
 lib.svo_world_chunk_fill_enclosed.argtypes = [_P, C.c_int, C.c_uint16, C.POINTER(C.c_uint64)]
+lib.svo_chunk_combine.argtypes = [C.POINTER(ChunkDesc), C.POINTER(ChunkDesc), C.c_int, C.POINTER(ChunkDesc), C.POINTER(C.c_uint64)]
+lib.svo_world_chunk_combine.argtypes = [_P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
 lib.svo_gbuffer_pack.argtypes = [_P, _P, C.c_int64, _P]
 lib.svo_gbuffer_unpack.argtypes = [_P, _P, C.c_int64, _P]
 lib.svo_shade_defaults.argtypes = [C.POINTER(ShadeParams)]
@@ -597,6 +603,35 @@ def chunk_fill_enclosed(chunk: dict, material: int):
         lib.svo_chunk_free(C.byref(d))
 
 
+def _host_chunk_desc(chunk: dict):
+    """A chunk dict as an svo_chunk_desc over host arrays, and what keeps those arrays alive."""
+    tree = np.ascontiguousarray(chunk["tree"], dtype=np.uint32)
+    twig = np.ascontiguousarray(chunk.get("twig", np.zeros(0, np.uint16)), dtype=np.uint16)
+    d = ChunkDesc()
+    d.position[:] = [float(x) for x in chunk["position"]]
+    d.size, d.depth = float(chunk["size"]), int(chunk["depth"])
+    d.tree, d.trees = tree.ctypes.data_as(C.POINTER(C.c_uint32)), tree.size
+    d.twig, d.twigs = twig.ctypes.data_as(C.POINTER(C.c_uint16)), twig.size // 64
+    return d, (tree, twig)
+
+
+def chunk_combine(a: dict, b: dict, op: int):
+    """svo_chunk_combine on the host: the chunk dicts a and b (one depth, 2 .. 16) combined cell by cell on their trees by COMBINE_* -
+    MAX max(a, b), UNDER b where a is empty, OVER b on top, SUBTRACT b's shape carved out of a, INTERSECT a where b is -, rebuilt
+    minimal and in FIFO order without a dense grid, in a's frame; a and b are left as they are.  Returns (the combined chunk dict, how
+    many voxels differ from a's)."""
+    da, keep_a = _host_chunk_desc(a)
+    db, keep_b = _host_chunk_desc(b)
+    d, changed = ChunkDesc(), C.c_uint64(0)
+    _check(lib.svo_chunk_combine(C.byref(da), C.byref(db), int(op), C.byref(d), C.byref(changed)), "svo_chunk_combine")
+    try:
+        otree = np.ctypeslib.as_array(d.tree, shape=(d.trees,)).copy()
+        otwig = np.ctypeslib.as_array(d.twig, shape=(d.twigs * 64,)).copy() if d.twigs else np.zeros(0, np.uint16)
+        return {"position": tuple(d.position), "size": d.size, "depth": d.depth, "tree": otree, "twig": otwig}, int(changed.value)
+    finally:
+        lib.svo_chunk_free(C.byref(d))
+
+
 def gbuffer_pack(gbuffer_ptr: int, packed_ptr: int, n: int, stream: int = 0):
     _check(lib.svo_gbuffer_pack(gbuffer_ptr, packed_ptr, n, stream), "svo_gbuffer_pack")
 
@@ -893,6 +928,15 @@ class World:
         filled = C.c_uint64(0)
         self.fill_status = _check(lib.svo_world_chunk_fill_enclosed(self._h, int(chunk), int(material), C.byref(filled)), "svo_world_chunk_fill_enclosed")
         return int(filled.value)
+
+    def chunk_combine(self, chunk: int, src_world: "World", src_chunk: int, op: int) -> int:
+        """svo_world_chunk_combine: chunk replaced by its cell-wise combination (COMBINE_*) with chunk src_chunk of src_world - an
+        uploaded world on the same device, which may be this one -, built on the device on the two trees (one chunk depth, 2 .. 16);
+        complete when it returns.  Returns how many voxels changed; the status (SVO_OK or SVO_OK_LITERAL_ONLY) is in self.combine_status."""
+        changed = C.c_uint64(0)
+        self.combine_status = _check(lib.svo_world_chunk_combine(self._h, int(chunk), None if src_world is None else src_world._h, int(src_chunk), int(op),
+                                                                 C.byref(changed)), "svo_world_chunk_combine")
+        return int(changed.value)
 
     def chunk_to_grid(self, chunk: int, depth: int, out_ptr: int, stream: int = 0):
         """svo_world_chunk_to_grid: the chunk's voxels as a (2^depth)^3 uint16 grid at out_ptr (device memory), asynchronous on stream."""

@@ -20,6 +20,8 @@
 //   svo::World::chunk_from_mesh  <- (none) a chunk from triangle meshes without the dense grid, to depth 16 (svo_world_chunk_from_mesh),
 //   svo::World::chunk_fill_enclosed / svo::chunk_fill_enclosed  <- (none) the voxels a chunk encloses filled on its tree, without a dense grid, to
 //                                       depth 16 (svo_world_chunk_fill_enclosed on the device, svo_chunk_fill_enclosed on host pools)
+//   svo::World::chunk_combine / svo::chunk_combine  <- (none) two chunks of one depth combined cell by cell on their trees (union, under / over,
+//                                       subtraction, intersection), to depth 16 (svo_world_chunk_combine on the device, svo_chunk_combine on host pools)
 //   svo::World::chunk_from_grid / chunk_to_grid  <- grow() over a dense voxel grid instead of the height pyramid (svo_world_chunk_from_grid),
 //                                       and the chunk's voxels back as a grid (svo_world_chunk_to_grid)   src/Octree.cpp:74-176
 //   svo::grid_add_mesh / grid_fill_enclosed, svo::device_grid_add_mesh / device_grid_fill_enclosed  <- (none: the reference rasterises its
@@ -336,6 +338,15 @@ public:
         check(rc, "World::chunk_fill_enclosed");
         return rc;                                          // SVO_OK, or SVO_OK_LITERAL_ONLY
     }
+    // Chunk i replaced by its cell-wise combination (SVO_COMBINE_*) with chunk src_chunk of `src` - an uploaded world on the same device,
+    // which may be this one -, on the two trees, one chunk depth in [2, 16] (svo_world_chunk_combine; svo.h states the rule).  What puts
+    // a voxelised mesh into a terrain chunk or carves its shape out.  *changed_out (may be null) receives how many voxels changed.
+    int chunk_combine(int i, World &src, int src_chunk, int op, uint64_t *changed_out = nullptr)
+    {
+        const int rc = svo_world_chunk_combine(world_, i, src.world_, src_chunk, op, changed_out);
+        check(rc, "World::chunk_combine");
+        return rc;                                          // SVO_OK, or SVO_OK_LITERAL_ONLY
+    }
 
     // The voxel box of each of n G-buffer records (svo_hit_voxels: hit.bmin / hit.size, shaders/World.Fragment.glsl:168-172) into out_dev;
     // all zero for a record without a usable hit.  What the edit cursor is placed from (src/Main.cpp:317,340-367) and what leafUV needs.
@@ -552,6 +563,14 @@ inline uint64_t chunk_fill_enclosed(const svo_chunk_desc &in, uint16_t material,
     uint64_t filled = 0;
     check(svo_chunk_fill_enclosed(&in, material, out, &filled), "chunk_fill_enclosed");
     return filled;
+}
+// Two chunks' host pools of one depth in [2, 16] combined cell by cell on their trees (SVO_COMBINE_*), without a grid: *out receives
+// malloc'ed pools in a's frame (svo_chunk_free), `a` and `b` stay as they are.  Returns how many voxels differ from a's.
+inline uint64_t chunk_combine(const svo_chunk_desc &a, const svo_chunk_desc &b, int op, svo_chunk_desc *out)
+{
+    uint64_t changed = 0;
+    check(svo_chunk_combine(&a, &b, op, out, &changed), "chunk_combine");
+    return changed;
 }
 
 } // namespace svo
