@@ -6,18 +6,14 @@
 //   fold    on the way back, a result word per pair: two uniform sides give the word of f(a, b) and edge^3 changed cells if that
 //           differs from a; at level depth-2 a TWIG on either side gives 64 cells f(a, b), one value among them its LEAF / EMPTY, several
 //           TWIG | 0; a descended pair whose eight results are one EMPTY / LEAF word is that word, else BRANCH | 0
-//   emit    the FIFO walk of svo_chunk_from_grid over the results: the pools are minimal and in visiting order whatever the inputs were
+//   emit    the FIFO walk over the results (chunk_pools.h: emit_fifo, which also holds the validation pass and the desc's producer)
 // Working memory is proportional to the node words and the bricks the two roots reach; nothing has N^3 entries.  No HIP include: plain
 // g++ compiles this file (host/combine_check.cpp runs it under the sanitizers), and it links without world.cpp.
-#include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <new>
-#include <vector>
 
+#include "chunk_pools.h"
 #include "combine_rule.h"
-#include "world.h"
 
 namespace svo {
 
@@ -80,54 +76,22 @@ struct Combine {
         return pairs[at].res = r;
     }
 
-    struct Out { uint32_t pair, at; };
     void emit(std::vector<uint32_t> &otree, std::vector<uint16_t> &otwig) const
     {
-        otree.assign(1, node_make(EMPTY, 0));
-        otwig.clear();
-        std::vector<Out> level(1, Out{ 0, 0 }), next;
-        while (!level.empty()) {
-            next.clear();
-            for (const Out &o : level) {
-                const Pair &p = pairs[o.pair];
-                if (node_type(p.res) == TWIG) {
-                    otree[o.at] = node_make(TWIG, (uint32_t)(otwig.size() / TWIG_WORDS));
-                    otwig.insert(otwig.end(), cells.begin() + (size_t)p.below * TWIG_WORDS, cells.begin() + ((size_t)p.below + 1) * TWIG_WORDS);
-                } else if (node_type(p.res) == BRANCH) {
-                    const uint32_t first = (uint32_t)otree.size();
-                    otree[o.at] = node_make(BRANCH, first);
-                    otree.resize(otree.size() + 8, node_make(EMPTY, 0));
-                    for (uint32_t c = 0; c < 8; ++c) next.push_back(Out{ p.below + c, first + c });
-                } else otree[o.at] = p.res;
-            }
-            level.swap(next);
-        }
+        emit_fifo(0u, [&](uint32_t at) { return pairs[at].res; }, [&](uint32_t at, uint32_t c) { return pairs[at].below + c; },
+                  [&](uint32_t at, std::vector<uint16_t> &to) {
+                      const auto first = cells.begin() + (size_t)pairs[at].below * TWIG_WORDS;
+                      to.insert(to.end(), first, first + TWIG_WORDS);
+                  }, otree, otwig);
     }
 };
 
-// what svo_world_create's validation asks of one chunk's pools (world.cpp: validate_chunk), for a depth in [2, 16]: 0, or
-// SVO_ERR_INVALID_ARG with the message set.  *shallow: the root reaches a TWIG above level depth-2
+// one chunk's pools, for a depth in [2, 16], against what a world asks of them (chunk_pools.h: pools_walk): 0, or SVO_ERR_INVALID_ARG
+// with the message set - any malformed word, wherever a shallow TWIG lies.  *shallow: the root reaches a TWIG above level depth-2
 int pools_status(const svo_chunk_desc &c, const char *who, const char *which, bool *shallow)
 {
-    const uint64_t trees = c.trees, twigs = c.twigs;
-    const char *why = nullptr;
-    if ((trees - 1) % 8 != 0 || trees > (1ull << 30) || twigs > (1ull << 30)) why = "the tree pool is not 1 + 8k node words";
-    const uint32_t maxlevel = c.depth - TWIG_LEVELS;
-    std::vector<int8_t> block_level(why ? 0 : (trees - 1) / 8, (int8_t)-1);
-    for (uint64_t i = 0; !why && i < trees; ++i) {
-        const int level = i ? block_level[(i - 1) / 8] : 0;
-        if (level < 0) continue;                            // an orphan: nothing reaches it
-        const uint64_t off = node_offset(c.tree[i]);
-        if (node_type(c.tree[i]) == BRANCH) {
-            if ((uint32_t)level >= maxlevel) why = "BRANCH below level depth-2";
-            else if (off <= i || off + 8 > trees || (off - 1) % 8 != 0) why = "BRANCH offset outside pool or not a forward 8-block";
-            else if (block_level[(off - 1) / 8] >= 0) why = "child block referenced twice";
-            else block_level[(off - 1) / 8] = (int8_t)(level + 1);
-        } else if (node_type(c.tree[i]) == TWIG) {
-            if (off >= twigs) why = "TWIG offset outside brick pool";
-            else if ((uint32_t)level != maxlevel) *shallow = true;
-        }
-    }
+    const char *why = (c.trees - 1) % 8 != 0 || c.trees > (1ull << 30) || c.twigs > (1ull << 30) ? "the tree pool is not 1 + 8k node words"
+                                                                                                  : pools_walk(c.tree, c.trees, c.twigs, c.depth, shallow);
     if (!why) return SVO_OK;
     set_error(std::string(who) + ": chunk " + which + ": " + why);
     return SVO_ERR_INVALID_ARG;
@@ -156,7 +120,7 @@ int svo_chunk_combine(const svo_chunk_desc *a, const svo_chunk_desc *b, int op, 
         if (depth_ok(b->depth)) if (const int rc = pools_status(*b, who, "b", &shallow)) return rc;
         if (a->depth != b->depth) { set_error(std::string(who) + ": the two chunks differ in depth"); return SVO_ERR_UNSUPPORTED; }
         if (!depth_ok(a->depth)) { set_error(std::string(who) + ": the chunks' depth is outside [2, 16]"); return SVO_ERR_UNSUPPORTED; }
-        if (shallow) { set_error(std::string(who) + ": a TWIG above level depth-2 (a sparsely refined chunk) is not supported"); return SVO_ERR_UNSUPPORTED; }
+        if (shallow) { set_error(std::string(who) + ": " + SHALLOW_TWIG_WHY); return SVO_ERR_UNSUPPORTED; }
         Combine K;
         K.A = Side{ a->tree, a->twig }; K.B = Side{ b->tree, b->twig };
         K.op = (uint32_t)op; K.maxlevel = a->depth - TWIG_LEVELS; K.N = 1u << a->depth;
@@ -167,15 +131,7 @@ int svo_chunk_combine(const svo_chunk_desc *a, const svo_chunk_desc *b, int op, 
         std::vector<uint16_t> twig;
         K.emit(tree, twig);
         if (tree.size() > (1ull << 30) || twig.size() / TWIG_WORDS > (1ull << 30)) { set_error(std::string(who) + ": 2^30 nodes or bricks"); return SVO_ERR_UNSUPPORTED; }
-        uint32_t *t = (uint32_t *)std::malloc(tree.size() * sizeof(uint32_t));
-        uint16_t *k = (uint16_t *)std::malloc(std::max<size_t>(twig.size(), TWIG_WORDS) * sizeof(uint16_t));
-        if (!t || !k) { std::free(t); std::free(k); set_error(std::string(who) + ": out of memory"); return SVO_ERR_OUT_OF_MEMORY; }
-        std::memcpy(t, tree.data(), tree.size() * sizeof(uint32_t));
-        if (!twig.empty()) std::memcpy(k, twig.data(), twig.size() * sizeof(uint16_t));
-        std::memcpy(out->position, a->position, sizeof out->position);
-        out->size = a->size; out->depth = a->depth; out->_pad = 0;
-        out->tree = t; out->trees = tree.size();
-        out->twig = k; out->twigs = twig.size() / TWIG_WORDS;
+        if (const int rc = chunk_desc_take(out, a->position, a->size, a->depth, tree, twig, who)) return rc;
         if (changed_out) *changed_out = K.changed;
         return SVO_OK;
     } catch (const std::bad_alloc &) {

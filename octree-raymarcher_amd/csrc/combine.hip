@@ -1,38 +1,30 @@
 // combine.hip — svo_world_chunk_combine: two chunks of one depth combined cell by cell on their trees, on the device the two worlds live
 // on, without a dense grid, depth 2 .. 16.  combine.cpp is the host twin and states the combination as a recursive pair walk, a fold and
 // a FIFO emit; combine_rule.h holds the cell function.  On the null stream, behind a hipDeviceSynchronize like
-// svo_world_chunk_fill_enclosed; complete at the return.
-//   walk              level-synchronous from the two roots.  An entry is the pair of node WORDS (w_A, w_B) and its parent's entry; the rule
-//                     has no geometry, so there is no corner.  k_walk flags the entries to descend (either side a BRANCH; every offset is
-//                     checked against its pool), gives every other entry above the bricks its result word f(a, b) and counts its edge^3
-//                     cells if that differs from a; one hipcub scan ranks the descended entries; k_children, one thread per child,
-//                     appends their children in parent order - the FIFO walk's visiting order.  A side that is EMPTY or LEAF hands its
-//                     own word down, a BRANCH hands down tree[offset + c]
+// svo_world_chunk_fill_enclosed; complete at the return.  tree_rebuild.hip.h holds the frame of the rebuild (the walk's tail, the
+// fold's ranks, the emit); this file's own:
+//   walk              An entry is the pair of node WORDS (w_A, w_B) and its parent's entry; the rule has no geometry, so there is no
+//                     corner.  k_walk flags the entries to descend (either side a BRANCH; every offset is checked against its pool),
+//                     gives every other entry above the bricks its result word f(a, b) and counts its edge^3 cells if that differs
+//                     from a; k_children, one thread per child: a side that is EMPTY or LEAF hands its own word down, a BRANCH hands
+//                     down tree[offset + c]
 //   bricks            at level depth-2 an entry with a TWIG on either side is a brick candidate.  k_bricks, one wave per entry of that
 //                     level, sixteen entries a wave: lane l reads cell l of each side (the brick's, or the side's one value), applies f, one ballot compare
 //                     decides "one value", one ballot of r != a gives the changed cells
-//   count             64 bits, reduced per block, one atomic per block (sparse_fill.hip's k_count, hip_own.h's block_take argument)
-//   fold, emit        bottom-up k_fold: a descended entry whose eight results are one EMPTY / LEAF word is that word, else BRANCH | 0, and
-//                     flags what stays a BRANCH / TWIG; a scan per level ranks them (the lists are in visiting order and what stays is
-//                     reachable, so the ranks are the FIFO walk's numbers); top-down k_emit writes an entry whose parent stays a BRANCH
-//                     to first + slot, k_write_bricks one wave per surviving brick, the cells computed again.  Every index written is
-//                     checked against the pool it goes to
+//   count             64 bits, one atomic per block (hip_own.h: block_sum64)
+//   fold, bricks out  k_fold: a descended entry whose eight results are one EMPTY / LEAF word is that word, else BRANCH | 0;
+//                     k_write_bricks one wave per surviving brick, the cells computed again
 // The output is sized from the fold's totals (it can exceed either input) and installed by install_rebuilt.  B is read completely
 // before A is replaced.  Plain C++ and vector stores; integer arithmetic only.
-#include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-
 #include <cstdio>
 #include <cstdlib>
 
-#include "hip_own.h"
+#include "tree_rebuild.hip.h"
 #include "combine_rule.h"
 
 namespace svo {
 
 namespace {
-
-enum : uint32_t { ERR_MALFORMED = 1, ERR_SHALLOW_TWIG = 2 };
 
 // One level's entries in visiting order: [n] of each; kids and rank have n + 1 entries (a scan's last item is the total)
 struct LevelList {
@@ -46,8 +38,9 @@ struct LevelList {
 
 struct Pools { const uint32_t *tree; const uint16_t *twig; uint32_t trees, twigs; };
 
-// a BRANCH the walk follows: above the last level, an 8-block inside the pool behind the root.  (The entries carry words, not pool
-// indices, so "forward" is not asked: the walk ends at level depth-2 and at the arrays' capacity whatever the offsets say.)
+// a BRANCH the walk follows: above the last level, an 8-block inside the pool behind the root.  off >= 1, where sparse_fill.hip asks
+// off > node: the entries here carry words, not pool indices, so "forward" cannot be asked - and need not be: the walk ends at level
+// depth-2 and at the arrays' capacity whatever the offsets say
 __device__ __forceinline__ bool walk_branch(const Pools &P, uint32_t w, bool last)
 {
     const uint32_t off = node_offset(w);
@@ -59,18 +52,6 @@ __device__ __forceinline__ uint32_t walk_error(const Pools &P, uint32_t w, bool 
     if (node_type(w) == BRANCH && !walk_branch(P, w, last)) return ERR_MALFORMED;
     if (node_type(w) == TWIG) return node_offset(w) >= P.twigs ? ERR_MALFORMED : last ? 0u : ERR_SHALLOW_TWIG;
     return 0u;
-}
-
-// every thread of the block calls this: the block's sum of v, one atomic per block
-__device__ __forceinline__ void block_count(unsigned long long v, unsigned long long *sh, unsigned long long *total)
-{
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (uint32_t s = 128u; s > 0u; s >>= 1) {
-        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0u && sh[0] != 0ull) atomicAdd(total, sh[0]);
 }
 
 // entry i of level V (edge `edge` cells): descended (kids flag 1), a brick candidate (left to k_bricks), or settled here
@@ -92,7 +73,7 @@ __global__ __launch_bounds__(256) void k_walk(Pools A, Pools B, LevelList V, uin
             if (r != a) v = (unsigned long long)edge * edge * edge;
         } else V.res[i] = node_make(BRANCH, 0);             // (the fold and k_bricks write what it is)
     }
-    block_count(v, sh, total);
+    block_sum64<256>(v, sh, total);
 }
 
 // thread t: child t & 7 of entry t >> 3 of level V, into C, whose capacity is `room` entries
@@ -137,7 +118,7 @@ __global__ __launch_bounds__(256) void k_bricks(Pools A, Pools B, LevelList V, u
         if (r != a) v += 1ull;
         if (lane == 0u) V.res[k] = one ? combine_word(r0) : node_make(TWIG, 0);
     }
-    block_count(v, sh, total);
+    block_sum64<256>(v, sh, total);
 }
 
 // the result of every descended entry of level V from its children in C (V.res of the others stands), and the flags of what stays;
@@ -160,23 +141,6 @@ __global__ __launch_bounds__(256) void k_fold(LevelList V, LevelList C)
     V.rank[i] = node_type(r) == BRANCH || node_type(r) == TWIG ? 1u : 0u;
 }
 
-// level C into the blocks of its parents' level V; above_v / above_c = the BRANCHes that stay above V / above C.  V.res == null: C is
-// level 0 and its one entry the root
-__global__ __launch_bounds__(256) void k_emit(LevelList C, LevelList V, uint32_t above_v, uint32_t above_c, uint32_t *tree, uint32_t trees)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= C.n) return;
-    uint32_t at = 0u;
-    if (V.res) {
-        const uint32_t p = C.parent[i];
-        if (node_type(V.res[p]) != BRANCH) return;
-        at = 1u + 8u * (above_v + V.rank[p]) + (i & 7u);
-    }
-    const uint32_t r = C.res[i], type = node_type(r);
-    const uint32_t w = type == BRANCH ? node_make(BRANCH, 1u + 8u * (above_c + C.rank[i])) : type == TWIG ? node_make(TWIG, C.rank[i]) : r;
-    if (at < trees) tree[at] = w;
-}
-
 // one wave per entry of level depth-2: one that stays a TWIG is written as brick V.rank[entry], its cells computed again
 __global__ __launch_bounds__(256) void k_write_bricks(Pools A, Pools B, LevelList V, uint32_t op, uint16_t *twig, uint32_t twigs)
 {
@@ -186,23 +150,6 @@ __global__ __launch_bounds__(256) void k_write_bricks(Pools A, Pools B, LevelLis
     if (to >= twigs) return;
     twig[(size_t)to * TWIG_WORDS + lane] = (uint16_t)combine_cell(op, brick_cell(A, V.wa[k], lane), brick_cell(B, V.wb[k], lane));
 }
-
-// An arena of the pool cache carved into 256-byte aligned parts, at least 1 MiB, as the voxelisers and the fill take theirs
-// (mesh_tiles.hip.h, whose kernels this file has no use for)
-struct Arena {
-    Pooled<unsigned char> mem;
-    std::vector<size_t> off;
-    size_t bytes = 0;
-    size_t add(size_t n) { off.push_back(bytes); bytes += (n + 255) & ~(size_t)255; return off.size() - 1; }
-    int alloc(const char *who, int device)
-    {
-        if (mem.alloc(std::max<size_t>(bytes, (size_t)1 << 20), device) == hipSuccess) return SVO_OK;
-        set_error(std::string(who) + ": no device memory for the working arrays");
-        return SVO_ERR_OUT_OF_MEMORY;
-    }
-    template <typename T> T *at(size_t k) const { return reinterpret_cast<T *>(mem.p + off[k]); }
-};
-struct SyncAtExit { hipStream_t s; ~SyncAtExit() { (void)hipStreamSynchronize(s); } };     // the arena goes back to the cache behind the work
 
 Pools pools_of(const svo_world &w, int chunk)
 {
@@ -232,7 +179,7 @@ int combine_resident(svo_world &w, int chunk, const svo_world &src, int src_chun
                  k_rank = M.add((cap + maxlevel + 2) * 4), k_tmp = M.add(need_scan + 16), k_words = M.add(256);
     if (const int rc = M.alloc(who, w.device)) return rc;
     SyncAtExit sync{ s };
-    unsigned char *const tmp = M.at<unsigned char>(k_tmp);
+    const Rebuild R{ who, s, M.at<unsigned char>(k_tmp), need_scan };
     // words: [0] the walk's error, [2, 3] the cells changed (64 bits)
     uint32_t *const words = M.at<uint32_t>(k_words), *const err = words;
     unsigned long long *const total = reinterpret_cast<unsigned long long *>(words + 2);
@@ -253,15 +200,10 @@ int combine_resident(svo_world &w, int chunk, const svo_world &src, int src_chun
         const LevelList &V = lv[L];
         hipLaunchKernelGGL(k_walk, dim3(blocks_for((uint64_t)V.n + 1, 256)), dim3(256), 0, s, A, B, V, L == maxlevel ? 1u : 0u, op, (1u << depth) >> L, err, total);
         if (const int rc = launch_status(who)) return rc;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, need_scan, V.kids, V.kids, (int)V.n + 1, s));
-        uint32_t back[2] = { 0, 0 };                    // the level's descended entries, the walk's error
-        HIP_TRY(hipMemcpyAsync(&back[0], V.kids + V.n, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&back[1], err, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (back[1] == ERR_SHALLOW_TWIG) { set_error(std::string(who) + ": a TWIG above level depth-2 (a sparsely refined chunk) is not supported"); return SVO_ERR_UNSUPPORTED; }
-        if (back[1] != 0 || back[0] > V.n || used + 8ull * back[0] > cap) { set_error(std::string(who) + ": a chunk's pools are malformed"); return SVO_ERR_MALFORMED_TREE; }
-        if (back[0] == 0) break;
-        LevelList C = level_at(used, L + 1, 8 * back[0]);
+        uint32_t descended = 0;
+        if (const int rc = walk_level_tail(R, "a chunk's", V.kids, V.n, err, used, cap, &descended)) return rc;
+        if (descended == 0) break;
+        LevelList C = level_at(used, L + 1, 8 * descended);
         hipLaunchKernelGGL(k_children, dim3(blocks_for(8ull * V.n, 256)), dim3(256), 0, s, A, B, V, C, C.n);
         if (const int rc = launch_status(who)) return rc;
         used += C.n;
@@ -278,36 +220,19 @@ int combine_resident(svo_world &w, int chunk, const svo_world &src, int src_chun
     HIP_TRY(hipMemcpyAsync(&changed, total, 8, hipMemcpyDeviceToHost, s));
 
     // 3. the fold, bottom-up, and the ranks of what stays
-    std::vector<uint32_t> stay(levels, 0);
-    for (uint32_t L = levels; L-- > 0;) {
-        const LevelList &V = lv[L];
-        const LevelList C = L + 1 < levels ? lv[L + 1] : LevelList{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0 };
-        hipLaunchKernelGGL(k_fold, dim3(blocks_for((uint64_t)V.n + 1, 256)), dim3(256), 0, s, V, C);
-        if (const int rc = launch_status(who)) return rc;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, need_scan, V.rank, V.rank, (int)V.n + 1, s));
-        HIP_TRY(hipMemcpyAsync(&stay[L], V.rank + V.n, 4, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    uint64_t branches = 0, twigs = 0;
-    std::vector<uint32_t> above(levels, 0);
-    for (uint32_t L = 0; L < levels; ++L) {
-        above[L] = (uint32_t)branches;
-        if (L == maxlevel) twigs = stay[L]; else branches += stay[L];
-    }
-    const uint64_t otrees = 1 + 8 * branches;
+    Ranks ranks;
+    if (const int rc = fold_and_rank(R, lv, maxlevel, [&](uint32_t L) {
+            const LevelList C = L + 1 < levels ? lv[L + 1] : LevelList{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0 };
+            hipLaunchKernelGGL(k_fold, dim3(blocks_for((uint64_t)lv[L].n + 1, 256)), dim3(256), 0, s, lv[L], C);
+        }, ranks)) return rc;
+    const uint64_t otrees = ranks.otrees, twigs = ranks.twigs;
     if (otrees > used || (levels == maxlevel + 1 ? twigs > lv[maxlevel].n : twigs != 0)) { set_error(std::string(who) + ": the fold disagrees with the walk"); return SVO_ERR_HIP; }
     if (otrees > (1ull << 30) || twigs > (1ull << 30)) { set_error(std::string(who) + ": 2^30 nodes or bricks"); return SVO_ERR_UNSUPPORTED; }
 
     // 4. the emit, top-down, into the edits' resident scratch of the destination: sized from the fold's totals, not from A
     uint32_t *otree = nullptr;
     uint16_t *otwig = nullptr;
-    if (const int rc = edit_scratch(w, otrees, twigs, &otree, &otwig)) return rc;
-    HIP_TRY(hipMemsetAsync(otree, 0, otrees * sizeof(uint32_t), s));
-    for (uint32_t L = 0; L < levels; ++L) {
-        const LevelList V = L ? lv[L - 1] : LevelList{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0 };
-        hipLaunchKernelGGL(k_emit, dim3(blocks_for(lv[L].n, 256)), dim3(256), 0, s, lv[L], V, L ? above[L - 1] : 0u, above[L], otree, (uint32_t)otrees);
-        if (const int rc = launch_status(who)) return rc;
-    }
+    if (const int rc = emit_levels(R, w, levels, [&](uint32_t L) { return EmitLevel{ lv[L].res, nullptr, lv[L].parent, lv[L].rank, lv[L].n }; }, ranks, &otree, &otwig)) return rc;
     if (twigs) {
         hipLaunchKernelGGL(k_write_bricks, dim3(blocks_for(lv[maxlevel].n, 4)), dim3(256), 0, s, A, B, lv[maxlevel], op, otwig, (uint32_t)twigs);
         if (const int rc = launch_status(who)) return rc;

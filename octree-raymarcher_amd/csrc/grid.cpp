@@ -7,14 +7,10 @@
 //   tree      the FIFO walk of grow(): root at slot 0, a node that is MIXED becomes a TWIG at level depth-2 (its 64 cells copied,
 //             brick index z*16 + y*4 + x) and a BRANCH above it (its 8 children at the pool's tail, slot x + 2y + 4z)
 // Integer arithmetic only; no HIP include: plain g++ compiles this file (host/grid_check.cpp runs it under the sanitizers).
-#include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <new>
-#include <vector>
 
-#include "world.h"
+#include "chunk_pools.h"
 
 namespace svo {
 
@@ -105,16 +101,7 @@ int svo_chunk_from_grid(const uint16_t *grid, uint32_t depth, const float positi
         std::vector<uint16_t> twig;
         chunk_from_grid(grid, depth, tree, twig);
         // (trees <= 1 + 8 * (8^8 - 1) / 7 and twigs <= 8^8 at depth 10: the 30-bit node offset is never reached)
-        uint32_t *t = (uint32_t *)std::malloc(tree.size() * sizeof(uint32_t));
-        uint16_t *b = (uint16_t *)std::malloc(std::max<size_t>(twig.size(), TWIG_WORDS) * sizeof(uint16_t));
-        if (!t || !b) { std::free(t); std::free(b); set_error("svo_chunk_from_grid: out of memory"); return SVO_ERR_OUT_OF_MEMORY; }
-        std::memcpy(t, tree.data(), tree.size() * sizeof(uint32_t));
-        if (!twig.empty()) std::memcpy(b, twig.data(), twig.size() * sizeof(uint16_t));
-        std::memcpy(out->position, position, sizeof out->position);
-        out->size = size; out->depth = depth; out->_pad = 0;
-        out->tree = t; out->trees = tree.size();
-        out->twig = b; out->twigs = twig.size() / TWIG_WORDS;
-        return SVO_OK;
+        return chunk_desc_take(out, position, size, depth, tree, twig, "svo_chunk_from_grid");
     } catch (const std::bad_alloc &) {
         set_error("svo_chunk_from_grid: out of host memory");
         return SVO_ERR_OUT_OF_MEMORY;

@@ -1,5 +1,6 @@
 // hip_own.h — what the .hip files share: the HIP status mapping, the "one thread per element, blocks of 256" launch with its size
-// check and error mapping, block_take for the numbering kernels, the owners of HIP resources and svo::Hbm, the device half of a world
+// check and error mapping, block_take and block_sum64 for the numbering and counting kernels, the owners of HIP resources (a call's
+// Arena of the pool cache among them) and svo::Hbm, the device half of a world
 // (the struct behind svo_world::hbm).  HIP only: world.h stays free of it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -73,6 +74,19 @@ template <unsigned BLOCK> __device__ __forceinline__ uint32_t block_take(uint32_
     return r;
 }
 
+// The sum of v over the threads of a block of BLOCK threads (a power of two) added to *total, 64 bits - by the same argument ONE
+// global atomic per block, none when the sum is 0.  Every thread of the block calls this; sh holds BLOCK words.
+template <unsigned BLOCK> __device__ __forceinline__ void block_sum64(unsigned long long v, unsigned long long *sh, unsigned long long *total)
+{
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (uint32_t s = BLOCK / 2; s > 0u; s >>= 1) {
+        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0u && sh[0] != 0ull) atomicAdd(total, sh[0]);
+}
+
 // ---- owners: each frees what it holds, none can be copied; the two that change hands can be moved --------------------------------
 struct NoCopy { NoCopy() = default; NoCopy(const NoCopy &) = delete; NoCopy &operator=(const NoCopy &) = delete; };
 
@@ -105,6 +119,23 @@ template <typename T> struct Pooled {
     // n elements on `dev`, whatever it held goes back to the cache first
     hipError_t alloc(size_t n, int dev) { *this = Pooled(); bytes = n * sizeof(T); device = dev; return pool_malloc((void **)&p, &bytes, dev); }
 };
+
+// The working memory of one call as one buffer of the pool cache carved into 256-byte aligned parts, at least 1 MiB: add() every
+// part, alloc(), then at<T>(k).  Declared before the call's SyncAtExit, so that it goes back to the cache behind the work
+struct Arena {
+    Pooled<unsigned char> mem;
+    std::vector<size_t> off;
+    size_t bytes = 0;
+    size_t add(size_t n) { off.push_back(bytes); bytes += (n + 255) & ~(size_t)255; return off.size() - 1; }
+    int alloc(const char *who, int device)
+    {
+        if (mem.alloc(std::max<size_t>(bytes, (size_t)1 << 20), device) == hipSuccess) return SVO_OK;
+        set_error(std::string(who) + ": no device memory for the working arrays");
+        return SVO_ERR_OUT_OF_MEMORY;
+    }
+    template <typename T> T *at(size_t k) const { return reinterpret_cast<T *>(mem.p + off[k]); }
+};
+struct SyncAtExit { hipStream_t s; ~SyncAtExit() { (void)hipStreamSynchronize(s); } };
 
 template <typename T> struct Pinned : NoCopy {              // n elements of pinned host memory, allocated once
     T *p = nullptr;

@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void k_fill_write(uint16_t *grid, FillDims D, 
     if (((empty[w] & ~outside[w]) >> bit) & 1ull) grid[i] = material;
 }
 
-// ---- the host side (mesh_tiles.hip.h: current_device, Arena, SyncAtExit) ------------------------------------------------------------
+// ---- the host side (mesh_tiles.hip.h: current_device; hip_own.h: Arena, SyncAtExit) ------------------------------------------------
 int add_mesh_device(const svo_mesh &m, float inv, uint32_t depth, uint16_t *grid, hipStream_t s)
 {
     const char *who = "svo_device_grid_add_mesh";

@@ -1,6 +1,6 @@
 // mesh_tiles.hip.h — what the two device voxelisers share (mesh.hip: into a dense grid; sparse_mesh.hip: into a list of cells): the
-// setup kernel, the decode of a tile job, and the host-side helpers of a world-less call that takes its working memory from the
-// device buffer cache.  Everything sits in an unnamed namespace: each of the two files compiles its own copy.
+// setup kernel, the decode of a tile job, and the host-side helpers of a world-less call (its working memory is an Arena of
+// hip_own.h).  Everything sits in an unnamed namespace: each of the two files compiles its own copy.
 //   k_mesh_setup     one thread per triangle: the record of mesh_setup (48 words: plane, box, nine edge functions, the clamped cell
 //                    box) and the number of 4x4x4-cell tiles its cell box touches; 0 for a dropped triangle
 //   tile_job_cell    one wave per tile job: the triangle by binary search in the scan of those counts, its record through the scalar
@@ -66,8 +66,6 @@ __device__ __forceinline__ const MeshTri &tile_job_cell(const MeshTri *__restric
 }
 
 // ---- the host side --------------------------------------------------------------------------------------------------------------
-struct SyncAtExit { hipStream_t s; ~SyncAtExit() { (void)hipStreamSynchronize(s); } };     // the arena goes back to the cache behind the work
-
 inline int current_device(const char *who, int *device)
 {
     int n = 0;
@@ -75,21 +73,6 @@ inline int current_device(const char *who, int *device)
     HIP_TRY(hipGetDevice(device));
     return SVO_OK;
 }
-
-// An arena of the pool cache carved into 256-byte aligned parts: add() every part, alloc(), then at<T>(k)
-struct Arena {
-    Pooled<unsigned char> mem;
-    std::vector<size_t> off;
-    size_t bytes = 0;
-    size_t add(size_t n) { off.push_back(bytes); bytes += (n + 255) & ~(size_t)255; return off.size() - 1; }
-    int alloc(const char *who, int device)
-    {
-        if (mem.alloc(std::max<size_t>(bytes, (size_t)1 << 20), device) == hipSuccess) return SVO_OK;
-        set_error(std::string(who) + ": no device memory for the working arrays");
-        return SVO_ERR_OUT_OF_MEMORY;
-    }
-    template <typename T> T *at(size_t k) const { return reinterpret_cast<T *>(mem.p + off[k]); }
-};
 
 inline MeshArgs mesh_kernel_args(const svo_mesh &m, float inv, uint32_t depth)
 {

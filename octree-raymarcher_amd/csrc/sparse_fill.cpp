@@ -10,18 +10,14 @@
 //              recursive descent restricted to the children on that face.  A brick floods inside its own mask by shifts of 1, 4, 16
 //   fold       bottom-up, a result word per reached node: an EMPTY node that is not outside is LEAF | material; a brick that holds one
 //              value after the fill is that LEAF (EMPTY for 0); a BRANCH whose eight results are one EMPTY / LEAF word is that word
-//   emit       the FIFO walk of svo_chunk_from_grid over the results: the pools are minimal and in visiting order whatever the input was
+//   emit       the FIFO walk over the results (chunk_pools.h: emit_fifo, which also holds the validation pass and the desc's producer)
 // Working memory is proportional to the node words and the bricks; nothing has N^3 entries.  No HIP include: plain g++ compiles this
 // file (host/sparse_fill_check.cpp runs it under the sanitizers).
-#include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <new>
-#include <vector>
 
+#include "chunk_pools.h"
 #include "sparse_fill_rule.h"
-#include "world.h"
 
 namespace svo {
 
@@ -141,62 +137,18 @@ struct Fill {
         return res[node] = r;
     }
 
-    struct Out { uint32_t node, at; };
-    int emit(std::vector<uint32_t> &otree, std::vector<uint16_t> &otwig)
+    void emit(std::vector<uint32_t> &otree, std::vector<uint16_t> &otwig) const
     {
-        otree.assign(1, node_make(EMPTY, 0));
-        otwig.clear();
-        std::vector<Out> level(1, Out{ 0, 0 }), next;
-        while (!level.empty()) {
-            next.clear();
-            for (const Out &o : level) {
-                const uint32_t r = res[o.node];
-                if (node_type(r) == TWIG) {
-                    const uint64_t in = empty[slot[o.node]] & ~out[slot[o.node]];
-                    const uint16_t *cells = twig + (size_t)node_offset(tree[o.node]) * TWIG_WORDS;
-                    otree[o.at] = node_make(TWIG, (uint32_t)(otwig.size() / TWIG_WORDS));
-                    for (uint32_t i = 0; i < TWIG_WORDS; ++i) otwig.push_back((in >> i) & 1ull ? (uint16_t)material : cells[i]);
-                } else if (node_type(r) == BRANCH) {
-                    const uint32_t first = (uint32_t)otree.size();
-                    otree[o.at] = node_make(BRANCH, first);
-                    otree.resize(otree.size() + 8, node_make(EMPTY, 0));
-                    for (uint32_t c = 0; c < 8; ++c) next.push_back(Out{ node_offset(tree[o.node]) + c, first + c });
-                } else otree[o.at] = r;
-            }
-            level.swap(next);
-        }
-        return SVO_OK;
+        emit_fifo(0u, [&](uint32_t node) { return res[node]; }, [&](uint32_t node, uint32_t c) { return node_offset(tree[node]) + c; },
+                  [&](uint32_t node, std::vector<uint16_t> &to) {
+                      const uint64_t in = empty[slot[node]] & ~out[slot[node]];
+                      const uint16_t *cells = twig + (size_t)node_offset(tree[node]) * TWIG_WORDS;
+                      for (uint32_t i = 0; i < TWIG_WORDS; ++i) to.push_back((in >> i) & 1ull ? (uint16_t)material : cells[i]);
+                  }, otree, otwig);
     }
 };
 
 } // namespace
-
-// what svo_world_create's validation asks of one chunk's pools (world.cpp: validate_chunk), and a depth the fill reaches; 0, or the status
-int fill_pools_status(const uint32_t *tree, uint64_t trees, uint64_t twigs, uint32_t depth, const char *who)
-{
-    if (depth < SVO_FILL_MIN_DEPTH || depth > SVO_FILL_MAX_DEPTH) { set_error(std::string(who) + ": the chunk's depth is outside [2, 16]"); return SVO_ERR_UNSUPPORTED; }
-    const char *why = nullptr;
-    if (trees == 0 || (trees - 1) % 8 != 0 || trees > (1ull << 30) || twigs > (1ull << 30)) why = "the tree pool is not 1 + 8k node words";
-    const uint32_t maxlevel = depth - TWIG_LEVELS;
-    std::vector<int8_t> block_level(why ? 0 : (trees - 1) / 8, (int8_t)-1);
-    for (uint64_t i = 0; !why && i < trees; ++i) {
-        const int level = i ? block_level[(i - 1) / 8] : 0;
-        if (level < 0) continue;                            // an orphan: nothing reaches it
-        const uint64_t off = node_offset(tree[i]);
-        if (node_type(tree[i]) == BRANCH) {
-            if ((uint32_t)level >= maxlevel) why = "BRANCH below level depth-2";
-            else if (off <= i || off + 8 > trees || (off - 1) % 8 != 0) why = "BRANCH offset outside pool or not a forward 8-block";
-            else if (block_level[(off - 1) / 8] >= 0) why = "child block referenced twice";
-            else block_level[(off - 1) / 8] = (int8_t)(level + 1);
-        } else if (node_type(tree[i]) == TWIG) {
-            if (off >= twigs) why = "TWIG offset outside brick pool";
-            else if ((uint32_t)level != maxlevel) { set_error(std::string(who) + ": a TWIG above level depth-2 (a sparsely refined chunk) is not supported"); return SVO_ERR_UNSUPPORTED; }
-        }
-    }
-    if (!why) return SVO_OK;
-    set_error(std::string(who) + ": " + why);
-    return SVO_ERR_INVALID_ARG;
-}
 
 } // namespace svo
 
@@ -211,7 +163,14 @@ int svo_chunk_fill_enclosed(const svo_chunk_desc *in, uint16_t material, svo_chu
         return SVO_ERR_INVALID_ARG;
     }
     try {
-        if (const int rc = fill_pools_status(in->tree, in->trees, in->twigs, in->depth, who)) return rc;
+        // a depth the fill reaches, then what a world asks of the pools (chunk_pools.h: pools_walk); a shallow TWIG met before the
+        // first malformed word is the answer
+        if (in->depth < SVO_FILL_MIN_DEPTH || in->depth > SVO_FILL_MAX_DEPTH) { set_error(std::string(who) + ": the chunk's depth is outside [2, 16]"); return SVO_ERR_UNSUPPORTED; }
+        bool shallow = false;
+        const char *why = (in->trees - 1) % 8 != 0 || in->trees > (1ull << 30) || in->twigs > (1ull << 30) ? "the tree pool is not 1 + 8k node words"
+                                                                                                            : pools_walk(in->tree, in->trees, in->twigs, in->depth, &shallow);
+        if (shallow) { set_error(std::string(who) + ": " + SHALLOW_TWIG_WHY); return SVO_ERR_UNSUPPORTED; }
+        if (why) { set_error(std::string(who) + ": " + why); return SVO_ERR_INVALID_ARG; }
         Fill F;
         F.tree = in->tree; F.twig = in->twig;
         F.depth = in->depth; F.maxlevel = in->depth - TWIG_LEVELS; F.N = 1u << in->depth;
@@ -225,15 +184,7 @@ int svo_chunk_fill_enclosed(const svo_chunk_desc *in, uint16_t material, svo_chu
         std::vector<uint32_t> tree;
         std::vector<uint16_t> twig;
         F.emit(tree, twig);
-        uint32_t *t = (uint32_t *)std::malloc(tree.size() * sizeof(uint32_t));
-        uint16_t *b = (uint16_t *)std::malloc(std::max<size_t>(twig.size(), TWIG_WORDS) * sizeof(uint16_t));
-        if (!t || !b) { std::free(t); std::free(b); set_error(std::string(who) + ": out of memory"); return SVO_ERR_OUT_OF_MEMORY; }
-        std::memcpy(t, tree.data(), tree.size() * sizeof(uint32_t));
-        if (!twig.empty()) std::memcpy(b, twig.data(), twig.size() * sizeof(uint16_t));
-        std::memcpy(out->position, in->position, sizeof out->position);
-        out->size = in->size; out->depth = in->depth; out->_pad = 0;
-        out->tree = t; out->trees = tree.size();
-        out->twig = b; out->twigs = twig.size() / TWIG_WORDS;
+        if (const int rc = chunk_desc_take(out, in->position, in->size, in->depth, tree, twig, who)) return rc;
         if (filled_out) *filled_out = F.filled;
         return SVO_OK;
     } catch (const std::bad_alloc &) {

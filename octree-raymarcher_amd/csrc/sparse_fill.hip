@@ -1,10 +1,10 @@
 // sparse_fill.hip — svo_world_chunk_fill_enclosed: svo_grid_fill_enclosed's rule applied to a chunk of an uploaded world on its tree,
 // without the dense grid, depth 2 .. 16.  sparse_fill.cpp is the host twin and states the fill as a walk, a queue flood, a fold and a
 // FIFO emit; sparse_fill_rule.h holds the bit arithmetic of a brick's 64-bit mask.  On the world's device, on the null stream, behind
-// a hipDeviceSynchronize like svo_world_chunk_from_mesh; complete at the return.
-//   walk              level-synchronous from the root: per level k_walk flags the BRANCHes of the level's list (and checks every offset
-//                     against the pools), one hipcub scan ranks them, k_children appends their eight children to the next level's list
-//                     in parent order - the FIFO walk's visiting order.  An entry is { old pool index, corner in cells, parent's entry }
+// a hipDeviceSynchronize like svo_world_chunk_from_mesh; complete at the return.  tree_rebuild.hip.h holds the frame of the rebuild
+// (the walk's tail, the fold's ranks, the emit); this file's own:
+//   walk              An entry is { old pool index, corner in cells, parent's entry }.  k_walk flags the BRANCHes of the level's list
+//                     (and checks every offset against the pools), k_children appends their eight children to the next level's list
 //   state             one byte per node word ("the EMPTY node here is OUTSIDE") and two 64-bit masks per brick (its empty cells, its
 //                     OUTSIDE cells).  k_seed_nodes lists the EMPTY nodes (block_take: one atomic per block) and raises those that touch
 //                     a face of the chunk; k_brick_slots / k_seed_bricks number the TWIGs of the last level and seed their border cells
@@ -15,20 +15,14 @@
 //                     two EMPTY nodes exchange in both directions.  The state only ever moves towards the fixed point, so the plain racy
 //                     stores are harmless (the argument of mesh.hip's k_fill_sweep).  The host launches SWEEP_BATCH sweeps, reads the
 //                     last one's "something changed" word and stops at 0: no number of sweeps is assumed
-//   count             edge^3 per EMPTY node that is not outside + a popcount per brick, 64 bits, one atomic per block
-//   fold, emit        bottom-up k_fold writes every reached node's result word into an array indexed by the old pool and flags the
-//                     BRANCHes / TWIGs that stay; a scan per level ranks them (the lists are in visiting order and what stays is
-//                     reachable, so the ranks are the FIFO walk's numbers); top-down k_emit writes a node whose parent stays a BRANCH to
-//                     first + slot, k_write_bricks one wave per surviving brick with the fill applied.  Every index written is checked
-//                     against the pool it goes to
+//   count             edge^3 per EMPTY node that is not outside + a popcount per brick, 64 bits, one atomic per block (block_sum64)
+//   fold, bricks out  k_fold writes every reached node's result word into an array indexed by the old pool (k_emit reads it through
+//                     the entries' pool indices); k_write_bricks one wave per surviving brick with the fill applied
 // The install is svo_world_chunk_from_grid's (install_rebuilt).  Plain C++ and vector stores; integer arithmetic only.
-#include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
-
 #include <cstdio>
 #include <cstdlib>
 
-#include "hip_own.h"
+#include "tree_rebuild.hip.h"
 #include "sparse_fill_rule.h"
 
 namespace svo {
@@ -37,7 +31,6 @@ namespace {
 
 constexpr uint32_t SWEEP_BATCH = 8;
 constexpr uint32_t NONE = 0xFFFFFFFFu;
-enum : uint32_t { ERR_MALFORMED = 1, ERR_SHALLOW_TWIG = 2 };
 
 // One level's reached nodes in visiting order: [n] of each, rank has n + 1 entries (a scan's last item is the total)
 struct LevelList {
@@ -50,7 +43,8 @@ struct LevelList {
 
 struct Pools { const uint32_t *tree; const uint16_t *twig; uint32_t trees, twigs, depth; };
 
-// a BRANCH the walk follows: above the last level, a forward 8-block inside the pool (what validate_chunk asks)
+// a BRANCH the walk follows: above the last level, a forward 8-block inside the pool (what validate_chunk asks).  off > node, where
+// combine.hip can only ask off >= 1: the entries here carry pool indices, so a back edge is seen where it is met
 __device__ __forceinline__ bool walk_branch(const Pools &P, uint32_t node, uint32_t w, bool last)
 {
     const uint32_t off = node_offset(w);
@@ -223,13 +217,7 @@ __global__ __launch_bounds__(256) void k_count(const uint4 *__restrict__ elist, 
         const uint4 e = elist[t];
         if (!outside[e.x]) v = (unsigned long long)e.w * e.w * e.w;
     } else if (t - ne < B.n) v = (unsigned long long)__popcll(B.empty[t - ne] & ~B.out[t - ne]);
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (uint32_t s = 128u; s > 0u; s >>= 1) {
-        if (threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0u && sh[0] != 0ull) atomicAdd(total, sh[0]);
+    block_sum64<256>(v, sh, total);
 }
 
 // res[node] of every node of level V (the levels below are done): BRANCH | 0 and TWIG | 0 for what stays one; V.rank flags those
@@ -256,23 +244,6 @@ __global__ __launch_bounds__(256) void k_fold(Pools P, LevelList V, uint32_t las
     V.rank[i] = node_type(r) == BRANCH || node_type(r) == TWIG ? 1u : 0u;
 }
 
-// level C into the blocks of its parents' level V; above_v / above_c = the BRANCHes that stay above V / above C.  V.node == null: C is
-// level 0 and its one node the root
-__global__ __launch_bounds__(256) void k_emit(LevelList C, LevelList V, uint32_t above_v, uint32_t above_c, const uint32_t *__restrict__ res, uint32_t *tree, uint32_t trees)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= C.n) return;
-    uint32_t at = 0u;
-    if (V.node) {
-        const uint32_t p = C.parent[i];
-        if (node_type(res[V.node[p]]) != BRANCH) return;
-        at = 1u + 8u * (above_v + V.rank[p]) + (i & 7u);
-    }
-    const uint32_t r = res[C.node[i]], type = node_type(r);
-    const uint32_t w = type == BRANCH ? node_make(BRANCH, 1u + 8u * (above_c + C.rank[i])) : type == TWIG ? node_make(TWIG, C.rank[i]) : r;
-    if (at < trees) tree[at] = w;
-}
-
 // one wave per brick of the input: one that stays is written, the fill applied, as brick V.rank[its entry]
 __global__ __launch_bounds__(256) void k_write_bricks(Pools P, LevelList V, Bricks B, const uint32_t *__restrict__ res, uint32_t material, uint16_t *twig, uint32_t twigs)
 {
@@ -283,23 +254,6 @@ __global__ __launch_bounds__(256) void k_write_bricks(Pools P, LevelList V, Bric
     const bool in = (((B.empty[k] & ~B.out[k]) >> lane) & 1ull) != 0ull;
     twig[(size_t)to * TWIG_WORDS + lane] = in ? (uint16_t)material : P.twig[(size_t)off * TWIG_WORDS + lane];
 }
-
-// An arena of the pool cache carved into 256-byte aligned parts, at least 1 MiB, as the voxelisers take theirs (mesh_tiles.hip.h, whose
-// kernels this file has no use for)
-struct Arena {
-    Pooled<unsigned char> mem;
-    std::vector<size_t> off;
-    size_t bytes = 0;
-    size_t add(size_t n) { off.push_back(bytes); bytes += (n + 255) & ~(size_t)255; return off.size() - 1; }
-    int alloc(const char *who, int device)
-    {
-        if (mem.alloc(std::max<size_t>(bytes, (size_t)1 << 20), device) == hipSuccess) return SVO_OK;
-        set_error(std::string(who) + ": no device memory for the working arrays");
-        return SVO_ERR_OUT_OF_MEMORY;
-    }
-    template <typename T> T *at(size_t k) const { return reinterpret_cast<T *>(mem.p + off[k]); }
-};
-struct SyncAtExit { hipStream_t s; ~SyncAtExit() { (void)hipStreamSynchronize(s); } };     // the arenas go back to the cache behind the work
 
 int fill_resident(svo_world &w, int chunk, uint32_t material, uint64_t *filled_out)
 {
@@ -330,6 +284,7 @@ int fill_resident(svo_world &w, int chunk, uint32_t material, uint64_t *filled_o
     uint8_t *const outside = A.at<uint8_t>(k_outside);
     uint4 *const elist = A.at<uint4>(k_elist);
     unsigned char *const tmp = A.at<unsigned char>(k_tmp);
+    const Rebuild R{ who, s, tmp, need_scan };
     // words: [0] the walk's error, [1] the EMPTY nodes listed, [2, 3] the cells filled (64 bits), [8 .. 8 + SWEEP_BATCH) a batch's "changed"
     uint32_t *const err = words, *const ecount = words + 1, *const changed = words + 8;
     unsigned long long *const total = reinterpret_cast<unsigned long long *>(words + 2);
@@ -353,15 +308,10 @@ int fill_resident(svo_world &w, int chunk, uint32_t material, uint64_t *filled_o
         const LevelList &V = lv[L];
         hipLaunchKernelGGL(k_walk, dim3(blocks_for((uint64_t)V.n + 1, 256)), dim3(256), 0, s, P, V, L == maxlevel ? 1u : 0u, err);
         if (const int rc = launch_status(who)) return rc;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, need_scan, V.rank, V.rank, (int)V.n + 1, s));
-        uint32_t back[2] = { 0, 0 };                    // the level's BRANCHes, the walk's error
-        HIP_TRY(hipMemcpyAsync(&back[0], V.rank + V.n, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(&back[1], err, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (back[1] == ERR_SHALLOW_TWIG) { set_error(std::string(who) + ": a TWIG above level depth-2 (a sparsely refined chunk) is not supported"); return SVO_ERR_UNSUPPORTED; }
-        if (back[1] != 0 || back[0] > V.n || used + 8ull * back[0] > cap) { set_error(std::string(who) + ": the chunk's pools are malformed"); return SVO_ERR_MALFORMED_TREE; }
-        if (back[0] == 0) break;
-        LevelList C = level_at(used, L + 1, 8 * back[0]);
+        uint32_t branches = 0;
+        if (const int rc = walk_level_tail(R, "the chunk's", V.rank, V.n, err, used, cap, &branches)) return rc;
+        if (branches == 0) break;
+        LevelList C = level_at(used, L + 1, 8 * branches);
         hipLaunchKernelGGL(k_children, dim3(blocks_for(V.n, 256)), dim3(256), 0, s, P, V, (1u << depth) >> (L + 1), C, C.n);
         if (const int rc = launch_status(who)) return rc;
         used += C.n;
@@ -420,34 +370,17 @@ int fill_resident(svo_world &w, int chunk, uint32_t material, uint64_t *filled_o
     HIP_TRY(hipMemcpyAsync(&filled, total, 8, hipMemcpyDeviceToHost, s));
 
     // 5. the fold, bottom-up, and the ranks of what stays
-    std::vector<uint32_t> stay(levels, 0);
-    for (uint32_t L = levels; L-- > 0;) {
-        const LevelList &V = lv[L];
-        hipLaunchKernelGGL(k_fold, dim3(blocks_for((uint64_t)V.n + 1, 256)), dim3(256), 0, s, P, V, L == maxlevel ? 1u : 0u, outside, slot, B, material, res);
-        if (const int rc = launch_status(who)) return rc;
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, need_scan, V.rank, V.rank, (int)V.n + 1, s));
-        HIP_TRY(hipMemcpyAsync(&stay[L], V.rank + V.n, 4, hipMemcpyDeviceToHost, s));
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    uint64_t branches = 0, twigs = 0;
-    std::vector<uint32_t> above(levels, 0);
-    for (uint32_t L = 0; L < levels; ++L) {
-        above[L] = (uint32_t)branches;
-        if (L == maxlevel) twigs = stay[L]; else branches += stay[L];
-    }
-    const uint64_t otrees = 1 + 8 * branches;
+    Ranks ranks;
+    if (const int rc = fold_and_rank(R, lv, maxlevel, [&](uint32_t L) {
+            hipLaunchKernelGGL(k_fold, dim3(blocks_for((uint64_t)lv[L].n + 1, 256)), dim3(256), 0, s, P, lv[L], L == maxlevel ? 1u : 0u, outside, slot, B, material, res);
+        }, ranks)) return rc;
+    const uint64_t otrees = ranks.otrees, twigs = ranks.twigs;
     if (otrees > trees || twigs > nbricks) { set_error(std::string(who) + ": the fold disagrees with the walk"); return SVO_ERR_HIP; }
 
     // 6. the emit, top-down, into the edits' resident scratch
     uint32_t *otree = nullptr;
     uint16_t *otwig = nullptr;
-    if (const int rc = edit_scratch(w, otrees, twigs, &otree, &otwig)) return rc;
-    HIP_TRY(hipMemsetAsync(otree, 0, otrees * sizeof(uint32_t), s));
-    for (uint32_t L = 0; L < levels; ++L) {
-        const LevelList V = L ? lv[L - 1] : LevelList{ nullptr, nullptr, nullptr, nullptr, nullptr, 0 };
-        hipLaunchKernelGGL(k_emit, dim3(blocks_for(lv[L].n, 256)), dim3(256), 0, s, lv[L], V, L ? above[L - 1] : 0u, above[L], res, otree, (uint32_t)otrees);
-        if (const int rc = launch_status(who)) return rc;
-    }
+    if (const int rc = emit_levels(R, w, levels, [&](uint32_t L) { return EmitLevel{ res, lv[L].node, lv[L].parent, lv[L].rank, lv[L].n }; }, ranks, &otree, &otwig)) return rc;
     if (twigs) {
         hipLaunchKernelGGL(k_write_bricks, dim3(blocks_for(nbricks, 4)), dim3(256), 0, s, P, Last, B, res, material, otwig, (uint32_t)twigs);
         if (const int rc = launch_status(who)) return rc;

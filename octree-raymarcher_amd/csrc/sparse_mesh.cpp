@@ -12,13 +12,10 @@
 // under the sanitizers).
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <new>
-#include <vector>
 
+#include "chunk_pools.h"
 #include "sparse_mesh_rule.h"
-#include "world.h"
 
 namespace svo {
 
@@ -152,16 +149,7 @@ int svo_chunk_from_mesh(const svo_mesh *meshes, int nmeshes, uint32_t depth, con
         std::vector<uint16_t> twig;
         if (const int rc = collect(meshes, nmeshes, inv, depth, words)) return rc;
         if (const int rc = chunk_from_words(words, depth, tree, twig)) return rc;
-        uint32_t *t = (uint32_t *)std::malloc(tree.size() * sizeof(uint32_t));
-        uint16_t *b = (uint16_t *)std::malloc(std::max<size_t>(twig.size(), TWIG_WORDS) * sizeof(uint16_t));
-        if (!t || !b) { std::free(t); std::free(b); set_error("svo_chunk_from_mesh: out of memory"); return SVO_ERR_OUT_OF_MEMORY; }
-        std::memcpy(t, tree.data(), tree.size() * sizeof(uint32_t));
-        if (!twig.empty()) std::memcpy(b, twig.data(), twig.size() * sizeof(uint16_t));
-        std::memcpy(out->position, position, sizeof out->position);
-        out->size = size; out->depth = depth; out->_pad = 0;
-        out->tree = t; out->trees = tree.size();
-        out->twig = b; out->twigs = twig.size() / TWIG_WORDS;
-        return SVO_OK;
+        return chunk_desc_take(out, position, size, depth, tree, twig, "svo_chunk_from_mesh");
     } catch (const std::bad_alloc &) {
         set_error("svo_chunk_from_mesh: out of host memory");
         return SVO_ERR_OUT_OF_MEMORY;

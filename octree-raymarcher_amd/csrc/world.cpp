@@ -19,43 +19,20 @@ namespace svo {
 static thread_local std::string g_error;
 void set_error(const std::string &msg) { g_error = msg; }
 
-// One forward pass over the node words.  Accepts what grow() and the box edits produce
-// (children blocks always lie after their parent, at indices 1+8k); rejects anything a kernel
-// could run off: out-of-pool offsets, back edges (cycles), branches deeper than depth-2.
-// Blocks no reachable BRANCH points at (orphans left behind by Ocroot::destroy) are ignored.
+// A chunk a world may hold: its own pre-checks, then the forward pass over the node words (chunk_pools.h: pools_walk).  A TWIG above
+// level depth-2 is no refusal here: the kernels march a sparsely refined chunk.
 int validate_chunk(const ChunkPools &c, std::string &why)
 {
     const uint64_t n = c.tree.size();
-    if (n == 0) { why = "empty tree pool"; return SVO_ERR_MALFORMED_TREE; }
-    if (c.depth < TWIG_LEVELS || c.depth > 30) { why = "depth out of range [2,30]"; return SVO_ERR_MALFORMED_TREE; }
-    if ((n - 1) % 8 != 0) { why = "tree pool is not 1 + 8k nodes"; return SVO_ERR_MALFORMED_TREE; }
-    if (!(c.size > 0.0f) || !std::isfinite(c.size)) { why = "chunk size must be positive"; return SVO_ERR_MALFORMED_TREE; }
-    const uint32_t maxlevel = c.depth - TWIG_LEVELS;
-    const uint64_t nbricks = c.twig_count();
-    std::vector<int8_t> block_level((n - 1) / 8, (int8_t)-1);
-    for (uint64_t i = 0; i < n; ++i) {
-        int level = 0;
-        if (i > 0) {
-            level = block_level[(i - 1) / 8];
-            if (level < 0) continue;                       // orphan
-        }
-        const uint32_t word = c.tree[i];
-        const uint64_t off = node_offset(word);
-        switch (node_type(word)) {
-        case BRANCH:
-            if ((uint32_t)level >= maxlevel) { why = "BRANCH below level depth-2"; return SVO_ERR_MALFORMED_TREE; }
-            if (off <= i || off + 8 > n || (off - 1) % 8 != 0) { why = "BRANCH offset outside pool or not a forward 8-block"; return SVO_ERR_MALFORMED_TREE; }
-            if (block_level[(off - 1) / 8] >= 0) { why = "child block referenced twice"; return SVO_ERR_MALFORMED_TREE; }
-            block_level[(off - 1) / 8] = (int8_t)(level + 1);
-            break;
-        case TWIG:
-            if (off >= nbricks) { why = "TWIG offset outside brick pool"; return SVO_ERR_MALFORMED_TREE; }
-            break;
-        default:
-            break;
-        }
-    }
-    return SVO_OK;
+    const char *bad = nullptr;
+    if (n == 0) bad = "empty tree pool";
+    else if (c.depth < TWIG_LEVELS || c.depth > 30) bad = "depth out of range [2,30]";
+    else if ((n - 1) % 8 != 0) bad = "tree pool is not 1 + 8k nodes";
+    else if (!(c.size > 0.0f) || !std::isfinite(c.size)) bad = "chunk size must be positive";
+    else bad = pools_walk(c.tree.data(), n, c.twig_count(), c.depth, nullptr);
+    if (!bad) return SVO_OK;
+    why = bad;
+    return SVO_ERR_MALFORMED_TREE;
 }
 
 // True when every corner of every possible node / brick cell of the chunk is an exactly

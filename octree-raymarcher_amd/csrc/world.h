@@ -80,3 +80,5 @@ int  edit_scratch(svo_world &w, uint64_t trees, uint64_t twigs, uint32_t **tree,
 // compact.hip: Ocroot::defragcopy (lod = false) or Ocroot::lodmm (lod = true) + World::modify on an uploaded world
 int  rebuild_resident(svo_world &w, int chunk, bool lod);
 } // namespace svo
+
+#include "chunk_pools.h"                          // validate_chunk's forward pass; it comes with the declaration (it needs the ones above)
