@@ -17,6 +17,7 @@
  *   svo_chunk_fill_enclosed / svo_world_chunk_fill_enclosed <- (no counterpart) the cells a chunk's voxels enclose, filled on the tree
  *                           without a dense grid, to depth 16, on the host or on the device
  *   svo_chunk_combine / svo_world_chunk_combine <- (no counterpart) two chunks of one depth combined cell by cell on their trees
+ *   svo_chunk_stamp / svo_world_chunk_stamp <- (no counterpart) a chunk placed into another at a cell offset, in one of 48 orientations
  *                           (union, B under / over A, subtraction, intersection), to depth 16, on the host or on the device
  *   svo_grid_add_mesh / svo_device_grid_add_mesh <- (no counterpart: the reference rasterises its one mesh, src/Worm.cpp, with GL) a
  *                           triangle mesh voxelised into a dense grid, on the host or in device memory
@@ -140,7 +141,8 @@ extern "C" {
                                           svo_device_grid_fill_enclosed and svo_mesh,
                                           svo_chunk_from_mesh, svo_world_chunk_from_mesh and SVO_MESH_MIN_DEPTH / SVO_MESH_MAX_DEPTH,
                                           svo_chunk_fill_enclosed, svo_world_chunk_fill_enclosed and SVO_FILL_MIN_DEPTH / SVO_FILL_MAX_DEPTH,
-                                          svo_chunk_combine, svo_world_chunk_combine, SVO_COMBINE_* and SVO_COMBINE_MIN_DEPTH / SVO_COMBINE_MAX_DEPTH
+                                          svo_chunk_combine, svo_world_chunk_combine, SVO_COMBINE_* and SVO_COMBINE_MIN_DEPTH / SVO_COMBINE_MAX_DEPTH,
+                                          svo_chunk_stamp, svo_world_chunk_stamp, svo_placement and SVO_STAMP_MIN_DEPTH / SVO_STAMP_MAX_DEPTH
                                           (functions added, nothing changed) */
 
 typedef enum svo_status {
@@ -683,6 +685,45 @@ enum { SVO_COMBINE_MAX = 0, SVO_COMBINE_UNDER = 1, SVO_COMBINE_OVER = 2, SVO_COM
 #define SVO_COMBINE_MAX_DEPTH 16
 int svo_chunk_combine(const svo_chunk_desc *a, const svo_chunk_desc *b, int op, svo_chunk_desc *out, uint64_t *changed_out);
 int svo_world_chunk_combine(svo_world *dst, int chunk, svo_world *src, int src_chunk, int op, uint64_t *changed_out);
+
+/* ---- the stamp: a chunk placed into another at any cell offset, in any orientation of the cube ---------------------------------
+ * A depth-6 model put into a depth-12 terrain chunk, the same tree model placed forty times, an instance that came to rest baked into
+ * the world - WITHOUT a dense grid and without voxelising anything again.  Definition: A has depth D_A and B depth D_B, both in
+ * [SVO_STAMP_MIN_DEPTH, SVO_STAMP_MAX_DEPTH] with D_B <= D_A; N_A = 2^D_A, N_B = 2^D_B, and G_A, G_B the grids of their finest
+ * voxels, as svo_world_chunk_to_grid reports them (as for the chunk CSG above).  The two chunks' positions and sizes are not
+ * consulted: ONE CELL OF B IS ONE CELL OF A, and the result keeps A's frame.  The placement gives A's cell that B's cube starts at and
+ * an orientation orient = perm * 8 + flips: perm indexes the table pi = (x,y,z), (x,z,y), (y,x,z), (y,z,x), (z,x,y), (z,y,x), which
+ * gives pi(0), pi(1), pi(2) (axis 0 is x), and flips has one bit per OUTPUT axis.  For a cell p of A take d = p - offset:
+ *   if any d_i lies outside [0, N_B):  b = 0
+ *   otherwise  q[pi(i)] = (flips bit i) ? N_B - 1 - d_i : d_i  and  b = G_B[q]
+ *   G[p] = f_op(G_A[p], b), with f the SVO_COMBINE_* table above, unchanged
+ * B's cube therefore covers A's cells [offset, offset + N_B)^3 in every orientation; what lies outside A is dropped.  OUTSIDE B'S CUBE
+ * b IS 0, SO SVO_COMBINE_INTERSECT CLEARS A THERE (and SVO_COMBINE_SUBTRACT, MAX, UNDER and OVER leave A as it is).  The orientation
+ * is proper (a rotation) iff parity(perm) * (-1)^popcount(flips) = +1; the other 24 are mirrors and are allowed.  The result is the
+ * tree of G by svo_chunk_from_grid's rule, ALWAYS rebuilt, in A's frame; *changed_out (may be NULL) receives the number of cells with
+ * G[p] != G_A[p].  With D_B = D_A, offset 0 and orient 0 the pools and the count are svo_chunk_combine's, index for index.  No grid is
+ * allocated: working memory is proportional to the entries of the walk, which follow the RESULT - a B that is one LEAF word, placed
+ * at an odd offset, leaves bricks along all six faces of its cube, so the result can exceed trees_A + trees_B node words and twigs_A
+ * + twigs_B bricks.  The host form and the device form give the same pools and the same count.
+ *
+ * A model that straddles a chunk border is two calls whose offsets differ by N_A on that axis.
+ *
+ * svo_chunk_stamp (host) and svo_world_chunk_stamp (device) take their chunks, leave B alone and are ordered, complete and installed
+ * as svo_chunk_combine and svo_world_chunk_combine; src == dst with src_chunk == chunk is defined: B is read completely before A is
+ * replaced.
+ *
+ * Refusals, in combine's order and all before anything changes or is written: SVO_ERR_INVALID_ARG as there, and for a NULL placement,
+ * orient > 47 or an offset outside [-65536, 65536]; then SVO_ERR_NOT_UPLOADED (device form); then SVO_ERR_UNSUPPORTED for D_B > D_A, a
+ * depth outside [2, 16], a TWIG above level depth-2 in either chunk and 2^30 entries, nodes or bricks; SVO_ERR_OUT_OF_MEMORY when the
+ * working arrays do not fit; on the device a malformed pool found by the walk is SVO_ERR_MALFORMED_TREE, with nothing installed. */
+typedef struct svo_placement {      /* 16 bytes */
+    int32_t  offset[3];             /* A's cell that B's cube starts at; each in [-65536, 65536] */
+    uint32_t orient;                /* 0 .. 47: perm * 8 + flips */
+} svo_placement;
+#define SVO_STAMP_MIN_DEPTH 2
+#define SVO_STAMP_MAX_DEPTH 16
+int svo_chunk_stamp(const svo_chunk_desc *a, const svo_chunk_desc *b, const svo_placement *pl, int op, svo_chunk_desc *out, uint64_t *changed_out);
+int svo_world_chunk_stamp(svo_world *dst, int chunk, svo_world *src, int src_chunk, const svo_placement *pl, int op, uint64_t *changed_out);
 
 /* ---- the hot path ------------------------------------------------------------------------ */
 

@@ -26,6 +26,7 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     chunk_from_mesh, World.chunk_from_mesh   <- (none)   the tree of a mesh's shell without the dense grid, to depth 16
     chunk_fill_enclosed, World.chunk_fill_enclosed   <- (none)   the cells a chunk's voxels enclose, filled on the tree, to depth 16
     chunk_combine, World.chunk_combine   <- (none)   two chunks of one depth combined cell by cell on their trees (COMBINE_*), to depth 16
+    chunk_stamp, World.chunk_stamp, Placement   <- (none)   a chunk placed into another at a cell offset, in one of 48 orientations, through a COMBINE_* rule
     grid_add_mesh / grid_fill_enclosed, device_grid_add_mesh / device_grid_fill_enclosed, Mesh   <- (none: the reference rasterises its one mesh with GL)   a triangle mesh into a dense grid, its shell filled
 
 There is NO CPU fallback: if libsvo_amd.so is missing the import raises, and every device call
@@ -67,6 +68,9 @@ KERNEL_AUTO, KERNEL_LITERAL, KERNEL_STACK = 0, 1, 2
 EDIT_BUILD, EDIT_DESTROY, EDIT_REPLACE = 0, 1, 2     # svo_world_edit_box
 COMBINE_MAX, COMBINE_UNDER, COMBINE_OVER, COMBINE_SUBTRACT, COMBINE_INTERSECT = 0, 1, 2, 3, 4     # svo_chunk_combine / svo_world_chunk_combine
 COMBINE_MIN_DEPTH, COMBINE_MAX_DEPTH = 2, 16
+STAMP_MIN_DEPTH, STAMP_MAX_DEPTH, STAMP_ORIENTS, STAMP_OFFSET_LIMIT = 2, 16, 48, 65536      # svo_chunk_stamp / svo_world_chunk_stamp
+# the 24 proper orientations (rotations) among orient = perm * 8 + flips: parity(perm) * (-1)^popcount(flips) = +1; perms 1, 2, 5 are odd
+ORIENT_ROTATIONS = tuple(o for o in range(48) if ((o >> 3 in (1, 2, 5)) + bin(o & 7).count("1")) % 2 == 0)
 HIT_FLAG, SHADOW_TRACED, SHADOWED, FACE_NORMAL, SEE_THROUGH, ERR_FLAG = 1, 2, 4, 8, 16, 1 << 15
 LOCAL_SHADOWS, SHADOWED_POINT, SHADOWED_SPOT = 1 << 5, 1 << 6, 1 << 7     # svo_trace_local_shadows
 NORMAL_CUBE, NORMAL_FACE = 0, 1
@@ -103,6 +107,14 @@ class ChunkDesc(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("size", C.c_float), ("depth", C.c_uint32), ("_pad", C.c_uint32),
                 ("tree", C.POINTER(C.c_uint32)), ("trees", C.c_uint64),
                 ("twig", C.POINTER(C.c_uint16)), ("twigs", C.c_uint64)]
+
+
+class Placement(C.Structure):
+    """svo_placement: A's cell that B's cube starts at (each offset in [-65536, 65536]) and the orientation 0 .. 47."""
+    _fields_ = [("offset", C.c_int32 * 3), ("orient", C.c_uint32)]
+
+    def __init__(self, offset=(0, 0, 0), orient=0):
+        super().__init__((C.c_int32 * 3)(*[int(x) for x in offset]), int(orient))
 
 
 class TerrainParams(C.Structure):
@@ -250,7 +262,7 @@ ABI_SYMBOLS = [
     "svo_chunk_from_grid", "svo_world_chunk_from_grid", "svo_world_chunk_to_grid",
     "svo_grid_add_mesh", "svo_device_grid_add_mesh", "svo_grid_fill_enclosed", "svo_device_grid_fill_enclosed",
     "svo_chunk_from_mesh", "svo_world_chunk_from_mesh", "svo_chunk_fill_enclosed", "svo_world_chunk_fill_enclosed",
-    "svo_chunk_combine", "svo_world_chunk_combine",
+    "svo_chunk_combine", "svo_world_chunk_combine", "svo_chunk_stamp", "svo_world_chunk_stamp",
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_edit_cube", "svo_world_edit_ball", "svo_world_edit_ball_all", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_cursor_place", "svo_shade_boxes", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_shadowmap_fit", "svo_shadowmap_render", "svo_shadowmap_apply", "svo_hit_ao", "svo_shade_ao",
@@ -296,6 +308,8 @@ lib.svo_chunk_fill_enclosed.argtypes = [C.POINTER(ChunkDesc), C.c_uint16, C.POIN
 lib.svo_world_chunk_fill_enclosed.argtypes = [_P, C.c_int, C.c_uint16, C.POINTER(C.c_uint64)]
 lib.svo_chunk_combine.argtypes = [C.POINTER(ChunkDesc), C.POINTER(ChunkDesc), C.c_int, C.POINTER(ChunkDesc), C.POINTER(C.c_uint64)]
 lib.svo_world_chunk_combine.argtypes = [_P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+lib.svo_chunk_stamp.argtypes = [C.POINTER(ChunkDesc), C.POINTER(ChunkDesc), C.POINTER(Placement), C.c_int, C.POINTER(ChunkDesc), C.POINTER(C.c_uint64)]
+lib.svo_world_chunk_stamp.argtypes = [_P, C.c_int, _P, C.c_int, C.POINTER(Placement), C.c_int, C.POINTER(C.c_uint64)]
 lib.svo_gbuffer_pack.argtypes = [_P, _P, C.c_int64, _P]
 lib.svo_gbuffer_unpack.argtypes = [_P, _P, C.c_int64, _P]
 lib.svo_shade_defaults.argtypes = [C.POINTER(ShadeParams)]
@@ -632,6 +646,23 @@ def chunk_combine(a: dict, b: dict, op: int):
         lib.svo_chunk_free(C.byref(d))
 
 
+def chunk_stamp(a: dict, b: dict, offset, orient: int, op: int):
+    """svo_chunk_stamp on the host: chunk dict b (depth <= a's, both 2 .. 16) placed into chunk dict a with its cube starting at a's
+    cell `offset` (x, y, z), in orientation `orient` (0 .. 47: perm * 8 + flips, ORIENT_ROTATIONS are the proper ones), through
+    COMBINE_* `op` - one cell of b is one cell of a, outside b's cube b is empty -, rebuilt minimal and in FIFO order without a dense
+    grid, in a's frame; a and b are left as they are.  Returns (the stamped chunk dict, how many voxels differ from a's)."""
+    da, keep_a = _host_chunk_desc(a)
+    db, keep_b = _host_chunk_desc(b)
+    d, changed, pl = ChunkDesc(), C.c_uint64(0), Placement(offset, orient)
+    _check(lib.svo_chunk_stamp(C.byref(da), C.byref(db), C.byref(pl), int(op), C.byref(d), C.byref(changed)), "svo_chunk_stamp")
+    try:
+        otree = np.ctypeslib.as_array(d.tree, shape=(d.trees,)).copy()
+        otwig = np.ctypeslib.as_array(d.twig, shape=(d.twigs * 64,)).copy() if d.twigs else np.zeros(0, np.uint16)
+        return {"position": tuple(d.position), "size": d.size, "depth": d.depth, "tree": otree, "twig": otwig}, int(changed.value)
+    finally:
+        lib.svo_chunk_free(C.byref(d))
+
+
 def gbuffer_pack(gbuffer_ptr: int, packed_ptr: int, n: int, stream: int = 0):
     _check(lib.svo_gbuffer_pack(gbuffer_ptr, packed_ptr, n, stream), "svo_gbuffer_pack")
 
@@ -936,6 +967,16 @@ class World:
         changed = C.c_uint64(0)
         self.combine_status = _check(lib.svo_world_chunk_combine(self._h, int(chunk), None if src_world is None else src_world._h, int(src_chunk), int(op),
                                                                  C.byref(changed)), "svo_world_chunk_combine")
+        return int(changed.value)
+
+    def chunk_stamp(self, chunk: int, src_world: "World", src_chunk: int, offset, orient: int, op: int) -> int:
+        """svo_world_chunk_stamp: chunk replaced by itself with chunk src_chunk of src_world - an uploaded world on the same device,
+        which may be this one; its depth at most this chunk's - placed at cell `offset` in orientation `orient` through COMBINE_* `op`,
+        built on the device on the two trees; complete when it returns.  Returns how many voxels changed; the status (SVO_OK or
+        SVO_OK_LITERAL_ONLY) is in self.stamp_status."""
+        changed, pl = C.c_uint64(0), Placement(offset, orient)
+        self.stamp_status = _check(lib.svo_world_chunk_stamp(self._h, int(chunk), None if src_world is None else src_world._h, int(src_chunk), C.byref(pl), int(op),
+                                                             C.byref(changed)), "svo_world_chunk_stamp")
         return int(changed.value)
 
     def chunk_to_grid(self, chunk: int, depth: int, out_ptr: int, stream: int = 0):

@@ -22,6 +22,8 @@
 //                                       depth 16 (svo_world_chunk_fill_enclosed on the device, svo_chunk_fill_enclosed on host pools)
 //   svo::World::chunk_combine / svo::chunk_combine  <- (none) two chunks of one depth combined cell by cell on their trees (union, under / over,
 //                                       subtraction, intersection), to depth 16 (svo_world_chunk_combine on the device, svo_chunk_combine on host pools)
+//   svo::World::chunk_stamp / svo::chunk_stamp  <- (none) a chunk placed into another at a cell offset, in one of the 48 orientations of the cube, through a
+//                                       SVO_COMBINE_* rule, to depth 16 (svo_world_chunk_stamp on the device, svo_chunk_stamp on host pools)
 //   svo::World::chunk_from_grid / chunk_to_grid  <- grow() over a dense voxel grid instead of the height pyramid (svo_world_chunk_from_grid),
 //                                       and the chunk's voxels back as a grid (svo_world_chunk_to_grid)   src/Octree.cpp:74-176
 //   svo::grid_add_mesh / grid_fill_enclosed, svo::device_grid_add_mesh / device_grid_fill_enclosed  <- (none: the reference rasterises its
@@ -347,6 +349,16 @@ public:
         check(rc, "World::chunk_combine");
         return rc;                                          // SVO_OK, or SVO_OK_LITERAL_ONLY
     }
+    // Chunk i with chunk src_chunk of `src` - an uploaded world on the same device, which may be this one; its depth at most chunk i's -
+    // placed into it: its cube starts at cell pl.offset, in orientation pl.orient, through SVO_COMBINE_* op (svo_world_chunk_stamp; svo.h
+    // states the rule).  What puts a small model into a deep terrain chunk, any number of times.  *changed_out (may be null) receives how
+    // many voxels changed.
+    int chunk_stamp(int i, World &src, int src_chunk, const svo_placement &pl, int op, uint64_t *changed_out = nullptr)
+    {
+        const int rc = svo_world_chunk_stamp(world_, i, src.world_, src_chunk, &pl, op, changed_out);
+        check(rc, "World::chunk_stamp");
+        return rc;                                          // SVO_OK, or SVO_OK_LITERAL_ONLY
+    }
 
     // The voxel box of each of n G-buffer records (svo_hit_voxels: hit.bmin / hit.size, shaders/World.Fragment.glsl:168-172) into out_dev;
     // all zero for a record without a usable hit.  What the edit cursor is placed from (src/Main.cpp:317,340-367) and what leafUV needs.
@@ -570,6 +582,14 @@ inline uint64_t chunk_combine(const svo_chunk_desc &a, const svo_chunk_desc &b, 
 {
     uint64_t changed = 0;
     check(svo_chunk_combine(&a, &b, op, out, &changed), "chunk_combine");
+    return changed;
+}
+// Host pools b (depth at most a's, both in [2, 16]) placed into host pools a at cell pl.offset in orientation pl.orient through
+// SVO_COMBINE_* op, without a grid: *out receives malloc'ed pools in a's frame (svo_chunk_free).  Returns how many voxels differ from a's.
+inline uint64_t chunk_stamp(const svo_chunk_desc &a, const svo_chunk_desc &b, const svo_placement &pl, int op, svo_chunk_desc *out)
+{
+    uint64_t changed = 0;
+    check(svo_chunk_stamp(&a, &b, &pl, op, out, &changed), "chunk_stamp");
     return changed;
 }
 
