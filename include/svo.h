@@ -19,6 +19,8 @@
  *   svo_chunk_combine / svo_world_chunk_combine <- (no counterpart) two chunks of one depth combined cell by cell on their trees
  *   svo_chunk_stamp / svo_world_chunk_stamp <- (no counterpart) a chunk placed into another at a cell offset, in one of 48 orientations
  *                           (union, B under / over A, subtraction, intersection), to depth 16, on the host or on the device
+ *   svo_chunk_extract / svo_world_chunk_extract <- (no counterpart) the stamp's inverse: a cube of cells copied out of a chunk at a cell
+ *                           offset, in one of 48 orientations, into a chunk of its own, to depth 16, on the host or on the device
  *   svo_grid_add_mesh / svo_device_grid_add_mesh <- (no counterpart: the reference rasterises its one mesh, src/Worm.cpp, with GL) a
  *                           triangle mesh voxelised into a dense grid, on the host or in device memory
  *   svo_grid_fill_enclosed / svo_device_grid_fill_enclosed <- (no counterpart) the cells that such a shell encloses, filled
@@ -142,7 +144,8 @@ extern "C" {
                                           svo_chunk_from_mesh, svo_world_chunk_from_mesh and SVO_MESH_MIN_DEPTH / SVO_MESH_MAX_DEPTH,
                                           svo_chunk_fill_enclosed, svo_world_chunk_fill_enclosed and SVO_FILL_MIN_DEPTH / SVO_FILL_MAX_DEPTH,
                                           svo_chunk_combine, svo_world_chunk_combine, SVO_COMBINE_* and SVO_COMBINE_MIN_DEPTH / SVO_COMBINE_MAX_DEPTH,
-                                          svo_chunk_stamp, svo_world_chunk_stamp, svo_placement and SVO_STAMP_MIN_DEPTH / SVO_STAMP_MAX_DEPTH
+                                          svo_chunk_stamp, svo_world_chunk_stamp, svo_placement and SVO_STAMP_MIN_DEPTH / SVO_STAMP_MAX_DEPTH,
+                                          svo_chunk_extract, svo_world_chunk_extract and SVO_EXTRACT_MIN_DEPTH / SVO_EXTRACT_MAX_DEPTH
                                           (functions added, nothing changed) */
 
 typedef enum svo_status {
@@ -724,6 +727,49 @@ typedef struct svo_placement {      /* 16 bytes */
 #define SVO_STAMP_MAX_DEPTH 16
 int svo_chunk_stamp(const svo_chunk_desc *a, const svo_chunk_desc *b, const svo_placement *pl, int op, svo_chunk_desc *out, uint64_t *changed_out);
 int svo_world_chunk_stamp(svo_world *dst, int chunk, svo_world *src, int src_chunk, const svo_placement *pl, int op, uint64_t *changed_out);
+
+/* ---- the extract: a cube of cells copied out of a chunk at any cell offset, in any orientation of the cube -----------------------
+ * The stamp is the editor's paste; this is its copy, and its exact inverse: a piece of a depth-12 terrain chunk lifted out as a depth-6
+ * model, a selection saved with svo_chunk_write, a deep chunk split into its eight octants, a chunk turned, mirrored or shifted in
+ * place - WITHOUT a dense grid.  Definition: A is the source, of depth D_A, and C the result, of depth D_C <= D_A, both in
+ * [SVO_EXTRACT_MIN_DEPTH, SVO_EXTRACT_MAX_DEPTH]; N_A = 2^D_A, N_C = 2^D_C, and G_A the grid of A's finest voxels, as
+ * svo_world_chunk_to_grid reports it (as for the chunk CSG above).  Positions and sizes are not consulted: ONE CELL OF A IS ONE CELL OF
+ * C.  The placement is the stamp's and is read exactly as the stamp reads it (orient = perm * 8 + flips, pi from the table there,
+ * flips one bit per OUTPUT axis).  For every d in [0, N_C)^3 take p = offset + d:
+ *   v = G_A[p] if every p_i lies in [0, N_A), else 0
+ *   q[pi(i)] = (flips bit i) ? N_C - 1 - d_i : d_i
+ *   G_C[q] = v
+ * So C, oriented by the placement the way the stamp orients B, is the window [offset, offset + N_C)^3 of A; WHAT LIES OUTSIDE A READS
+ * 0.  C is the tree of G_C by svo_chunk_from_grid's rule (FIFO visiting order, a uniform 4^3 block a LEAF, minimal pools), ALWAYS
+ * rebuilt; *occupied_out (may be NULL) receives the number of cells of G_C that are not 0.  For D_A <= SVO_GRID_MAX_DEPTH the result
+ * is, index for index, svo_chunk_from_grid of that window of svo_world_chunk_to_grid's grid, oriented; above it the same sentences
+ * define it.  No grid is allocated: working memory is proportional to the entries of the walk, which follow the RESULT - an A that is
+ * one LEAF word, read at an odd offset partly outside, leaves bricks along the faces.  The host form and the device form give the same
+ * pools and the same count.
+ * With E the one-word EMPTY chunk of A's depth and C = extract(A, pl):  stamp(A, C, pl, SVO_COMBINE_OVER) changes 0 cells;
+ * stamp(A, C, pl, SVO_COMBINE_SUBTRACT) changes exactly *occupied_out cells;  stamp(A, C, pl, SVO_COMBINE_INTERSECT) and
+ * stamp(E, C, pl, SVO_COMBINE_MAX) give the same pools;  with D_C = D_A, offset 0 and orient 0 the pools are
+ * svo_chunk_combine(A, E, SVO_COMBINE_MAX)'s, that is A rebuilt.
+ *
+ * svo_chunk_extract (host; `a` and `*out` host pools): D_C is `depth`, and *out receives malloc'ed pools with the frame `position` /
+ * `size`, as in svo_chunk_from_grid, freed with svo_chunk_free; `a` is not modified; out may not alias a.  It needs no device.
+ * svo_world_chunk_extract (device): A is chunk `src_chunk` of the UPLOADED world src, C chunk `chunk` of the UPLOADED world dst on the
+ * same device; D_C is that chunk's depth, and its position, size and depth stay; what it held is replaced.  src may be dst, and
+ * src_chunk == chunk of the same world is defined - the turn or the shift in place: A is read completely before C is installed.  The
+ * source chunk is never written.  Ordered, complete and installed as svo_world_chunk_stamp.  THE DEVICE WALK VISITS ONLY WHAT THE
+ * WINDOW REACHES: a malformed word elsewhere in A goes unseen.
+ *
+ * Refusals, in the stamp's order and all before anything changes or is written: SVO_ERR_INVALID_ARG for a NULL world / a / out, out ==
+ * a, a chunk out of range in either world, NULL pools, a NULL placement, orient > 47 or an offset outside [-65536, 65536], (host form)
+ * a NULL position, a size that is not finite or not > 0 and pools that svo_world_create's validation would refuse, (device form) two
+ * worlds resident on different devices; then SVO_ERR_NOT_UPLOADED for either world (device form); then SVO_ERR_UNSUPPORTED for D_C >
+ * D_A (that direction is the stamp into an empty chunk), a depth outside [2, 16], a TWIG above level depth-2 in A (host form: anywhere
+ * in A; device form: where the walk meets it) and 2^30 entries, nodes or bricks; SVO_ERR_OUT_OF_MEMORY when the working arrays do not
+ * fit; on the device a malformed pool found by the walk is SVO_ERR_MALFORMED_TREE, with nothing installed. */
+#define SVO_EXTRACT_MIN_DEPTH 2
+#define SVO_EXTRACT_MAX_DEPTH 16
+int svo_chunk_extract(const svo_chunk_desc *a, const svo_placement *pl, uint32_t depth, const float position[3], float size, svo_chunk_desc *out, uint64_t *occupied_out);
+int svo_world_chunk_extract(svo_world *dst, int chunk, svo_world *src, int src_chunk, const svo_placement *pl, uint64_t *occupied_out);
 
 /* ---- the hot path ------------------------------------------------------------------------ */
 

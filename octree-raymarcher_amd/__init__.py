@@ -27,6 +27,7 @@ it.  It mirrors the reference's `World` / `Traverse` surface (src/World.h:44-68,
     chunk_fill_enclosed, World.chunk_fill_enclosed   <- (none)   the cells a chunk's voxels enclose, filled on the tree, to depth 16
     chunk_combine, World.chunk_combine   <- (none)   two chunks of one depth combined cell by cell on their trees (COMBINE_*), to depth 16
     chunk_stamp, World.chunk_stamp, Placement   <- (none)   a chunk placed into another at a cell offset, in one of 48 orientations, through a COMBINE_* rule
+    chunk_extract, World.chunk_extract          <- (none)   the stamp's inverse: a cube of cells copied out of a chunk at a cell offset, in one of 48 orientations
     grid_add_mesh / grid_fill_enclosed, device_grid_add_mesh / device_grid_fill_enclosed, Mesh   <- (none: the reference rasterises its one mesh with GL)   a triangle mesh into a dense grid, its shell filled
 
 There is NO CPU fallback: if libsvo_amd.so is missing the import raises, and every device call
@@ -69,6 +70,7 @@ EDIT_BUILD, EDIT_DESTROY, EDIT_REPLACE = 0, 1, 2     # svo_world_edit_box
 COMBINE_MAX, COMBINE_UNDER, COMBINE_OVER, COMBINE_SUBTRACT, COMBINE_INTERSECT = 0, 1, 2, 3, 4     # svo_chunk_combine / svo_world_chunk_combine
 COMBINE_MIN_DEPTH, COMBINE_MAX_DEPTH = 2, 16
 STAMP_MIN_DEPTH, STAMP_MAX_DEPTH, STAMP_ORIENTS, STAMP_OFFSET_LIMIT = 2, 16, 48, 65536      # svo_chunk_stamp / svo_world_chunk_stamp
+EXTRACT_MIN_DEPTH, EXTRACT_MAX_DEPTH = 2, 16                # svo_chunk_extract / svo_world_chunk_extract
 # the 24 proper orientations (rotations) among orient = perm * 8 + flips: parity(perm) * (-1)^popcount(flips) = +1; perms 1, 2, 5 are odd
 ORIENT_ROTATIONS = tuple(o for o in range(48) if ((o >> 3 in (1, 2, 5)) + bin(o & 7).count("1")) % 2 == 0)
 HIT_FLAG, SHADOW_TRACED, SHADOWED, FACE_NORMAL, SEE_THROUGH, ERR_FLAG = 1, 2, 4, 8, 16, 1 << 15
@@ -262,7 +264,7 @@ ABI_SYMBOLS = [
     "svo_chunk_from_grid", "svo_world_chunk_from_grid", "svo_world_chunk_to_grid",
     "svo_grid_add_mesh", "svo_device_grid_add_mesh", "svo_grid_fill_enclosed", "svo_device_grid_fill_enclosed",
     "svo_chunk_from_mesh", "svo_world_chunk_from_mesh", "svo_chunk_fill_enclosed", "svo_world_chunk_fill_enclosed",
-    "svo_chunk_combine", "svo_world_chunk_combine", "svo_chunk_stamp", "svo_world_chunk_stamp",
+    "svo_chunk_combine", "svo_world_chunk_combine", "svo_chunk_stamp", "svo_world_chunk_stamp", "svo_chunk_extract", "svo_world_chunk_extract",
     "svo_chunk_write", "svo_chunk_read", "svo_chunk_free", "svo_world_shift", "svo_world_edit_box", "svo_world_edit_cube", "svo_world_edit_ball", "svo_world_edit_ball_all", "svo_world_compact", "svo_world_coarsen", "svo_shade", "svo_shade_packed", "svo_shade_translucent", "svo_shade_sky", "svo_frame_rgba8", "svo_cursor_place", "svo_shade_boxes", "svo_shade_defaults", "svo_gbuffer_pack", "svo_gbuffer_unpack",
     "svo_tile_order", "svo_trace", "svo_trace_rows", "svo_trace_frames", "svo_trace_rows_frames", "svo_trace_rays", "svo_trace_segments", "svo_trace_translucent", "svo_trace_local_shadows", "svo_trace_last_ray_count",
     "svo_shadowmap_fit", "svo_shadowmap_render", "svo_shadowmap_apply", "svo_hit_ao", "svo_shade_ao",
@@ -310,6 +312,8 @@ lib.svo_chunk_combine.argtypes = [C.POINTER(ChunkDesc), C.POINTER(ChunkDesc), C.
 lib.svo_world_chunk_combine.argtypes = [_P, C.c_int, _P, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
 lib.svo_chunk_stamp.argtypes = [C.POINTER(ChunkDesc), C.POINTER(ChunkDesc), C.POINTER(Placement), C.c_int, C.POINTER(ChunkDesc), C.POINTER(C.c_uint64)]
 lib.svo_world_chunk_stamp.argtypes = [_P, C.c_int, _P, C.c_int, C.POINTER(Placement), C.c_int, C.POINTER(C.c_uint64)]
+lib.svo_chunk_extract.argtypes = [C.POINTER(ChunkDesc), C.POINTER(Placement), C.c_uint32, C.POINTER(C.c_float), C.c_float, C.POINTER(ChunkDesc), C.POINTER(C.c_uint64)]
+lib.svo_world_chunk_extract.argtypes = [_P, C.c_int, _P, C.c_int, C.POINTER(Placement), C.POINTER(C.c_uint64)]
 lib.svo_gbuffer_pack.argtypes = [_P, _P, C.c_int64, _P]
 lib.svo_gbuffer_unpack.argtypes = [_P, _P, C.c_int64, _P]
 lib.svo_shade_defaults.argtypes = [C.POINTER(ShadeParams)]
@@ -645,7 +649,6 @@ def chunk_combine(a: dict, b: dict, op: int):
     finally:
         lib.svo_chunk_free(C.byref(d))
 
-
 def chunk_stamp(a: dict, b: dict, offset, orient: int, op: int):
     """svo_chunk_stamp on the host: chunk dict b (depth <= a's, both 2 .. 16) placed into chunk dict a with its cube starting at a's
     cell `offset` (x, y, z), in orientation `orient` (0 .. 47: perm * 8 + flips, ORIENT_ROTATIONS are the proper ones), through
@@ -659,6 +662,22 @@ def chunk_stamp(a: dict, b: dict, offset, orient: int, op: int):
         otree = np.ctypeslib.as_array(d.tree, shape=(d.trees,)).copy()
         otwig = np.ctypeslib.as_array(d.twig, shape=(d.twigs * 64,)).copy() if d.twigs else np.zeros(0, np.uint16)
         return {"position": tuple(d.position), "size": d.size, "depth": d.depth, "tree": otree, "twig": otwig}, int(changed.value)
+    finally:
+        lib.svo_chunk_free(C.byref(d))
+
+
+def chunk_extract(a: dict, offset, orient: int, depth: int, position=(0.0, 0.0, 0.0), size: float = 128.0):
+    """svo_chunk_extract on the host, the stamp's inverse: the cube of (2^depth)^3 cells of chunk dict a (depth <= a's, both 2 .. 16)
+    that starts at a's cell `offset` (x, y, z), as a chunk of its own in the frame `position` / `size` - oriented so that stamping it
+    back with the same `offset` and `orient` puts every cell where it came from; what lies outside a reads 0.  Rebuilt minimal and in
+    FIFO order without a dense grid; a is left as it is.  Returns (the extracted chunk dict, how many of its voxels are not 0)."""
+    da, keep_a = _host_chunk_desc(a)
+    d, occupied, pl = ChunkDesc(), C.c_uint64(0), Placement(offset, orient)
+    _check(lib.svo_chunk_extract(C.byref(da), C.byref(pl), int(depth), (C.c_float * 3)(*position), float(size), C.byref(d), C.byref(occupied)), "svo_chunk_extract")
+    try:
+        otree = np.ctypeslib.as_array(d.tree, shape=(d.trees,)).copy()
+        otwig = np.ctypeslib.as_array(d.twig, shape=(d.twigs * 64,)).copy() if d.twigs else np.zeros(0, np.uint16)
+        return {"position": tuple(d.position), "size": d.size, "depth": d.depth, "tree": otree, "twig": otwig}, int(occupied.value)
     finally:
         lib.svo_chunk_free(C.byref(d))
 
@@ -978,6 +997,17 @@ class World:
         self.stamp_status = _check(lib.svo_world_chunk_stamp(self._h, int(chunk), None if src_world is None else src_world._h, int(src_chunk), C.byref(pl), int(op),
                                                              C.byref(changed)), "svo_world_chunk_stamp")
         return int(changed.value)
+
+    def chunk_extract(self, chunk: int, src_world: "World", src_chunk: int, offset, orient: int) -> int:
+        """svo_world_chunk_extract, the stamp's inverse: chunk replaced by the cube of its own number of cells that starts at cell
+        `offset` of chunk src_chunk of src_world - an uploaded world on the same device, which may be this one, and the chunk may be
+        this chunk; its depth at least this chunk's -, oriented so that stamping it back with the same placement puts every cell where
+        it came from; built on the device on the tree; complete when it returns.  Returns how many of its voxels are not 0; the status
+        (SVO_OK or SVO_OK_LITERAL_ONLY) is in self.extract_status."""
+        occupied, pl = C.c_uint64(0), Placement(offset, orient)
+        self.extract_status = _check(lib.svo_world_chunk_extract(self._h, int(chunk), None if src_world is None else src_world._h, int(src_chunk), C.byref(pl),
+                                                                 C.byref(occupied)), "svo_world_chunk_extract")
+        return int(occupied.value)
 
     def chunk_to_grid(self, chunk: int, depth: int, out_ptr: int, stream: int = 0):
         """svo_world_chunk_to_grid: the chunk's voxels as a (2^depth)^3 uint16 grid at out_ptr (device memory), asynchronous on stream."""

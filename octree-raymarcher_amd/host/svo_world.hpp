@@ -24,6 +24,8 @@
 //                                       subtraction, intersection), to depth 16 (svo_world_chunk_combine on the device, svo_chunk_combine on host pools)
 //   svo::World::chunk_stamp / svo::chunk_stamp  <- (none) a chunk placed into another at a cell offset, in one of the 48 orientations of the cube, through a
 //                                       SVO_COMBINE_* rule, to depth 16 (svo_world_chunk_stamp on the device, svo_chunk_stamp on host pools)
+//   svo::World::chunk_extract / svo::chunk_extract  <- (none) the stamp's inverse: a cube of cells copied out of a chunk at a cell offset, in one of the 48
+//                                       orientations of the cube, into a chunk of its own, to depth 16 (svo_world_chunk_extract on the device, svo_chunk_extract on host pools)
 //   svo::World::chunk_from_grid / chunk_to_grid  <- grow() over a dense voxel grid instead of the height pyramid (svo_world_chunk_from_grid),
 //                                       and the chunk's voxels back as a grid (svo_world_chunk_to_grid)   src/Octree.cpp:74-176
 //   svo::grid_add_mesh / grid_fill_enclosed, svo::device_grid_add_mesh / device_grid_fill_enclosed  <- (none: the reference rasterises its
@@ -359,6 +361,16 @@ public:
         check(rc, "World::chunk_stamp");
         return rc;                                          // SVO_OK, or SVO_OK_LITERAL_ONLY
     }
+    // Chunk i replaced by the cube of its own number of cells that starts at cell pl.offset of chunk src_chunk of `src` - an uploaded
+    // world on the same device, which may be this one, and the chunk may be chunk i; its depth at least chunk i's -, oriented so that
+    // chunk_stamp with the same placement puts every cell back where it came from (svo_world_chunk_extract; svo.h states the rule).  What
+    // lifts a piece of a deep terrain chunk out as a model.  *occupied_out (may be null) receives how many of its voxels are not empty.
+    int chunk_extract(int i, World &src, int src_chunk, const svo_placement &pl, uint64_t *occupied_out = nullptr)
+    {
+        const int rc = svo_world_chunk_extract(world_, i, src.world_, src_chunk, &pl, occupied_out);
+        check(rc, "World::chunk_extract");
+        return rc;                                          // SVO_OK, or SVO_OK_LITERAL_ONLY
+    }
 
     // The voxel box of each of n G-buffer records (svo_hit_voxels: hit.bmin / hit.size, shaders/World.Fragment.glsl:168-172) into out_dev;
     // all zero for a record without a usable hit.  What the edit cursor is placed from (src/Main.cpp:317,340-367) and what leafUV needs.
@@ -591,6 +603,15 @@ inline uint64_t chunk_stamp(const svo_chunk_desc &a, const svo_chunk_desc &b, co
     uint64_t changed = 0;
     check(svo_chunk_stamp(&a, &b, &pl, op, out, &changed), "chunk_stamp");
     return changed;
+}
+// The cube of (2^depth)^3 cells of host pools a (depth at most a's, both in [2, 16]) that starts at cell pl.offset, in orientation
+// pl.orient - the stamp's inverse -, without a grid: *out receives malloc'ed pools in the frame position / size (svo_chunk_free).
+// Returns how many of its voxels are not empty.
+inline uint64_t chunk_extract(const svo_chunk_desc &a, const svo_placement &pl, uint32_t depth, const float position[3], float size, svo_chunk_desc *out)
+{
+    uint64_t occupied = 0;
+    check(svo_chunk_extract(&a, &pl, depth, position, size, out, &occupied), "chunk_extract");
+    return occupied;
 }
 
 } // namespace svo
